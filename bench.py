@@ -8,9 +8,17 @@
 
 One JSON line on rank 0.  A "step" is one optimisation step over one per-GPU batch resident in HBM (weak scaling:
 per-GPU batch fixed, the images are sharded over ranks, one RCCL all-reduce of the flat gradient per step).
+A plain run sets up, warms up, times --steps steps and prints the line (`value` images/s, `ms_per_step`).  The --warmup
+steps and the timed ones start from the state the set-up left (parameters, BatchNorm buffers, optimiser state, RNG seed),
+whatever the spin-up before them did, so `--dump-outputs DIR` writes the same arrays for the same arguments: what the last
+timed step handed its caller (loss record, parameters, gradient, optimiser moments, BatchNorm running statistics) as
+DIR/<name>.npy, float32.
+
+--full adds everything beyond the headline figure:
 `roofline` is measured live with HIP events (torch.cuda.Event on the stream the kernels are launched on) around every
 launch of the dominant kernel -- conv_bf16_ws_kernel (the stride-1 bf16 convolutions with 128 output channels: persistent, wavefront-specialised) by
-default, conv_igemm_f32_kernel<4,2> under --dtype f32;
+default, conv_igemm_f32_kernel<4,2> under --dtype f32; `conv_breakdown` from a few untimed steps after the timed ones;
+the gradient-transport check (N > 1), the inference and fp32 (configs[1]) legs;
 `cpu_baseline` times the CPU oracle (oracle/yogo_oracle.py: the reference's algorithm on torch CPU ops) on a bounded
 sample of the same workload -- a reported baseline, never the target.
 """
@@ -243,6 +251,104 @@ def fp32_forward_loss(dev, B: int = 64):
                          "achieved": round(tf, 2), "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(tf / FP32_MFMA_PEAK_TFLOPS, 4)}}
 
 
+def dump_outputs(out_dir: str, trainer, model) -> None:
+    """--dump-outputs: what the last timed step handed its caller, as <out_dir>/<name>.npy, float32: the loss record (total, iou,
+    objectness, classification), the flat parameter vector after AdamW, the flat clamped gradient, AdamW's two moments and
+    the BatchNorm running means / variances in module order.  Sizes follow the model alone (base_model: 8.7 MB in all)."""
+    import numpy as np
+
+    bn = [m for m in model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
+    arrays = {"loss": trainer.last_loss, "params": trainer.flat.flat, "grad": trainer.flat.grad,
+              "exp_avg": trainer.flat.exp_avg, "exp_avg_sq": trainer.flat.exp_avg_sq,
+              "bn_running_mean": torch.cat([m.running_mean.reshape(-1) for m in bn]),
+              "bn_running_var": torch.cat([m.running_var.reshape(-1) for m in bn])}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
+def roofline_fields(args, prof, prof_all, nb):
+    """--full: the rooflines of the dominant kernels from the HIP events inside the timed steps (`prof`) and the per-kind
+    convolution breakdown from the untimed steps after them (`prof_all`, `nb` steps)"""
+    def ms_of(es):
+        return sum(e[4].elapsed_time(e[5]) for e in es)
+
+    by_kind = {}
+    for kind in ("fwd", "dgrad", "wgrad"):
+        es = [e for e in prof_all if e[0] == kind]
+        t_ms = ms_of(es)
+        by_kind[kind] = {"ms_per_step": round(t_ms / nb, 3),
+                         "tflops": round(sum(e[3] for e in es) / max(t_ms, 1e-9) / 1e9, 2)}
+    if os.environ.get("YOGO_BENCH_VERBOSE"):
+        agg = {}
+        for e in prof_all:
+            k = (e[0], e[1])
+            a = agg.setdefault(k, [0.0, 0.0, 0.0])
+            a[0] += e[4].elapsed_time(e[5])
+            a[1] += e[3]
+            a[2] += e[6]
+        for (kind, layer), (t_ms, fl2, by2) in sorted(agg.items(), key=lambda kv: (kv[0][1], kv[0][0])):
+            print(f"[bench] layer {layer} {kind:6s} {t_ms / nb:8.3f} ms/step  {fl2 / t_ms / 1e9:7.2f} TFLOP/s  "
+                  f"{by2 / t_ms / 1e6:8.1f} GB/s", file=sys.stderr)
+    traffic = None
+    tpath = os.path.join(ROOT, "profiles", "traffic.json")
+    tj = {}
+    if os.path.exists(tpath):
+        try:
+            tj = json.load(open(tpath))
+        except Exception:
+            tj = {}
+    if args.dtype == "bf16":
+        # dominant kernel: conv_bf16_ws_kernel = every stride-1 convolution with 128 output channels (forward
+        # of layers 3/5/6, data gradient of layers 5/6).  Algorithmic FLOPs per launch: 2*B*Cout*Cin*k*k*OH*OW (DESIGN.md).
+        sel = [e for e in prof if e[0] in ("fwd", "dgrad") and e[2] == 34]
+        ms = ms_of(sel)
+        fl = sum(e[3] for e in sel)
+        achieved = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
+        # (the kernel has one instantiation per epilogue: <0> for layers 5 / 6, <7> for layer 3 -- weight their launches)
+        tw = [(v.get("hbm_bytes_per_launch"), v.get("launches_fetch", 0)) for k, v in tj.items() if k.startswith(("conv_bf16_ws_kernel", "conv_bf16_ws16_kernel"))]
+        tw = [(a, n) for a, n in tw if a is not None and n]
+        traffic = round(sum(a * n for a, n in tw) / sum(n for _, n in tw), 1) if tw else None
+        allc = [e for e in prof_all if e[0] in ("fwd", "dgrad") and e[2] in (30, 34)]
+        roof = {"bound": "mfma", "kernel": "conv_bf16_ws16_kernel + conv_bf16_ws_kernel<3|7> (persistent wavefront-specialised stride-1 bf16 convolutions with 128 "
+                                           "output channels: forward of layers 3/5/6, data gradient of layers 5/6)",
+                "achieved": round(achieved, 1), "peak": BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                "frac": round(achieved / BF16_MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
+                "calls_timed": len(sel), "avg_call_ms": round(ms / max(1, len(sel)), 4),
+                "traffic_source": "profiles/traffic.json: HBM bytes per launch from the committed rocprofv3 --pmc passes (FETCH_SIZE x 2 + "
+                                  "WRITE_SIZE, tools/collect_profile.sh) -- a committed constant, not measured in this run",
+                "algorithmic_gbs": round(sum(e[6] for e in sel) / max(ms, 1e-9) / 1e6, 1),
+                "all_bf16_conv_gbs": round(sum(e[6] for e in allc) / max(ms_of(allc), 1e-9) / 1e6, 1)}
+    else:
+        sel = [e for e in prof if e[0] in ("fwd", "dgrad") and e[2] == 4]
+        ms = ms_of(sel)
+        fl = sum(e[3] for e in sel)
+        achieved = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
+        traffic = tj.get("conv_igemm_f32_kernel<4,2,false>", {}).get("hbm_bytes_per_launch")
+        roof = {"bound": "mfma", "kernel": "conv_igemm_f32_kernel<4,2> (fwd+dgrad of the 128-channel 3x3 layers)",
+                "achieved": round(achieved, 2), "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                "frac": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
+                "traffic_source": "profiles/traffic.json (committed rocprofv3 --pmc passes), not measured in this run",
+                "calls_timed": len(sel), "avg_call_ms": round(ms / max(1, len(sel)), 4)}
+    rec_ns = None
+    if args.dtype == "bf16":
+        # what north_star names: ">= 70 % of gfx950 MFMA peak on the 3x3 conv GEMM" on the forward of the 64->128 / 128->128 3x3
+        # layers (SURVEY.md K5-K8 = yogo/model_defns.py:49-65, layers 3..6 here), stride-2 layer 4 included -- Sigma FLOPs / Sigma
+        # HIP-event time over those launches of the timed region
+        ns = [e for e in prof if e[0] == "fwd" and 3 <= e[1] <= 6]
+        ns_ms = ms_of(ns)
+        ns_tf = sum(e[3] for e in ns) / max(ns_ms, 1e-9) / 1e9
+        per = {}
+        for e in ns:
+            a = per.setdefault(e[1], [0.0, 0.0])
+            a[0] += e[4].elapsed_time(e[5])
+            a[1] += e[3]
+        rec_ns = {"bound": "mfma", "kernels": "forward of layers 3-6 (K5-K8: conv 64->128 s1, 128->128 s2, 128->128 s1 x 2)",
+                  "achieved": round(ns_tf, 1), "peak": BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(ns_tf / BF16_MFMA_PEAK_TFLOPS, 4),
+                  "calls_timed": len(ns), "ms_per_step": round(ns_ms / max(1, args.steps), 4),
+                  "per_layer_tflops": {str(k): round(v[1] / max(v[0], 1e-9) / 1e9, 1) for k, v in sorted(per.items())}}
+    return {"roofline": roof, "roofline_north_star_fwd": rec_ns, "conv_breakdown": by_kind}
+
 def spawn_ranks(n: int, argv) -> int:
     """run `python -m torch.distributed.run --nproc-per-node n bench.py <argv>` as a CHILD process and relay its output"""
     import socket
@@ -270,8 +376,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=128, help="per-GPU batch (BASELINE configs[2]/[3]: 128)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-inference", action="store_true", help="skip the secondary inference measurements (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: kernel rooflines (HIP events inside the timed steps), "
+                         "the per-kind convolution breakdown, the gradient-transport check, the inference / fp32 legs, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32), same arrays for the same arguments")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="under --full: skip the CPU baseline")
+    ap.add_argument("--no-inference", action="store_true", help="under --full: skip the secondary inference measurements (profiling runs)")
     ap.add_argument("--dtype", default="bf16", choices=["f32", "bf16"],
                     help="bf16 (default, BASELINE configs[2]): bf16 activations/gradients + bf16 MFMA, fp32 master weights and "
                          "statistics; f32: fp32 storage + exact fp32 MFMA")
@@ -280,6 +391,8 @@ def main():
                     help="gradient exchange transport: torch.distributed (backend above) or librccl called directly through the C ABI")
     ap.add_argument("--no-overlap", action="store_true", help="one all-reduce after backward instead of the overlapped two-part exchange")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves, like the reference's `yogo train` does
@@ -318,6 +431,9 @@ def main():
     trainer = HipTrainer(model, YOGOLoss().to(dev), total_steps=args.steps + args.warmup + 47, half=(args.dtype == "bf16"),
                          comm=args.comm, overlap=not args.no_overlap)
     trainer.broadcast_parameters()
+    # the state the warm-up and the timed steps start from (the spin-up below runs a clock-dependent number of steps)
+    start_model = {k: v.clone() for k, v in model.state_dict().items()}
+    start_opt = trainer.state_dict()
     imgs = synthetic_images(B, H, W, device=dev, seed=100 + rank)
     labels = synthetic_labels(B, model.Sx, model.Sy, K=64, num_classes=NUM_CLASSES, device=dev, seed=200 + rank)
 
@@ -342,16 +458,21 @@ def main():
             done = bool(flag.item() > 0.5)
         if done:
             break
+    # undo the spin-up: the W warm-up steps and the timed ones start from the set-up's state, so their results follow the arguments
+    model.load_state_dict(start_model)
+    trainer.load_state_dict(start_opt)
+    torch.manual_seed(0)   # the Dropout2d masks
     for _ in range(args.warmup):
         trainer.step(imgs, labels)
     torch.cuda.synchronize()
     barrier()
-    # the timed region carries HIP events around the DOMINANT kernel's launches only (the roofline's `achieved`); the per-kind
-    # breakdown of every convolution launch comes from a few untimed steps after it
-    dominant_tag = 34 if args.dtype == "bf16" else 4
-    trainer.engine.prof = []
-    # (tag 35: the stride-2 128 -> 128 forward, the one launch of north_star's K5-K8 forward set that is not the dominant kernel)
-    trainer.engine.prof_only = {dominant_tag, 35} if args.dtype == "bf16" else {dominant_tag}
+    if args.full:
+        dominant_tag = 34 if args.dtype == "bf16" else 4
+        # the timed region carries HIP events around the DOMINANT kernel's launches only (the roofline's `achieved`); the per-kind
+        # breakdown of every convolution launch comes from a few untimed steps after it
+        trainer.engine.prof = []
+        # (tag 35: the stride-2 128 -> 128 forward, the one launch of north_star's K5-K8 forward set that is not the dominant kernel)
+        trainer.engine.prof_only = {dominant_tag, 35} if args.dtype == "bf16" else {dominant_tag}
     # per step: host time to ENQUEUE the step (perf_counter around trainer.step, no sync) and one HIP event pair on the launch
     # stream -- whether the timed region was GPU-bound or waiting for the host shows in the record itself
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
@@ -368,17 +489,20 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     gpu_step_ms = [ev[i].elapsed_time(ev[i + 1]) for i in range(args.steps)]
-    prof = trainer.engine.prof
     loss_rec = trainer.loss_components()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, model)
     nb = max(1, min(args.steps, 5))
-    trainer.engine.prof = []
-    trainer.engine.prof_only = None
-    for _ in range(nb):
-        trainer.step(imgs, labels)
-    torch.cuda.synchronize()
-    barrier()
-    prof_all = trainer.engine.prof
-    trainer.engine.prof = None
+    if args.full:
+        prof = trainer.engine.prof
+        trainer.engine.prof = []
+        trainer.engine.prof_only = None
+        for _ in range(nb):
+            trainer.step(imgs, labels)
+        torch.cuda.synchronize()
+        barrier()
+        prof_all = trainer.engine.prof
+        trainer.engine.prof = None
 
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -388,7 +512,7 @@ def main():
     # exchange_begin / exchange_end the step uses: torch.distributed "nccl" = RCCL, or librccl through the C ABI under --comm rccl)
     transport = "none (one rank)"
     rccl_ranks = 1
-    if world > 1:
+    if args.full and world > 1:
         keep = trainer.flat.grad[:64].clone()
         trainer.flat.grad[:64].fill_(1.0)
         trainer.exchange_begin(0, 64)
@@ -401,85 +525,7 @@ def main():
         rccl_ranks = joined if is_rccl else 0
 
     if rank == 0:
-        # ---- roofline of the dominant kernel, from the in-loop HIP events ---------------------------------------
-        def ms_of(es):
-            return sum(e[4].elapsed_time(e[5]) for e in es)
-
-        by_kind = {}
-        for kind in ("fwd", "dgrad", "wgrad"):
-            es = [e for e in prof_all if e[0] == kind]
-            t_ms = ms_of(es)
-            by_kind[kind] = {"ms_per_step": round(t_ms / nb, 3),
-                             "tflops": round(sum(e[3] for e in es) / max(t_ms, 1e-9) / 1e9, 2)}
-        if os.environ.get("YOGO_BENCH_VERBOSE"):
-            agg = {}
-            for e in prof_all:
-                k = (e[0], e[1])
-                a = agg.setdefault(k, [0.0, 0.0, 0.0])
-                a[0] += e[4].elapsed_time(e[5])
-                a[1] += e[3]
-                a[2] += e[6]
-            for (kind, layer), (t_ms, fl2, by2) in sorted(agg.items(), key=lambda kv: (kv[0][1], kv[0][0])):
-                print(f"[bench] layer {layer} {kind:6s} {t_ms / nb:8.3f} ms/step  {fl2 / t_ms / 1e9:7.2f} TFLOP/s  "
-                      f"{by2 / t_ms / 1e6:8.1f} GB/s", file=sys.stderr)
-        traffic = None
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")
-        tj = {}
-        if os.path.exists(tpath):
-            try:
-                tj = json.load(open(tpath))
-            except Exception:
-                tj = {}
-        if args.dtype == "bf16":
-            # dominant kernel: conv_bf16_ws_kernel = every stride-1 convolution with 128 output channels (forward
-            # of layers 3/5/6, data gradient of layers 5/6).  Algorithmic FLOPs per launch: 2*B*Cout*Cin*k*k*OH*OW.
-            sel = [e for e in prof if e[0] in ("fwd", "dgrad") and e[2] == 34]
-            ms = ms_of(sel)
-            fl = sum(e[3] for e in sel)
-            achieved = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
-            # (the kernel has one instantiation per epilogue: <0> for layers 5 / 6, <7> for layer 3 -- weight their launches)
-            tw = [(v.get("hbm_bytes_per_launch"), v.get("launches_fetch", 0)) for k, v in tj.items() if k.startswith(("conv_bf16_ws_kernel", "conv_bf16_ws16_kernel"))]
-            tw = [(a, n) for a, n in tw if a is not None and n]
-            traffic = round(sum(a * n for a, n in tw) / sum(n for _, n in tw), 1) if tw else None
-            allc = [e for e in prof_all if e[0] in ("fwd", "dgrad") and e[2] in (30, 34)]
-            roof = {"bound": "mfma", "kernel": "conv_bf16_ws16_kernel + conv_bf16_ws_kernel<3|7> (persistent wavefront-specialised stride-1 bf16 convolutions with 128 "
-                                               "output channels: forward of layers 3/5/6, data gradient of layers 5/6)",
-                    "achieved": round(achieved, 1), "peak": BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                    "frac": round(achieved / BF16_MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
-                    "calls_timed": len(sel), "avg_call_ms": round(ms / max(1, len(sel)), 4),
-                    "traffic_source": "profiles/traffic.json: HBM bytes per launch from the committed rocprofv3 --pmc passes (FETCH_SIZE x 2 + "
-                                      "WRITE_SIZE, tools/collect_profile.sh) -- a committed constant, not measured in this run",
-                    "algorithmic_gbs": round(sum(e[6] for e in sel) / max(ms, 1e-9) / 1e6, 1),
-                    "all_bf16_conv_gbs": round(sum(e[6] for e in allc) / max(ms_of(allc), 1e-9) / 1e6, 1)}
-        else:
-            sel = [e for e in prof if e[0] in ("fwd", "dgrad") and e[2] == 4]
-            ms = ms_of(sel)
-            fl = sum(e[3] for e in sel)
-            achieved = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
-            traffic = tj.get("conv_igemm_f32_kernel<4,2,false>", {}).get("hbm_bytes_per_launch")
-            roof = {"bound": "mfma", "kernel": "conv_igemm_f32_kernel<4,2> (fwd+dgrad of the 128-channel 3x3 layers)",
-                    "achieved": round(achieved, 2), "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                    "frac": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
-                    "traffic_source": "profiles/traffic.json (committed rocprofv3 --pmc passes), not measured in this run",
-                    "calls_timed": len(sel), "avg_call_ms": round(ms / max(1, len(sel)), 4)}
         value = world * B * args.steps / dt
-        rec_ns = None
-        if args.dtype == "bf16":
-            # what north_star names: ">= 70 % of gfx950 MFMA peak on the 3x3 conv GEMM" on the forward of the 64->128 / 128->128 3x3
-            # layers (SURVEY.md K5-K8 = yogo/model_defns.py:49-65, layers 3..6 here), stride-2 layer 4 included -- Sigma FLOPs / Sigma
-            # HIP-event time over those launches of the timed region
-            ns = [e for e in prof if e[0] == "fwd" and 3 <= e[1] <= 6]
-            ns_ms = ms_of(ns)
-            ns_tf = sum(e[3] for e in ns) / max(ns_ms, 1e-9) / 1e9
-            per = {}
-            for e in ns:
-                a = per.setdefault(e[1], [0.0, 0.0])
-                a[0] += e[4].elapsed_time(e[5])
-                a[1] += e[3]
-            rec_ns = {"bound": "mfma", "kernels": "forward of layers 3-6 (K5-K8: conv 64->128 s1, 128->128 s2, 128->128 s1 x 2)",
-                      "achieved": round(ns_tf, 1), "peak": BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(ns_tf / BF16_MFMA_PEAK_TFLOPS, 4),
-                      "calls_timed": len(ns), "ms_per_step": round(ns_ms / max(1, args.steps), 4),
-                      "per_layer_tflops": {str(k): round(v[1] / max(v[0], 1e-9) / 1e9, 1) for k, v in sorted(per.items())}}
         rec = {
             "metric": "training images/sec (772x1032 gray)", "value": round(value, 2), "unit": "images/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3),
@@ -487,23 +533,22 @@ def main():
             "config": {"workload": "BASELINE configs[2]: full train step (fwd+loss+bwd+clamp+AdamW), base_model, 772x1032x1 uint8, "
                                    "7 classes" + ("" if args.dtype == "bf16" else " -- run at fp32 storage+arithmetic"),
                        "per_gpu_batch": B, "global_batch": B * world, "parallelism": f"dp{world}"},
-            "roofline": roof,
-            "roofline_north_star_fwd": rec_ns,
             "host_enqueue_ms_per_step": round(1e3 * _median(enq), 3),
             "host_enqueue_ms_per_step_max": round(1e3 * max(enq), 3),
             "gpu_ms_per_step_events": round(_median(gpu_step_ms), 3),
             "gpu_ms_per_step_events_min_max": [round(min(gpu_step_ms), 3), round(max(gpu_step_ms), 3)],
-            "rccl_ranks": rccl_ranks,
-            "gradient_transport": transport,
             "step_tflops": round(value * TRAIN_GFLOP_PER_IMG / 1e3, 2),
-            "conv_breakdown": by_kind,
             "loss": round(loss_rec["loss"], 4),
         }
-        if world == 1 and not args.no_inference:
-            rec["inference"] = inference_extras(model, dev)
-            rec["configs1_fp32_forward_loss"] = fp32_forward_loss(dev)
-        if world == 1 and not args.no_cpu_baseline:
-            rec["cpu_baseline"] = cpu_baseline()
+        if args.full:
+            rec.update(roofline_fields(args, prof, prof_all, nb))
+            rec["rccl_ranks"] = rccl_ranks
+            rec["gradient_transport"] = transport
+            if world == 1 and not args.no_inference:
+                rec["inference"] = inference_extras(model, dev)
+                rec["configs1_fp32_forward_loss"] = fp32_forward_loss(dev)
+            if world == 1 and not args.no_cpu_baseline:
+                rec["cpu_baseline"] = cpu_baseline()
         print(json.dumps(rec))
     if world > 1:
         torch.distributed.destroy_process_group()

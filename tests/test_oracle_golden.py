@@ -58,6 +58,14 @@ def test_backbone_decode_eval(fix):
         torch.testing.assert_close(out, outs[key], rtol=1e-5, atol=1e-6)
 
 
+def _feeds_batchnorm(key, sd):
+    """model.<i>.<j>.bias of a convolution whose next module in the block, model.<i>.<j + 1>, is a BatchNorm"""
+    parts = key.split(".")
+    if len(parts) != 4 or parts[3] != "bias" or not parts[2].isdigit():
+        return False
+    return f"{parts[0]}.{parts[1]}.{int(parts[2]) + 1}.running_mean" in sd
+
+
 @pytest.mark.parametrize("fix", NETS)
 def test_backbone_train_forward_backward(fix):
     meta, x, sd, grads, after, outs = load_net_fixture(fix)
@@ -72,7 +80,14 @@ def test_backbone_train_forward_backward(fix):
     g = O.clamp_grads({k: v.grad for k, v in leaf.items()}, 1.0)
     assert set(g) == set(grads)
     for k in grads:
-        assert rel_err(g[k], grads[k]) < 2e-4, k
+        if _feeds_batchnorm(k, sd):
+            # a conv bias right in front of BatchNorm: its exact gradient is zero (BatchNorm subtracts the batch mean), so the
+            # oracle's and the reference's values are both rounding noise that follows the summation order (CPU thread count):
+            # both must be zero up to that noise, against the scale of the same convolution's weight gradient
+            scale = float(grads[k[:-len("bias")] + "weight"].abs().max())
+            assert float(g[k].abs().max()) < 1e-5 * scale and float(grads[k].abs().max()) < 1e-5 * scale, k
+        else:
+            assert rel_err(g[k], grads[k]) < 2e-4, k
     for k, v in after.items():
         torch.testing.assert_close(new_stats[k].to(v.dtype), v, rtol=1e-4, atol=1e-5)
 
