@@ -13,6 +13,7 @@ The per-parameter gradient clamp of yogo/model.py:76-77 is fused into the gradie
 """
 from __future__ import annotations
 
+import threading
 import weakref
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
@@ -608,14 +609,19 @@ def forward_bf16_train(eng: Engine, x: torch.Tensor) -> Tuple[torch.Tensor, List
 
 def backward_bf16_train(eng: Engine, saved: List[Saved], graw: torch.Tensor,
                         grad_out: Optional[Dict[int, torch.Tensor]] = None, on_layer=None,
-                        trace: Optional[dict] = None, flush_layers=None) -> List[Optional[torch.Tensor]]:
+                        trace: Optional[dict] = None, flush_layers=None, stop_at: int = 0) -> List[Optional[torch.Tensor]]:
     """``on_layer(i)`` is called once every gradient kernel of layer i has been enqueued.  With ``flush_layers`` (layer indices) the
     hook only needs COMPLETE parameter gradients at those layers: the split-K reductions stay deferred and are flushed in front of
     the hook there (and behind the last layer) -- two launches for the data-parallel trainer's two-part exchange instead of one
     reduction per layer, the same bits.  Without it a hook gets every layer's gradients reduced as soon as the layer is through.
     ``trace`` (tests / probes only): a dict that receives clones of the activation gradients as they exist between the
     kernels -- ("g", i): gradient w.r.t. block i's output, ("dz", i): BatchNorm-backward output of block i -- so that every
-    kernel of a real step can be checked against the oracle given its ACTUAL inputs (tests/_util.py, teacher-forced check)."""
+    kernel of a real step can be checked against the oracle given its ACTUAL inputs (tests/_util.py, teacher-forced check).
+    ``stop_at`` (frozen lower layers, the autograd path): the pass ends with the parameter gradients of layer ``stop_at`` -- no data
+    gradient of that layer and nothing of the layers below it is computed; their entries of the result are None."""
+    n = len(eng.layers)
+    if not 0 <= stop_at < n:
+        raise ValueError(f"yogo_amd: stop_at {stop_at} is not a layer of this {n}-layer network")
     st, dev, clip = _hip.stream_ptr(), graw.device, float(eng.clip)
     grads: Dict[int, torch.Tensor] = {}
 
@@ -639,10 +645,9 @@ def backward_bf16_train(eng: Engine, saved: List[Saved], graw: torch.Tensor,
         B, P, Sy, Sx = graw.shape
         g = torch.empty(B, _blocks(P), Sy, Sx, 8, dtype=torch.bfloat16, device=dev)
         _hip.call("yogo_nchw_f32_to_bf16_8c", graw, g, B, P, Sy * Sx, st)
-    n = len(eng.layers)
     head_g = None    # (head gradient, head weights) when the head's data gradient is left to the BatchNorm backward of the block under it
     fused01 = None   # (part, rows) of layer 0's backward sums when layer 1's data gradient produced them (g is then None at layer 0)
-    for i in range(n - 1, -1, -1):
+    for i in range(n - 1, stop_at - 1, -1):
         L, S = eng.layers[i], saved[i]
         OH, OW = (int(g.shape[2]), int(g.shape[3])) if g is not None else fused01[2:]
         if i == 0:
@@ -656,7 +661,7 @@ def backward_bf16_train(eng: Engine, saved: List[Saved], graw: torch.Tensor,
         # gradient straight into layer 0's backward sums (layer 0 has no data gradient of its own, so its dy need not exist; a trace wants
         # to see it)
         fuse01 = False
-        if _L01_FUSE_BWD and i == 1 and trace is None and _FUSE_LAYER0_BWD and _WGRAD_BF16_MFMA:
+        if _L01_FUSE_BWD and i == 1 and stop_at == 0 and trace is None and _FUSE_LAYER0_BWD and _WGRAD_BF16_MFMA:
             L0, S0 = eng.layers[0], saved[0]
             fuse01 = bool(S0.signs0 is not None and S0.x_in.dtype == torch.uint8 and L0.bn is not None and L0.conv.bias is None and L0.cin == 1
                           and L0.s == 2 and L0.act in (ACT_NONE, ACT_LEAKY) and L.k == 3 and L.s == 1 and S0.mask is None
@@ -780,7 +785,7 @@ def backward_bf16_train(eng: Engine, saved: List[Saved], graw: torch.Tensor,
         if fuse01:   # (layer 1's data gradient went into layer 0's sums above)
             g = None
             continue
-        if i > 0:
+        if i > stop_at:
             Lp, Sp = eng.layers[i - 1], saved[i - 1]
             # the 1x1 head above a BatchNorm block: 12 multiply-adds per element inside that block's BatchNorm backward are cheaper than
             # writing and twice reading its 128-channel data gradient (a trace wants to see the tensor)
@@ -859,6 +864,91 @@ class _BackboneFn(torch.autograd.Function):
         return (None, None, *grads)
 
 
+# ---- bf16 training through autograd: the module surface under torch.autocast("cuda", dtype=torch.bfloat16) -------------------------
+# The same kernel sequence as HipTrainer(half=True), with the autograd semantics a torch training loop relies on: the parameters are
+# saved for backward (an in-place update between forward and backward raises torch's version error instead of differentiating repacked
+# new weights), one backward per graph (the Saved records are handed over to it), several live graphs, gradients accumulated by autograd,
+# and frozen parameters -- None for them, and the backward pass ends at the lowest trainable layer when that layer is >= 2.
+_BF16_BWD_LOCK = threading.Lock()   # autograd runs backward on one thread per device; the deferred-reduction queue is one per process
+
+
+def bf16_training_requested() -> bool:
+    """True inside `torch.autocast("cuda", dtype=torch.bfloat16)` -- how the reference's training loop asks for half precision
+    (yogo/train.py:315-318, there in fp16; fp16 autocast keeps the fp32 kernels here)"""
+    return bf16_inference_requested()
+
+
+def bf16_train_supported(eng: Engine) -> bool:
+    """the network is one forward_bf16_train / backward_bf16_train take: False for everything forward_bf16_train refuses (which still
+    raises on its own) -- a first convolution that is not a 1- or 3-channel 3x3, a first or last SiLU block without BatchNorm,
+    BatchNorm or Dropout2d on the last layer, BatchNorm2d(momentum=None) -- and for a network of one layer"""
+    layers = eng.layers
+    n = len(layers)
+    if n < 2 or not eng._first_direct(0):
+        return False
+    for i, L in enumerate(layers):
+        if i > 0 and L.cin != layers[i - 1].cout:
+            return False
+        if L.act == ACT_SILU and L.bn is None and i in (0, n - 1):
+            return False
+        if L.bn is not None and L.bn.momentum is None:
+            return False
+    return layers[-1].bn is None and layers[-1].drop is None
+
+
+def _param_layers(eng: Engine) -> Dict[int, int]:
+    """id(parameter) -> index of the layer it belongs to"""
+    out: Dict[int, int] = {}
+    for i, L in enumerate(eng.layers):
+        for m in (L.conv, L.bn):
+            if m is not None:
+                for p in m.parameters(recurse=False):
+                    out[id(p)] = i
+    return out
+
+
+def bf16_autograd_backward(eng: Engine, saved: List[Saved], g: torch.Tensor, needs) -> List[Optional[torch.Tensor]]:
+    """backward of the autograd functions: ``g`` = head gradient (bf16 NCHW8c or fp32 NCHW), ``needs`` = ctx.needs_input_grad of the
+    backbone's parameters in ``backbone.parameters()`` order.  Gradients of the parameters that need none are None; when the lowest
+    layer holding a trainable parameter is >= 2 the pass stops there (layers 0 / 1 keep their fused sweep: the full pass runs)."""
+    bb = eng.backbone_ref()
+    params = list(bb.parameters())
+    needs = list(needs)
+    if len(needs) != len(params):
+        raise RuntimeError("yogo_amd: the backbone's parameters changed between forward and backward")
+    if not any(needs):
+        return [None] * len(params)
+    layer_of = _param_layers(eng)
+    lo = min(layer_of[id(p)] for p, nd in zip(params, needs) if nd)
+    with _BF16_BWD_LOCK:
+        grads = backward_bf16_train(eng, saved, g, stop_at=lo if lo >= 2 else 0)
+    return [gr if nd else None for gr, nd in zip(grads, needs)]
+
+
+class _BackboneBF16Fn(torch.autograd.Function):
+    """the backbone alone on the bf16 training path: returns the fp32 head output; backward takes its fp32 gradient"""
+
+    @staticmethod
+    def forward(ctx, x, backbone, *params):  # type: ignore[override]
+        eng = get_engine(backbone)
+        with torch.cuda.device(x.device):
+            raw, saved = forward_bf16_train(eng, x)
+        ctx.save_for_backward(*params)
+        ctx.eng, ctx.saved = eng, saved
+        return raw
+
+    @staticmethod
+    def backward(ctx, graw):  # type: ignore[override]
+        if ctx.saved is None:
+            raise RuntimeError("yogo_amd: a second backward through a bf16 training graph is not supported (its forward records "
+                               "belong to the first backward); run the forward again")
+        ctx.saved_tensors   # (raises torch's version error if a parameter was modified in place since the forward)
+        saved, ctx.saved = ctx.saved, None
+        with torch.cuda.device(graw.device):
+            grads = bf16_autograd_backward(ctx.eng, saved, graw, ctx.needs_input_grad[2:])
+        return (None, None, *grads)
+
+
 def backbone_apply(backbone: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
     _hip.require_cuda(x, "the input batch")
     params = list(backbone.parameters())
@@ -869,6 +959,8 @@ def backbone_apply(backbone: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
             return raw
     with torch.cuda.device(x.device):
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            if bf16_training_requested() and bf16_train_supported(get_engine(backbone)):
+                return _BackboneBF16Fn.apply(x, backbone, *params)
             return _BackboneFn.apply(x, backbone, *params)
         raw, _ = get_engine(backbone).forward(x, need_grad=False)
         return raw

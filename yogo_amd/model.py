@@ -38,6 +38,43 @@ class _DecodeFn(torch.autograd.Function):
         return graw, None, None, None, None, None, None, None
 
 
+class _TrainBF16Fn(torch.autograd.Function):
+    """backbone + box decode on the bf16 training path (``model(x)`` under bf16 autocast with gradients on): forward_bf16_train, then
+    the decode; backward writes the head's gradient straight to bf16 NCHW8c (yogo_decode_bwd_bf16) and runs backward_bf16_train -- with
+    YOGOLoss the kernel sequence of HipTrainer(half=True).step, so the same gradients bit for bit"""
+
+    @staticmethod
+    def forward(ctx, x, model, *params):  # type: ignore[override]
+        from yogo_amd.engine import forward_bf16_train
+
+        eng = get_engine(model.model)
+        eng.clip = model._clip
+        aw, ah, wm, hm = model._decode_scalars()
+        with torch.cuda.device(x.device):
+            raw, saved = forward_bf16_train(eng, x)
+            pred = _decode(raw, model._Cxs, model._Cys, aw, ah, wm, hm, bool(model.inference))
+        ctx.save_for_backward(raw, pred, *params)
+        ctx.eng, ctx.saved, ctx.inference = eng, saved, bool(model.inference)
+        return pred
+
+    @staticmethod
+    def backward(ctx, gpred):  # type: ignore[override]
+        from yogo_amd.engine import bf16_autograd_backward
+
+        if ctx.saved is None:
+            raise RuntimeError("yogo_amd: a second backward through a bf16 training graph is not supported (its forward records "
+                               "belong to the first backward); run the forward again")
+        raw, pred = ctx.saved_tensors[:2]   # (raises torch's version error if a parameter was modified in place since the forward)
+        saved, ctx.saved = ctx.saved, None
+        B, P, Sy, Sx = raw.shape
+        with torch.cuda.device(raw.device):
+            g8 = torch.empty(B, ((P + 15) // 16) * 2, Sy, Sx, 8, dtype=torch.bfloat16, device=raw.device)
+            _hip.call("yogo_decode_bwd_bf16", raw, pred, gpred.contiguous().float(), g8, B, P, Sy, Sx, int(ctx.inference),
+                      _hip.stream_ptr())
+            grads = bf16_autograd_backward(ctx.eng, saved, g8, ctx.needs_input_grad[2:])
+        return (None, None, *grads)
+
+
 def _decode(raw, cxs, cys, anchor_w, anchor_h, wmul, hmul, inference) -> torch.Tensor:
     B, P, Sy, Sx = raw.shape
     if tuple(cxs.shape) != (Sy, Sx) or tuple(cys.shape) != (Sy, Sx):
@@ -262,6 +299,18 @@ class YOGO(nn.Module):
                 if res is not None:
                     out, decoded = res
                     return out if decoded else _decode(out, self._Cxs, self._Cys, aw, ah, wm, hm, bool(self.inference))
+        if torch.is_grad_enabled():
+            # training under bf16 autocast (the reference's loop, yogo/train.py:315-325): backbone + decode on the bf16 kernels of
+            # HipTrainer(half=True), through autograd; fp16 autocast and networks the bf16 path does not take keep the fp32 kernels
+            from yogo_amd.engine import bf16_train_supported, bf16_training_requested
+
+            params = list(self.model.parameters())
+            if bf16_training_requested() and any(p.requires_grad for p in params) and bf16_train_supported(get_engine(self.model)):
+                if x.ndim == 3:
+                    x.unsqueeze_(0)
+                _hip.require_cuda(x, "the input batch")
+                xin = x if (x.is_floating_point() or x.dtype == torch.uint8) else x.float()
+                return _TrainBF16Fn.apply(xin, self, *params)
         raw = self._backbone(x)
         if torch.is_grad_enabled() and raw.requires_grad:
             return _DecodeFn.apply(raw, self._Cxs, self._Cys, aw, ah, wm, hm, bool(self.inference))
