@@ -349,6 +349,26 @@ int yogo_labels_rasterize(const float* labels, const int* offsets, float* out, i
 int yogo_flip_batch(const void* img_in, void* img_out, int elem_bytes, const float* lab_in, float* lab_out, int B, int C, int H,
                     int W, int Sy, int Sx, int hflip, int vflip, yogo_stream_t stream);
 
+/* ---- thumbnail ("blob") augmentation, yogo/data/blobgen.py:208-263 (BlobDataset.__getitem__), S images per call ----------
+ * Thumbnails: atlas = every kept thumbnail's uint8 pixels back to back (row-major h x w); table = [T][5] int32 (atlas offset,
+ * h, w, class, shade), shade = blobgen.py:168-179 computed by the caller.  Every draw is a counter-based hash of
+ * (seed, epoch, indices[s], slot, kind, try): the exact rule is at the top of yogo_amd/csrc/blobgen.hip.  Three steps:
+ *   place      -> boxes [S][n][4] int32 (thumbnail, x, y, flips: bit 0 horizontal, bit 1 vertical), rows [S][n][5] fp32
+ *                 (class, x / W, y / H, (x + w) / W, (y + h) / H) in placement order, counts [S], background [S]; entries past
+ *                 counts[s] are zero.  n <= yogo_blobgen_max_n.  blobgen.py:140-160 (draws), :181-206 (100 tries, first try
+ *                 that intersects no accepted box), :210-249 (background = truncated mean shade of all n draws, flips, labels)
+ *   compose    -> images into rows positions[0 .. S) of out [B][1][H][W]: elem_bytes 1 = uint8, 4 = fp32 pixel / 255
+ *                 (normalize_images, blobgen.py:261-262).  W <= 4096.  Deterministic, one store per output element.
+ *   label_rows -> the placed rows as one flat list flat [S * n][5] with offsets [S + 1], the input of yogo_labels_rasterize
+ *                 (box_format 0, xyxy) -- format_labels_tensor at blobgen.py:259 */
+int yogo_blobgen_max_n(int* n);
+int yogo_blobgen_place(const int* table, int num_thumbnails, const int* indices, int S, int n, int H, int W, long long seed,
+                       long long epoch, int* boxes, float* rows, int* counts, int* background, yogo_stream_t stream);
+int yogo_blobgen_compose(const unsigned char* atlas, long long atlas_bytes, const int* table, const int* boxes, const int* counts,
+                         const int* background, const int* positions, int S, int n, int H, int W, void* out, int elem_bytes,
+                         yogo_stream_t stream);
+int yogo_blobgen_label_rows(const float* rows, const int* counts, int S, int n, float* flat, int* offsets, yogo_stream_t stream);
+
 /* ---- optimiser: torch.optim.AdamW over one flat buffer, yogo/train.py:213-217,324 ---------------------------------------- */
 int yogo_adamw_step(float* p, const float* g, float* m, float* v, long long n, int step, double lr, double beta1,
                     double beta2, double eps, double weight_decay, double grad_scale, yogo_stream_t stream);

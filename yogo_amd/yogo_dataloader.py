@@ -6,6 +6,12 @@ augmentations on the training split only).  What differs is WHERE the work happe
 files, the loader then moves the stacked uint8 images to the MI355X, rasterises all label tensors of the batch with one HIP
 launch and applies both flips in one fused pass (yogo_amd/data.py) -- a ``DeviceLoader`` yields ``(imgs [B,C,H,W] uint8,
 labels [B,6,Sy,Sx] fp32)`` already resident in HBM, which is what ``HipTrainer.step`` consumes.
+
+Thumbnail augmentation (``thumbnail_augmentation:`` in the definition, yogo_dataloader.py:137-152): the train split gets a
+``BlobDataset`` of ``len(train) // 2`` synthetic images appended, shuffled with the real ones by the sampler.  Workers never
+make a synthetic image: for its indices they hand over the index alone (``BlobIndices``), and ``DeviceLoader`` composes those
+images on the device straight into their rows of the batch (yogo_amd/blobgen.py), with ``epoch = sampler.epoch``.  A
+definition without the key takes exactly the path above.
 """
 from __future__ import annotations
 
@@ -17,6 +23,7 @@ import torch
 from torch.utils.data import ConcatDataset, DataLoader, Dataset, Subset, random_split
 from torch.utils.data.distributed import DistributedSampler
 
+from yogo_amd.blobgen import BlobDataset
 from yogo_amd.data import MultiArgSequential, RandomHorizontalFlipWithBBs, RandomVerticalFlipWithBBs, format_labels_batch
 from yogo_amd.dataset_definition_file import DatasetDefinition, SplitFractions
 from yogo_amd.yogo_dataset import ObjectDetectionDataset
@@ -51,20 +58,29 @@ def _concat(dataset_paths, Sx, Sy, classes, image_hw, rgb, normalize_images) -> 
 
 def get_datasets(dataset_definition: DatasetDefinition, Sx: int, Sy: int, rgb: bool = False, image_hw: Tuple[int, int] = (772, 1032),
                  normalize_images: bool = False, split_fraction_override: Optional[SplitFractions] = None) -> MutableMapping[str, Dataset]:
-    """dataset definition -> {"train": ..., "val": ..., "test": ...} (yogo_dataloader.py:69-151).  The thumbnail ("blob")
-    augmentation of the reference is not part of this build: a definition that asks for it is refused, not silently ignored."""
-    if getattr(dataset_definition, "thumbnail_augmentation", None):
-        raise NotImplementedError("yogo_amd: thumbnail_augmentation (yogo/data/blobgen.py) is out of scope of this build")
+    """dataset definition -> {"train": ..., "val": ..., "test": ...} (yogo_dataloader.py:69-152).  With thumbnail augmentation
+    the train split is ``ConcatDataset([train, BlobDataset(n=100, length=len(train) // 2)])``, as in the reference; it is
+    refused together with ``rgb`` (the reference then fails at collate: 1-channel blob images beside 3-channel ones)."""
+    thumbnails = getattr(dataset_definition, "thumbnail_augmentation", None)
+    if thumbnails and rgb:
+        raise ValueError("thumbnail_augmentation makes grayscale images; it cannot be combined with rgb")
     classes = dataset_definition.classes
     full = _concat(dataset_definition.dataset_paths, Sx, Sy, classes, image_hw, rgb, normalize_images)
     test_paths = dataset_definition.test_dataset_paths
     if test_paths is not None and len(test_paths) > 0:
         test = _concat(test_paths, Sx, Sy, classes, image_hw, rgb, normalize_images)
         if split_fraction_override is not None:
-            return split_dataset(ConcatDataset([full, test]), split_fraction_override)
-        assert "test" not in dataset_definition.split_fractions
-        return {**split_dataset(full, dataset_definition.split_fractions), "test": test}
-    return split_dataset(full, split_fraction_override if split_fraction_override is not None else dataset_definition.split_fractions)
+            split = split_dataset(ConcatDataset([full, test]), split_fraction_override)
+        else:
+            assert "test" not in dataset_definition.split_fractions
+            split = {**split_dataset(full, dataset_definition.split_fractions), "test": test}
+    else:
+        split = split_dataset(full, split_fraction_override if split_fraction_override is not None else dataset_definition.split_fractions)
+    if thumbnails:
+        bd = BlobDataset(thumbnails, Sx=Sx, Sy=Sy, classes=classes, n=100, length=len(split["train"]) // 2,   # type: ignore[arg-type]
+                         background_img_shape=tuple(image_hw), normalize_images=normalize_images)
+        split["train"] = ConcatDataset([split["train"], bd])
+    return split
 
 
 def split_dataset(dataset: Dataset, split_fractions: SplitFractions) -> MutableMapping[str, Dataset]:
@@ -85,16 +101,62 @@ def collate_rows(batch: List[Optional[Tuple[torch.Tensor, torch.Tensor]]]) -> Op
     return torch.stack(imgs), list(rows)
 
 
+class BlobIndices(Dataset):
+    """What the workers see of a ``BlobDataset``: item i is the index i itself (the image is made on the device)."""
+
+    def __init__(self, length: int):
+        self.length = length
+
+    def __len__(self) -> int:
+        return self.length
+
+    def __getitem__(self, i: int) -> int:
+        if not 0 <= i < self.length:
+            raise IndexError(f"index {i} is out of bounds for length {self.length}")
+        return int(i)
+
+
+def collate_mixed(batch: List[Any]) -> Optional[Tuple[Optional[torch.Tensor], List[torch.Tensor], List[int], List[int], List[int], int]]:
+    """``collate_rows`` for batches of real samples and blob indices (ints), in the sampler's order: unreadable real samples
+    are dropped and the rest close up.  -> (real images stacked or None, their label rows, their batch rows, blob indices,
+    their batch rows, batch size); None when nothing is left."""
+    imgs: List[torch.Tensor] = []
+    rows: List[torch.Tensor] = []
+    real_pos: List[int] = []
+    blob_idx: List[int] = []
+    blob_pos: List[int] = []
+    b = 0
+    for item in batch:
+        if item is None:
+            continue
+        if isinstance(item, int):
+            blob_idx.append(item)
+            blob_pos.append(b)
+        else:
+            imgs.append(item[0])
+            rows.append(item[1])
+            real_pos.append(b)
+        b += 1
+    if b == 0:
+        return None
+    return (torch.stack(imgs) if imgs else None), rows, real_pos, blob_idx, blob_pos, b
+
+
 class DeviceLoader:
     """wraps the host DataLoader: batch -> device, label rows -> [B, 6, Sy, Sx] with one launch, flips fused.  Keeps the
     attributes the training loop touches (``dataset``, ``sampler``, ``batch_size``, ``__len__``)."""
 
-    def __init__(self, loader: DataLoader, Sx: int, Sy: int, transforms: MultiArgSequential, device=None, strict_steps: bool = False):
+    def __init__(self, loader: DataLoader, Sx: int, Sy: int, transforms: MultiArgSequential, device=None, strict_steps: bool = False,
+                 blob: Optional[BlobDataset] = None, dataset: Optional[Dataset] = None):
         self.loader, self.Sx, self.Sy, self.transforms, self.device = loader, Sx, Sy, transforms, device
         # strict_steps (the TRAINING split only): every batch is one gradient all-reduce, so a skipped batch must fail loudly
         # under data parallelism; validation / test loaders issue no per-step collective and may skip, as the reference does
         self.strict_steps = strict_steps
-        self.dataset, self.sampler, self.batch_size = loader.dataset, loader.sampler, loader.batch_size
+        # blob: the BlobDataset behind the BlobIndices of a thumbnail-augmented train split (loader.collate_fn = collate_mixed);
+        # dataset: the split as get_datasets made it (the loader iterates its worker-side form)
+        self.blob = blob
+        self.dataset = loader.dataset if dataset is None else dataset
+        self.sampler, self.batch_size = loader.sampler, loader.batch_size
 
     def __len__(self) -> int:
         return len(self.loader)
@@ -111,10 +173,31 @@ class DeviceLoader:
                     raise RuntimeError("yogo_amd: a whole batch of this rank was unreadable; in a data-parallel run every rank must "
                                        "take the same number of steps (fix or remove the unreadable files)")
                 continue
-            imgs, rows = item
-            imgs = imgs.to(dev, non_blocking=True)
-            labels = format_labels_batch(rows, self.Sx, self.Sy, "cxcywh", device=dev)
+            if self.blob is not None:
+                imgs, labels = self._assemble(item, dev)
+            else:
+                imgs, rows = item
+                imgs = imgs.to(dev, non_blocking=True)
+                labels = format_labels_batch(rows, self.Sx, self.Sy, "cxcywh", device=dev)
             yield self.transforms(imgs, labels)
+
+    def _assemble(self, item, dev: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
+        """a mixed batch on the device: real images uploaded into their rows, blob images composed into theirs, both label sets
+        rasterised (one launch each) into their rows"""
+        real_imgs, real_rows, real_pos, blob_idx, blob_pos, B = item
+        blob = self.blob
+        H, W = blob.background_img_shape
+        with torch.cuda.device(dev):
+            imgs = torch.empty(B, 1, H, W, dtype=torch.float32 if blob.normalize_images else torch.uint8, device=dev)
+            labels = torch.empty(B, 6, self.Sy, self.Sx, dtype=torch.float32, device=dev)
+            if real_pos:
+                rp = torch.tensor(real_pos, dtype=torch.long).to(dev, non_blocking=True)
+                imgs.index_copy_(0, rp, real_imgs.to(dev, non_blocking=True).to(imgs.dtype))
+                labels.index_copy_(0, rp, format_labels_batch(real_rows, self.Sx, self.Sy, "cxcywh", device=dev))
+            if blob_idx:
+                _, blob_labels, _, _ = blob.generate(blob_idx, getattr(self.sampler, "epoch", 0), out_imgs=imgs, positions=blob_pos)
+                labels.index_copy_(0, torch.tensor(blob_pos, dtype=torch.long).to(dev, non_blocking=True), blob_labels)
+        return imgs, labels
 
 
 def get_dataloader(dataset_definition: DatasetDefinition, batch_size: int, Sx: int, Sy: int, training: bool = True,
@@ -138,14 +221,18 @@ def get_dataloader(dataset_definition: DatasetDefinition, batch_size: int, Sx: i
 
 def _get_dataloader(dataset: Dataset, batch_size: int, augmentations: list, rank: int, world_size: int, Sx: int, Sy: int,
                     device=None, strict_steps: bool = False) -> DeviceLoader:
-    sampler: Iterable = DistributedSampler(dataset, rank=rank, num_replicas=world_size)   # torch defaults: shuffle, seed 0, padded
+    blob = dataset.datasets[-1] if isinstance(dataset, ConcatDataset) and isinstance(dataset.datasets[-1], BlobDataset) else None
+    # the workers iterate the split with its blob part replaced by the indices alone (same length: same sampler order)
+    host_dataset = ConcatDataset([*dataset.datasets[:-1], BlobIndices(len(blob))]) if blob is not None else dataset
+    sampler: Iterable = DistributedSampler(host_dataset, rank=rank, num_replicas=world_size)   # torch defaults: shuffle, seed 0, padded
     num_workers = choose_dataloader_num_workers(len(dataset)) // world_size   # type: ignore[arg-type]
     if len(dataset) >= 1000:   # type: ignore[arg-type]
         num_workers = max(1, num_workers)
-    loader = DataLoader(dataset, shuffle=False, sampler=sampler, drop_last=False, pin_memory=torch.cuda.is_available(), batch_size=batch_size,
+    loader = DataLoader(host_dataset, shuffle=False, sampler=sampler, drop_last=False, pin_memory=torch.cuda.is_available(), batch_size=batch_size,
                         num_workers=num_workers, persistent_workers=num_workers > 0, generator=torch.Generator().manual_seed(SPLIT_SEED),
-                        collate_fn=collate_rows, multiprocessing_context="spawn" if num_workers > 0 else None)
-    return DeviceLoader(loader, Sx, Sy, MultiArgSequential(*augmentations), device, strict_steps=strict_steps)
+                        collate_fn=collate_rows if blob is None else collate_mixed, multiprocessing_context="spawn" if num_workers > 0 else None)
+    return DeviceLoader(loader, Sx, Sy, MultiArgSequential(*augmentations), device, strict_steps=strict_steps, blob=blob,
+                        dataset=dataset if blob is not None else None)
 
 
 def get_class_counts(d, num_classes: int, verbose: bool = True) -> torch.Tensor:
