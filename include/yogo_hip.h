@@ -369,6 +369,15 @@ int yogo_blobgen_compose(const unsigned char* atlas, long long atlas_bytes, cons
                          yogo_stream_t stream);
 int yogo_blobgen_label_rows(const float* rows, const int* counts, int S, int n, float* flat, int* offsets, yogo_stream_t stream);
 
+/* ---- decoded images resident in HBM (yogo_amd/image_cache.py, `yogo train --device-image-cache GIB`) ----------------------
+ * cache: [S][C][H][W] uint8, the images of split indices 0 .. S-1 decoded once; slots: [B] int32 device; out: [B][C][H][W],
+ * uint8 (out_fp32 = 0) or fp32 (out_fp32 = 1).  For every b with slots[b] >= 0, row b of out = cache[slots[b]], as uint8 or as
+ * fp32 x / 255 bit-identical to torch's CPU uint8_tensor / 255 (normalize_images).  Rows with slots[b] < 0 are not touched
+ * (uploaded rows, blob images); a slot >= S is skipped too, but the caller checks slots < S before the launch.  B <= 65535.
+ * One HBM-bound pass, 16-byte accesses when C * H * W is a multiple of 16 and both buffers are 16-byte aligned. */
+int yogo_image_cache_gather(const unsigned char* cache, int S, const int* slots, int B, int C, int H, int W, void* out, int out_fp32,
+                            yogo_stream_t stream);
+
 /* ---- optimiser: torch.optim.AdamW over one flat buffer, yogo/train.py:213-217,324 ---------------------------------------- */
 int yogo_adamw_step(float* p, const float* g, float* m, float* v, long long n, int step, double lr, double beta1,
                     double beta2, double eps, double weight_decay, double grad_scale, yogo_stream_t stream);

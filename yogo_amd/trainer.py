@@ -185,7 +185,8 @@ class Trainer:
             loaders = get_dataloader(self.dataset_definition, self.config["batch_size"], Sx=self.Sx, Sy=self.Sy,
                                      image_hw=tuple(self.config["image_hw"]), rgb=self.config["rgb"],
                                      normalize_images=self.config["normalize_images"],
-                                     split_fraction_override=self.config["dataset_split_override"], device=self._torch_device())
+                                     split_fraction_override=self.config["dataset_split_override"], device=self._torch_device(),
+                                     device_image_cache_gib=self.config.get("device_image_cache_gib"))
         self.train_dataloader = loaders["train"]
         self.validate_dataloader = loaders.get("val", [])
         self.test_dataloader = loaders.get("test", [])
@@ -390,6 +391,7 @@ def build_config(args) -> dict:
         "pretrained_path": args.from_pretrained,
         "normalize_images": args.normalize_images,
         "dataset_split_override": args.dataset_split_override,
+        "device_image_cache_gib": args.device_image_cache,
         "dataset_descriptor_file": args.dataset_descriptor_file,
         "slurm-job-id": os.getenv("SLURM_JOB_ID", default=None),
         "torch-version": torch.__version__,

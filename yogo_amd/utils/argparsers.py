@@ -4,6 +4,7 @@ is accepted by the parser and answered with an explanation by yogo_amd.__main__.
 from __future__ import annotations
 
 import argparse
+import math
 import os
 from pathlib import Path
 
@@ -49,6 +50,17 @@ def super_unitary_float(val: str) -> float:
         raise argparse.ArgumentTypeError(f"{val} is not a valid float")
     if v < 1:
         raise argparse.ArgumentTypeError(f"{val} must be greater than or equal to 1")
+    return v
+
+
+def positive_gib(val: str) -> float:
+    """a budget in GiB: a finite float > 0 (NaN, 0 and negative values are refused)"""
+    try:
+        v = float(val)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{val} is not a valid float")
+    if not (math.isfinite(v) and v > 0):
+        raise argparse.ArgumentTypeError(f"{val} must be a finite number of GiB greater than 0")
     return v
 
 
@@ -98,6 +110,9 @@ def train_parser(parser=None):
     parser.add_argument("--model", default=None, const=None, nargs="?", choices=list(MODELS.keys()), help="model version to use - do not use with --from-pretrained")
     parser.add_argument("--half", default=False, action=boolean_action,
                         help="half precision (bf16 activations and gradients on the bf16 matrix cores, fp32 master weights) (default: False)")
+    parser.add_argument("--device-image-cache", default=None, type=positive_gib, metavar="GIB",
+                        help="keep decoded images resident in GPU memory within this many GiB per rank: the train split first, the val "
+                             "split gets what is left (default: off)")
     parser.add_argument("--device", default=None, nargs="?", type=str, help="set a device for the run (accepted for compatibility; training uses one rank per visible GPU)")
     parser.add_argument("--note", default=None, type=str, help="note for the run (e.g. 'run on a TI-82')")
     parser.add_argument("--name", default=None, type=str, help="name for the run (e.g. 'ti-82_run')")

@@ -12,6 +12,12 @@ Thumbnail augmentation (``thumbnail_augmentation:`` in the definition, yogo_data
 make a synthetic image: for its indices they hand over the index alone (``BlobIndices``), and ``DeviceLoader`` composes those
 images on the device straight into their rows of the batch (yogo_amd/blobgen.py), with ``epoch = sampler.epoch``.  A
 definition without the key takes exactly the path above.
+
+Device image cache (``device_image_cache_gib``, ``yogo train --device-image-cache GIB``; yogo_amd/image_cache.py): the train
+split, then the val split with what is left of the budget, keeps split indices ``0 .. S-1`` decoded in HBM.  A fully
+resident split starts no worker at all: ``DeviceLoader`` walks the sampler's indices in batches and gathers them on the
+device.  A partially resident one hands the workers a ``ResidentMarkers`` wrapper, and each batch is assembled from uploaded,
+resident and blob rows.  Without a budget nothing of this exists: the same ``DeviceLoader`` path, no allocation, no prefill.
 """
 from __future__ import annotations
 
@@ -26,6 +32,7 @@ from torch.utils.data.distributed import DistributedSampler
 from yogo_amd.blobgen import BlobDataset
 from yogo_amd.data import MultiArgSequential, RandomHorizontalFlipWithBBs, RandomVerticalFlipWithBBs, format_labels_batch
 from yogo_amd.dataset_definition_file import DatasetDefinition, SplitFractions
+from yogo_amd.image_cache import ImageCache, ResidentMarkers, budget_bytes, collate_cached, gather, resident_count
 from yogo_amd.yogo_dataset import ObjectDetectionDataset
 
 SPLIT_SEED = 7271978   # yogo/data/yogo_dataloader.py:176
@@ -147,7 +154,7 @@ class DeviceLoader:
     attributes the training loop touches (``dataset``, ``sampler``, ``batch_size``, ``__len__``)."""
 
     def __init__(self, loader: DataLoader, Sx: int, Sy: int, transforms: MultiArgSequential, device=None, strict_steps: bool = False,
-                 blob: Optional[BlobDataset] = None, dataset: Optional[Dataset] = None):
+                 blob: Optional[BlobDataset] = None, dataset: Optional[Dataset] = None, cache: Optional[ImageCache] = None):
         self.loader, self.Sx, self.Sy, self.transforms, self.device = loader, Sx, Sy, transforms, device
         # strict_steps (the TRAINING split only): every batch is one gradient all-reduce, so a skipped batch must fail loudly
         # under data parallelism; validation / test loaders issue no per-step collective and may skip, as the reference does
@@ -155,6 +162,8 @@ class DeviceLoader:
         # blob: the BlobDataset behind the BlobIndices of a thumbnail-augmented train split (loader.collate_fn = collate_mixed);
         # dataset: the split as get_datasets made it (the loader iterates its worker-side form)
         self.blob = blob
+        # cache: the resident images of the split (loader.dataset = ResidentMarkers, loader.collate_fn = collate_cached)
+        self.cache = cache
         self.dataset = loader.dataset if dataset is None else dataset
         self.sampler, self.batch_size = loader.sampler, loader.batch_size
 
@@ -164,7 +173,9 @@ class DeviceLoader:
     def __iter__(self):
         dev = torch.device(self.device) if self.device is not None else torch.device("cuda", torch.cuda.current_device())
         multi = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
-        for item in self.loader:
+        if self.cache is not None:
+            self.cache.prefill()   # once, before the split's first batch (and before its workers start)
+        for item in (self._resident_batches() if self.cache is not None and self.cache.full else self.loader):
             if item is None:
                 # every sample of the batch was unreadable (the robust collate of yogo/data/utils.py:49-63 returned nothing).  A
                 # single process just skips it; under data parallelism a rank that skips a step issues one gradient all-reduce
@@ -173,7 +184,9 @@ class DeviceLoader:
                     raise RuntimeError("yogo_amd: a whole batch of this rank was unreadable; in a data-parallel run every rank must "
                                        "take the same number of steps (fix or remove the unreadable files)")
                 continue
-            if self.blob is not None:
+            if self.cache is not None:
+                imgs, labels = self._assemble_cached(item, dev)
+            elif self.blob is not None:
                 imgs, labels = self._assemble(item, dev)
             else:
                 imgs, rows = item
@@ -199,10 +212,52 @@ class DeviceLoader:
                 labels.index_copy_(0, torch.tensor(blob_pos, dtype=torch.long).to(dev, non_blocking=True), blob_labels)
         return imgs, labels
 
+    def _resident_batches(self):
+        """the batches of a fully resident split in collate_cached's form, without the host DataLoader: the sampler's indices
+        in chunks of batch_size (the DataLoader's boundaries, drop_last=False)"""
+        order = [int(i) for i in iter(self.sampler)]
+        for k in range(0, len(order), self.batch_size):
+            chunk = order[k:k + self.batch_size]
+            yield None, [], [], chunk, list(range(len(chunk))), [], [], len(chunk)
+
+    def _assemble_cached(self, item, dev: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
+        """a batch of a cached split on the device: uploaded rows with index_copy_, resident rows with one gather launch, blob
+        rows composed; the label rows of all real samples (uploaded and resident, in batch order) rasterised by one launch"""
+        up_imgs, up_rows, up_pos, res_idx, res_pos, blob_idx, blob_pos, B = item
+        cache = self.cache
+        C, H, W = cache.image_shape
+        dtype = torch.float32 if cache.normalize_images else torch.uint8
+        with torch.cuda.device(dev):
+            imgs = torch.empty(B, C, H, W, dtype=dtype, device=dev)
+            if up_pos:
+                imgs.index_copy_(0, torch.tensor(up_pos, dtype=torch.long).to(dev, non_blocking=True),
+                                 up_imgs.to(dev, non_blocking=True).to(dtype))
+            if res_pos:
+                slots = [-1] * B
+                for p, i in zip(res_pos, res_idx):
+                    slots[p] = i
+                gather(cache.images, slots, imgs)
+            rows_at = dict(zip(up_pos, up_rows))
+            rows_at.update((p, cache.label_rows(i)) for p, i in zip(res_pos, res_idx))
+            real_pos = sorted(rows_at)
+            real_labels = format_labels_batch([rows_at[p] for p in real_pos], self.Sx, self.Sy, "cxcywh", device=dev)
+            if not blob_pos:
+                return imgs, real_labels
+            labels = torch.empty(B, 6, self.Sy, self.Sx, dtype=torch.float32, device=dev)
+            if real_pos:
+                labels.index_copy_(0, torch.tensor(real_pos, dtype=torch.long).to(dev, non_blocking=True), real_labels)
+            _, blob_labels, _, _ = self.blob.generate(blob_idx, getattr(self.sampler, "epoch", 0), out_imgs=imgs, positions=blob_pos)
+            labels.index_copy_(0, torch.tensor(blob_pos, dtype=torch.long).to(dev, non_blocking=True), blob_labels)
+        return imgs, labels
+
 
 def get_dataloader(dataset_definition: DatasetDefinition, batch_size: int, Sx: int, Sy: int, training: bool = True,
                    image_hw: Tuple[int, int] = (772, 1032), rgb: bool = False, normalize_images: bool = False,
-                   split_fraction_override: Optional[SplitFractions] = None, device=None) -> Dict[str, DeviceLoader]:
+                   split_fraction_override: Optional[SplitFractions] = None, device=None,
+                   device_image_cache_gib: Optional[float] = None) -> Dict[str, DeviceLoader]:
+    """{split: DeviceLoader}.  device_image_cache_gib: keep decoded images of the train split, then of the val split with what
+    is left, resident in HBM within this many GiB (yogo_amd/image_cache.py); None: no cache."""
+    budget = budget_bytes(device_image_cache_gib) if device_image_cache_gib is not None else None
     split_datasets = get_datasets(dataset_definition, Sx, Sy, rgb=rgb, image_hw=image_hw, normalize_images=normalize_images,
                                   split_fraction_override=split_fraction_override)
     augmentations = [RandomHorizontalFlipWithBBs(0.5), RandomVerticalFlipWithBBs(0.5)] if training else []
@@ -210,29 +265,64 @@ def get_dataloader(dataset_definition: DatasetDefinition, batch_size: int, Sx: i
         rank, world_size = torch.distributed.get_rank(), torch.distributed.get_world_size()
     else:
         rank, world_size = 0, 1
+    # the budget covers the train split first, the val split gets what is left; the test split is read once and never cached
+    image_shape = (3 if rgb else 1, int(image_hw[0]), int(image_hw[1]))
+    resident: Dict[str, int] = {}
+    for designation in ("train", "val"):
+        if budget is not None and designation in split_datasets:
+            resident[designation] = resident_count(budget, _real_len(split_datasets[designation]), *image_shape)
+            budget -= resident[designation] * image_shape[0] * image_shape[1] * image_shape[2]
     d: Dict[str, DeviceLoader] = {}
     for designation, dataset in split_datasets.items():
         if len(dataset) == 0:   # type: ignore[arg-type]
             continue
         augs = augmentations if designation == "train" else []
-        d[designation] = _get_dataloader(dataset, batch_size, augs, rank, world_size, Sx, Sy, device, strict_steps=designation == "train")
+        cache_args = {}
+        if resident.get(designation, 0) > 0:
+            cache_args = dict(resident=resident[designation], image_shape=image_shape, normalize_images=normalize_images,
+                              name=designation, log=rank == 0)
+        d[designation] = _get_dataloader(dataset, batch_size, augs, rank, world_size, Sx, Sy, device, strict_steps=designation == "train",
+                                         **cache_args)
     return d
 
 
+def _real_len(dataset: Dataset) -> int:
+    """the number of real (file-backed) samples of a split: all of it, less the BlobDataset of a thumbnail-augmented one"""
+    if isinstance(dataset, ConcatDataset) and isinstance(dataset.datasets[-1], BlobDataset):
+        return len(dataset) - len(dataset.datasets[-1])
+    return len(dataset)   # type: ignore[arg-type]
+
+
+def _num_workers(dataset_size: int, world_size: int) -> int:
+    num_workers = choose_dataloader_num_workers(dataset_size) // world_size
+    if dataset_size >= 1000:
+        num_workers = max(1, num_workers)
+    return num_workers
+
+
 def _get_dataloader(dataset: Dataset, batch_size: int, augmentations: list, rank: int, world_size: int, Sx: int, Sy: int,
-                    device=None, strict_steps: bool = False) -> DeviceLoader:
+                    device=None, strict_steps: bool = False, resident: int = 0, image_shape: Optional[Tuple[int, int, int]] = None,
+                    normalize_images: bool = False, name: str = "train", log: bool = False) -> DeviceLoader:
+    """resident > 0: split indices 0 .. resident-1 are kept decoded on the device (image_shape = (C, H, W))"""
     blob = dataset.datasets[-1] if isinstance(dataset, ConcatDataset) and isinstance(dataset.datasets[-1], BlobDataset) else None
     # the workers iterate the split with its blob part replaced by the indices alone (same length: same sampler order)
     host_dataset = ConcatDataset([*dataset.datasets[:-1], BlobIndices(len(blob))]) if blob is not None else dataset
     sampler: Iterable = DistributedSampler(host_dataset, rank=rank, num_replicas=world_size)   # torch defaults: shuffle, seed 0, padded
-    num_workers = choose_dataloader_num_workers(len(dataset)) // world_size   # type: ignore[arg-type]
-    if len(dataset) >= 1000:   # type: ignore[arg-type]
-        num_workers = max(1, num_workers)
+    num_workers = _num_workers(len(dataset), world_size)   # type: ignore[arg-type]
+    cache = None
+    collate_fn = collate_rows if blob is None else collate_mixed
+    if resident > 0:
+        # every rank keeps all indices < resident (DistributedSampler hands it different ones every epoch), prefilled by its own
+        # workers; the split's workers see the resident indices as markers
+        cache = ImageCache(dataset, resident, image_shape, normalize_images, device=device, num_workers=num_workers, batch_size=batch_size,
+                           name=name, log=log)
+        host_dataset = ResidentMarkers(host_dataset, cache.resident)
+        collate_fn = collate_cached
     loader = DataLoader(host_dataset, shuffle=False, sampler=sampler, drop_last=False, pin_memory=torch.cuda.is_available(), batch_size=batch_size,
                         num_workers=num_workers, persistent_workers=num_workers > 0, generator=torch.Generator().manual_seed(SPLIT_SEED),
-                        collate_fn=collate_rows if blob is None else collate_mixed, multiprocessing_context="spawn" if num_workers > 0 else None)
+                        collate_fn=collate_fn, multiprocessing_context="spawn" if num_workers > 0 else None)
     return DeviceLoader(loader, Sx, Sy, MultiArgSequential(*augmentations), device, strict_steps=strict_steps, blob=blob,
-                        dataset=dataset if blob is not None else None)
+                        dataset=dataset if blob is not None or cache is not None else None, cache=cache)
 
 
 def get_class_counts(d, num_classes: int, verbose: bool = True) -> torch.Tensor:

@@ -135,6 +135,12 @@ class ObjectDetectionDataset(torch.utils.data.Dataset):
         """the reference's per-sample label tensor [6, Sy, Sx] (rasterised on the device)"""
         return label_file_to_tensor(str(self._label_paths[index]), self.Sx, self.Sy, self.classes, self.notes_data, device=device)
 
+    def image_uint8(self, index: int) -> Optional[torch.Tensor]:
+        """the uint8 image [C, H, W] of sample `index` after resize_image, before normalize_images' / 255 (what the device
+        image cache stores, yogo_amd/image_cache.py); None when the file stays unreadable"""
+        maybe_image = self.loader(str(self._image_paths[index]))
+        return None if maybe_image is None else resize_image(maybe_image, self.image_hw)
+
     def __getitem__(self, index: int) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
         maybe_image = self.loader(str(self._image_paths[index]))
         if maybe_image is None:
