@@ -1,4 +1,5 @@
 """shared helpers for the tests (fixture loading, tolerances)."""
+import contextlib
 import json
 import os
 
@@ -49,9 +50,21 @@ def rel_err(a, b):
 # sit at 0.90 ... 0.99).  The elementwise bounds live in the teacher-forced check further down -- the comment there says why two
 # correct bf16 implementations cannot agree more closely than this END TO END.
 # Round 6: conv_bf16_ws16_kernel sums chunk PAIRS inside one MFMA (another fp32 summation order for the plain-epilogue 128-channel
-# launches); the per-kernel bounds of the teacher-forced check did not move, the end-to-end loss of one architecture point
-# (depth_ver_3 at 130x70: 1.04e-3) now sits just outside the old 1e-3 -- a statistical bound, see above -- so it is 1.5e-3.
-BF16_STEP_LOSS_RTOL = 1.5e-3
+# launches); the per-kernel bounds of the teacher-forced check did not move, the end-to-end loss of ONE architecture point
+# (depth_ver_3 at 130x70 rgb B=1: 1.04e-3, test_gpu_bf16.py::test_bf16_training_other_architectures) sits just outside 1e-3 -- a
+# statistical bound, see above.  The global bound stays 1e-3; that point alone is held to 1.5e-3, by name (step_loss_rtol below).
+# Which of ws16 / the layer-0/1 sweep / the head fusion moved it has not been bisected (depth_ver_3 reaches neither fusion: its
+# layer 1 follows a 3-channel image and no BatchNorm sits under its head, which leaves ws16).
+BF16_STEP_LOSS_RTOL = 1e-3
+BF16_STEP_LOSS_RTOL_EXCEPTIONS = {("depth_ver_3", 130, 70): 1.5e-3}   # (architecture, H, W) -> bound; measured 1.04e-3 (round 6), 8.9e-4 (this suite's run)
+# every other point of test_bf16_training_other_architectures and of the 772x1032 tests passes at 1e-3 (pytest -s -m gpu tests/test_gpu_bf16.py -k other_arch)
+
+
+def step_loss_rtol(name, H, W):
+    """the end-to-end loss bound of one (architecture, image size) point: 1e-3 unless it is a named exception"""
+    return BF16_STEP_LOSS_RTOL_EXCEPTIONS.get((name, H, W), BF16_STEP_LOSS_RTOL)
+
+
 BF16_STEP_COS_MIN = 0.995
 
 
@@ -99,6 +112,12 @@ def assert_grads_match_bf16_oracle(got, want, what, cos_min=BF16_STEP_COS_MIN, v
 #     cancellation, and at most 0.2 % of the elements differing at all (measured, 772x1032 and ten other shapes: <= 2.7e-4);
 #   BatchNorm statistics 1e-5; parameter gradients 5e-5 of the tensor's maximum (measured <= 6e-6; layer 0: 5e-4, its sums cancel
 #     ~1000-fold).
+# Under the product's fused plan the tensor between two layers may not exist (layer 0's g under the layer-0/1 sweep, the g of the block
+# under the head under the head fusion); the chain is then continued with the oracle's own data gradient, which differs from the kernel's
+# internal one in a few bf16 roundings.  The same constants hold there, measured (772x1032, B = 2, pytest -s -m gpu
+# tests/test_gpu_production_shapes.py -k vs_cpu_oracle): layer 0 dW 3.5e-5 / dgamma 1.7e-5 / dbeta 3.0e-5 of max|g| against 4.4e-7 / 3.5e-7 /
+# 9.3e-8 when layer 0 is fed the step's own g (unfused plan) -- inside TF_GRAD_RTOL_L0 = 5e-4, so no flip-aware bound was needed;
+# depth_ver_0's fused head backward: dz 4 of 49152 elements differ, none beyond one ulp; dgamma / dbeta 6e-8 / 1e-7.
 TF_ULP = 2.0 ** -7
 TF_FLOOR = 8e-6
 TF_FLIP_FRAC = 2e-3
@@ -128,7 +147,14 @@ def assert_bf16_tensor_matches(got, want, what):
 def teacher_forced_bf16_step_check(O, tr, model, x, lab, spec, sd0, what):
     """``tr``: a HipTrainer(half=True) whose LAST step ran with ``tr.trace = {}`` on (x, lab) from the state ``sd0``.  Checks every
     stored tensor / statistic / parameter gradient of that step against oracle/yogo_oracle.py's per-block emulation fed with the
-    step's own tensors (see the comment above for the bounds)."""
+    step's own tensors (see the comment above for the bounds).  = the forward half, then the backward half."""
+    rec = teacher_forced_forward_check(O, tr, model, x, lab, spec, sd0, what)
+    return teacher_forced_backward_check(O, tr, model, x, lab, spec, sd0, what, rec)
+
+
+def teacher_forced_forward_check(O, tr, model, x, lab, spec, sd0, what):
+    """the forward half: every stored tensor and BatchNorm statistic of the step's forward pass.  Returns the per-block records
+    (holding the step's OWN stored tensors) that the backward half chains from."""
     tc = tr.trace
     saved, raw = tc["saved"], tc["raw"]
     n = len(spec)
@@ -176,6 +202,36 @@ def teacher_forced_bf16_step_check(O, tr, model, x, lab, spec, sd0, what):
                 assert_bf16_tensor_matches(from8c_cpu(Sv.pre, co), S["pre"], f"L{i} pre-activation")
                 S["pre"] = from8c_cpu(Sv.pre, co)
         rec.append(S)
+    return rec
+
+
+def assert_same_forward_trace(tc_a, tc_b, what):
+    """two steps from the same state on the same batch under two BACKWARD plans: everything the forward pass stored is the same
+    bits, so the forward half of the teacher-forced check (and its CPU oracle) is paid once"""
+    assert torch.equal(tc_a["raw"], tc_b["raw"]), (what, "head output")
+    assert len(tc_a["saved"]) == len(tc_b["saved"])
+    for i, (a, b) in enumerate(zip(tc_a["saved"], tc_b["saved"])):
+        for f in ("x_in", "y", "z", "pre", "mean", "invstd", "mask", "signs0", "signs", "w_used", "gram"):
+            ta, tb = getattr(a, f, None), getattr(b, f, None)
+            assert (ta is None) == (tb is None), (what, i, f)
+            if ta is not None:
+                assert torch.equal(ta, tb), (what, "forward differs between the two backward plans", i, f)
+
+
+def teacher_forced_backward_check(O, tr, model, x, lab, spec, sd0, what, rec):
+    """the backward half, from the forward records ``rec``: loss, head gradient, every BatchNorm-backward output, data gradient and
+    parameter gradient.  A fused kernel keeps the tensor between two layers in registers, so the trace has no ("g", i) for it (layer
+    0 under the layer-0/1 sweep, the block under the head under the head fusion): the chain then CONTINUES with the oracle's own
+    data gradient of the layer above, and everything the fused kernel does write (layer 0's dW / dgamma / dbeta, the block's dz /
+    dgamma / dbeta / dW) is held to the same constants as on the unfused plan.  Only the comparison of the tensor that does not
+    exist is skipped, and that is printed.  Returns the set of layers whose g was continued."""
+    tc = tr.trace
+    saved = tc["saved"]
+    n = len(spec)
+    L = tr.loss
+    l0_mfma = O.l0_on_matrix_cores(spec, x)
+    clip = float(model._clip)
+    print(f"[teacher-forced backward {what}]")
     # ---- loss and head gradient from the step's own head output
     loss_e, comps_e, g_e, _ = O.bf16_head_gradient(rec[-1]["y"], sd0, lab, float(model.anchor_w), float(model.anchor_h),
                                                    float(L.no_obj_weight), float(L.iou_weight), float(L.classify_weight), float(L.label_smoothing))
@@ -196,9 +252,17 @@ def teacher_forced_bf16_step_check(O, tr, model, x, lab, spec, sd0, what):
         print(f"   grad {name:24s} max|d|/max|g| {err / (gmax + 1e-30):.2e}")
         assert err <= rtol * gmax + atol + 1e-9, (what, name, err, gmax, atol)
 
+    continued = set()
+    dx_above = None   # the oracle's bf16 data gradient of layer i + 1
     for i in range(n - 1, -1, -1):
         co, k, s, hb, hbn, act, dp = spec[i]
-        g_in = from8c_cpu(tc[("g", i)], co)
+        if ("g", i) in tc:
+            g_in = from8c_cpu(tc[("g", i)], co)
+        else:
+            assert i < n - 1 and dx_above is not None, (what, i, "the step recorded no head gradient")
+            print(f"   L{i} g: not written by this plan (fused into the kernel below it) -- chain continued with the oracle's data gradient of L{i + 1}")
+            g_in = dx_above
+            continued.add(i)
         hdz = from8c_cpu(tc[("dz", i)], co) if ("dz", i) in tc else None
         # (the weight / bias / data gradients of a BatchNorm block are formed from the step's OWN dz, which is checked first)
         r = O.bf16_block_backward(i, g_in, rec[i], rec[i - 1] if i > 0 else None, spec, l0_mfma, dz_given=hdz,
@@ -215,7 +279,89 @@ def teacher_forced_bf16_step_check(O, tr, model, x, lab, spec, sd0, what):
             check_grad(f"model.{i}.1.weight", r["dgamma"], rt)
             check_grad(f"model.{i}.1.bias", r["dbeta"], rt)
         if i > 0:
-            assert_bf16_tensor_matches(from8c_cpu(tc[("g", i - 1)], spec[i - 1][0]), r["dx"], f"L{i - 1} g = bf16(data gradient of L{i})")
+            dx_above = r["dx"]
+            if ("g", i - 1) in tc:
+                assert_bf16_tensor_matches(from8c_cpu(tc[("g", i - 1)], spec[i - 1][0]), r["dx"], f"L{i - 1} g = bf16(data gradient of L{i})")
+    return continued
+
+
+# ---- the two backward plans -------------------------------------------------------------------------------------------------------
+# The product folds two tensors into the kernels around them (engine._L01_FUSE_BWD: layer 0's g, conv_first_fused_bwd.hip;
+# engine._HEAD_BN_FUSE: the g of the BatchNorm block under the 1x1 head, bn.hip: yogo_bn_bwd_bf16_head).  A trace records the plan that
+# runs, so the teacher-forced check runs for BOTH: the unfused plan (every tensor exists and is compared) and the product's.
+FUSED_L01_KERNEL = "conv_bf16_dgrad_first_bwd_kernel"
+FUSED_HEAD_KERNEL = "bn_bwd_apply_head_kernel"
+
+
+def expected_fused_kernels(O, spec, x):
+    """which fused backward kernels the product's plan MUST launch for this (architecture, batch), stated from the architecture table
+    and the shape rules of the two kernels (conv_first_fused_bwd.hip: df_shape_ok -- 16 -> 32 channels, even plane width; bn.hip:
+    yogo_bn_bwd_bf16_head -- 9..16 head channels over a BatchNorm block of a multiple of 16 channels that is not layer 0) -- NOT
+    from what the engine did: a planner that silently falls back fails the launch-log assertion of teacher_forced_both_plans"""
+    n = len(spec)
+    exp = {}
+    co0, k0, s0, hb0, hbn0, act0, dp0 = spec[0]
+    co1, k1, s1 = spec[1][:3]
+    W = int(x.shape[-1])
+    if (O.l0_keeps_no_z(spec, O.l0_on_matrix_cores(spec, x)) and co0 == 16 and n > 2 and co1 == 32 and k1 == 3 and s1 == 1 and dp0 == 0
+            and (W // 2) % 2 == 0):
+        exp[FUSED_L01_KERNEL] = 0
+    P = spec[-1][0]
+    cu, ku, su, hbu, hbnu = spec[n - 2][:5]
+    if hbnu and n - 2 > 0 and cu % 16 == 0 and spec[-1][1] == 1 and spec[-1][2] == 1 and 8 < P <= 16:
+        exp[FUSED_HEAD_KERNEL] = n - 2
+    return exp   # kernel -> the layer whose g it keeps in registers
+
+
+@contextlib.contextmanager
+def backward_plan(fused):
+    """the product's backward plan (fused=True: the module defaults) or the plan with both fusions off"""
+    from yogo_amd import engine
+
+    prev = (engine._L01_FUSE_BWD, engine._HEAD_BN_FUSE)
+    assert prev == (True, True), ("a test left the engine's plan flags changed", prev)
+    engine._L01_FUSE_BWD = engine._HEAD_BN_FUSE = bool(fused)
+    try:
+        yield
+    finally:
+        engine._L01_FUSE_BWD, engine._HEAD_BN_FUSE = prev
+
+
+def teacher_forced_both_plans(O, run_step, x, lab, spec, sd0, what):
+    """``run_step()`` -> (tr, model): a fresh model in state ``sd0`` and a HipTrainer(half=True) that has run ONE step on (x, lab)
+    with ``tr.trace = {}`` (synchronised).  Runs it under the unfused plan and under the product's plan; the forward halves of the two
+    traces must be the same bits (checked against the oracle once), the backward half is checked for each.  Under the product's plan
+    the launch log must show every fused kernel this architecture is entitled to, and the trace must lack exactly the tensors those
+    kernels keep in registers.  Returns the product plan's (tr, model)."""
+    from yogo_amd import _hip
+
+    expect = expected_fused_kernels(O, spec, x)
+    rec = None
+    if expect:
+        with backward_plan(False):
+            tr_u, m_u = run_step()
+        rec = teacher_forced_forward_check(O, tr_u, m_u, x, lab, spec, sd0, what)
+        cont = teacher_forced_backward_check(O, tr_u, m_u, x, lab, spec, sd0, what + " [unfused plan]", rec)
+        assert not cont, (what, "the unfused plan left no trace of g at layers", sorted(cont))
+    _hip.launch_log(True)
+    try:
+        tr, m = run_step()
+    finally:
+        _hip.launch_log(False)
+    launched = {ln.split("|")[0].split("<")[0].strip() for ln in _hip.read_launch_log()}
+    for kname in sorted(expect):
+        assert kname in launched, (f"{what}: the product's plan must run {kname} here, and it is not in the launch log of the traced "
+                                   f"step (a trace must not change the plan): {sorted(launched)}")
+    for kname in (FUSED_L01_KERNEL, FUSED_HEAD_KERNEL):
+        assert kname in expect or kname not in launched, (what, kname, "launched where expected_fused_kernels() does not expect it")
+    if rec is None:
+        rec = teacher_forced_forward_check(O, tr, m, x, lab, spec, sd0, what)
+    else:
+        assert_same_forward_trace(tr_u.trace, tr.trace, what)
+        del tr_u, m_u
+    cont = teacher_forced_backward_check(O, tr, m, x, lab, spec, sd0, what + " [product plan]", rec)
+    assert cont == set(expect.values()), (what, "layers whose g the trace lacks", sorted(cont), "expected", sorted(expect.values()))
+    return tr, m
 
 
 # ---- the test-hooks library ------------------------------------------------------------------------------------------------------
@@ -224,9 +370,6 @@ def teacher_forced_bf16_step_check(O, tr, model, x, lab, spec, sd0, what):
 # yogo_hook_conv_first_bn_wgrad_pairs / yogo_hook_conv_bf16_direct (0 = the tiled kernel in place of the direct stride-2 data gradients).
 # The product library has no such switch (no mutable global state); A/B and bit-identity tests bind the hooks library in place of the
 # product's for their duration.
-import contextlib
-
-
 @contextlib.contextmanager
 def hooks_library():
     import ctypes

@@ -103,7 +103,9 @@ class _Obj:
         self.__dict__.update(kw)
 
 
-def _mock_step(name, H, W, C=5, B=2):
+def _mock_step(name, H, W, C=5, B=2, drop_g=()):
+    """``drop_g``: layers whose ("g", i) the mock trace lacks -- the shape of a trace under the product's fused plan (layer 0 under
+    the layer-0/1 sweep, the block under the head under the head fusion)"""
     spec = O.arch(name, C)
     sd = O.init_state(spec, 1, seed=4)
     x = O.synthetic_images(B, H, W, seed=8)
@@ -122,7 +124,8 @@ def _mock_step(name, H, W, C=5, B=2):
                           pre=_to8c(S["pre"]) if S.get("pre") is not None else None))
     trace = {"saved": saved, "raw": taps[f"y{n - 1}"]}
     for i in range(n):
-        trace[("g", i)] = _to8c(taps[f"g{i}"])
+        if i not in drop_g:
+            trace[("g", i)] = _to8c(taps[f"g{i}"])
         if f"dz{i}" in taps:
             trace[("dz", i)] = _to8c(taps[f"dz{i}"])
     order = [k for k in sd if k in grads]   # state-dict order == named_parameters order
@@ -134,12 +137,105 @@ def _mock_step(name, H, W, C=5, B=2):
     return tr, model, x, lab, spec, sd
 
 
-@pytest.mark.parametrize("name,H,W", [("base_model", 64, 96), ("silu_model", 48, 64), ("depth_ver_3", 49, 67)])
+@pytest.mark.parametrize("name,H,W", [("base_model", 64, 96), ("silu_model", 48, 64), ("depth_ver_3", 49, 67), ("depth_ver_0", 96, 128),
+                                      ("depth_ver_0", 100, 132)])
 def test_teacher_forced_checker_accepts_the_emulation(name, H, W):
     from _util import teacher_forced_bf16_step_check
 
     tr, model, x, lab, spec, sd = _mock_step(name, H, W)
-    teacher_forced_bf16_step_check(O, tr, model, x, lab, spec, sd, name)
+    assert teacher_forced_bf16_step_check(O, tr, model, x, lab, spec, sd, name) == set()
+
+
+# the trace of the product's plan: a fused kernel keeps the tensor between two layers in registers, so its ("g", i) does not exist and
+# the checker continues the chain with the oracle's own data gradient of the layer above (tests/_util.py)
+_FUSED_TRACES = [("base_model", 64, 96, (0,)), ("depth_ver_0", 96, 128, (2,)), ("depth_ver_0", 100, 132, (2,)), ("depth_ver_3", 64, 96, (0,))]
+
+
+@pytest.mark.parametrize("name,H,W,drop_g", _FUSED_TRACES)
+def test_teacher_forced_checker_accepts_a_fused_plan_trace(name, H, W, drop_g, capsys):
+    from _util import expected_fused_kernels, teacher_forced_bf16_step_check
+
+    tr, model, x, lab, spec, sd = _mock_step(name, H, W, drop_g=drop_g)
+    assert set(expected_fused_kernels(O, spec, x).values()) == set(drop_g)   # (the architectures whose product plan has this shape of trace)
+    assert teacher_forced_bf16_step_check(O, tr, model, x, lab, spec, sd, name) == set(drop_g)
+    out = capsys.readouterr().out
+    for i in drop_g:
+        assert f"L{i} g: not written by this plan" in out   # the continuation is said, not silent
+
+
+def test_expected_fused_kernels_follow_the_architecture_table():
+    from _util import FUSED_HEAD_KERNEL, FUSED_L01_KERNEL, expected_fused_kernels
+
+    def exp(name, H, W, rgb=False):
+        x = torch.zeros(2, 3 if rgb else 1, H, W, dtype=torch.uint8)
+        return expected_fused_kernels(O, O.arch(name, 5), x)
+
+    assert exp("base_model", 772, 1032) == {FUSED_L01_KERNEL: 0}
+    assert exp("base_model", 97, 131) == {} and exp("base_model", 96, 130) == {}     # odd sizes / odd plane width: the unfused pair
+    assert exp("silu_model", 96, 128) == {} and exp("quarter_filters", 96, 128) == {} and exp("depth_ver_3", 130, 70, True) == {}
+    assert exp("depth_ver_0", 96, 128) == {FUSED_HEAD_KERNEL: 2}
+
+
+@pytest.mark.parametrize("what", ["dW0", "dW1", "dz4", "dgamma0", "dW0-small"])
+def test_teacher_forced_checker_rejects_a_wrong_value_under_a_continued_chain(what):
+    """the trace without ("g", 0) (base_model under the layer-0/1 sweep): what the fused kernels DO produce stays checked"""
+    from _util import TF_GRAD_RTOL_L0, teacher_forced_bf16_step_check
+
+    tr, model, x, lab, spec, sd = _mock_step("base_model", 64, 96, drop_g=(0,))
+    sizes = [(k, p.numel()) for k, p in model.named_parameters()]
+
+    def bump_grad(name, frac):
+        off = 0
+        for k, nel in sizes:
+            if k == name:
+                g = tr.flat.grad[off:off + nel]
+                g[int(g.abs().argmin())] += frac * float(g.abs().max())
+                return
+            off += nel
+        raise KeyError(name)
+
+    if what == "dW0":
+        bump_grad("model.0.0.weight", 1e-2)
+    elif what == "dW0-small":   # just outside layer 0's bound: the continued chain did not loosen it
+        bump_grad("model.0.0.weight", 2 * TF_GRAD_RTOL_L0)
+    elif what == "dW1":
+        bump_grad("model.1.0.weight", 1e-3)
+    elif what == "dgamma0":
+        bump_grad("model.0.1.weight", 1e-2)
+    else:
+        t = tr.trace[("dz", 4)]
+        f = t.float()
+        idx = int(f.abs().reshape(-1).argmax())
+        t.view(-1)[idx] = (f.reshape(-1)[idx] * (1 + 2.0 ** -6)).to(t.dtype)
+    with pytest.raises(AssertionError):
+        teacher_forced_bf16_step_check(O, tr, model, x, lab, spec, sd, what)
+
+
+@pytest.mark.parametrize("what", ["dz2", "dgamma2", "dW2", "dW3"])
+def test_teacher_forced_checker_rejects_a_wrong_value_under_the_head_fusion_trace(what):
+    """depth_ver_0 without the g of the block under the head: the fused BatchNorm backward's dz / dgamma / dbeta, that block's weight
+    gradient (formed from the step's own dz) and the head's weight gradient stay checked"""
+    from _util import teacher_forced_bf16_step_check
+
+    tr, model, x, lab, spec, sd = _mock_step("depth_ver_0", 96, 128, drop_g=(2,))
+    names = {"dgamma2": "model.2.1.weight", "dW2": "model.2.0.weight", "dW3": "model.3.weight"}
+    if what == "dz2":
+        t = tr.trace[("dz", 2)]
+        f = t.float()
+        idx = int(f.abs().reshape(-1).argmax())
+        t.view(-1)[idx] = (f.reshape(-1)[idx] * (1 + 2.0 ** -6)).to(t.dtype)
+    else:
+        off = 0
+        for k, p in model.named_parameters():
+            if k == names[what]:
+                g = tr.flat.grad[off:off + p.numel()]
+                g[int(g.abs().argmin())] += 1e-3 * float(g.abs().max())
+                break
+            off += p.numel()
+        else:
+            raise KeyError(names[what])
+    with pytest.raises(AssertionError):
+        teacher_forced_bf16_step_check(O, tr, model, x, lab, spec, sd, what)
 
 
 @pytest.mark.parametrize("what", ["y3", "dz4", "g2", "grad", "mean"])

@@ -1,6 +1,8 @@
 """Layer 1's data gradient folded into layer 0's backward sums (yogo_conv2d_dgrad_bf16_first_bwd, conv_first_fused_bwd.hip) against
 (a) a CPU fp64 restatement of what the unfused pair computes and (b) the unfused pair itself (yogo_conv2d_dgrad_bf16 +
 yogo_conv_first_bn_wgrad_bf16_xs), and the training step with and without it.  Reference: autograd of yogo/model_defns.py:34-41."""
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -26,23 +28,6 @@ def _sign_bits(signs_u8, H, W):
             out[:, 4 * h + i] = ((s[..., h] >> i) & 1).bool()
             out[:, 8 + 4 * h + i] = ((s[..., h] >> (4 + i)) & 1).bool()
     return out
-
-
-def _cpu_sums(g, w, img, signs_u8, leaky):
-    """fp64: dy = conv_transpose(g, bf16(w)) rounded to bf16; gb = dy * (sign ? 1 : 0.01); A1[c][j] = sum gb[c] patch_j, S1[c] = sum gb[c]"""
-    B, _, H, W = g.shape
-    wb = w.to(torch.bfloat16).double()
-    dy = F.conv_transpose2d(g.double(), wb, padding=1)
-    dyb = dy.float().to(torch.bfloat16).double()
-    if leaky:
-        pos = _sign_bits(signs_u8, H, W)
-        gb = dyb * torch.where(pos, torch.tensor(1.0, dtype=torch.float64), torch.tensor(float(np.float32(0.01)), dtype=torch.float64))
-    else:
-        gb = dyb
-    patches = F.unfold(img.double(), 3, padding=1, stride=2).reshape(B, 9, H * W)
-    A1 = torch.einsum("bcp,bjp->cj", gb.reshape(B, 16, H * W), patches)
-    S1 = gb.sum((0, 2, 3))
-    return A1, S1, dy
 
 
 def _run_pair(h, g8, pk, img, signs, B, H, W, act0, fused, x8=None, clip=0.0):
@@ -76,55 +61,241 @@ def _run_pair(h, g8, pk, img, signs, B, H, W, act0, fused, x8=None, clip=0.0):
     return (s[:, :NJ].double(), s[:, 2 * NJ].double()) + tuple(t.cpu().double() for t in extra)
 
 
-@pytest.mark.parametrize("B,H,W,act0", [(2, 37, 70, 1), (3, 64, 96, 1), (1, 9, 34, 1), (2, 21, 30, 0), (2, 4, 2, 1), (2, 386, 516, 1)])
-def test_fused_sweep_against_cpu_and_the_unfused_pair(B, H, W, act0):
-    from yogo_amd import _hip as h
+# ---- references ---------------------------------------------------------------------------------------------------------------
+LEAKY32 = float(np.float32(0.01))
+U24, U23 = 2.0 ** -24, 2.0 ** -23
 
-    assert h.lib().yogo_conv2d_dgrad_first_bwd_supported(16, 32, H, W, B, act0) == 1
-    gen = torch.Generator().manual_seed(1000 * H + W)
-    g = (torch.randn(B, 32, H, W, generator=gen) * 0.5).to(torch.bfloat16).float()
-    w = torch.randn(32, 16, 3, 3, generator=gen) * 0.1
+
+def _ref64(g, w, img, signs_u8, leaky):
+    """fp64, image by image (no size gate: the production plane 386 x 516 has its independent reference too):
+    dy = conv_transpose(g, bf16(w)), dyb = bf16(dy), gb = dyb * (sign ? 1 : float32(0.01)); A1[c][j] = sum gb[c] patch_j, S1[c] = sum gb[c],
+    and the sums of MAGNITUDES absA1 / absS1 (the scale of every rounding bound below).  Returns a dict; dy / dyb / gb are [B][16][H][W]."""
+    B, _, H, W = g.shape
+    wb = w.to(torch.bfloat16).double()
+    A1 = torch.zeros(16, 9, dtype=torch.float64)
+    S1 = torch.zeros(16, dtype=torch.float64)
+    absA1, absS1 = torch.zeros_like(A1), torch.zeros_like(S1)
+    dys, dybs, gbs, pts = [], [], [], []
+    pos = _sign_bits(signs_u8, H, W) if leaky else None
+    for b in range(B):
+        dy = F.conv_transpose2d(g[b:b + 1].double(), wb, padding=1)
+        dyb = dy.float().to(torch.bfloat16).double()
+        gb = dyb * torch.where(pos[b:b + 1], 1.0, LEAKY32).double() if leaky else dyb
+        pt = F.unfold(img[b:b + 1].double(), 3, padding=1, stride=2).reshape(9, H * W)
+        gf = gb.reshape(16, H * W)
+        A1 += gf @ pt.t()
+        S1 += gf.sum(1)
+        absA1 += gf.abs() @ pt.t()
+        absS1 += gf.abs().sum(1)
+        dys.append(dy), dybs.append(dyb), gbs.append(gb), pts.append(pt.reshape(1, 9, H, W))
+    return dict(A1=A1, S1=S1, absA1=absA1, absS1=absS1, dy=torch.cat(dys), dyb=torch.cat(dybs), gb=torch.cat(gbs), patch=torch.cat(pts))
+
+
+def _fp32_restatement_error(g, w, img, signs_u8, leaky, ref, orders=8):
+    """e_ref: what a CORRECT fp32 implementation is off by against fp64 on these inputs -- the plain restatement in fp32 (convolution,
+    bf16 rounding, products, sums) with the 32 gradient channels summed in ``orders`` different orders (order 0 = as given).  It differs
+    from fp64 mainly through the few dy that round to the other bf16 neighbour.  Returns (largest |A1 error|, largest |S1 error|)."""
+    B, _, H, W = g.shape
+    wb = w.to(torch.bfloat16).float()
+    pos = _sign_bits(signs_u8, H, W) if leaky else None
+    eA = eS = 0.0
+    for k in range(orders):
+        perm = torch.arange(32) if k == 0 else torch.randperm(32, generator=torch.Generator().manual_seed(k))
+        A1 = torch.zeros(16, 9)
+        S1 = torch.zeros(16)
+        for b in range(B):
+            dyb = F.conv_transpose2d(g[b:b + 1, perm], wb[perm], padding=1).to(torch.bfloat16).float()
+            gb = dyb * torch.where(pos[b:b + 1], 1.0, LEAKY32) if leaky else dyb
+            pt = F.unfold(img[b:b + 1].float(), 3, padding=1, stride=2).reshape(9, H * W)
+            A1 += gb.reshape(16, H * W) @ pt.t()
+            S1 += gb.reshape(16, H * W).sum(1)
+        eA = max(eA, float((A1.double() - ref["A1"]).abs().max()))
+        eS = max(eS, float((S1.double() - ref["S1"]).abs().max()))
+    return eA, eS
+
+
+def _chain_bounds(ref, fused_logs):
+    """The longest fp32 accumulation chains of the kernels, as sums of MAGNITUDES on this input (max over the 16 x 9 elements):
+      fused (conv_first_fused_bwd.hip): a wavefront keeps ONE accumulator pair (d2p, d2n) for the whole launch: every segment it walks
+        (ceil(ceil(nsegs / 8) / (grid / 8 * NWV)) of them), ``seg`` tiles each, a tile = R rows x 32 pixels -- R, NWV, nsegs, seg and grid
+        are read from the kernel's launch-log line, so the bound follows the plan the launch really had;
+      unfused (conv_first.hip: conv_first_bn_wgrad_pk2_kernel): one workgroup = one partial row = CF_THREADS * CFW_PPT = 8192
+        consecutive pixels of one image.
+    Where every term is an integer and the chain's sum of magnitudes is below 2^24, every partial sum is an exactly representable integer
+    whatever the order: the kernel must then agree with fp64 up to its final fp32 store.
+    Measured margins with g one quarter non-zero (`python -m pytest -s -m gpu tests/test_gpu_first_fused_bwd.py -k exact`, 256 CUs): at
+    (2, 386, 516) the fused sweep walks 2 tiles per wavefront, chain 3.8e5 = 2^24 / 44 (with the weight gradient 2.7e5 = 2^24 / 63); the
+    unfused kernel's 8192-pixel chain is the long one, 6.1e6 = 2^24 / 2.7 -- the density of g is chosen for it."""
+    a, pt = ref["gb"].abs(), ref["patch"]
+    B, _, H, W = a.shape
+    out = {}
+    for ln in fused_logs:
+        mm = re.match(r"conv_bf16_dgrad_first_bwd_kernel<(\d+), (\d+), (\w+)> \|.* segments=(\d+) of (\d+) tiles grid=(\d+)", ln)
+        assert mm, ln
+        R, nwv, wg, nsegs, seg, grid = int(mm[1]), int(mm[2]), mm[3] == "true", int(mm[4]), int(mm[5]), int(mm[6])
+        tiles = -(-(-(-nsegs // 8)) // (grid // 8 * nwv)) * seg
+        Hp, Wp = -(-H // R) * R, -(-W // 32) * 32
+        ap = F.pad(a, (0, Wp - W, 0, Hp - H)).reshape(B, 16, Hp // R, R, Wp // 32, 32)
+        pp = F.pad(pt, (0, Wp - W, 0, Hp - H)).reshape(B, 9, Hp // R, R, Wp // 32, 32)
+        per_tile = float(torch.einsum("bcyrxp,bjyrxp->byxcj", ap, pp).max())
+        out["fused_wg" if wg else "fused"] = (tiles * per_tile, f"R={R} tiles/wavefront={tiles} max tile sum|terms|={per_tile:.3g}")
+    n = 8192
+    P = H * W
+    Pp = -(-P // n) * n
+    ap = F.pad(a.reshape(B, 16, P), (0, Pp - P)).reshape(B, 16, Pp // n, n)
+    pp = F.pad(pt.reshape(B, 9, P), (0, Pp - P)).reshape(B, 9, Pp // n, n)
+    per_chunk = float(torch.einsum("bckp,bjkp->bkcj", ap, pp).max())
+    out["unfused"] = (per_chunk, f"8192-pixel workgroup, max sum|terms|={per_chunk:.3g}")
+    return out
+
+
+def _inputs(B, H, W, seed, exact, density=0.25):
+    gen = torch.Generator().manual_seed(seed)
+    if exact:   # g, w, x in {-1, 0, 1}: every dy is a small integer (exactly a bf16 value), every product dy * pixel and g * x an integer
+        g = torch.randint(-1, 2, (B, 32, H, W), generator=gen).float() * (torch.rand(B, 32, H, W, generator=gen) < density * 1.5).float()
+        w = torch.randint(-1, 2, (32, 16, 3, 3), generator=gen).float()
+        x = torch.randint(-1, 2, (B, 16, H, W), generator=gen).float()
+    else:
+        g = (torch.randn(B, 32, H, W, generator=gen) * 0.5).to(torch.bfloat16).float()
+        w = torch.randn(32, 16, 3, 3, generator=gen) * 0.1
+        x = (torch.randn(B, 16, H, W, generator=gen)).to(torch.bfloat16).float()
     img = torch.randint(0, 256, (B, 1, 2 * H, 2 * W), generator=gen, dtype=torch.uint8)
     signs = torch.randint(0, 256, (B, H * W * 2), generator=gen, dtype=torch.uint8)
+    return g, w, x, img, signs
+
+
+def _run_all(h, g, w, x, img, signs, act0):
+    """both fused entry points, the unfused pair and the stand-alone weight-gradient kernel on the same inputs; the fused launches' log lines"""
+    B, _, H, W = g.shape
     st = h.stream_ptr()
     pk = torch.empty(h.query_size("yogo_conv_bf16_packed_bytes", 16, 32, 3, 1), dtype=torch.uint8, device="cuda")
     h.call("yogo_conv_bf16_pack", w.cuda(), None, pk, 16, 32, 3, 1, st)
-    g8, imgc, sgc = _to8c(g).cuda(), img.cuda(), signs.cuda()
-    A1f, S1f = _run_pair(h, g8, pk, imgc, sgc, B, H, W, act0, 1)
-    A1u, S1u = _run_pair(h, g8, pk, imgc, sgc, B, H, W, act0, 0)
-    # ... and with layer 1's weight gradient in the same sweep: the same sums (another tile height: another summation order), dw / db against
-    # the weight-gradient kernel and fp64
-    x = (torch.randn(B, 16, H, W, generator=gen)).to(torch.bfloat16).float()
-    x8 = _to8c(x).cuda()
-    A1w, S1w, dw, db = _run_pair(h, g8, pk, imgc, sgc, B, H, W, act0, 2, x8=x8)
-    dwu = torch.full((32, 16, 3, 3), float("nan"), dtype=torch.float32, device="cuda")
-    dbu = torch.full((32,), float("nan"), dtype=torch.float32, device="cuda")
-    wsu = torch.empty(h.query_size("yogo_conv2d_wgrad_bf16_workspace_bytes", B, 16, 32, H, W, 3, 1) // 4, dtype=torch.float32, device="cuda")
-    h.call("yogo_conv2d_wgrad_bf16", x8, g8, dwu, dbu, wsu, B, 16, 32, H, W, 3, 1, 0.0, st)
-    torch.cuda.synchronize()
-    dwu, dbu = dwu.cpu().double(), dbu.cpu().double()
-    # products of bf16 values are exact, both kernels sum them in fp32 (in different orders) and reduce the partial sums in double
-    assert float((dw - dwu).abs().max()) < 1e-4 * float(dwu.abs().max()) + 1e-5, (float((dw - dwu).abs().max()), float(dwu.abs().max()))
-    assert float((db - dbu).abs().max()) < 1e-4 * float(dbu.abs().max()) + 1e-5, (float((db - dbu).abs().max()), float(dbu.abs().max()))
-    if B * H * W <= 40000:
-        dw64 = torch.nn.grad.conv2d_weight(x.double(), (32, 16, 3, 3), g.double(), padding=1)
-        assert float((dw - dw64).abs().max()) < 1e-4 * float(dw64.abs().max()) + 1e-5
-        assert float((db - g.double().sum((0, 2, 3))).abs().max()) < 1e-4 * float(g.double().sum((0, 2, 3)).abs().max()) + 1e-4
-    assert float((A1w - A1u).abs().max()) < 4e-3 * float(A1u.abs().max()) + 1e-3
-    assert float((S1w - S1u).abs().max()) < 4e-3 * float(S1u.abs().max()) + 1e-3
-    # fused against unfused: the same elements, another summation order (and one bf16 ulp of dy where the 32-channel MFMA rounds otherwise)
-    sa, ss = float(A1u.abs().max()), float(S1u.abs().max())
-    assert float((A1f - A1u).abs().max()) < 4e-3 * sa + 1e-3, (float((A1f - A1u).abs().max()), sa)
-    assert float((S1f - S1u).abs().max()) < 4e-3 * ss + 1e-3, (float((S1f - S1u).abs().max()), ss)
-    if B * H * W <= 40000:   # the independent reference
-        A1, S1, dy = _cpu_sums(g, w, img, signs, act0 == 1)
-        # a term is |dy| * 255 at most and dy's bf16 rounding moves it by 2^-9: the bound scales with sum |gb| * patch, not with the (cancelling) sum
-        scale = float(dy.abs().sum()) * 255.0 * 2.0 ** -9
-        assert float((A1f - A1).abs().max()) < 0.05 * scale + 1e-3, (float((A1f - A1).abs().max()), scale)
-        assert float((S1f - S1).abs().max()) < 0.05 * scale / 255.0 + 1e-3
-        assert float((A1u - A1).abs().max()) < 0.05 * scale + 1e-3
-        # and relative to the sums themselves where they do not cancel
-        assert float((A1f - A1).abs().max()) < 5e-3 * float(A1.abs().max()) + 1e-3, (float((A1f - A1).abs().max()), float(A1.abs().max()))
+    g8, imgc, sgc, x8 = _to8c(g).cuda(), img.cuda(), signs.cuda(), _to8c(x).cuda()
+    h.launch_log(True)
+    try:
+        A1f, S1f = _run_pair(h, g8, pk, imgc, sgc, B, H, W, act0, 1)
+        A1w, S1w, dw, db = _run_pair(h, g8, pk, imgc, sgc, B, H, W, act0, 2, x8=x8)
+        A1u, S1u = _run_pair(h, g8, pk, imgc, sgc, B, H, W, act0, 0)
+        dwu = torch.full((32, 16, 3, 3), float("nan"), dtype=torch.float32, device="cuda")
+        dbu = torch.full((32,), float("nan"), dtype=torch.float32, device="cuda")
+        wsu = torch.empty(h.query_size("yogo_conv2d_wgrad_bf16_workspace_bytes", B, 16, 32, H, W, 3, 1) // 4, dtype=torch.float32, device="cuda")
+        h.call("yogo_conv2d_wgrad_bf16", x8, g8, dwu, dbu, wsu, B, 16, 32, H, W, 3, 1, 0.0, st)
+        torch.cuda.synchronize()
+    finally:
+        h.launch_log(False)
+    log = h.read_launch_log()
+    fl = [ln for ln in log if ln.startswith("conv_bf16_dgrad_first_bwd_kernel")]
+    assert len(fl) == 2 and ", false>" in fl[0] and ", true>" in fl[1], log
+    return dict(A1f=A1f, S1f=S1f, A1w=A1w, S1w=S1w, A1u=A1u, S1u=S1u, dw=dw, db=db, dwu=dwu.cpu().double(), dbu=dbu.cpu().double()), fl, log
+
+
+def _dw64(x, g):
+    B = g.shape[0]
+    dw = torch.zeros(32, 16, 3, 3, dtype=torch.float64)
+    for b in range(B):   # image by image: the production plane fits
+        dw += torch.nn.grad.conv2d_weight(x[b:b + 1].double(), (32, 16, 3, 3), g[b:b + 1].double(), padding=1)
+    return dw, g.double().sum((0, 2, 3))
+
+
+# the existing six shapes + a partial last tile in each direction for both tile heights (R = 6 / 4 rows x 32 pixels) + one-tile images
+EXACT_SHAPES = [(2, 37, 70), (3, 64, 96), (1, 9, 34), (2, 21, 30), (2, 4, 2), (2, 386, 516), (2, 13, 66), (1, 25, 98), (1, 6, 32), (1, 4, 32), (1, 3, 20)]
+
+
+def check_exact_case(B, H, W, mode):
+    """mode "none" (layer 0 without activation), "allpos" (LeakyReLU, every sign positive): nothing is rounded anywhere, so A1, S1, dw,
+    db of both fused entry points and of the unfused pair must equal fp64 up to the final fp32 store (|d| <= 2^-23 |value|); any halo,
+    tile-tail, parity or sign-map indexing error is an integer-sized difference.  mode "random" (a random sign map): the one inexact step
+    is the float32(0.01) product on the negative side, |d| <= 2^-23 sum |gb * pixel| per element.  Returns the launch-log lines."""
+    from yogo_amd import _hip as h
+
+    act0 = 0 if mode == "none" else 1
+    assert h.lib().yogo_conv2d_dgrad_first_bwd_supported(16, 32, H, W, B, act0) == 1
+    g, w, x, img, signs = _inputs(B, H, W, 7000 * H + W, exact=True)
+    if mode == "allpos":
+        signs = torch.full_like(signs, 0xFF)
+    ref = _ref64(g, w, img, signs, act0 == 1)
+    # ---- preconditions, on the reference, before the GPU is looked at
+    assert torch.equal(ref["dyb"], ref["dy"]), "a dy that is no bf16 value: the case is not exact"
+    assert float(ref["dy"].abs().max()) <= 256 and torch.equal(ref["dy"], ref["dy"].round())
+    got, fl, log = _run_all(h, g, w, x, img, signs, act0)
+    chains = _chain_bounds(ref, fl)
+    for k, (bound, txt) in chains.items():
+        print(f"   exact {B}x{H}x{W} {mode}: longest fp32 chain of {k}: {txt}; bound {bound:.3g} = 2^24 / {2.0 ** 24 / max(bound, 1):.1f}")
+        assert bound < 2.0 ** 24, (k, bound, txt, "lower the density of g: the chain's partial sums must stay exact integers")
+    tolA = U23 * (ref["A1"].abs() if mode != "random" else ref["absA1"])
+    tolS = U23 * (ref["S1"].abs() if mode != "random" else ref["absS1"])
+    for k in ("A1f", "A1w", "A1u"):
+        d = (got[k] - ref["A1"]).abs()
+        print(f"   {k}: max|d| {float(d.max()):.3g} (max|A1| {float(ref['A1'].abs().max()):.3g}, sum|terms| {float(ref['absA1'].max()):.3g})")
+        assert bool((d <= tolA).all()), (k, mode, float(d.max()), float((d - tolA).max()))
+    for k in ("S1f", "S1w", "S1u"):
+        d = (got[k] - ref["S1"]).abs()
+        assert bool((d <= tolS).all()), (k, mode, float(d.max()))
+    dw64, db64 = _dw64(x, g)   # integers below 2^24 (|dw| <= B H W): exact in every summation order
+    assert float(dw64.abs().max()) < 2.0 ** 24 and float(g.abs().sum((0, 2, 3)).max()) < 2.0 ** 24
+    for k, r in (("dw", dw64), ("dwu", dw64), ("db", db64), ("dbu", db64)):
+        assert torch.equal(got[k], r), (k, mode, float((got[k] - r).abs().max()))
+    return log
+
+
+@pytest.mark.parametrize("mode", ["none", "allpos", "random"])
+@pytest.mark.parametrize("B,H,W", EXACT_SHAPES)
+def test_fused_sweep_exact_integer_case(B, H, W, mode):
+    check_exact_case(B, H, W, mode)
+
+
+def check_random_case(B, H, W, act0):
+    """random data: the kernels against fp64 with bounds taken from the REFERENCE on the test's own inputs: e_ref = the error of a plain
+    fp32 restatement over eight channel orders; a kernel may be off by 4 e_ref (the spread between orders seen at the large shapes is
+    2x .. 4x) + one more dy rounded to the other bf16 neighbour (max|dy| * 2^-8, times a pixel <= 255 for A1).  Measured: see the
+    comment above test_fused_sweep_against_cpu_and_the_unfused_pair.  The earlier fixed bounds stay wherever they are the tighter ones.  Returns the launch log."""
+    from yogo_amd import _hip as h
+
+    assert h.lib().yogo_conv2d_dgrad_first_bwd_supported(16, 32, H, W, B, act0) == 1
+    g, w, x, img, signs = _inputs(B, H, W, 1000 * H + W, exact=False)
+    ref = _ref64(g, w, img, signs, act0 == 1)
+    eA, eS = _fp32_restatement_error(g, w, img, signs, act0 == 1, ref)
+    dymax = float(ref["dy"].abs().max())
+    boundA, boundS = 4 * eA + dymax * 255 * 2.0 ** -8, 4 * eS + dymax * 2.0 ** -8
+    sa, ss = float(ref["A1"].abs().max()), float(ref["S1"].abs().max())
+    print(f"   random {B}x{H}x{W} act0={act0}: e_ref A1 {eA:.3g} ({eA / sa:.2e} of max|A1|), S1 {eS:.3g}; max|dy| {dymax:.3g}; bounds {boundA:.3g} / {boundS:.3g}")
+    got, fl, log = _run_all(h, g, w, x, img, signs, act0)
+    # the earlier bounds (kept where tighter): 0.05 * sum|dy| * 255 * 2^-9 + 1e-3 and 5e-3 max|A1| + 1e-3
+    scale = float(ref["dy"].abs().sum()) * 255.0 * 2.0 ** -9
+    oldA, oldS = min(0.05 * scale, 5e-3 * sa) + 1e-3, 0.05 * scale / 255.0 + 1e-3
+    for k in ("A1f", "A1w", "A1u"):
+        d = float((got[k] - ref["A1"]).abs().max())
+        print(f"   {k}: max|d| {d:.3g} = {d / sa:.2e} of max|A1| (bound {boundA:.3g}, earlier bound {oldA:.3g})")
+        assert d <= boundA and d < oldA, (k, d, boundA, oldA, eA)
+    for k in ("S1f", "S1w", "S1u"):
+        d = float((got[k] - ref["S1"]).abs().max())
+        assert d <= boundS and d < oldS, (k, d, boundS, oldS, eS)
+    # fused against unfused: each within its bound of fp64, so within twice the bound of each other; the earlier 4e-3 stays as well
+    for a, b_ in (("A1f", "A1u"), ("A1w", "A1u")):
+        d = float((got[a] - got[b_]).abs().max())
+        assert d <= 2 * boundA and d < 4e-3 * float(got[b_].abs().max()) + 1e-3, (a, b_, d)
+    for a, b_ in (("S1f", "S1u"), ("S1w", "S1u")):
+        d = float((got[a] - got[b_]).abs().max())
+        assert d <= 2 * boundS and d < 4e-3 * float(got[b_].abs().max()) + 1e-3, (a, b_, d)
+    # layer 1's weight / bias gradient: exact bf16 products summed in fp32 and reduced in double, against fp64 (no size gate) and each other
+    dw64, db64 = _dw64(x, g)
+    for k in ("dw", "dwu"):
+        assert float((got[k] - dw64).abs().max()) < 1e-4 * float(dw64.abs().max()) + 1e-5, k
+    for k in ("db", "dbu"):
+        assert float((got[k] - db64).abs().max()) < 1e-4 * float(db64.abs().max()) + 1e-4, k
+    assert float((got["dw"] - got["dwu"]).abs().max()) < 1e-4 * float(got["dwu"].abs().max()) + 1e-5
+    assert float((got["db"] - got["dbu"]).abs().max()) < 1e-4 * float(got["dbu"].abs().max()) + 1e-5
+    return log
+
+
+# Measured on an MI355X (`python -m pytest -s -m gpu tests/test_gpu_first_fused_bwd.py -k against_cpu`; e_ref is recomputed by every run,
+# 0.7 s of CPU at the production plane):
+#   (2, 386, 516): e_ref(A1) = 5.23 = 4.4e-5 of max|A1|, max|dy| = 4.29 -> bound 25.2 (the earlier bound: 594); fused 3.60, fused + wgrad 3.59,
+#                  unfused 2.95 (3.0e-5 / 3.0e-5 / 2.5e-5 of max|A1|)
+#   (1, 386, 516): e_ref(A1) = 5.13 = 6.0e-5, bound 25.0 (earlier: 428); fused 1.84, fused + wgrad 1.84, unfused 5.24
+@pytest.mark.parametrize("B,H,W,act0", [(2, 37, 70, 1), (3, 64, 96, 1), (1, 9, 34, 1), (2, 21, 30, 0), (2, 4, 2, 1), (2, 386, 516, 1), (1, 386, 516, 1)])
+def test_fused_sweep_against_cpu_and_the_unfused_pair(B, H, W, act0):
+    check_random_case(B, H, W, act0)
 
 
 def test_unsupported_shapes_are_refused():
@@ -149,6 +320,8 @@ def test_training_step_with_and_without_the_fused_sweep():
     from yogo_amd.train import HipTrainer
     from yogo_amd.yogo_loss import YOGOLoss
     import yogo_oracle as O
+
+    from _util import TF_GRAD_RTOL_L0
 
     for Himg, Wimg, B in ((96, 128, 4), (132, 72, 3)):
         x = O.synthetic_images(B, Himg, Wimg, seed=43).cuda()
@@ -184,6 +357,7 @@ def test_training_step_with_and_without_the_fused_sweep():
                 # another order (the sweep's per-wavefront partial sums against wgrad_bf16_kernel's split-K slabs)
                 d = float((a - b_).abs().max())
                 print(f"   {n:20s} max|d|/max|g| {d / float(b_.abs().max()):.2e}")
-                assert d < (5e-3 if n.startswith("model.0.") else 1e-4) * float(b_.abs().max()) + 1e-7, (n, d, float(b_.abs().max()))
+                # layer 0: each path is within TF_GRAD_RTOL_L0 of the oracle (the teacher-forced check, both plans) -> twice that of each other
+                assert d < (2 * TF_GRAD_RTOL_L0 if n.startswith("model.0.") else 1e-4) * float(b_.abs().max()) + 1e-7, (n, d, float(b_.abs().max()))
             else:
                 assert torch.equal(a, b_), n

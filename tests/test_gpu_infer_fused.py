@@ -228,3 +228,53 @@ def test_eval_model_call_runs_head_and_decode_as_one_launch_bit_identical(num_cl
         assert fused.shape == two.shape == (2, 5 + num_classes, m.Sy, m.Sx)
         assert torch.isfinite(fused).all()
         assert torch.equal(fused.view(torch.int32), two.view(torch.int32)), float((fused - two).abs().max())
+
+
+def _grid_model(num_classes=7):
+    from yogo_amd.model import YOGO
+
+    torch.manual_seed(5)
+    m = YOGO((128, 160), 0.0425, 0.0555, num_classes).cuda().eval()
+    for k, v in m.state_dict().items():
+        if k.endswith("running_var"):
+            v.fill_(900.0)
+    return m
+
+
+def test_eval_model_call_holds_the_grid_buffers_to_the_output_grid():
+    """The fused head + decode launch takes the model's _Cxs / _Cys as raw pointers and indexes them as [OH * OW].  A model built for
+    128x160 (grid 16x20) given a SMALLER 96x128 image (grid 12x16: every read stays inside the buffers, whatever the code does) must
+    raise what the two-launch path raises (yogo_amd/model.py: _decode) instead of decoding wrong box centres; after resize_model() the
+    call succeeds and is the two launches bit for bit.  Also: a non-contiguous grid buffer (a transposed view of the same storage)
+    gives the same bits as the contiguous one; a float64 buffer (larger in bytes than the kernel reads, never smaller) and a buffer
+    on the CPU are errors."""
+    m = _grid_model()
+    x = torch.randint(0, 256, (2, 1, 96, 128), dtype=torch.uint8, generator=torch.Generator().manual_seed(6)).cuda()
+    assert (m.Sy, m.Sx) == (16, 20)
+    with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+        with pytest.raises(RuntimeError, match="do not match the network output grid"):
+            m.forward_raw(x)                      # the two-launch path (RawPredictions) has always refused
+        with pytest.raises(RuntimeError, match="do not match the network output grid"):
+            m(x)
+        m.resize_model(96, 128)
+        assert (m.Sy, m.Sx) == (12, 16)
+        fused = m(x)
+        two = m.forward_raw(x).decoded()
+        assert fused.shape == (2, 12, 12, 16) and bool(torch.isfinite(fused).all())
+        assert torch.equal(fused.view(torch.int32), two.view(torch.int32))
+        good = (m._Cxs.clone(), m._Cys.clone())
+        try:
+            # the same VALUES through a transposed view of a (Sx, Sy) storage: logical shape (Sy, Sx), strides (1, Sy)
+            m._Cxs, m._Cys = good[0].t().contiguous().t(), good[1].t().contiguous().t()
+            assert not m._Cxs.is_contiguous() and tuple(m._Cxs.shape) == (12, 16) and torch.equal(m._Cxs, good[0])
+            strided = m(x)
+            assert torch.equal(strided.view(torch.int32), fused.view(torch.int32)), float((strided - fused).abs().max())
+            m._Cxs, m._Cys = good[0].double(), good[1].double()
+            with pytest.raises(RuntimeError, match="grid buffers"):
+                m(x)
+            m._Cxs, m._Cys = good[0].cpu(), good[1].cpu()
+            with pytest.raises(RuntimeError, match="grid buffers"):
+                m(x)
+        finally:
+            m._Cxs, m._Cys = good
+        assert torch.equal(m(x).view(torch.int32), fused.view(torch.int32))

@@ -6,15 +6,26 @@ conv_bf16_kernel<2,4,8,...> needs OH*OW >= 4096; the planner picks other band wi
       fp32-head variants the training step uses) at 772x1032 against F.conv2d + autograd in fp32 ON THE CPU on bf16-rounded
       inputs, with the per-kernel bf16 tolerances of test_gpu_bf16.py (8e-3 of the output range for one bf16 rounding, 1e-4
       of max|g| for fp32-accumulated weight gradients); weight gradients also at B = 128 (the split-K plan depends on B);
+      and the fused layer-0/1 backward sweep, both entry points, at the production plane against its fp64 reference;
   (B) one full bf16 HipTrainer.step at 772x1032 is compared with the CPU oracle's bf16-storage emulation of the step
       (O.bf16_train_step rounds where the HIP path stores bf16): end to end loss 1e-3, every gradient tensor cosine >= 0.995,
       running statistics 1e-3 -- and teacher-forced, every kernel of the step given its actual inputs: stored tensors to one
       bf16 ulp, parameter gradients to 2e-4 of max|g| (tests/_util.py says why the elementwise bound is applied per kernel);
   (C) the production batch 128 -- exactly bench.py's step -- with the launch log proving which instantiations / planner
-      parameters ran: they must include every conv_bf16_kernel<...> and wgrad_bf16_kernel<...> row of the committed
-      rocprofv3 summary (profiles/r*_kernel_stats.txt) and nothing the per-layer tests did not launch too.  Numerics through
-      a size-independent property: a batch of 64 copies of (B)'s two images has the same batch statistics, loss and
-      (mean) gradients as the two images, so the B = 128 step must reproduce the oracle's B = 2 step.
+      parameters ran.  The wanted set is READ from the kernel column of the newest committed rocprofv3 summary
+      (profiles/r*_kernel_stats.txt, first table), not kept by hand: every row that is not one of torch's / the runtime's own
+      kernels (TORCH_PREFIXES) and not of a family whose launcher writes no launch-log line (NOT_LOGGED_PREFIXES: BatchNorm,
+      layer 0's direct / matrix-core kernels, decode + loss, AdamW, weight packing -- api_common.hip's log is written by the
+      convolution, weight-gradient, fused-sweep and reduction launchers only; those families have kernel-level tests of their
+      own: test_gpu_kernels.py, test_gpu_bf16.py, test_gpu_round2.py, test_gpu_head_bn_fused.py).  Every excluded prefix must
+      match a row, every row is in exactly one of the three sets, and the wanted set must hold conv_bf16_ws16_kernel<...> and
+      conv_bf16_dgrad_first_bwd_kernel<...>, so neither a stale profile nor a stale list can hollow the check out.  A silent
+      planner fallback (the fused layer-0/1 sweep off, ws16 off) fails it: two negative controls below do exactly that.
+      In the other direction, every launched instantiation outside SEEN_EXCLUDED (the deferred split-K reduction
+      wgrad_reduce_multi_kernel: the per-layer tests call the immediate form; tests/test_gpu_bf16.py holds the two bit-identical)
+      must have been launched by the per-layer tests (A) too, which now include the fused sweep's two entry points.
+      Numerics through a size-independent property: a batch of 64 copies of (B)'s two images has the same batch statistics,
+      loss and (mean) gradients as the two images, so the B = 128 step must reproduce the oracle's B = 2 step.
 (torch's own GPU convolutions are deliberately not used as a reference: MIOpen has no precompiled gfx950 kernels in this
 image and would spend minutes compiling.)
 Reference rows: yogo/model_defns.py:30-77 (blocks), yogo/train.py:309-325 (step)."""
@@ -45,6 +56,46 @@ LAYERS = {
     7: (128, 5 + C, 1, 1, 97, 129, True, "head", "signs"),
 }
 SEEN = set()   # kernel instantiations launched by the per-layer tests (A)
+TORCH_PREFIXES = ("at::", "__amd_rocclr_")   # torch's own kernels and the runtime's copy kernel: not the library's
+# library kernels whose launchers write no launch-log line (yogo_amd/csrc: only conv_bf16*.hip, conv_first_fused_bwd.hip, wgrad_bf16.hip,
+# wgrad_f32.hip's reductions, conv_igemm_f32.hip, decode_fwd / nms / image_cache call yogo_launch_log)
+# (bn_: but for the head-fused pair bn_bwd_{reduce,apply}_head_kernel, which base_model -- no BatchNorm under its head -- never reaches)
+NOT_LOGGED_PREFIXES = ("bn_", "conv_first_", "decode_loss_bwd_bf16_kernel", "yogo_loss_finalize_kernel", "adamw_kernel", "conv_bf16_pack_multi_kernel")
+SEEN_EXCLUDED = ("wgrad_reduce_multi_kernel",)   # logged, but not something part (A) launches on its own (see the module docstring)
+MUST_WANT = ("conv_bf16_ws16_kernel<", "conv_bf16_dgrad_first_bwd_kernel<")
+
+
+def profile_kernel_sets(path):
+    """the kernel column of the FIRST table of a rocprofv3 summary -> (want, excluded, torch): names with whitespace and the leading
+    `void` removed"""
+    want, excluded, other = set(), set(), set()
+    started = False
+    for ln in open(path):
+        if not started:
+            started = ln.startswith("kernel") and "calls" in ln
+            continue
+        if not ln.strip():
+            break
+        mm = re.match(r"^(.*?)\s+\d+\s+[\d.]+\s+[\d.]+\s+[\d.]+\s*$", ln)
+        assert mm, (path, ln)
+        name = re.sub(r"\s+", "", re.sub(r"^void\s+", "", mm.group(1)))
+        (other if name.startswith(TORCH_PREFIXES) else excluded if name.startswith(NOT_LOGGED_PREFIXES) else want).add(name)
+    assert started and want, path
+    for pre in NOT_LOGGED_PREFIXES:
+        assert any(k.startswith(pre) for k in excluded), (path, pre, "an exclusion that excludes nothing: drop it from NOT_LOGGED_PREFIXES")
+    for pre in MUST_WANT:
+        assert any(k.startswith(pre) for k in want), (path, pre, "the committed profile has no such row: the check would be hollow")
+    return want, excluded, other
+
+
+def assert_step_kernel_set(launched, want, seen, what):
+    """launched: kernels_of(launch log of a B = 128 step); every wanted instantiation must be there, by name; and (when the per-layer
+    tests ran in this session) nothing outside SEEN_EXCLUDED that they did not launch too"""
+    missing = want - launched
+    assert not missing, f"{what}: kernels of the committed profile that this step did not launch: {sorted(missing)}"
+    if seen:
+        cov = {k for k in launched if not k.startswith(SEEN_EXCLUDED)}
+        assert cov <= seen, f"{what}: launched at B=128 but not covered by the per-layer parity tests: {sorted(cov - seen)}"
 
 
 def H():
@@ -179,7 +230,23 @@ def test_layer_every_direction_at_772x1032(layer):
         if b is not None:
             assert float((db.cpu() - bg).abs().max()) < 1e-4 * float(bg.abs().max()), (layer, Bw)
     h.launch_log(False)
-    SEEN.update(kernels_of(h.read_launch_log()))
+    mine = kernels_of(h.read_launch_log())
+    if layer in (5, 6):   # the plain-epilogue 128 -> 128 data gradients of the step are conv_bf16_ws16_kernel's (6 % of the step)
+        assert any(k.startswith("conv_bf16_ws16_kernel<") for k in mine), (layer, sorted(mine))
+    SEEN.update(mine)
+
+
+def test_fused_layer01_sweep_at_the_production_plane():
+    """(A) for the kernel that has no layer of its own: layer 1's data gradient folded into layer 0's backward sums, with and without
+    layer 1's weight gradient (yogo_conv2d_dgrad_bf16_first_bwd / yogo_conv2d_dgrad_wgrad_bf16_first_bwd), g at 386x516 = the 772x1032
+    image, against the fp64 reference of test_gpu_first_fused_bwd.py: random data within the reference-derived bound, and the integer
+    case with a random sign map exact up to the float32(0.01) product"""
+    from test_gpu_first_fused_bwd import check_exact_case, check_random_case
+
+    mine = kernels_of(check_random_case(2, 386, 516, 1) + check_exact_case(2, 386, 516, "random"))
+    for wg in ("false", "true"):   # both entry points
+        assert any(k.startswith("conv_bf16_dgrad_first_bwd_kernel<") and k.endswith(f",{wg}>") for k in mine), (wg, sorted(mine))
+    SEEN.update(mine)
 
 
 def _model(B, seed=0):
@@ -227,30 +294,45 @@ def test_bf16_training_step_at_772x1032_vs_cpu_oracle():
     """(B): one bf16 step at the production image size, B = 2, against the oracle's bf16-storage emulation of the same step on
     the CPU (O.bf16_train_step): end to end loss 1e-3, every gradient tensor cosine >= 0.995, running statistics 1e-3; then
     TEACHER-FORCED (tests/_util.py): every stored tensor, statistic and parameter gradient of the step against the per-block
-    emulation fed with the step's own tensors -- one bf16 ulp / 2e-4 of max|g|"""
+    emulation fed with the step's own tensors -- one bf16 ulp / 5e-5 of max|g| (layer 0: 5e-4) -- under the plan with the fusions
+    off AND under the product's plan, which must log the fused layer-0/1 sweep"""
     from yogo_amd.train import HipTrainer
     from yogo_amd.yogo_loss import YOGOLoss
 
-    B = 2
-    m = _model(B, seed=21)
-    sd0 = {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}
-    x = O.synthetic_images(B, HI, WI, seed=22)
-    lab = O.synthetic_labels(B, m.Sx, m.Sy, K=64, num_classes=C, seed=23)
-    tr = HipTrainer(m, YOGOLoss().cuda(), total_steps=10, half=True)
-    tr.trace = {}
-    tr.step(x.cuda(), lab.cuda())
-    torch.cuda.synchronize()
-    from _util import teacher_forced_bf16_step_check
+    from _util import FUSED_L01_KERNEL, expected_fused_kernels, teacher_forced_both_plans
 
-    teacher_forced_bf16_step_check(O, tr, m, x, lab, O.arch("base_model", C), sd0, "772x1032 B=2")
+    B = 2
+    m0 = _model(B, seed=21)
+    sd0 = {k: v.detach().cpu().clone() for k, v in m0.state_dict().items()}
+    x = O.synthetic_images(B, HI, WI, seed=22)
+    lab = O.synthetic_labels(B, m0.Sx, m0.Sy, K=64, num_classes=C, seed=23)
+    del m0
+    spec = O.arch("base_model", C)
+    assert expected_fused_kernels(O, spec, x) == {FUSED_L01_KERNEL: 0}   # the production plan folds layer 0's g into the layer-0/1 sweep
+
+    def run_step():
+        mm = _model(B, seed=21)
+        mm.load_state_dict(sd0)
+        t = HipTrainer(mm, YOGOLoss().cuda(), total_steps=10, half=True)
+        t.trace = {}
+        t.step(x.cuda(), lab.cuda())
+        torch.cuda.synchronize()
+        return t, mm
+
+    # the unfused plan and the product's plan (launch log: conv_bf16_dgrad_first_bwd_kernel); the forward half -- and its CPU oracle at
+    # 772x1032 -- once, the backward half for each
+    tr, m = teacher_forced_both_plans(O, run_step, x, lab, spec, sd0, "772x1032 B=2")
+    tr.trace = None
     loss_ref, grads_ref, ns = _oracle_step(sd0, x, lab, "cpu")
     _compare_step(tr, m, loss_ref, grads_ref, ns, "B=2 vs bf16-emulating CPU oracle")
 
 
 def test_production_batch_step_and_kernel_set():
-    """(C): bench.py's step (B = 128, bf16) on 64 copies of (B)'s two images: the launch log must contain every
-    conv_bf16_kernel / wgrad_bf16_kernel instantiation of the committed rocprofv3 summary and -- when the per-layer tests (A)
-    ran in this session -- nothing the per-layer tests did not launch too; loss, gradients and batch statistics must
+    """(C): bench.py's step (B = 128, bf16) on 64 copies of (B)'s two images: the launch log must contain every kernel row of the
+    committed rocprofv3 summary whose launcher writes the log (profile_kernel_sets: read from the profile, exclusions by stated rule,
+    conv_bf16_ws16_kernel and conv_bf16_dgrad_first_bwd_kernel required) and -- when the per-layer tests (A) ran in this session --
+    nothing the per-layer tests did not launch too; two negative controls (the fused layer-0/1 sweep off; ws16 off through the hooks
+    library) must fail that comparison by the missing kernel's name; loss, gradients and batch statistics must
     reproduce the oracle's bf16-storage emulation of the step on the two images (same batch statistics, mean-reduced loss)"""
     from yogo_amd.train import HipTrainer
     from yogo_amd.yogo_loss import YOGOLoss
@@ -288,17 +370,51 @@ def test_production_batch_step_and_kernel_set():
     print("\n".join(sorted(set(lines))))
     profs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_kernel_stats.txt")))
     assert profs, "no committed rocprofv3 summary"
-    want = set()
-    for ln in open(profs[-1]):
-        mm = re.search(r"((?:conv_bf16_kernel|conv_bf16_ws\d?_kernel|conv_bf16_s2d_direct_kernel|conv_bf16_staged_kernel|conv_bf16_1x1_f32_kernel|wgrad_bf16_kernel)<[^>]*>)", ln)
-        if mm:
-            want.add(re.sub(r"\s+", "", mm.group(1)))
-    assert want, profs[-1]
-    missing = want - launched
-    assert not missing, f"instantiations of {os.path.basename(profs[-1])} that this step did not launch: {sorted(missing)}"
-    if SEEN:
-        conv = {k for k in launched if k.startswith(("conv_bf16_kernel", "conv_bf16_ws_kernel", "conv_bf16_ws3_kernel", "conv_bf16_s2d_direct_kernel", "conv_bf16_staged_kernel", "conv_bf16_1x1_f32_kernel", "wgrad_bf16_kernel"))}
-        assert conv <= SEEN, f"launched at B=128 but not covered by the per-layer parity tests: {sorted(conv - SEEN)}"
+    want, excluded, other = profile_kernel_sets(profs[-1])
+    print(f"{os.path.basename(profs[-1])}: {len(want)} rows wanted in the launch log; not logged by their launchers: {sorted(excluded)}; "
+          f"torch / runtime: {len(other)} rows")
+    assert_step_kernel_set(launched, want, SEEN, f"B=128 step against {os.path.basename(profs[-1])}")
+    # ---- negative controls: a planner that silently falls back must FAIL the helper, naming the kernel that is gone -------------------
+    from yogo_amd import engine as E
+
+    from _util import hooks_library
+
+    def one_step():
+        import copy as _copy
+
+        mc = _copy.deepcopy(m)
+        t = HipTrainer(mc, YOGOLoss().cuda(), total_steps=10, half=True)
+        h_ = H()
+        h_.launch_log(True)
+        try:
+            t.step(x, lab)
+            torch.cuda.synchronize()
+        finally:
+            h_.launch_log(False)
+        return kernels_of(h_.read_launch_log())
+
+    prev = E._L01_FUSE_BWD
+    E._L01_FUSE_BWD = False
+    try:
+        no_sweep = one_step()
+    finally:
+        E._L01_FUSE_BWD = prev
+    # (the control steps run with Dropout2d off, so the channel-mask epilogues of the second step above are joined in: the ONLY row
+    # missing is then the one the switched-off plan no longer launches)
+    rest = {k for k in launched if not k.startswith("conv_bf16_dgrad_first_bwd_kernel")}
+    with pytest.raises(AssertionError, match=r"did not launch: \['conv_bf16_dgrad_first_bwd_kernel<[^']*>'\]"):
+        assert_step_kernel_set(no_sweep | rest, want, None, "control: no fused sweep")
+    assert not any(k.startswith("conv_bf16_dgrad_first_bwd_kernel") for k in no_sweep)
+    with hooks_library() as hl:
+        hl.yogo_hook_conv_bf16_ws16(0)
+        try:
+            no_ws16 = one_step()
+        finally:
+            hl.yogo_hook_conv_bf16_ws16(1)
+    assert not any(k.startswith("conv_bf16_ws16_kernel") for k in no_ws16)
+    rest = {k for k in launched if not k.startswith("conv_bf16_ws16_kernel")}
+    with pytest.raises(AssertionError, match=r"did not launch: \['conv_bf16_ws16_kernel<[^']*>'\]"):
+        assert_step_kernel_set(no_ws16 | rest, want, None, "control: ws16 switched off")
     loss_ref, grads_ref, ns = _oracle_step(sd0, x2, lab2, "cpu")
     _compare_step(tr, m, loss_ref, grads_ref, ns, "B=128 (64 x 2 images) vs bf16-emulating CPU oracle on the 2 images")
 

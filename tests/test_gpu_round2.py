@@ -322,3 +322,65 @@ def test_fused_decode_loss_backward_is_the_three_calls(shape):
     assert torch.equal(g1.view(torch.int16), g3.view(torch.int16))
     assert torch.equal(out1, out3) and bool(torch.isfinite(out1).all())
     assert float(g1.float().abs().max()) > 0
+
+
+@pytest.mark.parametrize("half", [True, False], ids=["bf16", "fp32"])
+def test_trainer_step_holds_the_grid_buffers_to_the_output_grid(half):
+    """HipTrainer.step hands the model's _Cxs / _Cys to yogo_decode_loss_bwd_bf16 (bf16) / yogo_decode_fwd (fp32, and bf16 without
+    the fused decode-loss) as raw pointers.  A model built for 128x160 (grid 16x20) given a SMALLER 96x128 batch (grid 12x16: no read
+    can leave the buffers) must raise model._decode's error, not train on wrong box centres; after resize_model() the step runs, and
+    on the bf16 path the one-kernel decode + loss equals the three calls bit for bit (loss and every gradient).  A transposed view
+    of the same values gives the same bits; float64 (never a narrower type) and CPU buffers are errors."""
+    from yogo_amd import train
+    from yogo_amd.model import YOGO
+    from yogo_amd.train import HipTrainer
+    from yogo_amd.yogo_loss import YOGOLoss
+
+    def fresh(resize, sd=None):
+        torch.manual_seed(7)
+        m = YOGO((128, 160), 0.0425, 0.0555, 4).cuda().train()
+        for mod in m.modules():
+            if isinstance(mod, torch.nn.Dropout2d):
+                mod.p = 0.0
+        if resize:
+            m.resize_model(96, 128)
+        return m
+
+    x = torch.randint(0, 256, (2, 1, 96, 128), dtype=torch.uint8, generator=torch.Generator().manual_seed(8)).cuda()
+    lab = O.synthetic_labels(2, 16, 12, K=5, num_classes=4, seed=9).cuda()
+
+    def step(m, fused_decode_loss=True):
+        prev = train._FUSED_DECODE_LOSS
+        train._FUSED_DECODE_LOSS = fused_decode_loss
+        try:
+            tr = HipTrainer(m, YOGOLoss().cuda(), total_steps=10, half=half)
+            tr.step(x, lab)
+            torch.cuda.synchronize()
+            return tr.loss_components(), tr.flat.grad.clone()
+        finally:
+            train._FUSED_DECODE_LOSS = prev
+
+    m = fresh(False)
+    assert (m.Sy, m.Sx) == (16, 20)
+    with pytest.raises(RuntimeError, match="do not match the network output grid"):
+        step(m)
+    comps, grad = step(fresh(True))
+    assert all(torch.isfinite(torch.tensor(v)) for v in comps.values()) and bool(torch.isfinite(grad).all()) and float(grad.abs().max()) > 0
+    if half:   # the one-pass decode + loss + decode backward against decode_fwd + loss_fwd_bwd + decode_bwd_bf16
+        comps3, grad3 = step(fresh(True), fused_decode_loss=False)
+        assert comps == comps3 and torch.equal(grad, grad3)
+    for fdl in ((True, False) if half else (True,)):
+        m = fresh(True)
+        good = (m._Cxs.clone(), m._Cys.clone())
+        m._Cxs, m._Cys = good[0].t().contiguous().t(), good[1].t().contiguous().t()
+        assert not m._Cxs.is_contiguous() and torch.equal(m._Cxs, good[0])
+        comps_t, grad_t = step(m, fdl)
+        assert comps_t == comps and torch.equal(grad_t, grad), fdl
+        m = fresh(True)
+        m._Cxs, m._Cys = m._Cxs.double(), m._Cys.double()
+        with pytest.raises(RuntimeError, match="grid buffers"):
+            step(m, fdl)
+        m = fresh(True)
+        m._Cxs, m._Cys = m._Cxs.cpu(), m._Cys.cpu()
+        with pytest.raises(RuntimeError, match="grid buffers"):
+            step(m, fdl)

@@ -94,6 +94,21 @@ def _ptr(t):
     return t
 
 
+def grid_buffers(cxs, cys, Sy: int, Sx: int, device):
+    """The cell-centre grids of a model (``_Cxs`` / ``_Cys``) as every decode kernel indexes them: fp32 ``[Sy * Sx]`` on ``device``.
+    The kernels take raw pointers, so this is the one place that holds the buffers to the network's OUTPUT grid -- a model built for
+    one image size and given another (no ``resize_model()``) would otherwise decode wrong box centres (smaller grid) or read past the
+    buffers (larger grid).  Host-side checks of shapes, dtypes and devices only (no synchronisation); returns contiguous tensors."""
+    for g in (cxs, cys):
+        if not isinstance(g, torch.Tensor) or tuple(g.shape) != (Sy, Sx):
+            shape = tuple(g.shape) if isinstance(g, torch.Tensor) else type(g).__name__
+            raise RuntimeError(f"yogo_amd: grid buffers {shape} do not match the network output grid ({Sy}, {Sx})")
+        if g.dtype != torch.float32 or g.device != device:
+            raise RuntimeError(f"yogo_amd: grid buffers ({g.dtype} on {g.device}) do not match the network output grid ({Sy}, {Sx}): "
+                               f"the decode reads float32 on {device}")
+    return cxs.contiguous(), cys.contiguous()
+
+
 def stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
 

@@ -706,6 +706,10 @@ extern "C" int yogo_bn_bwd_bf16_head(const void* gh, const float* head_w, int P,
   YOGO_CHECK_ARG(B * Cb <= 65535, "bn_bwd_bf16_head: batch * channel blocks exceeds 65535");
   const u32x4_t* g4 = reinterpret_cast<const u32x4_t*>(gh);
   const u32x4_t* z4 = reinterpret_cast<const u32x4_t*>(z);
+  if (yogo_launch_log_enabled()) {
+    yogo_launch_log("bn_bwd_reduce_head_kernel | B=%d C=%d HW=%d P=%d act=%d grid=%dx%d", B, C, HW, P, act, nb, B * (Cb / 2));
+    yogo_launch_log("bn_bwd_apply_head_kernel | B=%d C=%d HW=%d P=%d act=%d training=%d grid=%dx%d", B, C, HW, P, act, training, nb, B * (Cb / 2));
+  }
   hipLaunchKernelGGL(bn_bwd_reduce_head_kernel, dim3(nb, B * (Cb / 2)), dim3(256), 0, stream, g4, head_w, P, z4, mean, invstd, gamma, beta, act, part, C, Cb,
                      HW);
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, stream, part, B * nb, C, clip, dgamma, dbeta, sums, sums + C);

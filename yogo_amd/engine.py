@@ -615,7 +615,9 @@ def backward_bf16_train(eng: Engine, saved: List[Saved], graw: torch.Tensor,
     the hook there (and behind the last layer) -- two launches for the data-parallel trainer's two-part exchange instead of one
     reduction per layer, the same bits.  Without it a hook gets every layer's gradients reduced as soon as the layer is through.
     ``trace`` (tests / probes only): a dict that receives clones of the activation gradients as they exist between the
-    kernels -- ("g", i): gradient w.r.t. block i's output, ("dz", i): BatchNorm-backward output of block i -- so that every
+    kernels -- ("g", i): gradient w.r.t. block i's output, ("dz", i): BatchNorm-backward output of block i; a tensor that a fused
+    kernel never writes (layer 0's g under _L01_FUSE_BWD, the g of the block under the head under _HEAD_BN_FUSE) has no entry: a
+    trace records the plan the product runs, it does not change it -- so that every
     kernel of a real step can be checked against the oracle given its ACTUAL inputs (tests/_util.py, teacher-forced check).
     ``stop_at`` (frozen lower layers, the autograd path): the pass ends with the parameter gradients of layer ``stop_at`` -- no data
     gradient of that layer and nothing of the layers below it is computed; their entries of the result are None."""
@@ -658,15 +660,15 @@ def backward_bf16_train(eng: Engine, saved: List[Saved], graw: torch.Tensor,
         # sweep over (image, g, z) -- dz is never written (see conv_first_bn_wgrad_kernel)
         fuse0 = _FUSE_LAYER0_BWD and i == 0 and L.bn is not None and L.conv.bias is None and L.act in (ACT_NONE, ACT_LEAKY)
         # layer 1 above a matrix-core layer 0 that kept its sign map: ONE sweep over g does layer 1's weight gradient and folds its data
-        # gradient straight into layer 0's backward sums (layer 0 has no data gradient of its own, so its dy need not exist; a trace wants
-        # to see it)
+        # gradient straight into layer 0's backward sums (layer 0 has no data gradient of its own, so its dy need not exist; a trace
+        # then has no ("g", 0))
         fuse01 = False
-        if _L01_FUSE_BWD and i == 1 and stop_at == 0 and trace is None and _FUSE_LAYER0_BWD and _WGRAD_BF16_MFMA:
+        if _L01_FUSE_BWD and i == 1 and stop_at == 0 and _FUSE_LAYER0_BWD and _WGRAD_BF16_MFMA:
             L0, S0 = eng.layers[0], saved[0]
             fuse01 = bool(S0.signs0 is not None and S0.x_in.dtype == torch.uint8 and L0.bn is not None and L0.conv.bias is None and L0.cin == 1
                           and L0.s == 2 and L0.act in (ACT_NONE, ACT_LEAKY) and L.k == 3 and L.s == 1 and S0.mask is None
                           and _hip.lib().yogo_conv2d_dgrad_first_bwd_supported(L.cin, L.cout, IH, IW, B, L0.act))
-        if trace is not None and g is not None:
+        if trace is not None and g is not None and head_g is None:   # (under head_g, g is still the head's gradient: recorded above)
             trace[("g", i)] = g.clone()
         if L.bn is not None and not fuse0:
             bn = L.bn
@@ -788,8 +790,8 @@ def backward_bf16_train(eng: Engine, saved: List[Saved], graw: torch.Tensor,
         if i > stop_at:
             Lp, Sp = eng.layers[i - 1], saved[i - 1]
             # the 1x1 head above a BatchNorm block: 12 multiply-adds per element inside that block's BatchNorm backward are cheaper than
-            # writing and twice reading its 128-channel data gradient (a trace wants to see the tensor)
-            if (_HEAD_BN_FUSE and i == n - 1 and trace is None and L.k == 1 and L.s == 1 and L.cout <= 16 and Lp.bn is not None and i - 1 > 0
+            # writing and twice reading its 128-channel data gradient (a trace then has no ("g", n - 2))
+            if (_HEAD_BN_FUSE and i == n - 1 and L.k == 1 and L.s == 1 and L.cout <= 16 and Lp.bn is not None and i - 1 > 0
                     and Lp.cout % 16 == 0 and g.shape[1] == 2):
                 head_g = (g, _f32(L.conv.weight.detach()).reshape(L.cout, L.cin), L.cout)
                 continue
@@ -1060,6 +1062,7 @@ class InferEngineBF16:
                 out = torch.empty(B, L.cout, OH, OW, dtype=torch.float32, device=dev)
                 if decode is not None and head_decode_fusable(L):
                     cxs, cys, aw, ah, wm, hm, inference = decode
+                    cxs, cys = _hip.grid_buffers(cxs, cys, OH, OW, dev)   # (the kernel indexes them as [OH * OW])
                     _hip.call("yogo_head1x1_decode_fwd_bf16", cur, wq, bias, out, cxs, cys, B, L.cin, L.cout, OH, OW, aw, ah, wm, hm, 1 if inference else 0, st)
                     self.decoded = True
                 else:

@@ -77,11 +77,10 @@ class _TrainBF16Fn(torch.autograd.Function):
 
 def _decode(raw, cxs, cys, anchor_w, anchor_h, wmul, hmul, inference) -> torch.Tensor:
     B, P, Sy, Sx = raw.shape
-    if tuple(cxs.shape) != (Sy, Sx) or tuple(cys.shape) != (Sy, Sx):
-        raise RuntimeError(f"yogo_amd: grid buffers {tuple(cxs.shape)} do not match the network output grid ({Sy}, {Sx})")
+    cxs, cys = _hip.grid_buffers(cxs, cys, Sy, Sx, raw.device)
     out = torch.empty_like(raw)
     with torch.cuda.device(raw.device):
-        _hip.call("yogo_decode_fwd", raw, out, cxs.contiguous(), cys.contiguous(), B, P, Sy, Sx, float(anchor_w), float(anchor_h),
+        _hip.call("yogo_decode_fwd", raw, out, cxs, cys, B, P, Sy, Sx, float(anchor_w), float(anchor_h),
                   float(wmul), float(hmul), int(inference), _hip.stream_ptr())
     return out
 

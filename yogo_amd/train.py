@@ -329,6 +329,7 @@ class HipTrainer:
                 raw, saved = eng.forward(imgs, need_grad=True)
             B, P, Sy, Sx = raw.shape
             aw, ah, wm, hm = m._decode_scalars()
+            cxs, cys = _hip.grid_buffers(m._Cxs, m._Cys, Sy, Sx, raw.device)   # (a model built for another image size: resize_model())
             L = self.loss
             out = torch.empty(4, dtype=torch.float32, device=raw.device)
             ws = torch.empty(_hip.query_size("yogo_loss_workspace_bytes", B, Sy, Sx) // 4, dtype=torch.float32, device=raw.device)
@@ -341,12 +342,12 @@ class HipTrainer:
                 # ---- decode + loss forward/backward + decode backward in one pass over the cells (bit-identical to the three calls
                 #      below; the decoded prediction and its gradient never go to memory) ------------------------------------------
                 g8 = torch.empty(B, ((P + 15) // 16) * 2, Sy, Sx, 8, dtype=torch.bfloat16, device=raw.device)
-                _hip.call("yogo_decode_loss_bwd_bf16", raw, lab, m._Cxs, m._Cys, g8, out, ws, B, P, Sy, Sx, aw, ah, wm, hm,
+                _hip.call("yogo_decode_loss_bwd_bf16", raw, lab, cxs, cys, g8, out, ws, B, P, Sy, Sx, aw, ah, wm, hm,
                           float(L.no_obj_weight), float(L.iou_weight), float(L.classify_weight), float(L.label_smoothing), st)
                 backward_bf16_train(eng, saved, g8, grad_out=self.flat.grad_views, on_layer=hook, trace=self.trace, flush_layers=flush)
             else:
                 pred = torch.empty_like(raw)
-                _hip.call("yogo_decode_fwd", raw, pred, m._Cxs, m._Cys, B, P, Sy, Sx, aw, ah, wm, hm, int(bool(m.inference)), st)
+                _hip.call("yogo_decode_fwd", raw, pred, cxs, cys, B, P, Sy, Sx, aw, ah, wm, hm, int(bool(m.inference)), st)
                 # ---- loss forward + backward (one kernel) -------------------------------------------------------------
                 gpred = torch.empty_like(raw)
                 _hip.call("yogo_loss_fwd_bwd", pred, lab, gpred, out, ws, B, P, Sy, Sx, float(L.no_obj_weight), float(L.iou_weight),

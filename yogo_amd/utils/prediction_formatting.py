@@ -28,10 +28,8 @@ class RawPredictions:
             raise ValueError(f"RawPredictions expects (B, pred_shape, Sy, Sx), got {tuple(raw.shape)}")
         _hip.require_cuda(raw, "the raw prediction")
         Sy, Sx = raw.shape[2:]
-        if tuple(cxs.shape) != (Sy, Sx) or tuple(cys.shape) != (Sy, Sx):
-            raise RuntimeError(f"yogo_amd: grid buffers {tuple(cxs.shape)} do not match the network output grid ({Sy}, {Sx})")
+        self.cxs, self.cys = _hip.grid_buffers(cxs, cys, int(Sy), int(Sx), raw.device)
         self.raw = raw.detach().contiguous().float()
-        self.cxs, self.cys = cxs.contiguous(), cys.contiguous()
         self.scalars = (float(anchor_w), float(anchor_h), float(width_multiplier), float(height_multiplier))
         self.inference = bool(inference)
 
