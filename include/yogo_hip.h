@@ -142,6 +142,42 @@ int yogo_head1x1_decode_fwd_bf16(const void* x, const void* packed, const float*
                                  int B, int Cin, int P, int Sy, int Sx, float anchor_w, float anchor_h, float width_multiplier,
                                  float height_multiplier, int inference, yogo_stream_t stream);
 
+/* ---- evaluation: prediction <-> label matching and the class statistics of `Metrics`, batched over images -------------------- */
+/* format_preds_and_labels_v2 after its format_preds call (yogo/utils/prediction_formatting.py:287-330) for every image of a batch in
+ * ONE launch, one workgroup per image: the label cells with label[0] != 0 in ascending cell order (:292-293), cost = 1 - box_iou in
+ * fp32 (:297-299), scipy.optimize.linear_sum_assignment's shortest-augmenting-path solver in fp64 with its tie-breaking (:300), the
+ * unmatched labels and rows (:309-323).  rows [B][cap][P] / counts [B] = yogo_format_preds_batched's output with box_format 1;
+ * labels [B][6][Sy][Sx]; cap >= Sy*Sx.  Outputs at fixed strides (nothing depends on a host read): meta [B][8] int32 = {N labels,
+ * M rows, n_pairs, n_missed, n_extra, status, every class score of the matched rows lies in [0, 1], 0}; pair_label / pair_pred
+ * [B][cap] (ascending label index; indices into the compacted labels / the rows); un_label / un_pred [B][cap] ascending; lab_out
+ * [B][cap][6] the compacted label rows.  status: 0 ok, 1 a cost is NaN or -inf, 2 infeasible (scipy's two ValueErrors); an image with
+ * a status has no pairs and no unmatched entries.  The solver state is in LDS when N and M fit, else in the workspace. */
+int yogo_match_workspace_bytes(int B, int Sy, int Sx, int cap, size_t* bytes);
+int yogo_match_preds_labels_batched(const float* rows, const int* counts, const float* labels, int* meta, int* pair_label,
+                                    int* pair_pred, int* un_label, int* un_pred, float* lab_out, void* workspace, int B, int P, int Sy,
+                                    int Sx, int cap, yogo_stream_t stream);
+/* PredictionLabelMatch.concat over the images (prediction_formatting.py:183-204): preds [K][P], labels [K][6], missed [Km][6],
+ * extra [Ke][P] with K / Km / Ke the sums of n_pairs / n_missed / n_extra (outputs of a zero size may be null). */
+int yogo_match_gather(const float* rows, const float* lab_out, const int* meta, const int* pair_label, const int* pair_pred,
+                      const int* un_label, const int* un_pred, float* preds, float* labels, float* missed, float* extra, int B, int P,
+                      int cap, long long K, long long Km, long long Ke, yogo_stream_t stream);
+/* What Metrics.update adds per batch (yogo/metrics.py:113-158, include_background=False) from the match output, without a host read:
+ * acc (int64, laid out as yogo_metrics_state_layout reports) = confmat [C][C] (first argmax of the C class scores), pos [C], n, missed-by-class [C],
+ * extra-by-class [C], total true objects, bin_count [nbins], bin_acc [nbins], hist [T+1][C][2] (k = #{roc_thresholds <= p}, class,
+ * is-target; the binned ROC's tp / fp at threshold t are the sums over k > t), mAP row count, images with status 1, with status 2.
+ * Probabilities in fp64: the scores, or their softmax unless every class score of the batch's matched rows lies in [0, 1]
+ * (torchmetrics' rule).  bin_conf [nbins] fp64 += the confidences per calibration bin, summed in a fixed order through partial
+ * [B][nbins] (no floating-point atomics: two runs give the same bits).  roc_thresholds [T] / cal_edges [nbins + 1]: the doubles of
+ * torch.linspace, on the device.  map_rows [map_cap][11] fp32 or null: per pair the row's box, objectness, first-argmax class, the
+ * label's box and class, appended at the running count (rows past map_cap are counted, not written). */
+/* offsets (HOST pointer, 12 values): where confmat, pos, n, missed, extra, total, bin_count, bin_acc, hist, the mAP row count and the
+ * two status counts start in acc, then the number of int64 words of acc */
+int yogo_metrics_state_layout(int C, int T, int nbins, long long* offsets);
+int yogo_metrics_accumulate(const float* rows, const float* lab_out, const int* meta, const int* pair_label, const int* pair_pred,
+                            const int* un_label, const int* un_pred, const double* roc_thresholds, int T, const double* cal_edges,
+                            int nbins, long long* acc, double* bin_conf, double* partial, float* map_rows, long long map_cap, int B,
+                            int P, int cap, yogo_stream_t stream);
+
 /* ---- bf16 path: the bf16-autocast forward of `yogo infer` (yogo/infer.py:313-317) and half-precision training
  * (yogo/train.py:315-318, --half) -------------------------------------------------------------------------------------------
  * Activations and activation gradients in "NCHW8c" = [B][C/8][H][W][8] bf16 (C padded to a multiple of 16; padding

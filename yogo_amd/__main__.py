@@ -18,9 +18,11 @@ def main(argv=None) -> None:
 
         do_training(args)
     elif args.task == "test":
+        from yogo_amd.trainer import device_metrics_scope
         from yogo_amd.utils.test_model import do_model_test
 
-        do_model_test(args)
+        with device_metrics_scope(args.device_metrics):
+            do_model_test(args)
     elif args.task == "export":
         print("yogo_amd: `export` (ONNX / OpenVINO for another deployment target) is not part of this MI355X build; "
               "checkpoints written here load in the reference (same state_dict keys), export them there")

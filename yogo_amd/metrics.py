@@ -9,6 +9,10 @@ torch / numpy on the host (the one-box-per-image form ``Metrics`` feeds to mAP i
 images at once: a test split with 10^5 objects takes seconds).  PARITY UNPINNED against a
 real torchmetrics (none available); pinned by hand-computed cases in tests/test_metrics.py.
 
+``Metrics(device_matching=True)`` (``yogo test --device-metrics``) runs the matching and the per-batch additions as HIP kernels
+(yogo_amd/csrc/match.hip) into accumulators in HBM; ``update`` then reads nothing back (but see ``_DeviceState._reserve_map_rows``) and ``compute`` copies the state once into
+the same host objects, so everything after that point is the code below, unchanged.
+
 Quirks of the reference that are kept on purpose:
 * ``min_class_confidence_threshold`` defaults to 0.9 (yogo/metrics.py:30) and ``Trainer.test`` / ``yogo test`` run the network
   with ``inference=False``, so the "class confidences" that enter NMS scoring and that threshold are raw logits;
@@ -18,12 +22,15 @@ Quirks of the reference that are kept on purpose:
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
 
-from yogo_amd.utils.prediction_formatting import PredictionLabelMatch, format_preds_and_labels_v2_batched
+from yogo_amd import _hip
+from yogo_amd.utils.prediction_formatting import (PredictionLabelMatch, format_preds_and_labels_v2_batched, format_preds_batched,
+                                                  gather_device_match, match_rows_to_labels_device, raise_for_match_status)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -47,6 +54,11 @@ def _box_iou_np(a: np.ndarray, b: np.ndarray) -> np.ndarray:
         return np.where(union > 0, inter / union, 0.0)
 
 
+class _PairBlock(tuple):
+    """K one-detection / one-ground-truth images as arrays (det boxes [K,4], scores [K], labels [K], gt boxes [K,4], labels [K]):
+    one entry of ``MeanAveragePrecision._images`` standing for K images, in the order they were handed in"""
+
+
 class MeanAveragePrecision:
     """COCO mAP over lists of per-image dicts: preds {boxes [n,4] xyxy, scores [n], labels [n]}, targets {boxes, labels}."""
 
@@ -66,6 +78,29 @@ class MeanAveragePrecision:
                 p["boxes"].detach().cpu().double().numpy().reshape(-1, 4), p["scores"].detach().cpu().double().numpy().reshape(-1),
                 p["labels"].detach().cpu().long().numpy().reshape(-1),
                 t["boxes"].detach().cpu().double().numpy().reshape(-1, 4), t["labels"].detach().cpu().long().numpy().reshape(-1)))
+
+    def update_pairs(self, det_boxes, det_scores, det_labels, gt_boxes, gt_labels) -> None:
+        """K images of exactly one detection and one ground truth each, as [K, ...] arrays (tensors or numpy) -- the same state as
+        ``update`` on the K one-box dicts ``Metrics._format_for_mAP`` makes, without a Python object per row"""
+        def arr(x, dtype, shape):
+            x = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+            return np.ascontiguousarray(x.astype(dtype, copy=False)).reshape(shape)
+
+        db, gb = arr(det_boxes, np.float64, (-1, 4)), arr(gt_boxes, np.float64, (-1, 4))
+        ds, dl, gl = arr(det_scores, np.float64, (-1,)), arr(det_labels, np.int64, (-1,)), arr(gt_labels, np.int64, (-1,))
+        if not (len(db) == len(ds) == len(dl) == len(gb) == len(gl)):
+            raise ValueError("update_pairs: the five arrays must have the same number of rows")
+        if len(db):
+            self._images.append(_PairBlock((db, ds, dl, gb, gl)))
+
+    def _per_image(self):
+        """every entry as one (boxes, scores, labels, gt boxes, gt labels) image -- the general path's view"""
+        for im in self._images:
+            if isinstance(im, _PairBlock):
+                for k in range(len(im[1])):
+                    yield (im[0][k:k + 1], im[1][k:k + 1], im[2][k:k + 1], im[3][k:k + 1], im[4][k:k + 1])
+            else:
+                yield im
 
     def _evaluate_image(self, img, cls: int, area: Tuple[float, float], max_det: int):
         db, ds, dl, gb, gl = img
@@ -128,16 +163,25 @@ class MeanAveragePrecision:
         """the case ``Metrics`` produces (yogo/metrics.py:204-234: every matched pair is its own image with at most one detection
         and one ground truth): the per-image greedy matching collapses to one IoU per image, so a (class, area) cell is a few
         array operations over all images, and the three max-det settings (>= 1) give the same cell."""
-        N = len(self._images)
-        d_has = np.array([len(im[1]) == 1 for im in self._images])
-        g_has = np.array([len(im[4]) == 1 for im in self._images])
+        N = sum(len(im[1]) if isinstance(im, _PairBlock) else 1 for im in self._images)
+        d_has, g_has = np.zeros(N, dtype=bool), np.zeros(N, dtype=bool)
         d_box, g_box = np.zeros((N, 4)), np.zeros((N, 4))
         d_score, d_lab, g_lab = np.zeros(N), np.full(N, -1, dtype=np.int64), np.full(N, -1, dtype=np.int64)
-        for i, (db, ds, dl, gb, gl) in enumerate(self._images):
+        i = 0
+        for im in self._images:
+            db, ds, dl, gb, gl = im
+            if isinstance(im, _PairBlock):               # K rows at once
+                k = len(ds)
+                d_has[i:i + k], g_has[i:i + k] = True, True
+                d_box[i:i + k], d_score[i:i + k], d_lab[i:i + k], g_box[i:i + k], g_lab[i:i + k] = db, ds, dl, gb, gl
+                i += k
+                continue
+            d_has[i], g_has[i] = len(ds) == 1, len(gl) == 1
             if d_has[i]:
                 d_box[i], d_score[i], d_lab[i] = db[0], ds[0], dl[0]
             if g_has[i]:
                 g_box[i], g_lab[i] = gb[0], gl[0]
+            i += 1
         d_area = (d_box[:, 2] - d_box[:, 0]) * (d_box[:, 3] - d_box[:, 1])
         g_area = (g_box[:, 2] - g_box[:, 0]) * (g_box[:, 3] - g_box[:, 1])
         lt, rb = np.maximum(d_box[:, :2], g_box[:, :2]), np.minimum(d_box[:, 2:], g_box[:, 2:])
@@ -159,15 +203,15 @@ class MeanAveragePrecision:
                 self._accumulate(precision, recall, ki, ai, range(len(_MAX_DETS)), d_score[dsel], dm[:, dsel], dig[:, dsel], npig)
 
     def compute(self, _general: bool = False) -> Dict[str, torch.Tensor]:
-        classes = sorted({int(c) for im in self._images for c in np.concatenate((im[2], im[4]))})
+        classes = sorted({int(c) for im in self._images for c in np.unique(np.concatenate((im[2], im[4])))})
         T, R, K, A, M = len(_IOU_THRS), len(_REC_THRS), len(classes), len(_AREAS), len(_MAX_DETS)
         precision = -np.ones((T, R, K, A, M))
         recall = -np.ones((T, K, A, M))
-        single = not _general and all(len(im[1]) <= 1 and len(im[4]) <= 1 for im in self._images)
+        single = not _general and all(isinstance(im, _PairBlock) or (len(im[1]) <= 1 and len(im[4]) <= 1) for im in self._images)
         if single:
             self._compute_single_box_images(classes, precision, recall)
         for ki, cls in enumerate([] if single else classes):
-            imgs = [im for im in self._images if (im[2] == cls).any() or (im[4] == cls).any()]
+            imgs = [im for im in self._per_image() if (im[2] == cls).any() or (im[4] == cls).any()]
             for ai, area in enumerate(_AREAS.values()):
                 for mi, max_det in enumerate(_MAX_DETS):
                     ev = [e for e in (self._evaluate_image(im, cls, area, max_det) for im in imgs) if e is not None]
@@ -282,6 +326,86 @@ class _ClassStats:
         }
 
 
+class _DeviceState:
+    """The accumulators of ``Metrics(device_matching=True)`` in HBM (include/yogo_hip.h: yogo_metrics_accumulate): the integer state
+    (confusion matrix, positives, counts by class, calibration bins, the ROC histogram over k = #{thresholds <= p}), the fp64
+    confidence sums, and the rows mAP needs per matched pair.  The device is read back by ``map_rows_host`` /
+    ``Metrics._read_device_state`` (from ``compute``) and, when its bound overflows, by the capacity check of the mAP buffer."""
+
+    MAP_ROW = 11
+
+    def __init__(self, device: torch.device, C: int, thresholds: torch.Tensor, n_bins: int, include_mAP: bool) -> None:
+        self.device, self.C, self.T, self.nb = device, C, int(thresholds.numel()), n_bins
+        layout = (ctypes.c_longlong * 12)()
+        _hip.call("yogo_metrics_state_layout", C, self.T, n_bins, ctypes.addressof(layout))   # the library owns the layout
+        (_, self.off_pos, self.off_n, self.off_missed, self.off_extra, self.off_total, self.off_bin_count, self.off_bin_acc, self.off_hist,
+         self.off_map_count, self.off_status, words) = (int(v) for v in layout)
+        self.acc = torch.zeros(words, dtype=torch.int64, device=device)
+        self.bin_conf = torch.zeros(n_bins, dtype=torch.float64, device=device)
+        # the very doubles the host statistics compare against (never regenerated on the device)
+        self.thresholds = thresholds.to(device=device, dtype=torch.float64).contiguous()
+        self.edges = torch.linspace(0, 1, n_bins + 1, dtype=torch.float64).to(device)
+        self.include_mAP = include_mAP
+        self.map_rows: Optional[torch.Tensor] = None
+        self._rows_bound = 0          # upper bound of the mAP rows appended so far
+        self._pending: List[Tuple[torch.cuda.Event, torch.Tensor, int]] = []   # per update: (event after it, total rows after it, its bound)
+
+    def _reserve_map_rows(self, need: int) -> None:
+        """room for `need` more rows.  The host knows only a bound per update (an image has at most min(labels, rows) pairs, and both
+        counts live on the device), so the exact total of the latest FINISHED update, copied asynchronously after each one, replaces the
+        bounds up to it.  Only when the bound still does not fit is the counter itself read -- the one place where ``update`` may
+        wait, and only for metrics launches already queued; the buffer then grows if the exact count needs it.  The first buffer
+        holds two updates' bounds: a caller that synchronises once per batch (``Trainer.test`` reads the loss) never waits here."""
+        done = None
+        while self._pending and self._pending[0][0].query():
+            done = self._pending.pop(0)
+        if done is not None:          # its count is the total after that update; the later ones are still bounds
+            self._rows_bound = int(done[1]) + sum(bound for _, _, bound in self._pending)
+        if self.map_rows is None:
+            self.map_rows = torch.empty(max(2 * need, 1), self.MAP_ROW, dtype=torch.float32, device=self.device)
+        if self._rows_bound + need > self.map_rows.shape[0]:
+            exact = int(self.acc[self.off_map_count])
+            self._pending.clear()
+            self._rows_bound = exact
+            if exact + need > self.map_rows.shape[0]:
+                grown = torch.empty(max(2 * self.map_rows.shape[0], exact + 2 * need), self.MAP_ROW, dtype=torch.float32, device=self.device)
+                grown[:exact] = self.map_rows[:exact]
+                self.map_rows = grown
+        self._rows_bound += need
+
+    def accumulate(self, dm) -> None:
+        B, cap, P = dm.rows.shape
+        with torch.cuda.device(self.device):
+            if self.include_mAP:
+                self._reserve_map_rows(B * cap)
+            partial = torch.empty(B, self.nb, dtype=torch.float64, device=self.device)
+            _hip.call("yogo_metrics_accumulate", *dm.tail, self.thresholds, self.T, self.edges, self.nb, self.acc, self.bin_conf, partial,
+                      self.map_rows if self.include_mAP else None, self.map_rows.shape[0] if self.include_mAP else 0, B, P, cap,
+                      _hip.stream_ptr())
+            if self.include_mAP:
+                count = torch.empty(1, dtype=torch.int64).pin_memory()
+                count.copy_(self.acc[self.off_map_count: self.off_map_count + 1], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                self._pending.append((ev, count, B * cap))
+
+    def map_rows_host(self, count: int) -> torch.Tensor:
+        if self.map_rows is None or count == 0:
+            return torch.zeros(0, self.MAP_ROW)
+        if count > self.map_rows.shape[0]:
+            raise RuntimeError(f"yogo_amd: {count} matched pairs were counted but the mAP buffer holds {self.map_rows.shape[0]} rows")
+        return self.map_rows[:count].cpu()
+
+    def reset(self) -> None:
+        """what ``Metrics.reset`` resets on the host: the class statistics and mAP, not the missed / extra / total counters; and the
+        two status counts, so that an object is usable again after a batch that ``compute`` refused"""
+        self.acc[: self.off_missed].zero_()
+        self.acc[self.off_bin_count:].zero_()
+        self.bin_conf.zero_()
+        self._pending.clear()
+        self._rows_bound = 0
+
+
 class Metrics:
     """yogo/metrics.py:22-234 -- same constructor, ``update`` / ``compute`` / ``reset`` / ``forward`` and return tuple."""
 
@@ -294,7 +418,10 @@ class Metrics:
         min_class_confidence_threshold: float = 0.9,
         include_mAP: bool = True,
         include_background: bool = True,
+        device_matching: bool = False,
     ):
+        self.device_matching = bool(device_matching)   # match and accumulate on the MI355X (yogo_amd/csrc/match.hip); same results
+        self._dev: Optional[_DeviceState] = None
         self.device = device
         self.classes = classes + (["background"] if include_background else [])
         self.num_classes = len(classes)
@@ -311,10 +438,15 @@ class Metrics:
 
     @torch.no_grad()
     def update(self, preds: torch.Tensor, labels: torch.Tensor, use_IoU: bool = True) -> None:
-        # one batched threshold + NMS launch for the whole batch, then the per-image Hungarian matching on the host
-        matches = format_preds_and_labels_v2_batched(preds.detach(), labels.detach(),
-                                                     min_class_confidence_threshold=self.min_class_confidence_threshold)
-        plm = PredictionLabelMatch.concat(matches)
+        if self.device_matching:
+            plm = self._update_device(preds, labels)
+            if plm is None:
+                return                                   # accumulated on the device; read out by compute()
+        else:
+            # one batched threshold + NMS launch for the whole batch, then the per-image Hungarian matching on the host
+            matches = format_preds_and_labels_v2_batched(preds.detach(), labels.detach(),
+                                                         min_class_confidence_threshold=self.min_class_confidence_threshold)
+            plm = PredictionLabelMatch.concat(matches)
 
         def count_classes(cls: torch.Tensor) -> torch.Tensor:
             values, counts = cls.unique(return_counts=True)
@@ -334,8 +466,56 @@ class Metrics:
             self.mAP.update(*self._format_for_mAP(fps, fls))
         self._stats.update(fps[:, 5:], fls[:, 5:].squeeze(-1))
 
+    def _update_device(self, preds, labels) -> Optional[PredictionLabelMatch]:
+        """threshold + NMS launch, match launch, then either the accumulate launch (nothing is read back; returns None) or, with
+        ``include_background``, the gathered match on the host for the unchanged background conversion and host statistics"""
+        if isinstance(preds, torch.Tensor):
+            preds = preds.detach()
+            _hip.require_cuda(preds, "preds")
+        rows, _, counts = format_preds_batched(preds, 0.5, 0.5, "xyxy", self.min_class_confidence_threshold)
+        dm = match_rows_to_labels_device(rows, counts, labels.detach().to(rows.device))
+        if self.include_background:
+            plm = gather_device_match(dm)
+            return PredictionLabelMatch(plm.preds.cpu(), plm.labels.cpu(), plm.missed_labels.cpu(), plm.extra_predictions.cpu())
+        if rows.shape[2] - 5 != self.num_classes:
+            raise ValueError(f"predictions carry {rows.shape[2] - 5} class scores, the metrics were built for {self.num_classes} classes")
+        if self._dev is None:
+            self._dev = _DeviceState(rows.device, self.num_classes, self._stats.thresholds, self._stats.n_bins, self.include_mAP)
+        if rows.shape[0]:
+            self._dev.accumulate(dm)
+        return None
+
+    def _read_device_state(self) -> None:
+        """the accumulators of the device path into the host objects ``compute`` reads (one copy; idempotent).  Raises scipy's
+        ``ValueError`` if an image of any update since the last ``reset`` had an invalid or infeasible cost matrix.  Unlike the host
+        path, where the offending ``update`` raises before it adds anything, the OTHER images of such a batch have been added by then:
+        the sums are partial and the object is to be ``reset``."""
+        d = self._dev
+        acc = d.acc.cpu()
+        C, nb = self.num_classes, self._stats.n_bins
+        raise_for_match_status(int(acc[d.off_status]), int(acc[d.off_status + 1]))
+        st = self._stats
+        st.confmat = acc[: C * C].view(C, C).clone()
+        st.pos = acc[d.off_pos: d.off_pos + C].clone()
+        st.n = int(acc[d.off_n])
+        st.bin_count = acc[d.off_bin_count: d.off_bin_count + nb].double()
+        st.bin_acc = acc[d.off_bin_acc: d.off_bin_acc + nb].double()
+        st.bin_conf = d.bin_conf.cpu()
+        hist = acc[d.off_hist: d.off_map_count].view(-1, C, 2)            # [T + 1, C, is-target], k = #{thresholds <= p}
+        above = hist.flip(0).cumsum(0).flip(0)[1:]                        # [T, C, 2]: #{p >= threshold t} = sum over k > t
+        st.roc_tp, st.roc_fp = above[:, :, 1].contiguous(), above[:, :, 0].contiguous()
+        self.num_obj_missed_by_class = acc[d.off_missed: d.off_missed + C].clone()
+        self.num_obj_extra_by_class = acc[d.off_extra: d.off_extra + C].clone()
+        self.total_num_true_objects = acc[d.off_total: d.off_total + 1].clone()
+        if self.include_mAP:
+            rows = d.map_rows_host(int(acc[d.off_map_count]))
+            self.mAP.reset()
+            self.mAP.update_pairs(rows[:, :4], rows[:, 4], rows[:, 5], rows[:, 6:10], rows[:, 10])
+
     @torch.no_grad()
     def compute(self) -> Tuple[Any, ...]:
+        if self._dev is not None:
+            self._read_device_state()
         pr = self._stats.compute()
         mAP_metrics = self.mAP.compute() if self.include_mAP else {"map": torch.tensor(0.0)}
         return (
@@ -363,6 +543,8 @@ class Metrics:
         if self.include_mAP:
             self.mAP.reset()
         self._stats.reset()
+        if self._dev is not None:
+            self._dev.reset()
 
     @torch.no_grad()
     def forward(self, preds, labels):

@@ -14,6 +14,7 @@ wandb is optional: without it every ``wandb.log`` record goes to ``<run dir>/log
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import os
 import sys
@@ -267,7 +268,8 @@ class Trainer:
             self.backend.opt.broadcast_parameters()   # every rank tests rank 0's best checkpoint, not its own last weights
         if hasattr(self.backend, "sync_eval_state"):
             self.backend.sync_eval_state()
-        test_metrics = self.test(self.test_dataloader, self._torch_device(), self.config, self.net, rank=self._rank, backend=self.backend)
+        test_metrics = self.test(self.test_dataloader, self._torch_device(), self.config, self.net, rank=self._rank, backend=self.backend,
+                                 device_metrics=bool(self.config.get("device_metrics", False)))
         if self._rank == 0:
             if test_metrics is not None:
                 self._log_test_metrics(*test_metrics)
@@ -317,15 +319,16 @@ class Trainer:
     @staticmethod
     @torch.no_grad()
     def test(test_dataloader, device, config: WandbConfig, net: torch.nn.Module, rank: int = 0, include_mAP: bool = True,
-             include_background: bool = False, backend=None) -> Optional[Tuple[Any, ...]]:
-        """loss + Metrics over the test split (yogo/train.py:446-528); the network keeps ``inference=False`` like the reference"""
+             include_background: bool = False, backend=None, device_metrics: bool = False) -> Optional[Tuple[Any, ...]]:
+        """loss + Metrics over the test split (yogo/train.py:446-528); the network keeps ``inference=False`` like the reference.
+        device_metrics: match and accumulate on the MI355X (``Metrics(device_matching=True)``) -- the same tuple"""
         if Trainer._dataset_size(test_dataloader) == 0:
             return None
         net_state = net.training
         net.eval()
         Trainer._check_keys(config)
         metrics = Metrics(classes=config["class_names"], device=str(device), sync_on_compute=False, include_mAP=include_mAP,
-                          include_background=include_background)
+                          include_background=include_background, device_matching=bool(device_metrics) or _device_metrics_scope)
         if backend is None:
             loss_fn = YOGOLoss(no_obj_weight=config["no_obj_weight"], iou_weight=config["iou_weight"],
                                label_smoothing=config["label_smoothing"]).to(device)
@@ -367,6 +370,21 @@ class Trainer:
                 json.dump({**rec, "confusion": confusion_rows}, f, indent=1)
 
 
+_device_metrics_scope = False
+
+
+@contextlib.contextmanager
+def device_metrics_scope(enabled: bool):
+    """every ``Trainer.test`` call inside runs with ``device_metrics=True`` when `enabled`: how ``yogo test --device-metrics`` reaches
+    the call that ``yogo_amd.utils.test_model`` makes with the reference's arguments"""
+    global _device_metrics_scope
+    prev, _device_metrics_scope = _device_metrics_scope, bool(enabled) or _device_metrics_scope
+    try:
+        yield
+    finally:
+        _device_metrics_scope = prev
+
+
 def build_config(args) -> dict:
     """the flat config dict of yogo/train.py:612-643 (it doubles as the wandb config)"""
     return {
@@ -392,6 +410,7 @@ def build_config(args) -> dict:
         "normalize_images": args.normalize_images,
         "dataset_split_override": args.dataset_split_override,
         "device_image_cache_gib": args.device_image_cache,
+        "device_metrics": args.device_metrics,
         "dataset_descriptor_file": args.dataset_descriptor_file,
         "slurm-job-id": os.getenv("SLURM_JOB_ID", default=None),
         "torch-version": torch.__version__,

@@ -113,6 +113,9 @@ def train_parser(parser=None):
     parser.add_argument("--device-image-cache", default=None, type=positive_gib, metavar="GIB",
                         help="keep decoded images resident in GPU memory within this many GiB per rank: the train split first, the val "
                              "split gets what is left (default: off)")
+    parser.add_argument("--device-metrics", default=False, action=boolean_action,
+                        help="match predictions to labels and accumulate the test metrics on the GPU instead of per image on the host; "
+                             "same results (default: False)")
     parser.add_argument("--device", default=None, nargs="?", type=str, help="set a device for the run (accepted for compatibility; training uses one rank per visible GPU)")
     parser.add_argument("--note", default=None, type=str, help="note for the run (e.g. 'run on a TI-82')")
     parser.add_argument("--name", default=None, type=str, help="name for the run (e.g. 'ti-82_run')")
@@ -134,6 +137,9 @@ def test_parser(parser=None):
     parser.add_argument("--dump-to-disk", action=boolean_action, default=False, help="dump results to disk as a pkl file")
     parser.add_argument("--include-mAP", action=boolean_action, default=False, help="calculate mAP as well - just a bit slower (default: False)")
     parser.add_argument("--include-background", action=boolean_action, default=False, help="include 'backround' in confusion matrix (default: False)")
+    parser.add_argument("--device-metrics", default=False, action=boolean_action,
+                        help="match predictions to labels and accumulate the test metrics on the GPU instead of per image on the host; "
+                             "same results (default: False)")
     parser.add_argument("--note", default=None, type=str, help="note for the run (e.g. 'run on a TI-82')")
     parser.add_argument("--tags", default=None, type=str, nargs="*", help="tags for the run (e.g. '--tags test fine-tune')")
     return parser

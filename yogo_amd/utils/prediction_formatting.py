@@ -288,6 +288,83 @@ def format_preds_and_labels_v2_batched(preds: torch.Tensor, labels: torch.Tensor
     return [_match_rows_to_labels(host[b, :n], lab[b]) for b, n in enumerate(counts.cpu().tolist())]
 
 
+class DeviceMatch:
+    """What the match kernel leaves on the device for a batch (include/yogo_hip.h: yogo_match_preds_labels_batched), at fixed
+    strides per image so that the next launch needs no host read: ``meta`` int32 [B, 8] = (labels, rows, pairs, missed, extra,
+    status, class scores of the matched rows all in [0, 1], 0); ``pair_label`` / ``pair_pred`` / ``un_label`` / ``un_pred`` int32
+    [B, cap]; ``labels`` [B, cap, 6] the compacted label rows; ``rows`` [B, cap, 5+C] the kept rows the indices point into."""
+
+    def __init__(self, rows, counts, meta, pair_label, pair_pred, un_label, un_pred, labels):
+        self.rows, self.counts, self.meta = rows, counts, meta
+        self.pair_label, self.pair_pred, self.un_label, self.un_pred, self.labels = pair_label, pair_pred, un_label, un_pred, labels
+
+    @property
+    def tail(self):
+        return (self.rows, self.labels, self.meta, self.pair_label, self.pair_pred, self.un_label, self.un_pred)
+
+
+MATCH_STATUS_MESSAGES = {1: "matrix contains invalid numeric entries", 2: "cost matrix is infeasible"}   # scipy's ValueErrors
+
+
+def raise_for_match_status(n_invalid: int, n_infeasible: int) -> None:
+    """the exception ``scipy.optimize.linear_sum_assignment`` raises on the host path (the first offending image decides there;
+    the device sees all of them at once, and an invalid entry is scipy's earlier check)"""
+    if n_invalid:
+        raise ValueError(MATCH_STATUS_MESSAGES[1])
+    if n_infeasible:
+        raise ValueError(MATCH_STATUS_MESSAGES[2])
+
+
+def match_rows_to_labels_device(rows: torch.Tensor, counts: torch.Tensor, labels: torch.Tensor) -> DeviceMatch:
+    """the assignment of every image of a batch in ONE launch (yogo_amd/csrc/match.hip), no host synchronisation.  rows / counts as
+    ``format_preds_batched(..., box_format="xyxy")`` returns them, labels [B, 6, Sy, Sx] on the same device."""
+    _hip.require_cuda(rows, "the kept rows")
+    _hip.require_cuda(labels, "the labels")
+    B, cap, P = rows.shape
+    if labels.ndim != 4 or labels.shape[0] != B or labels.shape[1] != 6 or labels.shape[2] * labels.shape[3] != cap:
+        raise ValueError(f"labels {tuple(labels.shape)} do not match the {B} x {cap} kept-row buffer (expected [B, 6, Sy, Sx])")
+    Sy, Sx = int(labels.shape[2]), int(labels.shape[3])
+    dev = rows.device
+    lab = labels.detach().contiguous().float()
+    meta = torch.empty(B, 8, dtype=torch.int32, device=dev)
+    idx = torch.empty(4, B, cap, dtype=torch.int32, device=dev)
+    lab_out = torch.empty(B, cap, 6, dtype=torch.float32, device=dev)
+    if B:
+        with torch.cuda.device(dev):
+            ws = torch.empty(_hip.query_size("yogo_match_workspace_bytes", B, Sy, Sx, cap), dtype=torch.uint8, device=dev)
+            _hip.call("yogo_match_preds_labels_batched", rows, counts, lab, meta, idx[0], idx[1], idx[2], idx[3], lab_out, ws, B, P, Sy,
+                      Sx, cap, _hip.stream_ptr())
+    return DeviceMatch(rows, counts, meta, idx[0], idx[1], idx[2], idx[3], lab_out)
+
+
+def format_preds_and_labels_v2_device(preds: Union[torch.Tensor, RawPredictions], labels: torch.Tensor, objectness_thresh: float = 0.5,
+                                      min_class_confidence_threshold: float = 0.0) -> PredictionLabelMatch:
+    """``PredictionLabelMatch.concat(format_preds_and_labels_v2_batched(...))`` of a batch with the assignment on the MI355X: the
+    threshold + NMS launch, the match launch, one small read of the per-image sizes and statuses, the gather launch.  The four
+    tensors stay on the device; ``missed_labels`` / ``extra_predictions`` are ``[0, ...]`` tensors when empty.  Raises the
+    ``ValueError`` scipy raises on the host path (a NaN / -inf cost, an infeasible matrix)."""
+    rows, _, counts = format_preds_batched(preds, objectness_thresh, 0.5, "xyxy", min_class_confidence_threshold)
+    dm = match_rows_to_labels_device(rows, counts, labels.detach().to(rows.device))
+    return gather_device_match(dm)
+
+
+def gather_device_match(dm: DeviceMatch) -> PredictionLabelMatch:
+    B, cap, P = dm.rows.shape
+    dev = dm.rows.device
+    meta = dm.meta.cpu()
+    raise_for_match_status(int((meta[:, 5] == 1).sum()), int((meta[:, 5] == 2).sum()))
+    K, Km, Ke = (int(v) for v in meta[:, 2:5].sum(0).tolist()) if B else (0, 0, 0)
+    preds = torch.empty(K, P, dtype=torch.float32, device=dev)
+    labels = torch.empty(K, 6, dtype=torch.float32, device=dev)
+    missed = torch.empty(Km, 6, dtype=torch.float32, device=dev)
+    extra = torch.empty(Ke, P, dtype=torch.float32, device=dev)
+    if B:
+        with torch.cuda.device(dev):
+            _hip.call("yogo_match_gather", *dm.tail, preds if K else None, labels if K else None, missed if Km else None,
+                      extra if Ke else None, B, P, cap, K, Km, Ke, _hip.stream_ptr())
+    return PredictionLabelMatch(preds=preds, labels=labels, missed_labels=missed, extra_predictions=extra)
+
+
 def format_preds_and_labels_v2(pred: torch.Tensor, label: torch.Tensor, objectness_thresh: float = 0.5,
                                min_class_confidence_threshold: float = 0.0) -> PredictionLabelMatch:
     """reference signature (one image; prediction_formatting.py:254-330).  Results live on the host."""
