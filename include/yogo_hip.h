@@ -414,6 +414,23 @@ int yogo_blobgen_label_rows(const float* rows, const int* counts, int S, int n, 
 int yogo_image_cache_gather(const unsigned char* cache, int S, const int* slots, int B, int C, int H, int W, void* out, int out_fp32,
                             yogo_stream_t stream);
 
+/* ---- zarr image stacks for inference (yogo_amd/zarr_feed.py, `yogo infer --path-to-zarr`) ---------------------------------
+ * What the reference does per image on the host -- zarr_store[:, :, idx][None], CenterCrop, / 255
+ * (yogo/data/image_path_dataset.py:115-126, yogo/infer.py:221-226) -- as one launch per batch over decoded chunks.
+ * staged: staged_bytes of device memory, 16-byte aligned, holding whole decoded uint8 chunks of shape (ch, cw, cn) in C
+ * (order_f = 0) or F (order_f = 1) order, each at a 16-byte aligned offset.  tile_off: [B][gh][gw] int64 device, the offset of
+ * the chunk with tile (ty, tx) of batch row b's frame; a negative offset (the key is absent from the store), or one whose
+ * chunk would not lie inside staged, makes the tile read as `fill`.  tile_k: [B] int32 device, the frame's position on the
+ * chunk's innermost axis (idx % cn; the caller checks 0 <= tile_k < cn, a value outside reads as fill).  gh = ceil(H / ch),
+ * gw = ceil(W / cw).  out: [B][1][OH][OW] uint8 (out_fp32 = 0) or fp32 x / 255 bit-identical to torch's CPU uint8_tensor / 255
+ * (out_fp32 = 1): out[b][0][oy][ox] = frame_b[top + oy][left + ox], 1 <= OH <= H - top, 1 <= OW <= W - left (CenterCrop:
+ * top = int(round((H - OH) / 2.0)), likewise left).  B <= 65535, H, W <= 65535.  Paths (named in the launch log): rows (C order,
+ * cn == 1; 16-byte accesses when every segment is 16-byte aligned, else byte-wise), deinterleave (C order, 1 < cn <= 1024;
+ * consecutive batch rows with one tile offset are served by one read of the chunk), gather (F order; byte-wise). */
+int yogo_zarr_unpack(const unsigned char* staged, long long staged_bytes, const long long* tile_off, const int* tile_k, int B, int gh,
+                     int gw, int ch, int cw, int cn, int order_f, int fill, int H, int W, int top, int left, int OH, int OW, void* out,
+                     int out_fp32, yogo_stream_t stream);
+
 /* ---- optimiser: torch.optim.AdamW over one flat buffer, yogo/train.py:213-217,324 ---------------------------------------- */
 int yogo_adamw_step(float* p, const float* g, float* m, float* v, long long n, int step, double lr, double beta1,
                     double beta2, double eps, double weight_decay, double grad_scale, yogo_stream_t stream);

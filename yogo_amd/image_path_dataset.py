@@ -1,7 +1,9 @@
-"""Inference datasets (yogo/data/image_path_dataset.py:17-159): a directory (or one file) of .png images -> (image, path).
-The zarr variant of the reference needs the `zarr` package, which this build does not have: asking for it raises."""
+"""Inference datasets (yogo/data/image_path_dataset.py:17-159): a directory (or one file) of .png images -> (image, path), or
+a zarr stack of uint8 frames -> (image, made-up name).  The zarr store is read by yogo_amd/zarr_store.py (the `zarr` package
+is not needed); `predict` does not index a ZarrDataset per image but hands it to yogo_amd/zarr_feed.py."""
 from __future__ import annotations
 
+import math
 from pathlib import Path
 from typing import Callable, List, Optional, Tuple, Union
 
@@ -10,6 +12,7 @@ import torch
 from torch.utils.data import Dataset
 
 from yogo_amd.yogo_dataset import read_image
+from yogo_amd.zarr_store import ZarrArray, open_zarr
 
 
 class ImageAndIdDataset(Dataset):
@@ -53,6 +56,41 @@ class ImagePathDataset(ImageAndIdDataset):
         return image, image_path
 
 
+class ZarrDataset(ImageAndIdDataset):
+    """yogo/data/image_path_dataset.py:76-126: frame idx of an [H, W, N] array (or member idx of a group of 2-D arrays) as a
+    uint8 [1, H, W] tensor, with the name ``img_<idx, zero padded>.png``.  ``len`` is what the reference's is: the number of
+    chunks present in the store for an array (``zarr.Array.initialized``), the member count for a group."""
+
+    def __init__(self, zarr_path: Union[str, Path], image_name_from_idx: Optional[Callable[[int], str]] = None,
+                 image_transforms: Optional[List[Callable]] = None, normalize_images: bool = False):
+        self.zarr_path = Path(zarr_path)
+        if not self.zarr_path.exists():
+            raise FileNotFoundError(f"{self.zarr_path} does not exist")
+        self.zarr_store = open_zarr(self.zarr_path)
+        self.image_name_from_idx = image_name_from_idx or self._image_name_from_idx
+        self.transforms = list(image_transforms or [])
+        self.normalize_images = normalize_images
+        self._len = len(self.zarr_store)
+        if self._len == 0:   # (the reference: math.log(0) -> ValueError)
+            raise ValueError(f"{self.zarr_path} holds no images")
+        self._N = int(math.log(self._len, 10) + 1)
+
+    def _image_name_from_idx(self, idx: int) -> str:
+        return f"img_{idx:0{self._N}}.png"
+
+    def __len__(self) -> int:
+        return self._len
+
+    def __getitem__(self, idx: int) -> Tuple[torch.Tensor, str]:
+        frame = self.zarr_store[:, :, idx] if isinstance(self.zarr_store, ZarrArray) else self.zarr_store[idx][:]
+        image = torch.from_numpy(frame[None, ...])
+        for t in self.transforms:
+            image = t(image)
+        if self.normalize_images:
+            image = image / 255
+        return image, self.image_name_from_idx(idx)
+
+
 class CenterCrop:
     """torchvision.transforms.CenterCrop((h, w)) for [C, H, W] tensors no smaller than the crop (yogo/infer.py:221-226)"""
 
@@ -80,5 +118,5 @@ def get_dataset(path_to_images: Optional[Path] = None, path_to_zarr: Optional[Pa
     if path_to_images is not None:
         return ImagePathDataset(path_to_images, image_transforms=image_transforms, normalize_images=normalize_images)
     if path_to_zarr is not None:
-        raise NotImplementedError("yogo_amd: zarr input needs the `zarr` package, which is not part of this build; use --path-to-images")
+        return ZarrDataset(path_to_zarr, image_transforms=image_transforms, normalize_images=normalize_images)
     raise ValueError("one of 'path_to_images' or 'path_to_zarr' must not be None")

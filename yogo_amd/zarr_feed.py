@@ -1,0 +1,311 @@
+"""Inference batches from a zarr stack, unpacked on the device (``yogo infer --path-to-zarr``).
+
+The reference indexes its ZarrDataset per image in the main process (workers forced to 0, yogo/infer.py:257-265) and stacks the
+frames on the host.  Here a ``ZarrDeviceFeed`` takes the DataLoader's place: per batch it works out which chunks the frames
+``[lo, hi)`` live in, reads and decodes them on a thread pool straight into a pinned staging buffer (an uncompressed chunk with one
+copy), uploads the buffer on a side stream and launches ``yogo_zarr_unpack`` (yogo_amd/csrc/zarr_feed.hip) on the compute stream
+behind an event: de-interleave / crop / optional ``/ 255`` happen there.  Two staging and two device buffers: the reading and the
+upload of batch n+1 overlap whatever the caller does with batch n.  A chunk that two consecutive batches share (more than one
+frame per chunk, batch size no multiple of it) is read and decoded once and copied from the previous staging buffer.
+"""
+from __future__ import annotations
+
+import os
+import threading
+from collections import Counter
+from concurrent.futures import Future, ThreadPoolExecutor
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from yogo_amd import _hip
+from yogo_amd.zarr_store import ZarrArray, ZarrGroup
+
+ALIGN = 256          # every staged chunk starts on a multiple of this (the kernel asks for 16)
+MAX_THREADS = 16
+
+
+def center_crop_origin(H: int, W: int, OH: int, OW: int) -> Tuple[int, int]:
+    """(top, left) of torchvision's CenterCrop((OH, OW)) on an H x W image (yogo_amd.image_path_dataset.CenterCrop)"""
+    if OH > H or OW > W or OH < 1 or OW < 1:
+        raise ValueError(f"crop {(OH, OW)} does not fit the image {(H, W)}")
+    return int(round((H - OH) / 2.0)), int(round((W - OW) / 2.0))
+
+
+class FrameSource:
+    """Where frame idx of a store lives: an [H, W, N] array (chunk (ty, tx, idx // cn), position idx % cn) or a group of 2-D
+    arrays (member idx, chunk (ty, tx), position 0).  The members of a group must agree with member 0 in everything the
+    kernel is told once per launch."""
+
+    def __init__(self, root: Union[ZarrArray, ZarrGroup]):
+        self.root = root
+        if isinstance(root, ZarrArray):
+            if root.ndim != 3:
+                raise ValueError(f"zarr store {root.where}: an [H, W, N] array is expected, got shape {root.shape}")
+            first, self.num_frames = root, root.shape[2]
+        else:
+            if len(root) == 0:
+                raise ValueError(f"zarr store {root.where}: the group has no members")
+            first, self.num_frames = root[0], len(root)
+            if first.ndim != 2:
+                raise ValueError(f"zarr store {first.where}: the members of the group must be 2-D, got shape {first.shape}")
+        self.first = first
+        self.H, self.W = first.shape[:2]
+        self.ch, self.cw = first.chunks[:2]
+        self.cn = first.chunks[2] if first.ndim == 3 else 1
+        self.gh, self.gw = first.grid[:2]
+        self.order_f = first.order == "F"
+        self.fill = first.fill_value
+        self.chunk_nbytes = first.chunk_nbytes
+        self.chunk_stride = -(-self.chunk_nbytes // ALIGN) * ALIGN
+
+    def locate(self, idx: int) -> Tuple[ZarrArray, Optional[int], int]:
+        """-> (array, its chunk coordinate on the frame axis or None for a 2-D member, position inside the chunk)"""
+        if not 0 <= idx < self.num_frames:
+            raise IndexError(f"frame {idx} is out of range for {self.num_frames} frames")
+        if isinstance(self.root, ZarrArray):
+            return self.root, idx // self.cn, idx % self.cn
+        arr, f = self.root[idx], self.first
+        if (arr.shape, arr.chunks, arr.order, arr.fill_value) != (f.shape, f.chunks, f.order, f.fill_value):
+            raise RuntimeError(f"zarr store {arr.where}: shape {arr.shape} / chunks {arr.chunks} / order {arr.order} / fill "
+                               f"{arr.fill_value} differ from member 0 ({f.shape} / {f.chunks} / {f.order} / {f.fill_value})")
+        return arr, None, 0
+
+    def max_chunks(self, batch_size: int) -> int:
+        """the most chunks a batch of consecutive frames touches"""
+        per_tile = batch_size if self.cn == 1 else min(batch_size, (batch_size + self.cn - 2) // self.cn + 1)
+        return self.gh * self.gw * per_tile
+
+
+@dataclass
+class BatchPlan:
+    """What frames [lo, hi) need: the distinct chunks present in the store, in staging order, and the kernel's tables."""
+    lo: int
+    hi: int
+    keys: List[str]                       # store keys of the chunks to stage
+    chunks: List[Tuple[ZarrArray, Tuple[int, ...]]]
+    offsets: Dict[str, int]               # key -> byte offset in the staging buffer
+    tile_off: np.ndarray                  # int64 [B, gh, gw], -1 where the key is absent from the store
+    tile_k: np.ndarray                    # int32 [B]
+    nbytes: int                           # bytes of the staging buffer in use
+
+
+def plan_batch(src: FrameSource, lo: int, hi: int) -> BatchPlan:
+    B = hi - lo
+    keys: List[str] = []
+    chunks: List[Tuple[ZarrArray, Tuple[int, ...]]] = []
+    offsets: Dict[str, int] = {}
+    absent = set()
+    tile_off = np.full((B, src.gh, src.gw), -1, dtype=np.int64)
+    tile_k = np.zeros(B, dtype=np.int32)
+    for b, idx in enumerate(range(lo, hi)):
+        arr, tk, k = src.locate(idx)
+        tile_k[b] = k
+        for ty in range(src.gh):
+            for tx in range(src.gw):
+                coords = (ty, tx) if tk is None else (ty, tx, tk)
+                key = arr.chunk_key(coords)
+                if key in absent:
+                    continue
+                if key not in offsets:
+                    if not arr.has_chunk(coords):
+                        absent.add(key)
+                        continue
+                    offsets[key] = len(keys) * src.chunk_stride
+                    keys.append(key)
+                    chunks.append((arr, coords))
+                tile_off[b, ty, tx] = offsets[key]
+    return BatchPlan(lo, hi, keys, chunks, offsets, tile_off, tile_k, max(len(keys) * src.chunk_stride, ALIGN))
+
+
+class ChunkStager:
+    """Reads the chunks of a plan into a staging buffer on a thread pool (file reads and zlib release the GIL); one store
+    handle per thread.  ``reads`` counts, per key, how often a chunk was read from the store."""
+
+    def __init__(self, src: FrameSource, threads: Optional[int] = None):
+        self.src = src
+        self.threads = max(1, min(MAX_THREADS, threads or os.cpu_count() or 1))
+        self._pool = ThreadPoolExecutor(max_workers=self.threads, thread_name_prefix="zarr-read")
+        self._local = threading.local()
+        self._stores: List = []
+        self._lock = threading.Lock()
+        self.reads: Counter = Counter()
+
+    def close(self) -> None:
+        self._pool.shutdown(wait=True)
+        with self._lock:
+            for s in self._stores:
+                s.close()
+            self._stores.clear()
+
+    def _read(self, arr: ZarrArray, coords: Tuple[int, ...], out: np.ndarray) -> None:
+        store = getattr(self._local, "store", None)
+        if store is None:
+            store = self._local.store = arr.store.clone()
+            with self._lock:
+                self._stores.append(store)
+        try:
+            arr.with_store(store).read_chunk_into(coords, out)
+        except KeyError:
+            raise RuntimeError(f"zarr store {arr.where}: chunk {arr.chunk_key(coords)!r} disappeared from the store") from None
+
+    def stage(self, plan: BatchPlan, buf: np.ndarray, prev: Optional[Tuple[BatchPlan, np.ndarray]] = None) -> None:
+        """every chunk of ``plan`` at its offset in ``buf``; a chunk that ``prev`` (the previous plan and its filled buffer)
+        holds is copied from there.  Raises the first chunk's RuntimeError after every read has ended."""
+        n = self.src.chunk_nbytes
+        futures: List[Future] = []
+        for key, (arr, coords) in zip(plan.keys, plan.chunks):
+            off = plan.offsets[key]
+            if prev is not None and key in prev[0].offsets:
+                poff = prev[0].offsets[key]
+                buf[off:off + n] = prev[1][poff:poff + n]
+                continue
+            self.reads[key] += 1
+            futures.append(self._pool.submit(self._read, arr, coords, buf[off:off + n]))
+        err: Optional[BaseException] = None
+        for f in futures:
+            e = f.exception()
+            if e is not None and err is None:
+                err = e
+        if err is not None:
+            raise err
+
+
+def unpack(staged: torch.Tensor, tile_off: np.ndarray, tile_k: np.ndarray, *, chunks: Sequence[int], order_f: bool, fill: int,
+           frame_shape: Tuple[int, int], out: torch.Tensor, top: int = 0, left: int = 0,
+           tile_off_dev: Optional[torch.Tensor] = None, tile_k_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One ``yogo_zarr_unpack`` launch on the current stream.  staged: 1-D uint8 device tensor of decoded chunks; tile_off
+    [B, gh, gw] / tile_k [B]: the host tables (checked here: the kernel trusts them), optionally with their device copies;
+    out: contiguous [B, 1, OH, OW] uint8 or float32 on the same device."""
+    _hip.require_cuda(staged, "the staged zarr chunks")
+    _hip.require_cuda(out, "the unpack output")
+    ch, cw, cn = (int(v) for v in chunks)
+    H, W = (int(v) for v in frame_shape)
+    if staged.dtype != torch.uint8 or staged.ndim != 1 or not staged.is_contiguous() or staged.numel() == 0:
+        raise ValueError(f"unpack: staged must be a non-empty contiguous 1-D uint8 tensor, got {tuple(staged.shape)} {staged.dtype}")
+    if out.dtype not in (torch.uint8, torch.float32) or out.ndim != 4 or out.shape[1] != 1 or not out.is_contiguous():
+        raise ValueError(f"unpack: out must be a contiguous [B, 1, OH, OW] uint8 or float32 tensor, got {tuple(out.shape)} {out.dtype}")
+    if out.device != staged.device:
+        raise ValueError(f"unpack: the chunks are on {staged.device}, out on {out.device}")
+    B, _, OH, OW = (int(v) for v in out.shape)
+    gh, gw = -(-H // ch), -(-W // cw)
+    toff = np.ascontiguousarray(tile_off, dtype=np.int64)
+    tk = np.ascontiguousarray(tile_k, dtype=np.int32)
+    if toff.shape != (B, gh, gw) or tk.shape != (B,):
+        raise ValueError(f"unpack: tile_off {toff.shape} / tile_k {tk.shape} for {B} rows of a {gh} x {gw} tile grid")
+    if B == 0:
+        return out
+    if int(tk.min()) < 0 or int(tk.max()) >= cn:
+        raise IndexError(f"unpack: tile_k outside [0, {cn})")
+    used = toff[toff >= 0]
+    if used.size and (int((used % 16).max()) != 0 or int(used.max()) + ch * cw * cn > staged.numel()):
+        raise IndexError(f"unpack: a tile offset is not 16-byte aligned or its chunk ends after the {staged.numel()} staged bytes")
+    dev = out.device
+    if tile_off_dev is None:
+        tile_off_dev = torch.from_numpy(toff).to(dev)
+    if tile_k_dev is None:
+        tile_k_dev = torch.from_numpy(tk).to(dev)
+    with torch.cuda.device(dev):
+        _hip.call("yogo_zarr_unpack", staged, staged.numel(), tile_off_dev, tile_k_dev, B, gh, gw, ch, cw, cn, 1 if order_f else 0,
+                  int(fill), H, W, int(top), int(left), OH, OW, out, 1 if out.dtype == torch.float32 else 0, _hip.stream_ptr())
+    return out
+
+
+class ZarrDeviceFeed:
+    """Iterator over ``(device batch [B, 1, OH, OW], names)`` in index order; the last batch may be partial.  An object, not a
+    generator: when a batch raises RuntimeError (an unreadable chunk), the next ``next()`` goes on with the following batch.
+    ``crop``: (OH, OW) of a centre crop done in the kernel; ``normalize``: fp32 ``/ 255`` in the kernel, else uint8.
+    ``num_frames``: how many frames to walk (default: ``len(dataset)``, as the reference's DataLoader does, and never more
+    than the stack holds)."""
+
+    def __init__(self, dataset, batch_size: int, device, crop: Optional[Tuple[int, int]] = None, normalize: bool = False,
+                 num_frames: Optional[int] = None):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError(f"yogo_amd: the zarr feed unpacks on an MI355X device (got {dev}); there is no CPU fallback")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if batch_size < 1 or batch_size > 65535:
+            raise ValueError(f"batch size {batch_size} outside [1, 65535]")
+        self.dataset, self.batch_size, self.device, self.normalize = dataset, int(batch_size), dev, bool(normalize)
+        self.src = src = FrameSource(dataset.zarr_store)
+        n = min(len(dataset) if num_frames is None else int(num_frames), src.num_frames)
+        self.num_frames = n
+        self.batches = [(lo, min(lo + self.batch_size, n)) for lo in range(0, n, self.batch_size)]
+        self.OH, self.OW = (src.H, src.W) if crop is None else (int(crop[0]), int(crop[1]))
+        self.top, self.left = center_crop_origin(src.H, src.W, self.OH, self.OW)
+        cap = max(ALIGN, src.max_chunks(self.batch_size) * src.chunk_stride)
+        self._pinned = [torch.empty(cap, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self._host = [p.numpy() for p in self._pinned]
+        self._dev = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(2)]
+        self._side = torch.cuda.Stream(dev)
+        self._uploaded: List[Optional[torch.cuda.Event]] = [None, None]   # slot's pinned buffer may be overwritten after this
+        self._consumed: List[Optional[torch.cuda.Event]] = [None, None]   # slot's device buffer may be overwritten after this
+        self._last: Optional[Tuple[int, BatchPlan, np.ndarray]] = None
+        self.stager = ChunkStager(src)
+        self._loader = ThreadPoolExecutor(max_workers=1, thread_name_prefix="zarr-feed")   # loads run one after the other
+        self._pending: Dict[int, Future] = {}
+        self._pos = 0
+
+    def __len__(self) -> int:
+        return len(self.batches)
+
+    def __iter__(self) -> "ZarrDeviceFeed":
+        return self
+
+    def close(self) -> None:
+        for f in self._pending.values():
+            f.cancel()
+        self._loader.shutdown(wait=True)
+        self._pending.clear()
+        self.stager.close()
+
+    def _load(self, n: int):
+        """(loader thread) stage batch n and start its upload on the side stream"""
+        slot = n % 2
+        lo, hi = self.batches[n]
+        plan = plan_batch(self.src, lo, hi)
+        if self._uploaded[slot] is not None:
+            self._uploaded[slot].synchronize()
+        prev = (self._last[1], self._last[2]) if self._last is not None and self._last[0] == n - 1 else None
+        self._last = None
+        self.stager.stage(plan, self._host[slot], prev)
+        self._last = (n, plan, self._host[slot])
+        with torch.cuda.device(self.device), torch.cuda.stream(self._side):
+            if self._consumed[slot] is not None:
+                self._side.wait_event(self._consumed[slot])
+            self._dev[slot][:plan.nbytes].copy_(self._pinned[slot][:plan.nbytes], non_blocking=True)
+            toff = torch.from_numpy(plan.tile_off).to(self.device)
+            tk = torch.from_numpy(plan.tile_k).to(self.device)
+            ev = torch.cuda.Event()
+            ev.record(self._side)
+        self._uploaded[slot] = ev
+        return plan, toff, tk, ev
+
+    def __next__(self) -> Tuple[torch.Tensor, Tuple[str, ...]]:
+        if self._pos >= len(self.batches):
+            self.close()
+            raise StopIteration
+        n = self._pos
+        self._pos += 1
+        fut = self._pending.pop(n, None) or self._loader.submit(self._load, n)
+        if n + 1 < len(self.batches):
+            self._pending[n + 1] = self._loader.submit(self._load, n + 1)
+        plan, toff, tk, ev = fut.result()
+        slot = n % 2
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            cur.wait_event(ev)
+            toff.record_stream(cur)
+            tk.record_stream(cur)
+            out = torch.empty((plan.hi - plan.lo, 1, self.OH, self.OW), dtype=torch.float32 if self.normalize else torch.uint8,
+                              device=self.device)
+            unpack(self._dev[slot][:plan.nbytes], plan.tile_off, plan.tile_k, chunks=(self.src.ch, self.src.cw, self.src.cn),
+                   order_f=self.src.order_f, fill=self.src.fill, frame_shape=(self.src.H, self.src.W), out=out, top=self.top,
+                   left=self.left, tile_off_dev=toff, tile_k_dev=tk)
+            done = torch.cuda.Event()
+            done.record(cur)
+        self._consumed[slot] = done
+        return out, tuple(self.dataset.image_name_from_idx(i) for i in range(plan.lo, plan.hi))
