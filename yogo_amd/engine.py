@@ -10,6 +10,15 @@ Fusion plan (fp32):
   backward         :  [BN backward] -> wgrad (+bias grad, +clamp) -> dgrad whose epilogue applies the previous block's
                       activation derivative and dropout mask, so no separate element-wise backward passes exist.
 The per-parameter gradient clamp of yogo/model.py:76-77 is fused into the gradient-finishing kernels.
+
+bf16 training (forward_bf16_train / backward_bf16_train): activations and their gradients in NCHW8c bf16, everything else fp32.
+  layer 0          :  uint8 image + BatchNorm on the matrix cores: statistics from the exact integer patch Gram matrix, then
+                      conv + BatchNorm + activation in one sweep; any other first layer through yogo_conv_first_fwd_train_bf16
+                      with the statistics from its epilogue
+  layers > 0       :  conv (+bias, activation, dropout mask; sign map or pre-activation for the data gradient below) | BatchNorm
+                      statistics by a sweep over the stored output | finalize | normalise + activation
+  backward         :  per layer BatchNorm backward -> weight gradient -> hook -> data gradient, all on the current stream; the
+                      fused kernels that replace some of these passes are named by the five switches defined above _packed_bf16
 """
 from __future__ import annotations
 
@@ -106,6 +115,45 @@ def _f32(t: torch.Tensor) -> torch.Tensor:
     return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.contiguous().float()
 
 
+def _bn_affine(L: Layer, dev) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(gamma, beta) of the block's BatchNorm as fp32 device tensors; ones / zeros for affine=False"""
+    bn = L.bn
+    gamma = _f32(bn.weight.detach()) if bn.weight is not None else torch.ones(L.cout, device=dev)
+    beta = _f32(bn.bias.detach()) if bn.bias is not None else torch.zeros(L.cout, device=dev)
+    return gamma, beta
+
+
+def _bn_grad_dst(bn: nn.BatchNorm2d, dst, grads: Dict[int, torch.Tensor], cout: int, dev) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(dgamma, dbeta) destinations: the parameters' own through ``dst``, entered into ``grads``; scratch for affine=False (the
+    kernels always write them)"""
+    dgamma = dst(bn.weight) if bn.weight is not None else torch.empty(cout, dtype=torch.float32, device=dev)
+    dbeta = dst(bn.bias) if bn.bias is not None else torch.empty(cout, dtype=torch.float32, device=dev)
+    if bn.weight is not None:
+        grads[id(bn.weight)] = dgamma
+        grads[id(bn.bias)] = dbeta
+    return dgamma, dbeta
+
+
+def _bn_finalize(eng: "Engine", L: Layer, fn: str, *lead_args, count: int, dev, st) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Batch (mean, invstd) of the block's BatchNorm by ``fn`` (yogo_bn_finalize over partial sums, or yogo_bn_stats_from_gram), which
+    also updates the running statistics when the module tracks them"""
+    bn = L.bn
+    mean = torch.empty(L.cout, dtype=torch.float32, device=dev)
+    invstd = torch.empty(L.cout, dtype=torch.float32, device=dev)
+    track = bn.track_running_stats and bn.running_mean is not None
+    _hip.call(fn, *lead_args, L.cout, count, float(bn.eps), float(bn.momentum if bn.momentum is not None else 0.0), mean, invstd,
+              bn.running_mean if track else None, bn.running_var if track else None, bn.num_batches_tracked if track else None, st)
+    if track:
+        eng.generation += 1   # running statistics rewritten by raw pointer
+    return mean, invstd
+
+
+def _pack_hit(eng: "Engine", key: Tuple[int, int], w: torch.Tensor) -> Optional[torch.Tensor]:
+    """the cached packing ``key`` of weight ``w``, unless torch has seen ``w`` written or moved since it was made"""
+    hit = eng._pack.get(key)
+    return hit[2] if hit is not None and hit[0] == w._version and hit[1] == w.data_ptr() else None
+
+
 class Engine:
     def __init__(self, backbone: nn.Sequential):
         self.backbone_ref = weakref.ref(backbone)
@@ -120,6 +168,9 @@ class Engine:
         # bn_finalize / bn_stats_from_gram on the running statistics): torch's _version does not see those writes, so every
         # cache of derived tensors (packed weights, folded inference weights) keys on this counter as well
         self.generation: int = 0
+        self._pack_multi = None     # (weight pointers, buffers, job table, blocks) of _pack_all_bf16
+        self._drop_consts = None    # (key, sizes, p, 1 / (1 - p)) of _dropout_masks
+        self._infer_bf16: Optional["InferEngineBF16"] = None
 
     def _tick(self, kind: str, layer: int, flops: float, mw: int = 0, nbytes: float = 0.0) -> None:
         """open a HIP-event bracket around one kernel call (bench.py): algorithmic FLOPs and bytes of that call"""
@@ -144,9 +195,9 @@ class Engine:
         L = self.layers[i]
         w = L.conv.weight
         key = (i, mode)
-        hit = self._pack.get(key)
-        if hit is not None and hit[0] == w._version and hit[1] == w.data_ptr():
-            return hit[2]
+        buf = _pack_hit(self, key, w)
+        if buf is not None:
+            return buf
         nbytes = _hip.query_size("yogo_conv_packed_bytes", L.cin, L.cout, L.k, L.s, mode)
         buf = torch.empty(nbytes // 4, dtype=torch.float32, device=w.device)
         _hip.call("yogo_conv_pack_f32", _f32(w.detach()), buf, L.cin, L.cout, L.k, L.s, mode, _hip.stream_ptr())
@@ -217,21 +268,12 @@ class Engine:
                 self._tock()
             if has_bn:
                 bn = L.bn
-                gamma = _f32(bn.weight.detach()) if bn.weight is not None else torch.ones(L.cout, device=dev)
-                beta = _f32(bn.bias.detach()) if bn.bias is not None else torch.zeros(L.cout, device=dev)
+                gamma, beta = _bn_affine(L, dev)
                 y = torch.empty_like(out) if need_grad else out
                 if bn_train:
-                    mean = torch.empty(L.cout, dtype=torch.float32, device=dev)
-                    invstd = torch.empty(L.cout, dtype=torch.float32, device=dev)
-                    track = bn.track_running_stats and bn.running_mean is not None
-                    if track and bn.momentum is None:
+                    if bn.track_running_stats and bn.running_mean is not None and bn.momentum is None:
                         raise RuntimeError("yogo_amd: BatchNorm2d(momentum=None) is not supported")
-                    _hip.call("yogo_bn_finalize", stats, rows, mpad, L.cout, B * OH * OW, float(bn.eps),
-                              float(bn.momentum if bn.momentum is not None else 0.0), mean, invstd,
-                              bn.running_mean if track else None, bn.running_var if track else None,
-                              bn.num_batches_tracked if track else None, st)
-                    if track:
-                        self.generation += 1   # running statistics rewritten by raw pointer
+                    mean, invstd = _bn_finalize(self, L, "yogo_bn_finalize", stats, rows, mpad, count=B * OH * OW, dev=dev, st=st)
                     _hip.call("yogo_bn_apply_act", out, y, mean, invstd, 0, float(bn.eps), gamma, beta, B, L.cout, OH * OW,
                               L.act, st)
                     S.mean, S.invstd = mean, invstd
@@ -278,19 +320,14 @@ class Engine:
             IH, IW = int(S.x_in.shape[2]), int(S.x_in.shape[3])
             if L.bn is not None:
                 bn = L.bn
-                gamma = _f32(bn.weight.detach()) if bn.weight is not None else torch.ones(L.cout, device=dev)
-                beta = _f32(bn.bias.detach()) if bn.bias is not None else torch.zeros(L.cout, device=dev)
-                dgamma = dst(bn.weight) if bn.weight is not None else torch.empty(L.cout, dtype=torch.float32, device=dev)
-                dbeta = dst(bn.bias) if bn.bias is not None else torch.empty(L.cout, dtype=torch.float32, device=dev)
+                gamma, beta = _bn_affine(L, dev)
+                dgamma, dbeta = _bn_grad_dst(bn, dst, grads, L.cout, dev)
                 rows = _hip.query_ints("yogo_bn_bwd_rows", 1, B, OH * OW)[0]
                 part = torch.empty(rows * L.cout * 2, dtype=torch.float32, device=dev)
                 sums = torch.empty(2 * L.cout, dtype=torch.float32, device=dev)
                 # g arrives as dL/d(block output): the BN-backward kernels apply the activation derivative themselves
                 _hip.call("yogo_bn_bwd", g, S.z, g, S.mean, S.invstd, gamma, beta, L.act, dgamma, dbeta, part, sums, B, L.cout,
                           OH * OW, 1 if S.bn_train else 0, clip, st)
-                if bn.weight is not None:
-                    grads[id(bn.weight)] = dgamma
-                    grads[id(bn.bias)] = dbeta
             # ---- weight / bias gradient -------------------------------------------------------------------------
             dw = dst(L.conv.weight)
             has_bias = L.conv.bias is not None
@@ -355,41 +392,23 @@ def _blocks(c: int) -> int:
     return ((c + 15) // 16) * 2
 
 
-# Execution plan of the bf16 training path.  Plain module constants (no environment switches): the alternatives they once
-# selected were measured in round 1 ("measured and dropped") and only the winners stayed; the tests flip
-# _FUSE_LAYER0_BWD / _L0_GRAM to compare the fused kernels with the separate passes they replace.
-_WGRAD_BF16_MFMA = True     # weight gradients on the bf16 matrix cores (False: exact fp32 MFMA on the widened inputs)
-# weight gradients on a second HIP stream, beside the data-gradient / BatchNorm-backward chain they do not feed (-2 % step
-# time).  bench.py switches it off while it times single kernels with HIP events (two kernels sharing the chip are not
-# attributable).
-_WGRAD_SIDE_STREAM = False
-_FUSE_LAYER0_BWD = True     # BatchNorm backward + activation derivative + first-conv weight gradient in one sweep
-_LEAKY_SIGNS = True         # LeakyReLU blocks without BatchNorm hand the next data gradient a 1-bit sign map, not the bf16 output
-_L0_MFMA = True             # layer 0 (uint8 image, 1 -> <=16 channels, stride 2, BatchNorm) on the matrix cores
-_L0_GRAM = True             # ... with the batch statistics from the exact integer patch Gram matrix (backward reuses it)
-_WGRAD_DEFER_REDUCE = True  # the per-layer split-K reductions of the weight gradients in one launch at the end of the backward pass
-_L0_NO_Z = True             # ... and without its conv output in memory: sign map + derived sums (yogo_conv_first_*_xs)
-_PACK_MULTI = True          # all weight packings of a step in one launch
-_L01_FUSE_BWD = True        # layer 1's data gradient folded into layer 0's backward sums (yogo_conv2d_dgrad_bf16_first_bwd): no dy of layer 0 in memory
-_HEAD_BN_FUSE = True        # the 1x1 head's data gradient computed inside the BatchNorm backward of the block under it (yogo_bn_bwd_bf16_head)
-_BN_STATS_PASS = True       # BatchNorm statistics of layers > 0 by a sweep over the stored bf16 output (not the conv epilogue)
-_SIDE_STREAMS: Dict[int, "torch.cuda.Stream"] = {}
-
-
-def _side_stream(dev: torch.device) -> "torch.cuda.Stream":
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
-    if key not in _SIDE_STREAMS:
-        _SIDE_STREAMS[key] = torch.cuda.Stream(device=dev)
-    return _SIDE_STREAMS[key]
+# Fused kernels of the bf16 backward pass.  Each switch names one fused kernel; True is what the product runs, and the test named
+# beside it rebinds the switch (``E._NAME = False``) to compare the kernel with the separate passes it replaces -- so they are
+# plain module globals read at call time.  tools/ab_flag.py times a step either way.
+_FUSE_LAYER0_BWD = True     # BatchNorm backward + activation derivative + first-conv weight gradient in one sweep (tests/test_gpu_bf16.py)
+_L0_NO_Z = True             # ... without layer 0's conv output in memory: sign map + derived sums, yogo_conv_first_*_xs (tests/test_gpu_bf16.py)
+_WGRAD_DEFER_REDUCE = True  # the per-layer split-K reductions of the weight gradients in one launch at the end of the backward pass (tests/test_gpu_bf16.py)
+_L01_FUSE_BWD = True        # layer 1's data gradient folded into layer 0's backward sums, yogo_conv2d_dgrad_wgrad_bf16_first_bwd: no dy of layer 0 in memory (tests/test_gpu_first_fused_bwd.py)
+_HEAD_BN_FUSE = True        # the 1x1 head's data gradient computed inside the BatchNorm backward of the block under it, yogo_bn_bwd_bf16_head (tests/test_gpu_head_bn_fused.py)
 
 
 def _packed_bf16(eng: Engine, i: int, mode: int) -> torch.Tensor:
     L = eng.layers[i]
     w = L.conv.weight
     key = (i, 10 + mode)
-    hit = eng._pack.get(key)
-    if hit is not None and hit[0] == w._version and hit[1] == w.data_ptr():
-        return hit[2]
+    buf = _pack_hit(eng, key, w)
+    if buf is not None:
+        return buf
     nbytes = _hip.query_size("yogo_conv_bf16_packed_bytes", L.cin, L.cout, L.k, mode)
     buf = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
     _hip.call("yogo_conv_bf16_pack", _f32(w.detach()), None, buf, L.cin, L.cout, L.k, mode, _hip.stream_ptr())
@@ -401,13 +420,13 @@ def _pack_all_bf16(eng: Engine) -> None:
     """Forward and data-gradient packings of every matrix-core layer in ONE launch (the weights change every step)."""
     jobs = [(i, mode) for i in range(1, len(eng.layers)) for mode in (0, 2 if (eng.layers[i].s == 2 and eng.layers[i].k == 3) else 1)]
     ws = [eng.layers[i].conv.weight for i, _ in jobs]
-    if any(w.dtype != torch.float32 or not w.is_contiguous() for w in ws) or not jobs or not _PACK_MULTI:
+    if any(w.dtype != torch.float32 or not w.is_contiguous() for w in ws) or not jobs:
         return   # (the per-layer path converts)
-    if all((h := eng._pack.get((i, 10 + m))) is not None and h[0] == w._version and h[1] == w.data_ptr() for (i, m), w in zip(jobs, ws)):
+    if all(_pack_hit(eng, (i, 10 + m), w) is not None for (i, m), w in zip(jobs, ws)):
         return
     dev = ws[0].device
     key = tuple(w.data_ptr() for w in ws)
-    st = getattr(eng, "_pack_multi", None)
+    st = eng._pack_multi
     if st is None or st[0] != key:
         bufs, rows, blk = [], [], 0
         for (i, mode), w in zip(jobs, ws):
@@ -430,7 +449,7 @@ def _dropout_masks(eng: Engine, B: int, dev) -> Dict[int, torch.Tensor]:
     if not act:
         return {}
     key = (B, tuple(act), str(dev))
-    cached = getattr(eng, "_drop_consts", None)
+    cached = eng._drop_consts
     if cached is None or cached[0] != key:
         sizes = [B * eng.layers[i].cout for i, _ in act]
         pvec = torch.cat([torch.full((n,), p, dtype=torch.float32) for n, (_, p) in zip(sizes, act)]).to(dev)
@@ -445,7 +464,7 @@ def _dropout_masks(eng: Engine, B: int, dev) -> Dict[int, torch.Tensor]:
     return out
 
 
-def forward_bf16_train(eng: Engine, x: torch.Tensor) -> Tuple[torch.Tensor, List[Saved]]:
+def _check_bf16_train_input(eng: Engine, x: torch.Tensor) -> None:
     _hip.require_cuda(x, "the input batch")
     if x.ndim != 4:
         raise RuntimeError(f"yogo_amd: expected a [B,C,H,W] batch, got {tuple(x.shape)}")
@@ -454,14 +473,108 @@ def forward_bf16_train(eng: Engine, x: torch.Tensor) -> Tuple[torch.Tensor, List
     for j in range(1, len(eng.layers)):
         if eng.layers[j].cin != eng.layers[j - 1].cout:
             raise RuntimeError(f"yogo_amd: layer {j} expects {eng.layers[j].cin} channels, layer {j - 1} produces {eng.layers[j - 1].cout}")
-    for j, Lj in enumerate(eng.layers):
+    for Lj in eng.layers:
         bnj = Lj.bn
         if (bnj is not None and (bnj.training or bnj.running_mean is None) and bnj.track_running_stats
                 and bnj.running_mean is not None and bnj.momentum is None):
             raise RuntimeError("yogo_amd: BatchNorm2d(momentum=None) is not supported")
-    dev, st, B = x.device, _hip.stream_ptr(), x.shape[0]
     if not eng._first_direct(0):
         raise RuntimeError("yogo_amd: bf16 training needs a 1- or 3-channel 3x3 first convolution")
+
+
+def _first_mfma_fwd_bf16(eng: Engine, L: Layer, S: Saved, bias, bn_train: bool, B: int, H: int, W: int, st) -> torch.Tensor:
+    """Layer 0 (uint8 image, 1 -> <= 16 channels, stride 2, BatchNorm) on the matrix cores: fills ``S``, returns the block output"""
+    cur, dev = S.x_in, S.x_in.device
+    OH, OW = L.out_hw(H, W)
+    bn = L.bn
+    gamma, beta = _bn_affine(L, dev)
+    w32 = _f32(L.conv.weight.detach())
+    y = torch.empty(B, _blocks(L.cout), OH, OW, 8, dtype=torch.bfloat16, device=dev)
+    if bn_train:   # sweep 1: exact integer patch sums -> statistics of all channels (and backward's G)
+        rows = _hip.query_ints("yogo_conv_first_gram_rows", 1, B, H, W)[0]
+        gpart = torch.empty(rows * 54, dtype=torch.int32, device=dev)
+        gram64 = torch.empty(90, dtype=torch.float64, device=dev)
+        S.gram = torch.empty(90, dtype=torch.float32, device=dev)
+        _hip.call("yogo_conv_first_gram", cur, gpart, gram64, S.gram, B, H, W, st)
+        mean, invstd = _bn_finalize(eng, L, "yogo_bn_stats_from_gram", gram64, w32, bias, count=B * OH * OW, dev=dev, st=st)
+    else:
+        invstd = torch.empty(L.cout, dtype=torch.float32, device=dev)
+        _hip.call("yogo_bn_invstd", bn.running_var, float(bn.eps), invstd, L.cout, st)
+        mean = bn.running_mean
+    # sweep 2: the convolution again, y = act(BatchNorm(z)) and what backward needs of z: its sign map when the fused backward
+    # sweep can take that (it derives everything else from its own sums), else z itself
+    no_z = (_L0_NO_Z and _FUSE_LAYER0_BWD and S.gram is not None and L.conv.bias is None
+            and _hip.lib().yogo_conv_first_bn_wgrad_xs_supported(0, L.cin, L.cout, H, W, L.s, L.act))
+    if no_z:
+        out8 = None
+        S.signs0 = torch.empty(B, OH * OW * 2, dtype=torch.uint8, device=dev)
+        _hip.call("yogo_conv_first_mfma_signs", cur, w32, bias, None, y, S.signs0, mean, invstd, gamma, beta, B, L.cout, H, W, L.act, st)
+    else:
+        out8 = torch.empty_like(y)
+        _hip.call("yogo_conv_first_mfma", cur, w32, bias, out8, y, mean, invstd, gamma, beta, None, B, L.cout, H, W, L.act, st)
+    S.mean, S.invstd, S.bn_train, S.z, S.y = mean, invstd, bn_train, out8, y
+    S.w_used = w32.to(torch.bfloat16).to(torch.float32)
+    return y
+
+
+def _layer_fwd_bf16(eng: Engine, i: int, L: Layer, S: Saved, bias, bn_train: bool, last: bool, B: int, H: int, W: int, st) -> torch.Tensor:
+    """One block: the convolution (+bias, activation and dropout mask without BatchNorm), then BatchNorm + activation over its stored
+    output.  The last layer writes fp32 NCHW.  Fills ``S``, returns the block output"""
+    cur, mask, dev = S.x_in, S.mask, S.x_in.device
+    OH, OW = L.out_hw(H, W)
+    has_bn = L.bn is not None
+    if last and (has_bn or mask is not None):
+        raise RuntimeError("yogo_amd: BatchNorm / Dropout on the last layer is not supported by the bf16 path")
+    fused_act = ACT_NONE if has_bn else L.act
+    out8 = None if last else torch.empty(B, _blocks(L.cout), OH, OW, 8, dtype=torch.bfloat16, device=dev)
+    out32 = torch.empty(B, L.cout, OH, OW, dtype=torch.float32, device=dev) if last else None
+    stats = None
+    rows = mpad = 0
+    if i == 0:
+        if bn_train:   # the only conv whose epilogue sums the BatchNorm statistics
+            rows, mpad = _hip.query_ints("yogo_conv_first_stats_rows", 1, B, H, W, L.s)[0], L.cout
+            stats = torch.empty(rows * mpad * 2, dtype=torch.float32, device=dev)
+        _hip.call("yogo_conv_first_fwd_train_bf16", cur, 0 if cur.dtype == torch.uint8 else 1, _f32(L.conv.weight.detach()), bias,
+                  out8, mask, stats, B, L.cin, L.cout, H, W, L.s, fused_act, st)
+    else:
+        pk = _packed_bf16(eng, i, 0)
+        # algorithmic bytes: input + output once at storage precision (bf16 NCHW8c, channels padded to 16; fp32 head)
+        nbytes = B * (_blocks(L.cin) * 8 * H * W * 2 + (L.cout * OH * OW * 4 if last else _blocks(L.cout) * 8 * OH * OW * 2))
+        # mw tags the kernel variant for bench.py: 34 = conv_bf16_kernel<4,2,8,...> (128 output channels, stride 1)
+        eng._tick("fwd", i, 2.0 * B * L.cout * L.cin * L.k * L.k * OH * OW, mw=34 if (L.cout > 64 and L.s == 1) else (35 if (L.cout > 64 and L.cin > 64 and L.k == 3) else 30), nbytes=nbytes)
+        if L.act == ACT_SILU and not has_bn:   # silu'(z) needs the pre-activation: the conv writes it next to the output
+            S.pre = torch.empty_like(out8)
+            _hip.call("yogo_conv2d_fwd_bf16_pre", cur, pk, bias, out8, S.pre, mask, B, L.cin, L.cout, H, W, L.k, L.s, fused_act, st)
+        elif L.act == ACT_LEAKY and not has_bn and not last:   # the data gradient below takes a 1-bit sign map, not the bf16 output
+            S.signs = torch.empty(_hip.query_size("yogo_bf16_signs_bytes", B, L.cout, OH, OW), dtype=torch.uint8, device=dev)
+            _hip.call("yogo_conv2d_fwd_bf16_signs", cur, pk, bias, out8, S.signs, mask, B, L.cin, L.cout, H, W, L.k, L.s, fused_act, st)
+        else:
+            _hip.call("yogo_conv2d_fwd_bf16", cur, pk, bias, out8, out32, mask, None, B, L.cin, L.cout, H, W, L.k, L.s, fused_act, st)
+        eng._tock()
+    if not has_bn:
+        S.y = out32 if last else out8
+        return S.y
+    bn = L.bn
+    gamma, beta = _bn_affine(L, dev)
+    y = torch.empty_like(out8)
+    if bn_train:
+        if i > 0:   # statistics by a sweep over the stored bf16 output
+            rows, mpad = _hip.query_ints("yogo_bn_bwd_bf16_rows", 1, B, OH * OW)[0], L.cout
+            stats = torch.empty(rows * mpad * 2, dtype=torch.float32, device=dev)
+            _hip.call("yogo_bn_stats_bf16", out8, stats, B, L.cout, OH * OW, st)
+        mean, invstd = _bn_finalize(eng, L, "yogo_bn_finalize", stats, rows, mpad, count=B * OH * OW, dev=dev, st=st)
+    else:
+        invstd = torch.empty(L.cout, dtype=torch.float32, device=dev)
+        _hip.call("yogo_bn_invstd", bn.running_var, float(bn.eps), invstd, L.cout, st)
+        mean = bn.running_mean
+    _hip.call("yogo_bn_apply_act_bf16", out8, y, mean, invstd, 0, float(bn.eps), gamma, beta, B, L.cout, OH * OW, L.act, st)
+    S.mean, S.invstd, S.bn_train, S.z, S.y = mean, invstd, bn_train, out8, y
+    return y
+
+
+def forward_bf16_train(eng: Engine, x: torch.Tensor) -> Tuple[torch.Tensor, List[Saved]]:
+    _check_bf16_train_input(eng, x)
+    dev, st, B = x.device, _hip.stream_ptr(), x.shape[0]
     _pack_all_bf16(eng)
     masks = _dropout_masks(eng, B, dev)
     cur = x.contiguous() if x.dtype == torch.uint8 else _f32(x)
@@ -474,134 +587,16 @@ def forward_bf16_train(eng: Engine, x: torch.Tensor) -> Tuple[torch.Tensor, List
             raise RuntimeError(f"yogo_amd: image too small at layer {i}")
         last = i == n - 1
         has_bn = L.bn is not None
-        silu_pre = L.act == ACT_SILU and not has_bn   # silu'(z) needs the pre-activation: the conv writes it next to the output
-        if silu_pre and (i == 0 or last):
+        if L.act == ACT_SILU and not has_bn and (i == 0 or last):
             raise RuntimeError("yogo_amd: bf16 training of a first / last SiLU block without BatchNorm is not implemented (use fp32)")
         bias = _f32(L.conv.bias.detach()) if L.conv.bias is not None else None
-        S = Saved(x_in=cur)
-        mask = None
-        if i in masks:
-            mask = masks[i]
-            S.mask = mask
+        S = Saved(x_in=cur, mask=masks.get(i))
         bn_train = has_bn and (L.bn.training or L.bn.running_mean is None)
-        if (i == 0 and _L0_MFMA and has_bn and mask is None and not last and cur.dtype == torch.uint8
+        if (i == 0 and has_bn and S.mask is None and not last and cur.dtype == torch.uint8
                 and _hip.lib().yogo_conv_first_mfma_supported(0, L.cin, L.cout, H, W, L.s)):
-            bn = L.bn
-            gamma = _f32(bn.weight.detach()) if bn.weight is not None else torch.ones(L.cout, device=dev)
-            beta = _f32(bn.bias.detach()) if bn.bias is not None else torch.zeros(L.cout, device=dev)
-            w32 = _f32(L.conv.weight.detach())
-            y = torch.empty(B, _blocks(L.cout), OH, OW, 8, dtype=torch.bfloat16, device=dev)
-            if bn_train and _L0_GRAM:   # sweep 1: exact integer patch sums -> statistics of all channels (and backward's G)
-                rows = _hip.query_ints("yogo_conv_first_gram_rows", 1, B, H, W)[0]
-                gpart = torch.empty(rows * 54, dtype=torch.int32, device=dev)
-                gram64 = torch.empty(90, dtype=torch.float64, device=dev)
-                S.gram = torch.empty(90, dtype=torch.float32, device=dev)
-                _hip.call("yogo_conv_first_gram", cur, gpart, gram64, S.gram, B, H, W, st)
-                mean = torch.empty(L.cout, dtype=torch.float32, device=dev)
-                invstd = torch.empty(L.cout, dtype=torch.float32, device=dev)
-                track = bn.track_running_stats and bn.running_mean is not None
-                _hip.call("yogo_bn_stats_from_gram", gram64, w32, bias, L.cout, B * OH * OW, float(bn.eps),
-                          float(bn.momentum if bn.momentum is not None else 0.0), mean, invstd,
-                          bn.running_mean if track else None, bn.running_var if track else None,
-                          bn.num_batches_tracked if track else None, st)
-                if track:
-                    eng.generation += 1
-            elif bn_train:   # sweep 1: batch statistics, nothing written
-                rows = _hip.query_ints("yogo_conv_first_mfma_stats_rows", 1, B, H, W)[0]
-                stats = torch.empty(rows * 16 * 2, dtype=torch.float32, device=dev)
-                _hip.call("yogo_conv_first_mfma", cur, w32, bias, None, None, None, None, None, None, stats, B, L.cout, H, W, L.act, st)
-                mean = torch.empty(L.cout, dtype=torch.float32, device=dev)
-                invstd = torch.empty(L.cout, dtype=torch.float32, device=dev)
-                track = bn.track_running_stats and bn.running_mean is not None
-                _hip.call("yogo_bn_finalize", stats, rows, 16, L.cout, B * OH * OW, float(bn.eps),
-                          float(bn.momentum if bn.momentum is not None else 0.0), mean, invstd,
-                          bn.running_mean if track else None, bn.running_var if track else None,
-                          bn.num_batches_tracked if track else None, st)
-                if track:
-                    eng.generation += 1
-            else:
-                invstd = torch.empty(L.cout, dtype=torch.float32, device=dev)
-                _hip.call("yogo_bn_invstd", bn.running_var, float(bn.eps), invstd, L.cout, st)
-                mean = bn.running_mean
-            # sweep 2: the convolution again, y = act(BatchNorm(z)) and what backward needs of z: its sign map when the fused backward
-            # sweep can take that (it derives everything else from its own sums), else z itself
-            no_z = (_L0_NO_Z and _FUSE_LAYER0_BWD and S.gram is not None and L.conv.bias is None
-                    and _hip.lib().yogo_conv_first_bn_wgrad_xs_supported(0, L.cin, L.cout, H, W, L.s, L.act))
-            if no_z:
-                out8 = None
-                S.signs0 = torch.empty(B, OH * OW * 2, dtype=torch.uint8, device=dev)
-                _hip.call("yogo_conv_first_mfma_signs", cur, w32, bias, None, y, S.signs0, mean, invstd, gamma, beta, B, L.cout, H, W, L.act, st)
-            else:
-                out8 = torch.empty_like(y)
-                _hip.call("yogo_conv_first_mfma", cur, w32, bias, out8, y, mean, invstd, gamma, beta, None, B, L.cout, H, W, L.act, st)
-            S.mean, S.invstd, S.bn_train, S.z, S.y = mean, invstd, bn_train, out8, y
-            S.w_used = w32.to(torch.bfloat16).to(torch.float32)
-            cur = y
-            saved.append(S)
-            H, W = OH, OW
-            continue
-        fused_act = ACT_NONE if has_bn else L.act
-        stats = None
-        rows = mpad = 0
-        stats_pass = bn_train and i > 0 and _BN_STATS_PASS   # statistics by a separate sweep over the stored output
-        if bn_train and not stats_pass:
-            if i == 0:
-                rows, mpad = _hip.query_ints("yogo_conv_first_stats_rows", 1, B, H, W, L.s)[0], L.cout
-            else:
-                rows, mpad = _hip.query_ints("yogo_conv2d_fwd_bf16_stats_shape", 2, B, L.cin, L.cout, H, W, L.k, L.s)
-            stats = torch.empty(rows * mpad * 2, dtype=torch.float32, device=dev)
-        out8 = None if last else torch.empty(B, _blocks(L.cout), OH, OW, 8, dtype=torch.bfloat16, device=dev)
-        out32 = torch.empty(B, L.cout, OH, OW, dtype=torch.float32, device=dev) if last else None
-        if last and (has_bn or mask is not None):
-            raise RuntimeError("yogo_amd: BatchNorm / Dropout on the last layer is not supported by the bf16 path")
-        if i == 0:
-            _hip.call("yogo_conv_first_fwd_train_bf16", cur, 0 if cur.dtype == torch.uint8 else 1, _f32(L.conv.weight.detach()), bias,
-                      out8, mask, stats, B, L.cin, L.cout, H, W, L.s, fused_act, st)
+            cur = _first_mfma_fwd_bf16(eng, L, S, bias, bn_train, B, H, W, st)
         else:
-            pk = _packed_bf16(eng, i, 0)
-            # algorithmic bytes: input + output once at storage precision (bf16 NCHW8c, channels padded to 16; fp32 head)
-            nbytes = B * (_blocks(L.cin) * 8 * H * W * 2 + (L.cout * OH * OW * 4 if last else _blocks(L.cout) * 8 * OH * OW * 2))
-            # mw tags the kernel variant for bench.py: 34 = conv_bf16_kernel<4,2,8,...> (128 output channels, stride 1)
-            eng._tick("fwd", i, 2.0 * B * L.cout * L.cin * L.k * L.k * OH * OW, mw=34 if (L.cout > 64 and L.s == 1) else (35 if (L.cout > 64 and L.cin > 64 and L.k == 3) else 30), nbytes=nbytes)
-            if silu_pre:
-                S.pre = torch.empty_like(out8)
-                _hip.call("yogo_conv2d_fwd_bf16_pre", cur, pk, bias, out8, S.pre, mask, B, L.cin, L.cout, H, W, L.k, L.s, fused_act, st)
-            elif _LEAKY_SIGNS and L.act == ACT_LEAKY and not has_bn and not last:
-                S.signs = torch.empty(_hip.query_size("yogo_bf16_signs_bytes", B, L.cout, OH, OW), dtype=torch.uint8, device=dev)
-                _hip.call("yogo_conv2d_fwd_bf16_signs", cur, pk, bias, out8, S.signs, mask, B, L.cin, L.cout, H, W, L.k, L.s, fused_act, st)
-            else:
-                _hip.call("yogo_conv2d_fwd_bf16", cur, pk, bias, out8, out32, mask, stats, B, L.cin, L.cout, H, W, L.k, L.s, fused_act, st)
-            eng._tock()
-        if has_bn:
-            bn = L.bn
-            gamma = _f32(bn.weight.detach()) if bn.weight is not None else torch.ones(L.cout, device=dev)
-            beta = _f32(bn.bias.detach()) if bn.bias is not None else torch.zeros(L.cout, device=dev)
-            y = torch.empty_like(out8)
-            if bn_train:
-                if stats_pass:
-                    rows, mpad = _hip.query_ints("yogo_bn_bwd_bf16_rows", 1, B, OH * OW)[0], L.cout
-                    stats = torch.empty(rows * mpad * 2, dtype=torch.float32, device=dev)
-                    _hip.call("yogo_bn_stats_bf16", out8, stats, B, L.cout, OH * OW, st)
-                mean = torch.empty(L.cout, dtype=torch.float32, device=dev)
-                invstd = torch.empty(L.cout, dtype=torch.float32, device=dev)
-                track = bn.track_running_stats and bn.running_mean is not None
-                _hip.call("yogo_bn_finalize", stats, rows, mpad, L.cout, B * OH * OW, float(bn.eps),
-                          float(bn.momentum if bn.momentum is not None else 0.0), mean, invstd,
-                          bn.running_mean if track else None, bn.running_var if track else None,
-                          bn.num_batches_tracked if track else None, st)
-                if track:
-                    eng.generation += 1
-                _hip.call("yogo_bn_apply_act_bf16", out8, y, mean, invstd, 0, float(bn.eps), gamma, beta, B, L.cout, OH * OW, L.act, st)
-            else:
-                invstd = torch.empty(L.cout, dtype=torch.float32, device=dev)
-                _hip.call("yogo_bn_invstd", bn.running_var, float(bn.eps), invstd, L.cout, st)
-                mean = bn.running_mean
-                _hip.call("yogo_bn_apply_act_bf16", out8, y, mean, invstd, 0, float(bn.eps), gamma, beta, B, L.cout, OH * OW, L.act, st)
-            S.mean, S.invstd, S.bn_train, S.z, S.y = mean, invstd, bn_train, out8, y
-            cur = y
-        else:
-            S.y = out32 if last else out8
-            cur = S.y
+            cur = _layer_fwd_bf16(eng, i, L, S, bias, bn_train, last, B, H, W, st)
         saved.append(S)
         H, W = OH, OW
     return cur, saved
@@ -632,7 +627,10 @@ def backward_bf16_train(eng: Engine, saved: List[Saved], graw: torch.Tensor,
             return grad_out[id(param)]
         return torch.empty(param.shape, dtype=torch.float32, device=dev)
 
-    keep: list = []   # tensors in use on the weight-gradient stream
+    # Everything runs on the current stream, so the caching allocator orders each tensor's reuse behind its last use -- except the
+    # split-K workspaces of a deferred reduction: the flush that reads them is enqueued layers later, so they stay referenced here
+    # until the pass returns (freed earlier, a later layer's tensors would be handed their memory and overwrite the partial sums).
+    queued_ws: List[torch.Tensor] = []
     # the split-K reductions of the weight gradients: deferred to ONE launch behind the last layer -- unless a per-layer hook wants
     # each layer's gradients as soon as the layer is through
     wq = _wgrad_queue() if (_WGRAD_DEFER_REDUCE and (on_layer is None or flush_layers is not None)) else None
@@ -647,179 +645,164 @@ def backward_bf16_train(eng: Engine, saved: List[Saved], graw: torch.Tensor,
         B, P, Sy, Sx = graw.shape
         g = torch.empty(B, _blocks(P), Sy, Sx, 8, dtype=torch.bfloat16, device=dev)
         _hip.call("yogo_nchw_f32_to_bf16_8c", graw, g, B, P, Sy * Sx, st)
-    head_g = None    # (head gradient, head weights) when the head's data gradient is left to the BatchNorm backward of the block under it
-    fused01 = None   # (part, rows) of layer 0's backward sums when layer 1's data gradient produced them (g is then None at layer 0)
+
+    def bn_backward(L, S, g, head_g, OH, OW):
+        """dz of the block (in place of g); given ``head_g``, the head's data gradient is computed inside both sweeps"""
+        gamma, beta = _bn_affine(L, dev)
+        dgamma, dbeta = _bn_grad_dst(L.bn, dst, grads, L.cout, dev)
+        rows = _hip.query_ints("yogo_bn_bwd_bf16_rows", 1, B, OH * OW)[0]
+        part = torch.empty(rows * L.cout * 2, dtype=torch.float32, device=dev)
+        sums = torch.empty(2 * L.cout, dtype=torch.float32, device=dev)
+        if head_g is not None:
+            dz = torch.empty(B, _blocks(L.cout), OH, OW, 8, dtype=torch.bfloat16, device=dev)
+            _hip.call("yogo_bn_bwd_bf16_head", *head_g, S.z, dz, S.mean, S.invstd, gamma, beta, L.act, dgamma, dbeta,
+                      part, sums, B, L.cout, OH * OW, 1 if S.bn_train else 0, clip, st)
+        else:
+            dz = g
+            _hip.call("yogo_bn_bwd_bf16", g, S.z, dz, S.mean, S.invstd, gamma, beta, L.act, dgamma, dbeta, part, sums, B, L.cout, OH * OW,
+                      1 if S.bn_train else 0, clip, st)
+        return dz
+
+    def wgrad_first_bn(L, S, g, fused01, dw, IH, IW):
+        """layer 0 with BatchNorm and no conv bias: BatchNorm backward, activation derivative and the weight gradient share ONE sweep
+        over (image, g, z or its sign map) -- dz is never written (see conv_first_bn_wgrad_kernel).  ``g`` is None exactly when
+        ``fused01`` is set: layer 1's sweep has then already folded its data gradient into the partial sums"""
+        gamma, beta = _bn_affine(L, dev)
+        dgamma, dbeta = _bn_grad_dst(L.bn, dst, grads, L.cout, dev)
+        cols = _hip.query_ints("yogo_conv_first_bn_wgrad_cols", 1, L.cin, L.cout)[0]
+        sums = torch.empty(cols, dtype=torch.float32, device=dev)
+        xg = "_xs" if S.signs0 is not None else "_xg" if S.gram is not None else ""
+        if fused01 is not None:   # layer 1's data gradient has filled the partial sums
+            part, rows = fused01[:2]
+        else:
+            rows = _hip.query_ints("yogo_conv_first_wgrad_rows", 1, B, IH, IW, L.s)[0]
+            part = torch.empty(rows * cols, dtype=torch.float32, device=dev)
+            _hip.call("yogo_conv_first_bn_wgrad_bf16" + xg, S.x_in, 0 if S.x_in.dtype == torch.uint8 else 1, g,
+                      S.signs0 if S.signs0 is not None else S.z, S.mean, S.invstd, gamma, beta, part, B, L.cin, L.cout, IH, IW, L.s, L.act, st)
+        _hip.call("yogo_partials_reduce", part, rows, cols, 0.0, sums, st)
+        _hip.call("yogo_conv_first_bn_wgrad_finalize" + xg, sums, *((S.gram,) if S.gram is not None else ()), S.mean, S.invstd, gamma,
+                  S.w_used if S.w_used is not None else _f32(L.conv.weight.detach()), dw, dgamma,
+                  dbeta, B, L.cin, L.cout, IH, IW, L.s, 1 if S.bn_train else 0, clip, st)
+
+    def wgrad_dgrad_first(L, S, g, dw, db, IH, IW, OH, OW):
+        """layer 1 above a matrix-core layer 0 that kept its sign map: ONE sweep over g does layer 1's weight gradient and folds its
+        data gradient straight into layer 0's backward sums, which it returns as (part, rows, IH, IW)"""
+        L0, S0 = eng.layers[0], saved[0]
+        ws = torch.empty(_hip.query_size("yogo_conv2d_dgrad_wgrad_first_bwd_workspace_bytes", B, IH, IW) // 4, dtype=torch.float32, device=dev)
+        rows = _hip.query_ints("yogo_conv2d_dgrad_first_bwd_rows", 1, B, IH, IW, 1)[0]
+        cols = _hip.query_ints("yogo_conv_first_bn_wgrad_cols", 1, L0.cin, L0.cout)[0]
+        part = torch.empty(rows * cols, dtype=torch.float32, device=dev)
+        queued_ws.append(ws)
+        eng._tick("wgrad", 1, 2.0 * B * L.cout * L.cin * L.k * L.k * OH * OW * 2, mw=30,
+                  nbytes=B * (16 * (_blocks(L.cout) + _blocks(L.cin)) * OH * OW + 2 * IH * IW + 4 * IH * IW))
+        _hip.call("yogo_conv2d_dgrad_wgrad_bf16_first_bwd", g, _packed_bf16(eng, 1, 1), S.x_in, S0.x_in, S0.signs0, part, dw, db, ws,
+                  B, L.cin, L.cout, IH, IW, L0.act, clip, wq, st)
+        eng._tock()
+        return part, rows, IH, IW
+
+    def wgrad_first(L, S, g, dw, db, IH, IW):
+        """any other layer 0: partial sums over the image rows, then one reduction of weight and bias gradient together"""
+        rows = _hip.query_ints("yogo_conv_first_wgrad_rows", 1, B, IH, IW, L.s)[0]
+        nj = L.cin * 9 + 1
+        part = torch.empty(rows * L.cout * nj, dtype=torch.float32, device=dev)
+        red = torch.empty(L.cout, nj, dtype=torch.float32, device=dev)
+        _hip.call("yogo_conv_first_wgrad_bf16g", S.x_in, 0 if S.x_in.dtype == torch.uint8 else 1, g, part, B, L.cin, L.cout, IH, IW, L.s, st)
+        _hip.call("yogo_partials_reduce", part, rows, L.cout * nj, clip, red, st)
+        dw.view(L.cout, nj - 1).copy_(red[:, : nj - 1])
+        if db is not None:
+            db.copy_(red[:, nj - 1])
+
+    def wgrad(i, L, S, g, dw, db, IH, IW, OH, OW):
+        """layers > 0 on the bf16 matrix cores; with the queue, the split-K reduction waits for the next flush"""
+        ws = torch.empty(_hip.query_size("yogo_conv2d_wgrad_bf16_workspace_bytes", B, L.cin, L.cout, IH, IW, L.k, L.s) // 4,
+                         dtype=torch.float32, device=dev)
+        eng._tick("wgrad", i, 2.0 * B * L.cout * L.cin * L.k * L.k * OH * OW, mw=30,
+                  nbytes=B * 2 * 8 * (_blocks(L.cout) * OH * OW + _blocks(L.cin) * IH * IW))
+        if wq is not None:
+            queued_ws.append(ws)
+            _hip.call("yogo_conv2d_wgrad_bf16_deferred", S.x_in, g, dw, db, ws, B, L.cin, L.cout, IH, IW, L.k, L.s, clip, wq, st)
+        else:
+            _hip.call("yogo_conv2d_wgrad_bf16", S.x_in, g, dw, db, ws, B, L.cin, L.cout, IH, IW, L.k, L.s, clip, st)
+        eng._tock()
+
+    def dgrad(i, L, g, Sp, act_ref, ref_act, IH, IW, OH, OW):
+        """data gradient of layer i with the activation derivative and dropout mask of the block below fused into its epilogue"""
+        pk = _packed_bf16(eng, i, 2 if (L.s == 2 and L.k == 3) else 1)
+        dx = torch.empty(B, _blocks(L.cin), IH, IW, 8, dtype=torch.bfloat16, device=dev)
+        signs = Sp.signs if ref_act == ACT_LEAKY else None   # one byte per 16-byte unit in place of the reference
+        if signs is not None:
+            nbytes = B * (16 * _blocks(L.cout) * OH * OW + 17 * _blocks(L.cin) * IH * IW)
+        else:
+            nbytes = B * 2 * 8 * (_blocks(L.cout) * OH * OW + _blocks(L.cin) * IH * IW * (2 if act_ref is not None else 1))
+        eng._tick("dgrad", i, 2.0 * B * L.cout * L.cin * L.k * L.k * OH * OW, mw=34 if (L.cin > 64 and L.s == 1 and act_ref is None) else 30, nbytes=nbytes)
+        if signs is not None:
+            _hip.call("yogo_conv2d_dgrad_bf16_signs", g, pk, dx, signs, Sp.mask, B, L.cin, L.cout, IH, IW, L.k, L.s, st)
+        else:
+            _hip.call("yogo_conv2d_dgrad_bf16", g, pk, dx, act_ref, ref_act, Sp.mask, B, L.cin, L.cout, IH, IW, L.k, L.s, st)
+        eng._tock()
+        return dx
+
+    head_g = None    # (head gradient, head weights, head channels) while the head's data gradient is left to the BatchNorm backward below
+    fused01 = None   # (part, rows, OH, OW) of layer 0's backward sums when layer 1's sweep produced them (g is then None at layer 0)
     for i in range(n - 1, stop_at - 1, -1):
         L, S = eng.layers[i], saved[i]
         OH, OW = (int(g.shape[2]), int(g.shape[3])) if g is not None else fused01[2:]
-        if i == 0:
-            IH, IW = int(S.x_in.shape[2]), int(S.x_in.shape[3])
-        else:
-            IH, IW = int(S.x_in.shape[2]), int(S.x_in.shape[3])   # NCHW8c: [B, Cb, H, W, 8]
-        # layer 0 with BatchNorm and no conv bias: BatchNorm backward, activation derivative and the weight gradient share ONE
-        # sweep over (image, g, z) -- dz is never written (see conv_first_bn_wgrad_kernel)
+        IH, IW = int(S.x_in.shape[2]), int(S.x_in.shape[3])
+        Lp, Sp = (eng.layers[i - 1], saved[i - 1]) if i > stop_at else (None, None)
+        # ---- the plan of this layer --------------------------------------------------------------------------------------
+        # layer 0's BatchNorm backward and weight gradient in one sweep (wgrad_first_bn)
         fuse0 = _FUSE_LAYER0_BWD and i == 0 and L.bn is not None and L.conv.bias is None and L.act in (ACT_NONE, ACT_LEAKY)
-        # layer 1 above a matrix-core layer 0 that kept its sign map: ONE sweep over g does layer 1's weight gradient and folds its data
-        # gradient straight into layer 0's backward sums (layer 0 has no data gradient of its own, so its dy need not exist; a trace
-        # then has no ("g", 0))
+        # layer 1's weight gradient and data gradient in one sweep that feeds layer 0's (wgrad_dgrad_first): layer 0 has no data
+        # gradient of its own, so its dy need not exist; a trace then has no ("g", 0)
         fuse01 = False
-        if _L01_FUSE_BWD and i == 1 and stop_at == 0 and _FUSE_LAYER0_BWD and _WGRAD_BF16_MFMA:
-            L0, S0 = eng.layers[0], saved[0]
-            fuse01 = bool(S0.signs0 is not None and S0.x_in.dtype == torch.uint8 and L0.bn is not None and L0.conv.bias is None and L0.cin == 1
-                          and L0.s == 2 and L0.act in (ACT_NONE, ACT_LEAKY) and L.k == 3 and L.s == 1 and S0.mask is None
-                          and _hip.lib().yogo_conv2d_dgrad_first_bwd_supported(L.cin, L.cout, IH, IW, B, L0.act))
+        if _L01_FUSE_BWD and i == 1 and stop_at == 0 and _FUSE_LAYER0_BWD:
+            fuse01 = bool(Sp.signs0 is not None and Sp.x_in.dtype == torch.uint8 and Lp.bn is not None and Lp.conv.bias is None and Lp.cin == 1
+                          and Lp.s == 2 and Lp.act in (ACT_NONE, ACT_LEAKY) and L.k == 3 and L.s == 1 and Sp.mask is None
+                          and _hip.lib().yogo_conv2d_dgrad_first_bwd_supported(L.cin, L.cout, IH, IW, B, Lp.act))
+        # the 1x1 head above a BatchNorm block leaves its data gradient to that block's BatchNorm backward: 12 multiply-adds per element
+        # there are cheaper than writing and twice reading the 128-channel data gradient (a trace then has no ("g", n - 2))
+        head_below = bool(_HEAD_BN_FUSE and i == n - 1 and Lp is not None and i - 1 > 0 and L.k == 1 and L.s == 1 and L.cout <= 16
+                          and Lp.bn is not None and Lp.cout % 16 == 0 and g.shape[1] == 2)
+        # the reference the data gradient takes for the activation derivative of the block below: none when that block's BatchNorm
+        # backward applies it, its output for LeakyReLU (sign of the output = sign of the pre-activation), its pre-activation for SiLU
+        act_ref, ref_act = None, ACT_NONE
+        if Lp is not None and Lp.bn is None and Lp.act != ACT_NONE:
+            act_ref, ref_act = (Sp.y if Lp.act == ACT_LEAKY else Sp.pre), Lp.act
         if trace is not None and g is not None and head_g is None:   # (under head_g, g is still the head's gradient: recorded above)
             trace[("g", i)] = g.clone()
+        # ---- BatchNorm backward ------------------------------------------------------------------------------------------
         if L.bn is not None and not fuse0:
-            bn = L.bn
-            gamma = _f32(bn.weight.detach()) if bn.weight is not None else torch.ones(L.cout, device=dev)
-            beta = _f32(bn.bias.detach()) if bn.bias is not None else torch.zeros(L.cout, device=dev)
-            dgamma = dst(bn.weight) if bn.weight is not None else torch.empty(L.cout, dtype=torch.float32, device=dev)
-            dbeta = dst(bn.bias) if bn.bias is not None else torch.empty(L.cout, dtype=torch.float32, device=dev)
-            rows = _hip.query_ints("yogo_bn_bwd_bf16_rows", 1, B, OH * OW)[0]
-            part = torch.empty(rows * L.cout * 2, dtype=torch.float32, device=dev)
-            sums = torch.empty(2 * L.cout, dtype=torch.float32, device=dev)
-            if head_g is not None:   # (g is still the head's output gradient: its data gradient is computed inside both sweeps)
-                dz = torch.empty(B, _blocks(L.cout), OH, OW, 8, dtype=torch.bfloat16, device=dev)
-                _hip.call("yogo_bn_bwd_bf16_head", head_g[0], head_g[1], head_g[2], S.z, dz, S.mean, S.invstd, gamma, beta, L.act, dgamma, dbeta,
-                          part, sums, B, L.cout, OH * OW, 1 if S.bn_train else 0, clip, st)
-                keep.extend(head_g[:2])
-                g, head_g = dz, None
-            else:
-                _hip.call("yogo_bn_bwd_bf16", g, S.z, g, S.mean, S.invstd, gamma, beta, L.act, dgamma, dbeta, part, sums, B, L.cout, OH * OW,
-                          1 if S.bn_train else 0, clip, st)
-            if bn.weight is not None:
-                grads[id(bn.weight)] = dgamma
-                grads[id(bn.bias)] = dbeta
+            g, head_g = bn_backward(L, S, g, head_g, OH, OW), None
             if trace is not None:
                 trace[("dz", i)] = g.clone()
-        # ---- weight / bias gradient: independent of everything downstream -> second stream -------------------------------
-        # Everything the side stream touches is allocated here, from the MAIN stream's pool, and kept alive until the main
-        # stream has waited for the side stream (end of this function): no record_stream bookkeeping, no allocator stalls.
-        main = torch.cuda.current_stream()
-        wstream = _side_stream(dev) if _WGRAD_SIDE_STREAM else main
+        # ---- weight / bias gradient --------------------------------------------------------------------------------------
         dw = dst(L.conv.weight)
-        has_bias = L.conv.bias is not None
-        db = dst(L.conv.bias) if has_bias else None
+        db = dst(L.conv.bias) if L.conv.bias is not None else None
         if fuse0:
-            bn = L.bn
-            gamma = _f32(bn.weight.detach()) if bn.weight is not None else torch.ones(L.cout, device=dev)
-            beta = _f32(bn.bias.detach()) if bn.bias is not None else torch.zeros(L.cout, device=dev)
-            dgamma = dst(bn.weight) if bn.weight is not None else torch.empty(L.cout, dtype=torch.float32, device=dev)
-            dbeta = dst(bn.bias) if bn.bias is not None else torch.empty(L.cout, dtype=torch.float32, device=dev)
-            cols = _hip.query_ints("yogo_conv_first_bn_wgrad_cols", 1, L.cin, L.cout)[0]
-            if fused01 is not None:
-                part, rows = fused01[:2]
-            else:
-                rows = _hip.query_ints("yogo_conv_first_wgrad_rows", 1, B, IH, IW, L.s)[0]
-                part = torch.empty(rows * cols, dtype=torch.float32, device=dev)
-            sums = torch.empty(cols, dtype=torch.float32, device=dev)
-            keep.extend((gamma, beta, dgamma, dbeta, part, sums))
-        elif i == 0:
-            rows = _hip.query_ints("yogo_conv_first_wgrad_rows", 1, B, IH, IW, L.s)[0]
-            nj = L.cin * 9 + 1
-            part = torch.empty(rows * L.cout * nj, dtype=torch.float32, device=dev)
-            red = torch.empty(L.cout, nj, dtype=torch.float32, device=dev)
-            keep.extend((part, red))
+            wgrad_first_bn(L, S, g, fused01, dw, IH, IW)
         elif fuse01:
-            ws = torch.empty(_hip.query_size("yogo_conv2d_dgrad_wgrad_first_bwd_workspace_bytes", B, IH, IW) // 4, dtype=torch.float32, device=dev)
-            rows01 = _hip.query_ints("yogo_conv2d_dgrad_first_bwd_rows", 1, B, IH, IW, 1)[0]
-            cols01 = _hip.query_ints("yogo_conv_first_bn_wgrad_cols", 1, L0.cin, L0.cout)[0]
-            part01 = torch.empty(rows01 * cols01, dtype=torch.float32, device=dev)
-            keep.extend((ws, part01))
+            fused01 = wgrad_dgrad_first(L, S, g, dw, db, IH, IW, OH, OW)
+        elif i == 0:
+            wgrad_first(L, S, g, dw, db, IH, IW)
         else:
-            wname = "yogo_conv2d_wgrad_bf16_workspace_bytes" if _WGRAD_BF16_MFMA else "yogo_conv2d_wgrad_workspace_bytes"
-            ws = torch.empty(_hip.query_size(wname, B, L.cin, L.cout, IH, IW, L.k, L.s) // 4, dtype=torch.float32, device=dev)
-            keep.append(ws)
-        keep.extend((g, S.x_in, dw))
-        if wstream is not main:
-            wstream.wait_stream(main)           # g (= dz of this layer) is complete
-        with torch.cuda.stream(wstream):
-            wst = _hip.stream_ptr()
-            xdt = 0 if S.x_in.dtype == torch.uint8 else 1
-            if fuse0:
-                xg = "_xs" if S.signs0 is not None else "_xg" if S.gram is not None else ""
-                zs = S.signs0 if S.signs0 is not None else S.z
-                keep.append(zs)
-                if fused01 is None:   # (else: layer 1's data gradient has filled `part`)
-                    _hip.call("yogo_conv_first_bn_wgrad_bf16" + xg, S.x_in, xdt, g, zs, S.mean, S.invstd, gamma, beta, part, B, L.cin, L.cout,
-                              IH, IW, L.s, L.act, wst)
-                _hip.call("yogo_partials_reduce", part, rows, cols, 0.0, sums, wst)
-                _hip.call("yogo_conv_first_bn_wgrad_finalize" + xg, sums, *((S.gram,) if S.gram is not None else ()), S.mean, S.invstd, gamma,
-                          S.w_used if S.w_used is not None else _f32(L.conv.weight.detach()), dw, dgamma,
-                          dbeta, B, L.cin, L.cout, IH, IW, L.s, 1 if S.bn_train else 0, clip, wst)
-                if bn.weight is not None:
-                    grads[id(bn.weight)] = dgamma
-                    grads[id(bn.bias)] = dbeta
-            elif fuse01:
-                eng._tick("wgrad", i, 2.0 * B * L.cout * L.cin * L.k * L.k * OH * OW * 2, mw=30,
-                          nbytes=B * (16 * (_blocks(L.cout) + _blocks(L.cin)) * OH * OW + 2 * IH * IW + 4 * IH * IW))
-                _hip.call("yogo_conv2d_dgrad_wgrad_bf16_first_bwd", g, _packed_bf16(eng, i, 1), S.x_in, S0.x_in, S0.signs0, part01, dw, db, ws,
-                          B, L.cin, L.cout, IH, IW, L0.act, clip, wq, wst)
-                eng._tock()
-                fused01 = (part01, rows01, IH, IW)
-            elif i == 0:
-                _hip.call("yogo_conv_first_wgrad_bf16g", S.x_in, xdt, g, part, B, L.cin, L.cout, IH, IW, L.s, wst)
-                _hip.call("yogo_partials_reduce", part, rows, L.cout * nj, clip, red, wst)
-                dw.view(L.cout, nj - 1).copy_(red[:, : nj - 1])
-                if has_bias:
-                    db.copy_(red[:, nj - 1])
-            else:
-                eng._tick("wgrad", i, 2.0 * B * L.cout * L.cin * L.k * L.k * OH * OW, mw=30,
-                          nbytes=B * 2 * 8 * (_blocks(L.cout) * OH * OW + _blocks(L.cin) * IH * IW))
-                if _WGRAD_BF16_MFMA and wq is not None:   # the split-K reduction waits for the flush behind the last layer
-                    _hip.call("yogo_conv2d_wgrad_bf16_deferred", S.x_in, g, dw, db, ws, B, L.cin, L.cout, IH, IW, L.k, L.s, clip, wq, wst)
-                elif _WGRAD_BF16_MFMA:
-                    _hip.call("yogo_conv2d_wgrad_bf16", S.x_in, g, dw, db, ws, B, L.cin, L.cout, IH, IW, L.k, L.s, clip, wst)
-                else:   # exact fp32 MFMA on the widened bf16 inputs
-                    _hip.call("yogo_conv2d_wgrad_bf16in", S.x_in, g, dw, db, ws, B, L.cin, L.cout, IH, IW, L.k, L.s, clip, wst)
-                eng._tock()
-        if has_bias:
+            wgrad(i, L, S, g, dw, db, IH, IW, OH, OW)
+        if db is not None:
             grads[id(L.conv.bias)] = db
         grads[id(L.conv.weight)] = dw
+        # ---- hook --------------------------------------------------------------------------------------------------------
         if on_layer is not None:
             if wq is not None and i in flush_at:   # the hook takes the gradients of layers >= i: their reductions run now, as one launch
-                with torch.cuda.stream(wstream):
-                    _hip.call("yogo_wgrad_reduce_flush", wq, _hip.stream_ptr())
-            if wstream is not main:
-                main.wait_stream(wstream)   # the weight gradient of this layer is part of what the hook hands over
+                _hip.call("yogo_wgrad_reduce_flush", wq, st)
             on_layer(i)
-        if fuse01:   # (layer 1's data gradient went into layer 0's sums above)
+        # ---- data gradient -----------------------------------------------------------------------------------------------
+        if fuse01:   # (went into layer 0's sums above)
             g = None
-            continue
-        if i > stop_at:
-            Lp, Sp = eng.layers[i - 1], saved[i - 1]
-            # the 1x1 head above a BatchNorm block: 12 multiply-adds per element inside that block's BatchNorm backward are cheaper than
-            # writing and twice reading its 128-channel data gradient (a trace then has no ("g", n - 2))
-            if (_HEAD_BN_FUSE and i == n - 1 and L.k == 1 and L.s == 1 and L.cout <= 16 and Lp.bn is not None and i - 1 > 0
-                    and Lp.cout % 16 == 0 and g.shape[1] == 2):
-                head_g = (g, _f32(L.conv.weight.detach()).reshape(L.cout, L.cin), L.cout)
-                continue
-            ref_act = Lp.act
-            if Lp.bn is not None or Lp.act == ACT_NONE:
-                act_ref, ref_act = None, ACT_NONE
-            elif Lp.act == ACT_LEAKY:
-                act_ref = Sp.y        # sign of the output = sign of the pre-activation
-            else:
-                act_ref = Sp.pre      # SiLU: the pre-activation saved by yogo_conv2d_fwd_bf16_pre
-            pk = _packed_bf16(eng, i, 2 if (L.s == 2 and L.k == 3) else 1)
-            dx = torch.empty(B, _blocks(L.cin), IH, IW, 8, dtype=torch.bfloat16, device=dev)
-            nbytes = B * 2 * 8 * (_blocks(L.cout) * OH * OW + _blocks(L.cin) * IH * IW * (2 if act_ref is not None else 1))
-            if ref_act == ACT_LEAKY and Sp.signs is not None:   # one byte per 16-byte unit in place of the reference
-                nbytes = B * (16 * _blocks(L.cout) * OH * OW + 17 * _blocks(L.cin) * IH * IW)
-            eng._tick("dgrad", i, 2.0 * B * L.cout * L.cin * L.k * L.k * OH * OW, mw=34 if (L.cin > 64 and L.s == 1 and act_ref is None) else 30, nbytes=nbytes)
-            if ref_act == ACT_LEAKY and Sp.signs is not None:
-                _hip.call("yogo_conv2d_dgrad_bf16_signs", g, pk, dx, Sp.signs, Sp.mask, B, L.cin, L.cout, IH, IW, L.k, L.s, st)
-            else:
-                _hip.call("yogo_conv2d_dgrad_bf16", g, pk, dx, act_ref, ref_act, Sp.mask, B, L.cin, L.cout, IH, IW, L.k, L.s, st)
-            eng._tock()
-            g = dx
+        elif head_below:
+            head_g = (g, _f32(L.conv.weight.detach()).reshape(L.cout, L.cin), L.cout)
+        elif i > stop_at:
+            g = dgrad(i, L, g, Sp, act_ref, ref_act, IH, IW, OH, OW)
     if wq is not None:   # every layer's split-K reduction in ONE launch (they are ~21 us each, mostly launch and tail latency)
-        with torch.cuda.stream(_side_stream(dev) if _WGRAD_SIDE_STREAM else torch.cuda.current_stream()):
-            _hip.call("yogo_wgrad_reduce_flush", wq, _hip.stream_ptr())
-    if _WGRAD_SIDE_STREAM:
-        torch.cuda.current_stream().wait_stream(_side_stream(dev))
-    keep.clear()
+        _hip.call("yogo_wgrad_reduce_flush", wq, st)
     bb = eng.backbone_ref()
     return [grads.get(id(p)) for p in bb.parameters()]
 
@@ -1051,7 +1034,7 @@ class InferEngineBF16:
                     raise RuntimeError(f"yogo_amd: layer 0 expects {L.cin} channels, got {cur.shape[1]}")
                 mb = _hip.lib().yogo_bf16_channel_blocks(L.cout)
                 out = torch.empty(B, mb, OH, OW, 8, dtype=torch.bfloat16, device=dev)
-                if _L0_MFMA and cur.dtype == torch.uint8 and _hip.lib().yogo_conv_first_mfma_supported(0, L.cin, L.cout, H, W, L.s):
+                if cur.dtype == torch.uint8 and _hip.lib().yogo_conv_first_mfma_supported(0, L.cin, L.cout, H, W, L.s):
                     _hip.call("yogo_conv_first_mfma", cur, wq, bias, out, None, None, None, None, None, None, B, L.cout, H, W, L.act, st)
                 else:
                     _hip.call("yogo_conv_first_fwd_bf16", cur, 0 if cur.dtype == torch.uint8 else 1, wq, bias, out, B, L.cin, L.cout, H, W,
@@ -1094,10 +1077,9 @@ def backbone_infer_bf16(backbone: nn.Sequential, x: torch.Tensor, decode=None):
     (the decode's operands, see InferEngineBF16.forward) the result is ``(tensor, decoded)``: decoded = True when head + decode ran as one
     launch and ``tensor`` already is the decoded prediction"""
     eng = get_engine(backbone)
-    inf = getattr(eng, "_infer_bf16", None)
+    inf = eng._infer_bf16
     if inf is None:
-        inf = InferEngineBF16(eng)
-        eng._infer_bf16 = inf
+        inf = eng._infer_bf16 = InferEngineBF16(eng)
     if not inf.supported():
         return None
     with torch.cuda.device(x.device):

@@ -337,29 +337,29 @@ class HipTrainer:
             hook = self._on_layer_done if self.world > 1 else None
             # the hook needs complete gradients at split_layer only: the deferred split-K reductions are flushed there and at the end
             flush = (self.split_layer,) if hook is not None else None
-            fused = self.half and not m.inference and _FUSED_DECODE_LOSS
-            if fused:
-                # ---- decode + loss forward/backward + decode backward in one pass over the cells (bit-identical to the three calls
-                #      below; the decoded prediction and its gradient never go to memory) ------------------------------------------
-                g8 = torch.empty(B, ((P + 15) // 16) * 2, Sy, Sx, 8, dtype=torch.bfloat16, device=raw.device)
-                _hip.call("yogo_decode_loss_bwd_bf16", raw, lab, cxs, cys, g8, out, ws, B, P, Sy, Sx, aw, ah, wm, hm,
-                          float(L.no_obj_weight), float(L.iou_weight), float(L.classify_weight), float(L.label_smoothing), st)
-                backward_bf16_train(eng, saved, g8, grad_out=self.flat.grad_views, on_layer=hook, trace=self.trace, flush_layers=flush)
-            else:
-                pred = torch.empty_like(raw)
+            lw = (float(L.no_obj_weight), float(L.iou_weight), float(L.classify_weight), float(L.label_smoothing))
+
+            def decode_and_loss():
+                """decode, then loss forward + backward (one kernel): the decoded prediction and the loss's gradient w.r.t. it"""
+                pred, gpred = torch.empty_like(raw), torch.empty_like(raw)
                 _hip.call("yogo_decode_fwd", raw, pred, cxs, cys, B, P, Sy, Sx, aw, ah, wm, hm, int(bool(m.inference)), st)
-                # ---- loss forward + backward (one kernel) -------------------------------------------------------------
-                gpred = torch.empty_like(raw)
-                _hip.call("yogo_loss_fwd_bwd", pred, lab, gpred, out, ws, B, P, Sy, Sx, float(L.no_obj_weight), float(L.iou_weight),
-                          float(L.classify_weight), float(L.label_smoothing), st)
-            # ---- backward: decode, then the backbone (clamp fused into the gradient kernels) -------------------------
-            if fused:
-                pass
-            elif self.half:   # the head's gradient goes straight to bf16 NCHW8c
-                g8 = torch.empty(B, ((P + 15) // 16) * 2, Sy, Sx, 8, dtype=torch.bfloat16, device=raw.device)
+                _hip.call("yogo_loss_fwd_bwd", pred, lab, gpred, out, ws, B, P, Sy, Sx, *lw, st)
+                return pred, gpred
+
+            # ---- loss and backward: decode, loss, decode backward, then the backbone (clamp fused into the gradient kernels) ----
+            # on the bf16 path the head's gradient goes straight to bf16 NCHW8c
+            g8 = torch.empty(B, ((P + 15) // 16) * 2, Sy, Sx, 8, dtype=torch.bfloat16, device=raw.device) if self.half else None
+            if self.half and not m.inference and _FUSED_DECODE_LOSS:
+                # decode + loss forward/backward + decode backward in one pass over the cells (bit-identical to the three calls of
+                # the next branch; the decoded prediction and its gradient never go to memory)
+                _hip.call("yogo_decode_loss_bwd_bf16", raw, lab, cxs, cys, g8, out, ws, B, P, Sy, Sx, aw, ah, wm, hm, *lw, st)
+                backward_bf16_train(eng, saved, g8, grad_out=self.flat.grad_views, on_layer=hook, trace=self.trace, flush_layers=flush)
+            elif self.half:
+                pred, gpred = decode_and_loss()
                 _hip.call("yogo_decode_bwd_bf16", raw, pred, gpred, g8, B, P, Sy, Sx, int(bool(m.inference)), st)
                 backward_bf16_train(eng, saved, g8, grad_out=self.flat.grad_views, on_layer=hook, trace=self.trace, flush_layers=flush)
             else:
+                pred, gpred = decode_and_loss()
                 graw = torch.empty_like(raw)
                 _hip.call("yogo_decode_bwd", raw, pred, gpred, graw, B, P, Sy, Sx, int(bool(m.inference)), st)
                 eng.backward(saved, graw, grad_out=self.flat.grad_views, on_layer=hook)
