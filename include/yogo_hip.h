@@ -178,6 +178,27 @@ int yogo_metrics_accumulate(const float* rows, const float* lab_out, const int* 
                             int nbins, long long* acc, double* bin_conf, double* partial, float* map_rows, long long map_cap, int B,
                             int P, int cap, yogo_stream_t stream);
 
+/* ---- inference outputs kept on the device: `yogo infer --device-outputs` (yogo_amd/pred_sink.py) ------------------------------- */
+/* What predict's output stage does per batch with the kept rows (yogo/infer.py:39-124,360-380), without a host read: rows [B][cap][P] /
+ * counts [B] = the output of yogo_format_preds_batched or yogo_decode_format_preds_batched (entries past counts[b] are never read; a
+ * counts[b] outside [0, cap] is clamped).  state (int64, laid out as yogo_pred_sink_state_layout reports) = records in the arena, images
+ * in img_counts, records dropped, image entries dropped, class_counts [C] (C = P - 5).  Record k of image b goes to row
+ * state.records + sum(counts[:b]) + k of arena [arena_cap][reclen], counts[b] to img_counts [img_cap] at state.images + b (int32);
+ * both totals then advance.  What does not fit is counted as dropped and not written.
+ * mode 0: reclen = 8 + C, the columns of format_to_numpy (yogo/utils/prediction_formatting.py:96-156): first_img_id + b, x1*img_w,
+ * y1*img_h, x2*img_w, y2*img_h (one fp32 multiply each), objectness, first-argmax class, its score, the C scores; C <= 255 (the
+ * reference holds the class in a uint8).  mode 1: reclen = P, the row itself.  arena null: nothing is compacted and the totals stay
+ * (mode, img_counts, workspace are not used; count_classes must be 1).
+ * count_classes 1: class_counts[first argmax] += 1 for every kept row whose maximum class score is > 0 (a NaN is the maximum and is
+ * not > 0) -- count_cells_for_formatted_preds, yogo/infer.py:90-124; integer adds only.  workspace: yogo_pred_sink_workspace_bytes. */
+/* offsets (HOST pointer, 6 values): where the record total, the image total, the dropped records, the dropped image entries and
+ * class_counts start in state, then the number of int64 words of state */
+int yogo_pred_sink_state_layout(int C, long long* offsets);
+int yogo_pred_sink_workspace_bytes(int B, size_t* bytes);
+int yogo_pred_sink_append(const float* rows, const int* counts, int B, int cap, int P, int mode, int count_classes,
+                          long long first_img_id, int img_h, int img_w, long long* state, float* arena, long long arena_cap,
+                          int* img_counts, long long img_cap, void* workspace, yogo_stream_t stream);
+
 /* ---- bf16 path: the bf16-autocast forward of `yogo infer` (yogo/infer.py:313-317) and half-precision training
  * (yogo/train.py:315-318, --half) -------------------------------------------------------------------------------------------
  * Activations and activation gradients in "NCHW8c" = [B][C/8][H][W][8] bf16 (C padded to a multiple of 16; padding

@@ -6,6 +6,11 @@ launch for the whole batch (``save_predictions`` / ``format_to_numpy_batched`` /
 reference's per-image Python loops over ``format_preds`` (infer.py:45,73); unless the decoded tensor itself is asked for, the box
 decode runs inside that launch's loads (``YOGO.forward_raw``).  No ``torch.compile``: there is no graph to trace,
 the model is already a fixed sequence of hand-written kernels.
+
+``device_outputs=True`` (``yogo infer --device-outputs``) keeps what those launches leave on the device: a ``PredictionSink`` per
+requested output (yogo_amd/pred_sink.py) compacts and counts the kept rows in HBM, and the host reads them when a sink is drained --
+after the loop, or when ``flush_rows`` records have piled up -- instead of copying the padded rows of every batch.  Same files, same
+counts.
 """
 from __future__ import annotations
 
@@ -21,7 +26,9 @@ from torch.utils.data import DataLoader
 
 from yogo_amd.image_path_dataset import CenterCrop, ZarrDataset, collate_fn, get_dataset
 from yogo_amd.model import YOGO
+from yogo_amd.pred_sink import PredictionSink, npy_columns, split_records
 from yogo_amd.utils import format_to_numpy_batched, get_prediction_class_counts, save_predictions  # noqa: F401
+from yogo_amd.utils.prediction_formatting import format_preds_batched, prediction_rows_to_text
 from yogo_amd.utils.utils import choose_device, draw_yogo_prediction
 from yogo_amd.yogo_dataloader import choose_dataloader_num_workers
 
@@ -59,6 +66,7 @@ def predict(
     min_class_confidence_threshold: float = 0.0,
     half: bool = False,
     return_full_predictions: bool = False,
+    device_outputs: bool = False,
 ) -> Optional[torch.Tensor]:
     if save_preds and draw_boxes:
         raise ValueError("cannot save predictions in YOGO format and draw_boxes at the same time")
@@ -114,6 +122,20 @@ def predict(
     results = torch.zeros((len(image_dataset), 5 + num_classes, model.Sy, model.Sx)) if return_full_predictions else None
     np_results: list = []
     tot_counts = torch.zeros((num_classes,)) if count_predictions else None
+    # device_outputs: one sink per requested output; the names of the images a sink still holds stay here
+    npy_sink = PredictionSink(device, num_classes, "npy", img_hw=(img_h, img_w)) if device_outputs and save_npy else None
+    txt_sink = PredictionSink(device, num_classes, "rows") if device_outputs and save_preds else None
+    count_sink = PredictionSink(device, num_classes, "rows") if device_outputs and count_predictions else None
+    txt_names: List[Path] = []
+    npy_chunks: list = []   # (records, per-image counts) per drain
+
+    def drain_txt() -> None:
+        records, per_image = txt_sink.drain()
+        assert len(per_image) == len(txt_names), f"{len(per_image)} images drained, {len(txt_names)} file names held"
+        for fname, r in zip(txt_names, split_records(records, per_image)):
+            with open(fname, "w") as f:
+                f.write(prediction_rows_to_text(torch.from_numpy(r)))
+        txt_names.clear()
 
     file_iterator = enumerate(loader)
     while True:
@@ -150,13 +172,31 @@ def predict(
                     ax.imshow(bbox_img)
                     plt.show()
                     plt.close()
-        if save_preds:
+        if device_outputs:
+            # the launches of the default path below with the same arguments (--save-npy's fixed 0.5 / 0.5 / xyxy included); the
+            # rows and counts go to the sinks instead of to the host, and nothing in here waits for the device
+            if save_preds:
+                assert output_dir is not None, "output_dir must not be None if save_preds is True"
+                rows, _, counts = format_preds_batched(res, obj_thresh, iou_thresh)
+                txt_sink.append(rows, counts, i * batch_size)
+                txt_names.extend(Path(output_dir) / Path(f).with_suffix(".txt").name for f in fnames)
+                if txt_sink.should_flush():
+                    drain_txt()
+            if save_npy:
+                rows, _, counts = format_preds_batched(res, box_format="xyxy")
+                npy_sink.append(rows, counts, i * batch_size)
+                if npy_sink.should_flush():
+                    npy_chunks.append(npy_sink.drain())
+            if count_predictions:
+                rows, _, counts = format_preds_batched(res, obj_thresh, iou_thresh, "cxcywh", min_class_confidence_threshold)
+                count_sink.add_counts(rows, counts)
+        if save_preds and not device_outputs:
             assert output_dir is not None, "output_dir must not be None if save_preds is True"
             save_predictions([Path(output_dir) / Path(f).with_suffix(".txt").name for f in fnames], res, obj_thresh=obj_thresh, iou_thresh=iou_thresh)
-        if save_npy:
+        if save_npy and not device_outputs:
             ids = [i * batch_size + j for j in range(res.shape[0])]
             np_results.extend(format_to_numpy_batched(ids, res, img_h, img_w))
-        if count_predictions:
+        if count_predictions and not device_outputs:
             tot_counts += get_prediction_class_counts(res, obj_thresh=obj_thresh, iou_thresh=iou_thresh,
                                                       min_class_confidence_threshold=min_class_confidence_threshold)
         if return_full_predictions:
@@ -166,10 +206,18 @@ def predict(
     if pbar is not None:
         pbar.close()
 
+    if txt_sink is not None:
+        drain_txt()
+    if count_sink is not None:
+        tot_counts = count_sink.class_counts()
     if count_predictions:
         print(list(zip(class_names or range(num_classes), map(int, tot_counts))))
     if save_npy:
-        pred_tensors = np.hstack(np_results) if np_results else np.zeros((8 + num_classes, 0), dtype=np.float32)
+        if npy_sink is not None:   # records [N, 8 + C] in image order -> the (8 + C) x N array np.hstack gives below
+            npy_chunks.append(npy_sink.drain())
+            pred_tensors = npy_columns(npy_chunks, num_classes)
+        else:
+            pred_tensors = np.hstack(np_results) if np_results else np.zeros((8 + num_classes, 0), dtype=np.float32)
         filename = Path(path_to_images).resolve().parent.stem if path_to_images else Path(path_to_zarr).resolve().stem
         base = Path(output_dir).resolve() if output_dir is not None else Path.cwd().resolve()
         fp = base / Path(filename).with_suffix(".npy")
@@ -186,5 +234,5 @@ def do_infer(args) -> None:
         draw_boxes=args.draw_boxes, save_preds=args.save_preds, save_npy=args.save_npy, class_names=args.class_names,
         obj_thresh=args.obj_thresh, iou_thresh=args.iou_thresh, batch_size=args.batch_size, device=args.device, use_tqdm=args.use_tqdm,
         vertical_crop_height=args.crop_height, count_predictions=args.count, output_img_ftype=args.output_img_filetype,
-        min_class_confidence_threshold=args.min_class_confidence_threshold, half=args.half,
+        min_class_confidence_threshold=args.min_class_confidence_threshold, half=args.half, device_outputs=args.device_outputs,
     )

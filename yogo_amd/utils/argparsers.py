@@ -172,6 +172,9 @@ def infer_parser(parser=None):
                         help="Parse and save predictions in the same format as on scope - requires `--output-dir` to be set (default: False)")
     parser.add_argument("--count", action=boolean_action, default=False,
                         help="display the final predicted counts per-class (default: False)")
+    parser.add_argument("--device-outputs", default=False, action=boolean_action,
+                        help="compact and count the kept predictions of --save-preds / --save-npy / --count on the GPU and read them once "
+                             "instead of copying every batch's padded rows to the host; same files and counts (default: False)")
     parser.add_argument("--output-dir", type=Path, default=None,
                         help="path to directory for results, either --draw-boxes or --save-preds")
     parser.add_argument("--class-names", help="list of class names - will default to integers if not provided", nargs="*", type=str, default=None)
