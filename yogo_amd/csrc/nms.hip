@@ -124,7 +124,12 @@ struct PredView {
 // [0.25, 1] union (Sterbenz) and keeps its sign and more than 2^-25 union of magnitude outside that range; an infinite union makes both
 // sides infinite or NaN (false, like the quotient); for a zero union the test reads inter > 0 (the quotient is +inf, or NaN for 0 / 0); a
 // negative or NaN union never suppresses.  Only 0 < union < 2^-100 and every other threshold take the division: same truth value for every input
-// (tests/test_gpu_parity.py, test_gpu_infer_fused.py: torch.equal to the oracle, degenerate boxes and thresholds 0.01 / 0.999 included).
+// a pair of boxes can produce (inter is a product of two max(0, .), never negative).  Held on the hardware by tests/test_gpu_nms_boundary.py:
+// pairs with fl32(inter / union) exactly 0.5 and its two neighbours, unions on both sides of 2^-100 and on it, subnormal and overflowing areas,
+// each steered onto the serial path, this loop and the fallback, against a keep list constructed from exact rational arithmetic
+// (tests/test_nms_predicate_host.py, tests/_nms_pairs.py) and against the oracle; random, degenerate and full-size predictions and the
+// thresholds 0.01 / 0.999 in tests/test_gpu_parity.py and test_gpu_infer_fused.py.  (No float32 quotient lies in (1/2, 1/2 + 2^-25] -- shown in
+// the host test --, so the 2^-25 union on the right is a margin the argument uses, not one an input can reach: with 0 there the test is the same.)
 // Measured on the way (dense batch of 256, one box, gpurun_out/r6_nms_ab*.log; 16.2 ms at the start): the general-threshold form of the
 // idea in double precision (inter >= M * union with M the rounding boundary: exact too) 20.6 ms -- two conversions and an fp64 multiply
 // cost more than the fp32 division here; the kept boxes in the outer loop (one LDS read per kept box, not per pair) 17.0 ms; a per-lane
