@@ -374,7 +374,7 @@ def test_decode_backward_straight_to_bf16(inference):
     raw[0, 2, 0, 0] = 90.0                         # beyond the exp clamp: zero gradient
     gout = torch.randn(B, P, Sy, Sx, generator=g).cuda()
     st = h.stream_ptr()
-    cx, cy = torch.linspace(0, 1 - 1 / Sx, Sx).cuda(), torch.linspace(0, 1 - 1 / Sy, Sy).cuda()
+    cx, cy = (t.cuda() for t in O.make_grids(Sx, Sy))   # [Sy, Sx] each: the kernel reads cxs[cell] for every cell
     out = torch.empty_like(raw)
     h.call("yogo_decode_fwd", raw, out, cx, cy, B, P, Sy, Sx, 0.05, 0.06, 1.0, 1.0, inference, st)
     g32 = torch.empty_like(raw)

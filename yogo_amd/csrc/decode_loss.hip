@@ -110,6 +110,14 @@ __global__ __launch_bounds__(256) void decode_bwd_bf16_kernel(const float* __res
 // d max(a,b)/da as torch's `maximum` backward: 1 if a > b, 0.5 on ties, 0 otherwise (min likewise)
 __device__ __forceinline__ float dmax_a(float a, float b) { return a > b ? 1.f : (a == b ? 0.5f : 0.f); }
 __device__ __forceinline__ float dmin_a(float a, float b) { return a < b ? 1.f : (a == b ? 0.5f : 0.f); }
+// log-softmax of one logit x, from the cell's largest logit mx and lsum = log(sum exp(x - mx)).  While |mx| <= LSE_FOLD_MAX the two
+// constants are folded, x - (mx + lsum): mx + lsum < 32 there (lsum <= log 64), so folding rounds by at most 2^-20, 8 float32 spacings
+// of the softmax, and these are the bits that every recorded run and fixture of ordinary logits holds.  Beyond, the folded sum would
+// round at the size of the largest logit (5e-4 at 1e4), so the shift goes first, (x - mx) - lsum, as in torch's log_softmax.
+#define LSE_FOLD_MAX 16.f
+__device__ __forceinline__ float log_softmax_(float x, float mx, float lsum) {
+  return fabsf(mx) <= LSE_FOLD_MAX ? x - (mx + lsum) : (x - mx) - lsum;
+}
 
 struct LossParams {
   const float* pred;   // [B][P][cells] decoded boxes + objectness, raw class logits
@@ -209,10 +217,10 @@ __global__ __launch_bounds__(256) void yogo_loss_kernel(const LossParams p) {
       for (int c = 0; c < C; ++c) mx = fmaxf(mx, pr[(size_t)(5 + c) * cells]);
       float sum = 0.f;
       for (int c = 0; c < C; ++c) sum += expf(pr[(size_t)(5 + c) * cells] - mx);
-      const float lse = mx + logf(sum);
+      const float lsum = logf(sum);
       float nll_t = 0.f, nll_sum = 0.f;
       for (int c = 0; c < C; ++c) {
-        const float lp = pr[(size_t)(5 + c) * cells] - lse;
+        const float lp = log_softmax_(pr[(size_t)(5 + c) * cells], mx, lsum);
         nll_sum -= lp;
         if (c == tgt) nll_t = -lp;
       }
@@ -220,7 +228,7 @@ __global__ __launch_bounds__(256) void yogo_loss_kernel(const LossParams p) {
       l_cls = m * ((1.f - ls) * nll_t + (ls / (float)C) * nll_sum);
       const float sc = m * p.classify_weight * p.inv_batch;
       for (int c = 0; c < C; ++c) {
-        const float sm = expf(pr[(size_t)(5 + c) * cells] - lse);
+        const float sm = expf(log_softmax_(pr[(size_t)(5 + c) * cells], mx, lsum));
         gr[(size_t)(5 + c) * cells] = sc * (sm - (c == tgt ? (1.f - ls) : 0.f) - ls / (float)C);
       }
     } else {
@@ -343,20 +351,20 @@ __global__ __launch_bounds__(256) void decode_loss_bwd_bf16_kernel(const FusedPa
         g3 = 0.5f * (gY2 * c4 - gY1 * c2) * sc;
       }
     }
-    // classification: value now, the per-class gradient in the output loop below (from lse / tgt / scl)
-    float lse = 0.f, scl = 0.f;
+    // classification: value now, the per-class gradient in the output loop below (from mx / lsum / tgt / scl)
+    float mx = 0.f, lsum = 0.f, scl = 0.f;
     int tgt = -1;
     const float ls = p.label_smoothing;
     if (m != 0.f) {
       tgt = (int)lb[(size_t)5 * cells];
-      float mx = -INFINITY;
+      mx = -INFINITY;
       for (int c = 0; c < C; ++c) mx = fmaxf(mx, r[(size_t)(5 + c) * cells]);
       float sum = 0.f;
       for (int c = 0; c < C; ++c) sum += expf(r[(size_t)(5 + c) * cells] - mx);
-      lse = mx + logf(sum);
+      lsum = logf(sum);
       float nll_t = 0.f, nll_sum = 0.f;
       for (int c = 0; c < C; ++c) {
-        const float lp = r[(size_t)(5 + c) * cells] - lse;
+        const float lp = log_softmax_(r[(size_t)(5 + c) * cells], mx, lsum);
         nll_sum -= lp;
         if (c == tgt) nll_t = -lp;
       }
@@ -378,7 +386,7 @@ __global__ __launch_bounds__(256) void decode_loss_bwd_bf16_kernel(const FusedPa
           else if (ch == 4) v = gobj * (po * (1.f - po));
           else if (m != 0.f) {
             const int c = ch - 5;
-            const float sm = expf(r[(size_t)ch * cells] - lse);
+            const float sm = expf(log_softmax_(r[(size_t)ch * cells], mx, lsum));
             v = scl * (sm - (c == tgt ? (1.f - ls) : 0.f) - ls / (float)C);
           }
         }
