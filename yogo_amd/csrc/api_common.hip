@@ -60,3 +60,46 @@ extern "C" int yogo_hip_launch_log_read(char* buf, size_t cap, size_t* needed) {
   }
   return YOGO_OK;
 }
+
+// ---- per-device launch state --------------------------------------------------------------------------------------------------
+// The library's only mutable state besides the log above: the CU count of each device and which (device, kernel) pairs have been
+// granted their dynamic LDS.  One lock guards both, so a second device in the process, or a first call from two host threads,
+// never sees another device's state; a failed attribute is not recorded and is asked for (and reported) again.
+#include <set>
+#include <utility>
+
+static std::mutex g_dev_mu;
+static int g_n_cu_of[64] = {0};
+static std::set<std::pair<int, const void*>> g_lds_granted;
+
+static bool current_device(const char* what, int* dev) {
+  if (hipGetDevice(dev) == hipSuccess && *dev >= 0 && *dev < 64) return true;
+  yogo_set_error("%s: hipGetDevice failed", what);
+  return false;
+}
+
+int yogo_device_cus(const char* what, int* n_cu) {
+  int dev = 0;
+  if (!current_device(what, &dev)) return YOGO_ERR_HIP;
+  std::lock_guard<std::mutex> lk(g_dev_mu);
+  if (g_n_cu_of[dev] == 0) {
+    hipDeviceProp_t prop;
+    g_n_cu_of[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+  }
+  *n_cu = g_n_cu_of[dev];
+  return YOGO_OK;
+}
+
+int yogo_func_dynamic_lds(const void* kernel, int bytes, const char* what) {
+  int dev = 0;
+  if (!current_device(what, &dev)) return YOGO_ERR_HIP;
+  std::lock_guard<std::mutex> lk(g_dev_mu);
+  if (g_lds_granted.count({dev, kernel})) return YOGO_OK;
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) {
+    yogo_set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize = %d) failed: %s", what, bytes, hipGetErrorString(e));
+    return YOGO_ERR_HIP;
+  }
+  g_lds_granted.insert({dev, kernel});
+  return YOGO_OK;
+}

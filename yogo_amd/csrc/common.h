@@ -16,6 +16,11 @@ void yogo_set_error(const char* fmt, ...);
 // launch log (api_common.hip): one line per kernel launch while yogo_hip_launch_log(1) is in effect
 bool yogo_launch_log_enabled();
 void yogo_launch_log(const char* fmt, ...);
+// per-device launch state (api_common.hip): the library's only lazily-set state, kept per device under one lock.  `what` names
+// the caller in the error text; both return YOGO_OK or YOGO_ERR_HIP with the error set.
+int yogo_device_cus(const char* what, int* n_cu);   // CUs of the current device
+// asks once per (device, kernel) for `bytes` of dynamic LDS (hipFuncAttributeMaxDynamicSharedMemorySize: anything above 64 KB)
+int yogo_func_dynamic_lds(const void* kernel, int bytes, const char* what);
 
 #define YOGO_CHECK_ARG(cond, ...)                 \
   do {                                            \
@@ -45,6 +50,8 @@ static inline bool magic_div_exact(long long nmax, int d) {
   const unsigned long long e = m * (unsigned long long)d - (1ull << 32);
   return e == 0 || (unsigned long long)nmax < ((1ull << 32) + e - 1ull) / e;
 }
+// the multiplier m of magic_div_exact as the kernel-argument structs carry it (d <= 1, where m does not fit 32 bits: all ones)
+static inline unsigned magic_u32(int d) { return d <= 1 ? 0xFFFFFFFFu : (unsigned)(((1ull << 32) + (unsigned)d - 1ull) / (unsigned)d); }
 
 #define ACT_NONE 0
 #define ACT_LEAKY 1

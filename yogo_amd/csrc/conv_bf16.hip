@@ -1339,17 +1339,25 @@ extern "C" int yogo_conv_bf16_pack_multi(const void* table, int n, int total_blo
 // channel blocks of a bf16 NCHW8c tensor with C channels AS THE NEXT LAYER READS IT (padded to 16 channels = 2 blocks)
 extern "C" int yogo_bf16_channel_blocks(int C) { return bf_kb_of(C); }
 
-#ifdef BF_NO_ROWDMA   // (A/B variant builds: bash build.sh variant slot conv_bf16 -DBF_NO_ROWDMA)
-static bool g_bf_rowdma = false;
+// The plan choices of the tiled kernel.  The product has NO run-time plan switch (no mutable global state in the library besides the
+// per-device launch state of api_common.hip): these are compile-time constants, and variables with setters in the diagnostic build only.
+#ifdef YOGO_DIAG
+#define BF_PLAN_SWITCH static bool
 #else
-static bool g_bf_rowdma = true;
+#define BF_PLAN_SWITCH static constexpr bool
 #endif
-// (diagnostic build: yogo_diag_conv_bf16_rowdma(0) keeps the per-lane slot staging of the lean 4-wavefront tiles)
-static bool g_bf_lean4 = true; // (diagnostic build: yogo_diag_conv_bf16_lean4(0) selects the generic step loop of the 4-wavefront tiles)
-static bool g_bf_ring = true; // (diagnostic build: yogo_diag_conv_bf16_ring(0) selects the two-buffer loop of the stride-2 data gradient)
+#ifdef BF_NO_ROWDMA   // (A/B variant builds: bash build.sh variant slot conv_bf16 -DBF_NO_ROWDMA)
+BF_PLAN_SWITCH g_bf_rowdma = false;
+#else
+BF_PLAN_SWITCH g_bf_rowdma = true;   // (yogo_diag_conv_bf16_rowdma(0) keeps the per-lane slot staging of the lean 4-wavefront tiles)
+#endif
+BF_PLAN_SWITCH g_bf_lean4 = true;    // (yogo_diag_conv_bf16_lean4(0) selects the generic step loop of the 4-wavefront tiles)
+BF_PLAN_SWITCH g_bf_ring = true;     // (yogo_diag_conv_bf16_ring(0) selects the two-buffer loop of the stride-2 data gradient)
+BF_PLAN_SWITCH g_bf_pp = true;       // (yogo_diag_conv_bf16_pp(0) selects the interleaved main loop for A/B runs)
+#undef BF_PLAN_SWITCH
 // the persistent wavefront-specialised kernels (conv_bf16_ws.hip, conv_bf16_ws3.hip) take the launches they are eligible for.  The
-// product has NO run-time plan switch (no mutable global state in the library): the switch below exists in the test-hooks build
-// (build.sh: libyogo_hip_hooks.so, -DYOGO_TEST_HOOKS; loaded by tests/ and tools/ only) and in the diagnostic build.
+// switch below exists in the test-hooks build (build.sh: libyogo_hip_hooks.so, -DYOGO_TEST_HOOKS; loaded by tests/ and tools/ only)
+// and in the diagnostic build.
 #if defined(YOGO_TEST_HOOKS) || defined(YOGO_DIAG)
 static bool g_bf_ws = true;
 // 0 = every launch goes to the tiled conv_bf16_kernel (A/B runs and the bit-identity tests of the two kernel families)
@@ -1386,7 +1394,6 @@ int launch_conv_bf16_staged(const void* in, const void* packed, const float* bia
                             int IW, int OH, int OW, int stride, int act, hipStream_t stream);
 bool conv_bf16_head_fwd_eligible(int K, int M, int plane, int B);
 int launch_conv_bf16_head_fwd(const void* in, const void* packed, const float* bias, float* out_f32, int B, int K, int M, int plane, hipStream_t stream);
-static bool g_bf_pp = true;   // (diagnostic build: yogo_diag_conv_bf16_pp(0) selects the interleaved main loop for A/B runs)
 #ifdef YOGO_DIAG
 extern "C" int yogo_diag_conv_bf16_pp(int on) { g_bf_pp = on != 0; return YOGO_OK; }
 extern "C" int yogo_diag_conv_bf16_ring(int on) { g_bf_ring = on != 0; return YOGO_OK; }
@@ -1402,116 +1409,73 @@ extern "C" int yogo_diag_conv_bf16(int dbg_bits, int no_dma, void* stamps, size_
   g_diag_stamps = reinterpret_cast<unsigned long long*>(stamps); g_diag_stamps_bytes = stamps_bytes;
   return YOGO_OK;
 }
+// the ablation bits and the (cleared) stamp buffer of a persistent kernel's launch: Q = ConvWsParams / ConvWs3Params
+template <typename Q>
+void bf_diag_persistent(Q* q, hipStream_t stream) {
+  q->dbg = g_diag_dbg;
+  q->stamps = (g_diag_stamps != nullptr && g_diag_stamps_bytes >= 512 * 128) ? g_diag_stamps : nullptr;
+  if (q->stamps) (void)hipMemsetAsync(g_diag_stamps, 0, 512 * 128, stream);
+}
+#else
+template <typename Q>
+void bf_diag_persistent(Q*, hipStream_t) {}
 #endif
 
 namespace {
 
-template <int MW, int NW, int NWV, bool S2D, int PF, bool F32, int REF, bool PP, bool LEPI = false>
-void bf_launch_one(dim3 grid, int lds_bytes, hipStream_t stream, const ConvBf16Params& p, const char* plan_txt) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_kernel<MW, NW, NWV, S2D, PF, F32, REF, PP, LEPI>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, BF_LDS_MAX);
-    attr_set = true;
+// One bf16 convolution launch as the GEMM sees it: (K, M) the contraction / output channel counts, (IH, IW) the physical input dims,
+// (OH, OW) the output dims, `a` the input step per output pixel; s2d = 1: parity-decomposed data gradient of a stride-2 3x3
+// convolution (input = dy, output = dx, weights packed with mode 2).  The pointers a launch does not use stay null.
+struct ConvBf16Request {
+  const void* in;
+  const void* packed;
+  const float* bias;
+  void* out;              // bf16 NCHW8c ...
+  float* out_f32;         // ... or fp32 NCHW
+  void* out_pre;          // second bf16 output: conv + bias before the activation
+  const void* act_ref;    // data gradient: the activation's reference tensor (REF = 1) ...
+  int ref_act;
+  void* signs;            // ... or its sign map (signs_read; REF = 2); forward: the sign map to write (REF = 3)
+  bool signs_read;
+  const float* chan_scale;
+  float* stats_part;
+  int B, K, M, IH, IW, OH, OW, ks, a, s2d, act;
+};
+enum BfDirection { BF_FORWARD, BF_DGRAD };
+
+// the request of the forward pass (direction BF_FORWARD) or the data gradient (BF_DGRAD) of a Cin -> Cout convolution on IH x IW inputs
+int bf_request(int B, int Cin, int Cout, int IH, int IW, int ks, int stride, BfDirection dir, ConvBf16Request* r) {
+  YOGO_CHECK_ARG((ks == 3 || ks == 1) && (stride == 1 || stride == 2) && !(ks == 1 && stride != 1) && B >= 0 && Cin > 0 &&
+                     Cout > 0 && IH > 0 && IW > 0, "conv_bf16: unsupported shape");
+  const int pad = ks == 3 ? 1 : 0;
+  const int OHf = (IH + 2 * pad - ks) / stride + 1, OWf = (IW + 2 * pad - ks) / stride + 1;
+  *r = ConvBf16Request{};
+  r->B = B; r->ks = ks; r->act = ACT_NONE;
+  if (dir == BF_FORWARD) {
+    r->K = Cin; r->M = Cout; r->IH = IH; r->IW = IW; r->OH = OHf; r->OW = OWf; r->a = stride; r->s2d = 0;
+  } else {
+    r->K = Cout; r->M = Cin; r->IH = OHf; r->IW = OWf; r->OH = IH; r->OW = IW; r->a = 1; r->s2d = (stride == 2 && ks == 3) ? 1 : 0;
   }
-  hipLaunchKernelGGL((conv_bf16_kernel<MW, NW, NWV, S2D, PF, F32, REF, PP, LEPI>), grid, dim3(64 * NWV), lds_bytes, stream, p);
-  yogo_launch_log("conv_bf16_kernel<%d, %d, %d, %s, %d, %s, %d, %s, %s> | %s", MW, NW, NWV, S2D ? "true" : "false", PF, F32 ? "true" : "false", REF,
-                  PP ? "true" : "false", LEPI ? "true" : "false", plan_txt);
-}
-// the ping-pong main loop exists for the 8-wavefront tiles with bf16 output (two wavefronts per SIMD)
-template <int MW, int NW, int NWV, bool S2D, int PF, bool F32, int REF>
-void bf_launch_t(dim3 grid, int lds_bytes, hipStream_t stream, const ConvBf16Params& p, bool use_pp, const char* plan_txt) {
-  if constexpr (NWV == 8 && !S2D && !F32) {
-    if (use_pp) {
-      bf_launch_one<MW, NW, NWV, S2D, PF, F32, REF, true>(grid, lds_bytes, stream, p, plan_txt);
-      return;
-    }
-  }
-  if constexpr (NWV == 4 && !S2D && !F32) {
-    if (p.lean4) {
-      // the epilogue's general order of operations (kernel: `general`) is only compiled into the LEPI = false instantiation
-      const bool general = p.stats_part != nullptr || p.act == ACT_SILU || p.out_pre != nullptr || ((REF == 1 || REF == 2) && p.ref_act != ACT_LEAKY);
-#ifndef BF_NO_LEPI   // (A/B variant builds: bash build.sh variant nolepi conv_bf16 -DBF_NO_LEPI)
-      if constexpr (REF != 1) {
-        if (!general) {
-          bf_launch_one<MW, NW, NWV, S2D, PF, F32, REF, true, true>(grid, lds_bytes, stream, p, plan_txt);
-          return;
-        }
-      }
-#else
-      (void)general;
-#endif
-      bf_launch_one<MW, NW, NWV, S2D, PF, F32, REF, true>(grid, lds_bytes, stream, p, plan_txt);
-      return;
-    }
-  }
-  // the 4-wavefront stride-2 data gradient (layer 2): the lean-epilogue instantiation too (the same arithmetic in the same order, -1 % in
-  // the same-box A/B, gpurun_out/r5_abs2dlepi.log)
-  if constexpr (NWV == 4 && S2D && !F32 && REF != 1) {
-    const bool general = p.stats_part != nullptr || p.act == ACT_SILU || p.out_pre != nullptr || (REF == 2 && p.ref_act != ACT_LEAKY);
-    if (!general) {
-      bf_launch_one<MW, NW, NWV, S2D, PF, F32, REF, false, true>(grid, lds_bytes, stream, p, plan_txt);
-      return;
-    }
-  }
-  bf_launch_one<MW, NW, NWV, S2D, PF, F32, REF, false>(grid, lds_bytes, stream, p, plan_txt);
+  return YOGO_OK;
 }
 
-// One launcher for forward and data-gradient.  (K, M) are the GEMM contraction / output channel counts, (IH, IW) the
-// physical input dims, (OH, OW) the output dims, `a` the input step per output pixel; s2d = 1: parity-decomposed data
-// gradient of a stride-2 3x3 convolution (input = dy, output = dx, weights packed with mode 2).
-int launch_conv_bf16(const void* in, const void* packed, const float* bias, void* out, float* out_f32, void* out_pre, const void* act_ref,
-                     int ref_act, void* signs, bool signs_read, const float* chan_scale, float* stats_part, int B, int K, int M, int IH, int IW, int OH,
-                     int OW, int ks, int a, int s2d, int act, hipStream_t stream, int* stats_rows, int* stats_mpad) {
-  const int T = ks * ks, pad = ks == 3 ? 1 : 0;
-  // stride-1 3x3 convolutions with 128 output channels and the lean epilogue: the persistent wavefront-specialised kernel
-  if (in != nullptr && g_bf_ws && !s2d && a == 1 && ks == 3 && out_f32 == nullptr && out_pre == nullptr && act_ref == nullptr && !signs_read &&
-      stats_part == nullptr && (act == ACT_NONE || act == ACT_LEAKY) && !(signs != nullptr && act != ACT_LEAKY) &&
-      conv_bf16_ws_eligible(K, M, IH, IW, B)) {
-    ConvWsParams q{};
-    q.in = in; q.wp = packed; q.bias = bias; q.out = out; q.signs = reinterpret_cast<unsigned char*>(signs); q.chan_scale = chan_scale;
-    q.B = B; q.Kb = bf_kb_of(K); q.IH = IH; q.IW = IW; q.act = act;
-#ifdef YOGO_DIAG
-    q.dbg = g_diag_dbg;
-    q.stamps = (g_diag_stamps != nullptr && g_diag_stamps_bytes >= 512 * 128) ? g_diag_stamps : nullptr;
-    if (q.stamps) (void)hipMemsetAsync(g_diag_stamps, 0, 512 * 128, stream);
-#endif
-    if (conv_bf16_ws_plan(&q)) {
-      // the plain epilogue without a bias (the data gradients of the 128 -> 128 layers): the 16x16x32 member of the family.  With a bias
-      // (layer 5's forward) it measured +7 % inside the training step (profiles/r06_kernel_stats.txt history, DESIGN.md 3.1f) and stays
-      // on conv_bf16_ws_kernel<0>
-      if ((g_bf_ws16 == 2 || (g_bf_ws16 == 1 && bias == nullptr)) && act == ACT_NONE && signs == nullptr && chan_scale == nullptr &&
-          conv_bf16_ws16_eligible(K, M, IH, IW, B))
-        return launch_conv_bf16_ws16(q, stream);
-      return launch_conv_bf16_ws(q, stream);
-    }
-  }
-  // stride-2 3x3 forward with 128 output channels and the lean epilogue: its persistent wavefront-specialised member (conv_bf16_ws3.hip)
-  if (in != nullptr && g_bf_ws && !s2d && a == 2 && ks == 3 && out_f32 == nullptr && out_pre == nullptr && act_ref == nullptr && !signs_read &&
-      stats_part == nullptr && (act == ACT_NONE || act == ACT_LEAKY) && !(signs != nullptr && act != ACT_LEAKY) && conv_bf16_ws3_eligible(K, M, IH, IW, B)) {
-    ConvWs3Params q{};
-    q.in = in; q.wp = packed; q.bias = bias; q.out = out; q.signs = reinterpret_cast<unsigned char*>(signs); q.chan_scale = chan_scale;
-    q.B = B; q.Kb = bf_kb_of(K); q.IH = IH; q.IW = IW; q.OH = OH; q.OW = OW; q.act = act;
-#ifdef YOGO_DIAG
-    q.dbg = g_diag_dbg;
-    q.stamps = (g_diag_stamps != nullptr && g_diag_stamps_bytes >= 512 * 128) ? g_diag_stamps : nullptr;
-    if (q.stamps) (void)hipMemsetAsync(g_diag_stamps, 0, 512 * 128, stream);
-#endif
-    if (conv_bf16_ws3_plan(&q)) return launch_conv_bf16_ws3(q, stream);
-  }
-  // the 1x1 head's fp32-output forward (bias only) with the weights in registers
-  if (in != nullptr && g_bf_head && ks == 1 && a == 1 && !s2d && out_pre == nullptr && act_ref == nullptr && stats_part == nullptr && act == ACT_NONE &&
-      out_f32 != nullptr && out == nullptr && signs == nullptr && chan_scale == nullptr && conv_bf16_head_fwd_eligible(K, M, OH * OW, B))
-    return launch_conv_bf16_head_fwd(in, packed, bias, out_f32, B, K, M, OH * OW, stream);
-  // 3x3 convolutions out of 16 / 32 channels into <= 64 with the lean epilogue: independent wavefronts, weights resident, private LDS staging
-  if (in != nullptr && g_bf_staged && !s2d && ks == 3 && out_f32 == nullptr && out_pre == nullptr && act_ref == nullptr && !signs_read && stats_part == nullptr &&
-      (act == ACT_NONE || act == ACT_LEAKY) && !(signs != nullptr && act != ACT_LEAKY) && conv_bf16_staged_eligible(K, M, a, IH, IW, OH, OW, B))
-    return launch_conv_bf16_staged(in, packed, bias, out, signs, chan_scale, B, K, M, IH, IW, OH, OW, a, act, stream);
-  // stride-2 3x3 data gradient into <= 32 or 65 - 128 channels (scale / LeakyReLU-sign-map epilogue): weights resident in LDS, operands straight from memory
-  if (in != nullptr && g_bf_direct && s2d && ks == 3 && out_f32 == nullptr && out_pre == nullptr && act_ref == nullptr && bias == nullptr &&
-      stats_part == nullptr && act == ACT_NONE && (!signs_read || (signs != nullptr && ref_act == ACT_LEAKY)) && (signs_read || signs == nullptr) &&
-      conv_bf16_s2d_direct_eligible(K, M, OH, OW, B))
-    return launch_conv_bf16_s2d_direct(in, packed, out, signs_read ? signs : nullptr, chan_scale, B, K, M, IH, IW, OH, OW, stream);
+// The plan of the tiled conv_bf16_kernel for a request: the tile (MW x NW x NWV, PF DMA slots), the LDS tiling, the loop variant
+// (ring / row-staged lean loop / ping-pong) and the grid.  Host arithmetic only: the shape query runs it without a device.
+struct BfTiledPlan {
+  int MW, NW, NWV, PF;
+  bool wide64;
+  BfTiling tl;          // as planned; the log prints its slots
+  bool ring;
+  int lean4, rowdma, lwp;
+  int dma;              // tl.dma (the diagnostic build: 0 = synchronous staging through registers)
+  bool use_pp;
+  int ni_slots, n_slots, ldsw_off, bufu, bufs, lds_bytes;   // the launch's slot layout: tl's, or the ping-pong loop's fixed one
+  dim3 grid;
+  int rows, mpad;       // of the BatchNorm partial-sum buffer a forward launch with stats_part fills
+};
+
+int bf_plan_tiled(const ConvBf16Request& r, BfTiledPlan* pl) {
+  const int K = r.K, M = r.M, OH = r.OH, OW = r.OW, ks = r.ks, a = r.a, s2d = r.s2d, T = ks * ks;
   const int MW = bf_pick_mw(M);
   const bool small_n = s2d || a == 2;  // two accumulator sets / four-fold input tile: half the pixel groups per wavefront
   // 64 GEMM rows at stride 1 with a long contraction: 8 wavefronts x 4 pixel groups (64 rows x 1024 px), the same staged
@@ -1544,10 +1508,11 @@ int launch_conv_bf16(const void* in, const void* packed, const float* bias, void
   }
   // the lean single-buffer 4-wavefront tiles (3x3, 16-channel chunks): stage the input row by row when that keeps the
   // workgroups-per-CU level of the slot plan
+  const bool lean4 = !s2d && NWV == 4 && T == 9 && tl.CKb == 2 && tl.dma == 2 && r.out_f32 == nullptr && g_bf_lean4;
   int rowdma = 0, lwp = 0;
   // (measured: -2.5 ... -5 % on the 16 <-> 32 channel layer in both directions; the stride-2 forward -2 ... -3.5 % with ONE piece
   //  per row -- bands of at most 31 output columns -- and +1 % with 87-unit rows in two pieces, so its pitch stays 64)
-  if (!s2d && NWV == 4 && T == 9 && tl.CKb == 2 && tl.dma == 2 && out_f32 == nullptr && g_bf_lean4 && g_bf_rowdma) {
+  if (lean4 && g_bf_rowdma) {
     const int ladder[3] = {40 * 1024, 53 * 1024, BF_LDS_BUDGET};
     int level = 0;
     while (level < 2 && tl.lds_bytes > ladder[level]) ++level;
@@ -1557,15 +1522,123 @@ int launch_conv_bf16(const void* in, const void* packed, const float* bias, void
       rowdma = 1;
     }
   }
-  dim3 grid(tl.ncb * tl.tiles_per_band, (Mpad / (32 * MW)) * (s2d ? 2 : 1), B);
-  if (stats_rows) *stats_rows = B * (int)grid.x;
-  if (stats_mpad) *stats_mpad = Mpad;
-  if (in == nullptr) return YOGO_OK;  // shape query only
+  pl->MW = MW; pl->NW = NW; pl->NWV = NWV; pl->PF = PF; pl->wide64 = wide64;
+  pl->tl = tl; pl->ring = ring; pl->rowdma = rowdma; pl->lwp = lwp;
+  // (the row-staged tiling keeps CKb = 2 and dma = 2, so `lean4` holds for the tiling the launch uses too)
+  pl->lean4 = lean4 ? 1 : 0;
+  pl->grid = dim3(tl.ncb * tl.tiles_per_band, (Mpad / (32 * MW)) * (s2d ? 2 : 1), r.B);
+  pl->rows = r.B * (int)pl->grid.x;
+  pl->mpad = Mpad;
+  pl->dma = tl.dma;
+#ifdef YOGO_DIAG
+  if (g_diag_nodma && (tl.lds_dummy + 1) * 16 <= BF_LDS_MAX) pl->dma = 0;  // synchronous staging through registers
+#endif
+  pl->ni_slots = tl.ni_slots; pl->n_slots = tl.n_slots; pl->ldsw_off = tl.ldsw_off; pl->bufu = tl.bufu; pl->bufs = tl.dma == 1 ? tl.bufu : 0;
+  pl->lds_bytes = max(pl->dma ? tl.lds_bytes : (tl.lds_dummy + 1) * 16, (2 + 2 * NWV) * 32 * MW * 4);
+  // ping-pong main loop: 3x3 taps, 16-channel chunks (one step per tap) through the double-buffered LDS-DMA pipeline, with its
+  // fixed slot layout: 5 slots for the input tile, 5 for the weight slices, two buffers of 10 slots = all of the LDS
+  pl->use_pp = NWV == 8 && !s2d && T == 9 && pl->dma == 1 && tl.CKb == 2 && tl.ni_slots <= 5 && tl.n_slots - tl.ni_slots <= 5 && g_bf_pp;
+  if (pl->use_pp) {
+    pl->ni_slots = 5; pl->n_slots = 10; pl->ldsw_off = 5 * 64 * NWV; pl->bufu = 10 * 64 * NWV; pl->bufs = pl->bufu;
+    pl->lds_bytes = 2 * pl->bufu * 16;
+  }
+  return YOGO_OK;
+}
+
+template <int MW, int NW, int NWV, bool S2D, int PF, bool F32, int REF, bool PP, bool LEPI = false>
+int bf_launch_one(dim3 grid, int lds_bytes, hipStream_t stream, const ConvBf16Params& p, const char* plan_txt) {
+  if (int e = yogo_func_dynamic_lds(reinterpret_cast<const void*>(&conv_bf16_kernel<MW, NW, NWV, S2D, PF, F32, REF, PP, LEPI>), BF_LDS_MAX, "conv_bf16")) return e;
+  hipLaunchKernelGGL((conv_bf16_kernel<MW, NW, NWV, S2D, PF, F32, REF, PP, LEPI>), grid, dim3(64 * NWV), lds_bytes, stream, p);
+  yogo_launch_log("conv_bf16_kernel<%d, %d, %d, %s, %d, %s, %d, %s, %s> | %s", MW, NW, NWV, S2D ? "true" : "false", PF, F32 ? "true" : "false", REF,
+                  PP ? "true" : "false", LEPI ? "true" : "false", plan_txt);
+  return YOGO_OK;
+}
+// the epilogue's general order of operations (kernel: `general`) is only compiled into the LEPI = false instantiation.  (Where REF = 1
+// is excluded beforehand -- the stride-2 data gradient below -- the last term reads REF == 2 && p.ref_act != ACT_LEAKY.)
+template <int REF>
+bool bf_epilogue_general(const ConvBf16Params& p) {
+  return p.stats_part != nullptr || p.act == ACT_SILU || p.out_pre != nullptr || ((REF == 1 || REF == 2) && p.ref_act != ACT_LEAKY);
+}
+// the ping-pong main loop exists for the 8-wavefront tiles with bf16 output (two wavefronts per SIMD)
+template <int MW, int NW, int NWV, bool S2D, int PF, bool F32, int REF>
+int bf_launch_t(dim3 grid, int lds_bytes, hipStream_t stream, const ConvBf16Params& p, bool use_pp, const char* plan_txt) {
+  if constexpr (NWV == 8 && !S2D && !F32) {
+    if (use_pp) return bf_launch_one<MW, NW, NWV, S2D, PF, F32, REF, true>(grid, lds_bytes, stream, p, plan_txt);
+  }
+  if constexpr (NWV == 4 && !S2D && !F32) {
+    if (p.lean4) {
+#ifndef BF_NO_LEPI   // (A/B variant builds: bash build.sh variant nolepi conv_bf16 -DBF_NO_LEPI)
+      if constexpr (REF != 1) {
+        if (!bf_epilogue_general<REF>(p)) return bf_launch_one<MW, NW, NWV, S2D, PF, F32, REF, true, true>(grid, lds_bytes, stream, p, plan_txt);
+      }
+#endif
+      return bf_launch_one<MW, NW, NWV, S2D, PF, F32, REF, true>(grid, lds_bytes, stream, p, plan_txt);
+    }
+  }
+  // the 4-wavefront stride-2 data gradient (layer 2): the lean-epilogue instantiation too (the same arithmetic in the same order, -1 % in
+  // the same-box A/B, gpurun_out/r5_abs2dlepi.log)
+  if constexpr (NWV == 4 && S2D && !F32 && REF != 1) {
+    if (!bf_epilogue_general<REF>(p)) return bf_launch_one<MW, NW, NWV, S2D, PF, F32, REF, false, true>(grid, lds_bytes, stream, p, plan_txt);
+  }
+  return bf_launch_one<MW, NW, NWV, S2D, PF, F32, REF, false>(grid, lds_bytes, stream, p, plan_txt);
+}
+
+// One launcher for forward and data-gradient: the specialised kernels take the requests their gates accept, in this order; everything
+// else runs on the tiled kernel with the plan of bf_plan_tiled.
+int launch_conv_bf16(const ConvBf16Request& r, hipStream_t stream) {
+  const int B = r.B, K = r.K, M = r.M, IH = r.IH, IW = r.IW, OH = r.OH, OW = r.OW, ks = r.ks, a = r.a, s2d = r.s2d, act = r.act;
+  // what every specialised kernel leaves to the tiled one: a second (pre-activation) output, a reference tensor, BatchNorm statistics
+  const bool plain = r.out_pre == nullptr && r.act_ref == nullptr && r.stats_part == nullptr;
+  // the LEAN EPILOGUE: plain, one bf16 output, no sign map to read, identity or LeakyReLU, a sign map written only beside LeakyReLU
+  const bool lean = plain && r.out_f32 == nullptr && !r.signs_read && (act == ACT_NONE || act == ACT_LEAKY) && !(r.signs != nullptr && act != ACT_LEAKY);
+  // stride-1 3x3 convolutions with 128 output channels and the lean epilogue: the persistent wavefront-specialised kernel
+  if (g_bf_ws && lean && !s2d && a == 1 && ks == 3 && conv_bf16_ws_eligible(K, M, IH, IW, B)) {
+    ConvWsParams q{};
+    q.in = r.in; q.wp = r.packed; q.bias = r.bias; q.out = r.out; q.signs = reinterpret_cast<unsigned char*>(r.signs); q.chan_scale = r.chan_scale;
+    q.B = B; q.Kb = bf_kb_of(K); q.IH = IH; q.IW = IW; q.act = act;
+    bf_diag_persistent(&q, stream);
+    if (conv_bf16_ws_plan(&q)) {
+      // the plain epilogue without a bias (the data gradients of the 128 -> 128 layers): the 16x16x32 member of the family.  With a bias
+      // (layer 5's forward) it measured +7 % inside the training step (profiles/r06_kernel_stats.txt history, DESIGN.md 3.1f) and stays
+      // on conv_bf16_ws_kernel<0>
+      if ((g_bf_ws16 == 2 || (g_bf_ws16 == 1 && r.bias == nullptr)) && act == ACT_NONE && r.signs == nullptr && r.chan_scale == nullptr &&
+          conv_bf16_ws16_eligible(K, M, IH, IW, B))
+        return launch_conv_bf16_ws16(q, stream);
+      return launch_conv_bf16_ws(q, stream);
+    }
+  }
+  // stride-2 3x3 forward with 128 output channels and the lean epilogue: its persistent wavefront-specialised member (conv_bf16_ws3.hip)
+  if (g_bf_ws && lean && !s2d && a == 2 && ks == 3 && conv_bf16_ws3_eligible(K, M, IH, IW, B)) {
+    ConvWs3Params q{};
+    q.in = r.in; q.wp = r.packed; q.bias = r.bias; q.out = r.out; q.signs = reinterpret_cast<unsigned char*>(r.signs); q.chan_scale = r.chan_scale;
+    q.B = B; q.Kb = bf_kb_of(K); q.IH = IH; q.IW = IW; q.OH = OH; q.OW = OW; q.act = act;
+    bf_diag_persistent(&q, stream);
+    if (conv_bf16_ws3_plan(&q)) return launch_conv_bf16_ws3(q, stream);
+  }
+  // the 1x1 head's forward with the weights in registers.  NOT the lean epilogue: the output is fp32 (and there is no bf16 one), bias only --
+  // no activation, no sign map in either role, no channel scale
+  if (g_bf_head && plain && ks == 1 && a == 1 && !s2d && act == ACT_NONE && r.out_f32 != nullptr && r.out == nullptr && r.signs == nullptr &&
+      r.chan_scale == nullptr && conv_bf16_head_fwd_eligible(K, M, OH * OW, B))
+    return launch_conv_bf16_head_fwd(r.in, r.packed, r.bias, r.out_f32, B, K, M, OH * OW, stream);
+  // 3x3 convolutions out of 16 / 32 channels into <= 64 with the lean epilogue: independent wavefronts, weights resident, private LDS staging
+  if (g_bf_staged && lean && !s2d && ks == 3 && conv_bf16_staged_eligible(K, M, a, IH, IW, OH, OW, B))
+    return launch_conv_bf16_staged(r.in, r.packed, r.bias, r.out, r.signs, r.chan_scale, B, K, M, IH, IW, OH, OW, a, act, stream);
+  // stride-2 3x3 data gradient into <= 32 or 65 - 128 channels (scale / LeakyReLU-sign-map epilogue): weights resident in LDS, operands straight
+  // from memory.  NOT the lean epilogue either: no bias and no activation of its own, and the sign map is one it READS (a LeakyReLU reference's),
+  // never one it writes
+  if (g_bf_direct && plain && s2d && ks == 3 && r.out_f32 == nullptr && r.bias == nullptr && act == ACT_NONE &&
+      (r.signs_read ? (r.signs != nullptr && r.ref_act == ACT_LEAKY) : r.signs == nullptr) && conv_bf16_s2d_direct_eligible(K, M, OH, OW, B))
+    return launch_conv_bf16_s2d_direct(r.in, r.packed, r.out, r.signs_read ? r.signs : nullptr, r.chan_scale, B, K, M, IH, IW, OH, OW, stream);
+  BfTiledPlan pl;
+  if (int e = bf_plan_tiled(r, &pl)) return e;
+  const BfTiling& tl = pl.tl;
+  const dim3 grid = pl.grid;
+  const int T = ks * ks, pad = ks == 3 ? 1 : 0, Kb = bf_kb_of(K);
   ConvBf16Params p{};
-  p.in = reinterpret_cast<const u32x4*>(in); p.wp = reinterpret_cast<const u32x4*>(packed); p.bias = bias;
-  p.out = reinterpret_cast<u32x2*>(out); p.out_f32 = out_f32; p.out_pre = reinterpret_cast<u32x2*>(out_pre);
-  p.act_ref = reinterpret_cast<const u32x2*>(act_ref); p.ref_act = ref_act; p.signs = reinterpret_cast<unsigned char*>(signs); p.chan_scale = chan_scale; p.stats_part = stats_part;
-  p.B = B; p.Kb = Kb; p.M = M; p.Mpad = Mpad; p.Mb = bf_kb_of(M);
+  p.in = reinterpret_cast<const u32x4*>(r.in); p.wp = reinterpret_cast<const u32x4*>(r.packed); p.bias = r.bias;
+  p.out = reinterpret_cast<u32x2*>(r.out); p.out_f32 = r.out_f32; p.out_pre = reinterpret_cast<u32x2*>(r.out_pre);
+  p.act_ref = reinterpret_cast<const u32x2*>(r.act_ref); p.ref_act = r.ref_act; p.signs = reinterpret_cast<unsigned char*>(r.signs); p.chan_scale = r.chan_scale; p.stats_part = r.stats_part;
+  p.B = B; p.Kb = Kb; p.M = M; p.Mpad = pl.mpad; p.Mb = bf_kb_of(M);
   p.IH = IH; p.IW = IW; p.OH = OH; p.OW = OW; p.T = T;
   if (s2d) {
     p.a = 1; p.dy_min = 0; p.dx_min = 0; p.span_y = 2; p.span_x = 2;
@@ -1574,22 +1647,18 @@ int launch_conv_bf16(const void* in, const void* packed, const float* bias, void
   }
   p.ncb = tl.ncb; p.TW = tl.TW; p.tiles_per_band = tl.tiles_per_band;
   {
-    auto magic = [](int d) -> unsigned { return d <= 1 ? 0xFFFFFFFFu : (unsigned)(((1ull << 32) + (unsigned)d - 1ull) / (unsigned)d); };
-    const int a_ = s2d ? 1 : a, span_ = s2d ? 2 : ks;
+    const int OWt = s2d ? (OW + 1) / 2 : OW;   // (the grid the workgroups tile: output pixels, or 2x2 output quads)
     const int bw_last = OWt - (tl.ncb - 1) * tl.TW;
-    p.m_gx = magic((int)grid.x); p.m_gy = magic((int)grid.y); p.m_gxy = magic((int)(grid.x * grid.y)); p.m_tpb = magic(tl.tiles_per_band);
-    p.m_bw = magic(tl.TW); p.m_bwl = magic(bw_last);
-    p.m_lw = magic((tl.TW - 1) * a_ + span_); p.m_lwl = magic((bw_last - 1) * a_ + span_);
+    p.m_gx = magic_u32((int)grid.x); p.m_gy = magic_u32((int)grid.y); p.m_gxy = magic_u32((int)(grid.x * grid.y)); p.m_tpb = magic_u32(tl.tiles_per_band);
+    p.m_bw = magic_u32(tl.TW); p.m_bwl = magic_u32(bw_last);
+    p.m_lw = magic_u32((tl.TW - 1) * p.a + p.span_x); p.m_lwl = magic_u32((bw_last - 1) * p.a + p.span_x);
   }
   p.CKb = tl.CKb; p.ckb_shift = tl.CKb == 8 ? 3 : (tl.CKb == 4 ? 2 : 1); p.nchunk = Kb / tl.CKb;
-  p.ldsw_off = tl.ldsw_off; p.lds_dummy = tl.lds_dummy; p.act = act;
-  p.dma = tl.dma; p.ni_slots = tl.ni_slots; p.n_slots = tl.n_slots; p.bufu = tl.bufu; p.bufs = tl.dma == 1 ? tl.bufu : 0;
-  p.ring = ring ? 1 : 0;
-  p.lean4 = (!s2d && NWV == 4 && T == 9 && tl.CKb == 2 && tl.dma == 2 && out_f32 == nullptr && g_bf_lean4) ? 1 : 0;
-  p.rowdma = rowdma; p.lwp = lwp;
+  p.lds_dummy = tl.lds_dummy; p.act = act;
+  p.dma = pl.dma; p.ni_slots = pl.ni_slots; p.n_slots = pl.n_slots; p.ldsw_off = pl.ldsw_off; p.bufu = pl.bufu; p.bufs = pl.bufs;
+  p.ring = pl.ring ? 1 : 0; p.lean4 = pl.lean4; p.rowdma = pl.rowdma; p.lwp = pl.lwp;
 #ifdef YOGO_DIAG
   p.dbg = g_diag_dbg;
-  if (g_diag_nodma && (tl.lds_dummy + 1) * 16 <= BF_LDS_MAX) p.dma = 0;  // synchronous staging through registers
   {
     const size_t nwg = (size_t)grid.x * grid.y * grid.z;
     if (g_diag_stamps != nullptr && nwg * 128 <= g_diag_stamps_bytes) {
@@ -1598,36 +1667,31 @@ int launch_conv_bf16(const void* in, const void* packed, const float* bias, void
     }
   }
 #endif
-  if ((act_ref != nullptr || signs_read) && bias != nullptr) {
+  if ((r.act_ref != nullptr || r.signs_read) && r.bias != nullptr) {
     yogo_set_error("conv_bf16: an activation reference goes with a data gradient (no bias)");
     return YOGO_ERR_ARG;
   }
   if (B == 0) return YOGO_OK;
-  int lds_bytes = max(p.dma ? tl.lds_bytes : (tl.lds_dummy + 1) * 16, (2 + 2 * NWV) * 32 * MW * 4);
-  // ping-pong main loop: 3x3 taps, 16-channel chunks (one step per tap) through the double-buffered LDS-DMA pipeline, with its
-  // fixed slot layout: 5 slots for the input tile, 5 for the weight slices, two buffers of 10 slots = all of the LDS
-  const bool use_pp = NWV == 8 && !s2d && T == 9 && p.dma == 1 && tl.CKb == 2 && tl.ni_slots <= 5 && tl.n_slots - tl.ni_slots <= 5 && g_bf_pp;
-  if (use_pp) {
-    p.ni_slots = 5; p.n_slots = 10; p.ldsw_off = 5 * 64 * NWV; p.bufu = 10 * 64 * NWV; p.bufs = p.bufu;
-    lds_bytes = 2 * p.bufu * 16;
-  }
+  const int MW = pl.MW, lds_bytes = pl.lds_bytes;
+  const bool wide64 = pl.wide64, use_pp = pl.use_pp;
   char plan_txt[256] = "";
   if (yogo_launch_log_enabled())
     snprintf(plan_txt, sizeof(plan_txt), "K=%d M=%d in=%dx%d out=%dx%d a=%d s2d=%d T=%d ncb=%d TW=%d tiles_per_band=%d CKb=%d nchunk=%d rows=%d LW=%d lds=%d dma=%d slots=%d+%d rowpitch=%d grid=%ux%ux%u",
              K, M, IH, IW, OH, OW, a, s2d, T, tl.ncb, tl.TW, tl.tiles_per_band, tl.CKb, Kb / tl.CKb, tl.rows_max, tl.LW, lds_bytes, p.dma, tl.ni_slots,
-             tl.n_slots - tl.ni_slots, rowdma ? lwp : 0, grid.x, grid.y, grid.z);
+             tl.n_slots - tl.ni_slots, pl.rowdma ? pl.lwp : 0, grid.x, grid.y, grid.z);
+  int rc = YOGO_OK;
 #define BFLAUNCH__(MW_, NW_, NWV_, S2D_, PF_, F32_, REF_)                                                               \
-  bf_launch_t<MW_, NW_, NWV_, S2D_, PF_, F32_, REF_>(grid, lds_bytes, stream, p, use_pp, plan_txt)
+  rc = bf_launch_t<MW_, NW_, NWV_, S2D_, PF_, F32_, REF_>(grid, lds_bytes, stream, p, use_pp, plan_txt)
 #define BFLAUNCH_(MW_, NW_, NWV_, S2D_, PF_, F32_)                             \
   do {                                                                         \
-    if (act_ref != nullptr) BFLAUNCH__(MW_, NW_, NWV_, S2D_, PF_, false, 1);   \
-    else if (signs_read) BFLAUNCH__(MW_, NW_, NWV_, S2D_, PF_, false, 2);      \
-    else if (signs != nullptr && NWV_ != 8) BFLAUNCH__(MW_, NW_, NWV_, S2D_, PF_, false, 3); \
+    if (r.act_ref != nullptr) BFLAUNCH__(MW_, NW_, NWV_, S2D_, PF_, false, 1); \
+    else if (r.signs_read) BFLAUNCH__(MW_, NW_, NWV_, S2D_, PF_, false, 2);    \
+    else if (r.signs != nullptr && NWV_ != 8) BFLAUNCH__(MW_, NW_, NWV_, S2D_, PF_, false, 3); \
     else BFLAUNCH__(MW_, NW_, NWV_, S2D_, PF_, F32_, 0);                       \
   } while (0)
 #define BFLAUNCH(MW_, NW_, NWV_, S2D_, PF_)                                    \
   do {                                                                         \
-    if (out_f32 != nullptr) BFLAUNCH_(MW_, NW_, NWV_, S2D_, PF_, true);        \
+    if (r.out_f32 != nullptr) BFLAUNCH_(MW_, NW_, NWV_, S2D_, PF_, true);      \
     else BFLAUNCH_(MW_, NW_, NWV_, S2D_, PF_, false);                          \
   } while (0)
   if (s2d) {
@@ -1647,24 +1711,23 @@ int launch_conv_bf16(const void* in, const void* packed, const float* bias, void
 #undef BFLAUNCH
 #undef BFLAUNCH_
 #undef BFLAUNCH__
+  if (rc != YOGO_OK) return rc;
   YOGO_CHECK_LAUNCH("conv_bf16");
-  return YOGO_OK;
-}
-
-int check_bf16_conv(int B, int Cin, int Cout, int IH, int IW, int ks, int stride) {
-  YOGO_CHECK_ARG((ks == 3 || ks == 1) && (stride == 1 || stride == 2) && !(ks == 1 && stride != 1) && B >= 0 && Cin > 0 &&
-                     Cout > 0 && IH > 0 && IW > 0, "conv_bf16: unsupported shape");
   return YOGO_OK;
 }
 
 }  // namespace
 
-// rows / row stride of the BatchNorm partial-sum buffer a forward launch fills when stats_part != NULL
+// rows / row stride of the BatchNorm partial-sum buffer a forward launch fills when stats_part != NULL: those of the tiled plan (a
+// launch with statistics always runs on the tiled kernel).  No device is needed.
 extern "C" int yogo_conv2d_fwd_bf16_stats_shape(int B, int Cin, int Cout, int IH, int IW, int ks, int stride, int* rows, int* mpad) {
-  if (int e = check_bf16_conv(B, Cin, Cout, IH, IW, ks, stride)) return e;
-  const int pad = ks == 3 ? 1 : 0;
-  return launch_conv_bf16(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, false, nullptr, nullptr, B, Cin, Cout, IH, IW,
-                          (IH + 2 * pad - ks) / stride + 1, (IW + 2 * pad - ks) / stride + 1, ks, stride, 0, 0, nullptr, rows, mpad);
+  ConvBf16Request r;
+  if (int e = bf_request(B, Cin, Cout, IH, IW, ks, stride, BF_FORWARD, &r)) return e;
+  BfTiledPlan pl;
+  if (int e = bf_plan_tiled(r, &pl)) return e;
+  if (rows) *rows = pl.rows;
+  if (mpad) *mpad = pl.mpad;
+  return YOGO_OK;
 }
 
 // in: bf16 NCHW8c [B][kb(Cin)][IH][IW][8]; out: bf16 NCHW8c [B][kb(Cout)][OH][OW][8], or fp32 NCHW when out_f32 != NULL.
@@ -1673,11 +1736,10 @@ extern "C" int yogo_conv2d_fwd_bf16(const void* in, const void* packed, const fl
                                     const float* chan_scale, float* stats_part, int B, int Cin, int Cout, int IH, int IW,
                                     int ks, int stride, int act, hipStream_t stream) {
   YOGO_CHECK_ARG(in && packed && (out || out_f32), "conv2d_fwd_bf16: null pointer");
-  if (int e = check_bf16_conv(B, Cin, Cout, IH, IW, ks, stride)) return e;
-  const int pad = ks == 3 ? 1 : 0;
-  return launch_conv_bf16(in, packed, bias, out, out_f32, nullptr, nullptr, 0, nullptr, false, chan_scale, stats_part, B, Cin, Cout, IH, IW,
-                          (IH + 2 * pad - ks) / stride + 1, (IW + 2 * pad - ks) / stride + 1, ks, stride, 0, act, stream,
-                          nullptr, nullptr);
+  ConvBf16Request r;
+  if (int e = bf_request(B, Cin, Cout, IH, IW, ks, stride, BF_FORWARD, &r)) return e;
+  r.in = in; r.packed = packed; r.bias = bias; r.out = out; r.out_f32 = out_f32; r.chan_scale = chan_scale; r.stats_part = stats_part; r.act = act;
+  return launch_conv_bf16(r, stream);
 }
 
 // the same with a second bf16 output `out_pre` = conv + bias before the activation (what the backward pass of a SiLU block
@@ -1686,11 +1748,10 @@ extern "C" int yogo_conv2d_fwd_bf16_pre(const void* in, const void* packed, cons
                                         const float* chan_scale, int B, int Cin, int Cout, int IH, int IW, int ks, int stride,
                                         int act, hipStream_t stream) {
   YOGO_CHECK_ARG(in && packed && out && out_pre, "conv2d_fwd_bf16_pre: null pointer");
-  if (int e = check_bf16_conv(B, Cin, Cout, IH, IW, ks, stride)) return e;
-  const int pad = ks == 3 ? 1 : 0;
-  return launch_conv_bf16(in, packed, bias, out, nullptr, out_pre, nullptr, 0, nullptr, false, chan_scale, nullptr, B, Cin, Cout, IH, IW,
-                          (IH + 2 * pad - ks) / stride + 1, (IW + 2 * pad - ks) / stride + 1, ks, stride, 0, act, stream,
-                          nullptr, nullptr);
+  ConvBf16Request r;
+  if (int e = bf_request(B, Cin, Cout, IH, IW, ks, stride, BF_FORWARD, &r)) return e;
+  r.in = in; r.packed = packed; r.bias = bias; r.out = out; r.out_pre = out_pre; r.chan_scale = chan_scale; r.act = act;
+  return launch_conv_bf16(r, stream);
 }
 
 // bytes of the LeakyReLU sign map of a bf16 NCHW8c tensor with C channels: [B][2][H][W][Cpad/16] bytes, Cpad = C rounded up
@@ -1708,11 +1769,10 @@ extern "C" int yogo_conv2d_fwd_bf16_signs(const void* in, const void* packed, co
                                           const float* chan_scale, int B, int Cin, int Cout, int IH, int IW, int ks, int stride,
                                           int act, hipStream_t stream) {
   YOGO_CHECK_ARG(in && packed && out && signs, "conv2d_fwd_bf16_signs: null pointer");
-  if (int e = check_bf16_conv(B, Cin, Cout, IH, IW, ks, stride)) return e;
-  const int pad = ks == 3 ? 1 : 0;
-  return launch_conv_bf16(in, packed, bias, out, nullptr, nullptr, nullptr, 0, signs, false, chan_scale, nullptr, B, Cin, Cout, IH, IW,
-                          (IH + 2 * pad - ks) / stride + 1, (IW + 2 * pad - ks) / stride + 1, ks, stride, 0, act, stream,
-                          nullptr, nullptr);
+  ConvBf16Request r;
+  if (int e = bf_request(B, Cin, Cout, IH, IW, ks, stride, BF_FORWARD, &r)) return e;
+  r.in = in; r.packed = packed; r.bias = bias; r.out = out; r.signs = signs; r.chan_scale = chan_scale; r.act = act;
+  return launch_conv_bf16(r, stream);
 }
 
 // yogo_conv2d_dgrad_bf16 with act = LeakyReLU and the sign map of the reference in place of the reference:
@@ -1721,12 +1781,10 @@ extern "C" int yogo_conv2d_dgrad_bf16_signs(const void* dy, const void* packed_d
                                             const float* chan_scale, int B, int Cin, int Cout, int IH, int IW, int ks, int stride,
                                             hipStream_t stream) {
   YOGO_CHECK_ARG(dy && packed_dgrad && dx && signs, "conv2d_dgrad_bf16_signs: null pointer");
-  if (int e = check_bf16_conv(B, Cin, Cout, IH, IW, ks, stride)) return e;
-  const int pad = ks == 3 ? 1 : 0;
-  const int OHf = (IH + 2 * pad - ks) / stride + 1, OWf = (IW + 2 * pad - ks) / stride + 1;
-  return launch_conv_bf16(dy, packed_dgrad, nullptr, dx, nullptr, nullptr, nullptr, ACT_LEAKY, const_cast<void*>(signs), true, chan_scale,
-                          nullptr, B, Cout, Cin, OHf, OWf, IH, IW, ks, 1, (stride == 2 && ks == 3) ? 1 : 0, ACT_NONE, stream, nullptr,
-                          nullptr);
+  ConvBf16Request r;
+  if (int e = bf_request(B, Cin, Cout, IH, IW, ks, stride, BF_DGRAD, &r)) return e;
+  r.in = dy; r.packed = packed_dgrad; r.out = dx; r.ref_act = ACT_LEAKY; r.signs = const_cast<void*>(signs); r.signs_read = true; r.chan_scale = chan_scale;
+  return launch_conv_bf16(r, stream);
 }
 
 // dx = conv_transpose(dy) * act'(act_ref) * chan_scale, all bf16 NCHW8c; (IH, IW) = the forward conv's INPUT dims.
@@ -1736,11 +1794,10 @@ extern "C" int yogo_conv2d_dgrad_bf16(const void* dy, const void* packed_dgrad, 
                                       const float* chan_scale, int B, int Cin, int Cout, int IH, int IW, int ks, int stride,
                                       hipStream_t stream) {
   YOGO_CHECK_ARG(dy && packed_dgrad && dx, "conv2d_dgrad_bf16: null pointer");
-  if (int e = check_bf16_conv(B, Cin, Cout, IH, IW, ks, stride)) return e;
-  const int pad = ks == 3 ? 1 : 0;
-  const int OHf = (IH + 2 * pad - ks) / stride + 1, OWf = (IW + 2 * pad - ks) / stride + 1;
-  return launch_conv_bf16(dy, packed_dgrad, nullptr, dx, nullptr, nullptr, act_ref, ref_act, nullptr, false, chan_scale, nullptr, B, Cout, Cin, OHf, OWf,
-                          IH, IW, ks, 1, (stride == 2 && ks == 3) ? 1 : 0, ACT_NONE, stream, nullptr, nullptr);
+  ConvBf16Request r;
+  if (int e = bf_request(B, Cin, Cout, IH, IW, ks, stride, BF_DGRAD, &r)) return e;
+  r.in = dy; r.packed = packed_dgrad; r.out = dx; r.act_ref = act_ref; r.ref_act = ref_act; r.chan_scale = chan_scale;
+  return launch_conv_bf16(r, stream);
 }
 
 // first conv (Cin 1|3; in_dtype 0 = uint8, 1 = float32), fp32 weights [Cout][Cin][3][3] with BatchNorm already folded;

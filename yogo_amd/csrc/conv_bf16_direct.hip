@@ -21,7 +21,6 @@
 #ifndef YOGO_ST_AUX
 #define YOGO_ST_AUX 2
 #endif
-#include <mutex>
 
 #ifndef DD_ABL
 #define DD_ABL 0   // (ablation variant builds: 1 = no stores, 2 = no MFMAs, 4 = no operand loads, 8 = no weight reads)
@@ -243,34 +242,10 @@ bool conv_bf16_s2d_direct_eligible(int K, int M, int OH, int OW, int B) {
 
 int launch_conv_bf16_s2d_direct(const void* in, const void* packed, void* out, const void* signs, const float* chan_scale, int B, int K, int M, int IH, int IW,
                                 int OH, int OW, hipStream_t stream) {
-  static std::mutex mu;
-  static int n_cu_of[64] = {0};
-  static bool attr_set[64] = {false};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-    yogo_set_error("conv_bf16_s2d_direct: hipGetDevice failed");
-    return YOGO_ERR_HIP;
-  }
   const int nmb = M <= 32 ? 1 : 2;
   const int lds = 9 * (K / 8) * 32 * nmb * 16 + 4 * nmb * 32 * nmb * 4;   // 18 / 36 KB (four workgroups per CU); 147 KB + 2 KB (one)
   int n_cu;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    if (n_cu_of[dev] == 0) {
-      hipDeviceProp_t prop;
-      n_cu_of[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    n_cu = n_cu_of[dev];
-    if (nmb == 2 && !attr_set[dev]) {   // more than 64 KB of dynamic LDS has to be asked for
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_s2d_direct_kernel<8, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_s2d_direct_kernel<8, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) {
-        yogo_set_error("conv_bf16_s2d_direct: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return YOGO_ERR_HIP;
-      }
-      attr_set[dev] = true;
-    }
-  }
+  if (int e = yogo_device_cus("conv_bf16_s2d_direct", &n_cu)) return e;
   ConvDirectS2dParams p{};
   p.in = reinterpret_cast<const u32x4*>(in); p.wp = reinterpret_cast<const u32x4*>(packed); p.out = reinterpret_cast<u32x4*>(out);
   p.signs = reinterpret_cast<const unsigned char*>(signs); p.chan_scale = chan_scale;
@@ -278,14 +253,17 @@ int launch_conv_bf16_s2d_direct(const void* in, const void* packed, void* out, c
   p.npass = p.Mpad / (32 * nmb);
   p.tiles_per_img = cdiv(IH * IW, 32);
   p.ntiles = B * p.tiles_per_img;
-  auto magic = [](int d) -> unsigned { return d <= 1 ? 0xFFFFFFFFu : (unsigned)(((1ull << 32) + (unsigned)d - 1ull) / (unsigned)d); };
-  p.m_iw = magic(IW); p.m_tpi = magic(p.tiles_per_img);
+  p.m_iw = magic_u32(IW); p.m_tpi = magic_u32(p.tiles_per_img);
   if (p.ntiles <= 0) return YOGO_OK;
   // whole rounds of the 8 XCDs (x the passes): NMB = 1 up to four workgroups per CU, NMB = 2 one
   const int t8 = cdiv(p.ntiles, 8);
   const int grid = nmb == 1 ? 8 * max(1, min(cdiv(t8, 4), 4 * n_cu / 8)) : 16 * max(1, min(cdiv(t8, 8), n_cu / 16));
   const bool sg = signs != nullptr;
 #define DD_LAUNCH(NK, NMB, S) hipLaunchKernelGGL((conv_bf16_s2d_direct_kernel<NK, NMB, S>), dim3(grid), dim3(256 * NMB), lds, stream, p)
+  if (nmb == 2) {   // more than 64 KB of dynamic LDS has to be asked for
+    const void* kernel = sg ? reinterpret_cast<const void*>(&conv_bf16_s2d_direct_kernel<8, 2, true>) : reinterpret_cast<const void*>(&conv_bf16_s2d_direct_kernel<8, 2, false>);
+    if (int e = yogo_func_dynamic_lds(kernel, lds, "conv_bf16_s2d_direct")) return e;
+  }
   if (K == 128) { if (sg) DD_LAUNCH(8, 2, true); else DD_LAUNCH(8, 2, false); }
   else if (K == 64) { if (sg) DD_LAUNCH(4, 1, true); else DD_LAUNCH(4, 1, false); }
   else { if (sg) DD_LAUNCH(2, 1, true); else DD_LAUNCH(2, 1, false); }

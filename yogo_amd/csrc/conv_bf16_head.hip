@@ -11,7 +11,6 @@
 //   of operations -- this file is built with -ffp-contract=off like that one -- so `model(x)` in eval mode gets the bits the two launches gave
 //   and the raw head output never goes through memory.
 #include "common.h"
-#include <mutex>
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -34,22 +33,6 @@ struct ConvHeadParams {
 
 namespace {
 __device__ __forceinline__ int ch_udivm1(int n, int d, unsigned m) { return d == 1 ? n : (int)__umulhi((unsigned)n, m); }
-unsigned ch_magic(int d) { return d <= 1 ? 0xFFFFFFFFu : (unsigned)(((1ull << 32) + (unsigned)d - 1ull) / (unsigned)d); }
-int ch_n_cu() {
-  static std::mutex mu;
-  static int n_cu_of[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-    yogo_set_error("conv_bf16_head: hipGetDevice failed");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(mu);
-  if (n_cu_of[dev] == 0) {
-    hipDeviceProp_t prop;
-    n_cu_of[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-  }
-  return n_cu_of[dev];
-}
 }  // namespace
 
 __device__ __forceinline__ float ch_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }   // (decode_loss.hip: sigmoidf_)
@@ -191,12 +174,12 @@ struct ConvHeadDecode {   // the decode's operands (null cxs: no decode)
 };
 static int launch_head(const void* in, const void* packed, const float* bias, float* out_f32, int B, int K, int M, int plane, const ConvHeadDecode* dec,
                        hipStream_t stream) {
-  const int n_cu = ch_n_cu();
-  if (n_cu < 0) return YOGO_ERR_HIP;
+  int n_cu;
+  if (int e = yogo_device_cus("conv_bf16_head", &n_cu)) return e;
   ConvHeadParams p{};
   p.in = reinterpret_cast<const u32x4*>(in); p.wp = reinterpret_cast<const u32x4*>(packed); p.bias = bias; p.out_f32 = out_f32;
   p.B = B; p.Kb = K / 8; p.M = M; p.plane = plane;
-  p.tiles_per_img = cdiv(plane, 32); p.ntiles = B * p.tiles_per_img; p.m_tpi = ch_magic(p.tiles_per_img);
+  p.tiles_per_img = cdiv(plane, 32); p.ntiles = B * p.tiles_per_img; p.m_tpi = magic_u32(p.tiles_per_img);
   if (dec != nullptr) {
     p.cxs = dec->cxs; p.cys = dec->cys; p.inv_sx = dec->inv_sx; p.inv_sy = dec->inv_sy; p.anchor_w = dec->anchor_w; p.anchor_h = dec->anchor_h;
     p.wmul = dec->wmul; p.hmul = dec->hmul; p.inference = dec->inference;

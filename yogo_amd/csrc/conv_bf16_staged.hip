@@ -15,7 +15,6 @@
 // tap-minor as conv_bf16_kernel with 16-channel chunks does (bit-identical); the epilogue is its lean form: fma(acc, scale, bias * scale),
 // LeakyReLU as max(v, 0.01 v), the sign map of the result, bf16, half-wave exchange, 512 contiguous bytes per half-wave and store.
 #include "common.h"
-#include <mutex>
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -224,33 +223,23 @@ bool conv_bf16_staged_eligible(int K, int M, int stride, int IH, int IW, int OH,
 }
 
 namespace {
-unsigned cs_magic(int d) { return d <= 1 ? 0xFFFFFFFFu : (unsigned)(((1ull << 32) + (unsigned)d - 1ull) / (unsigned)d); }
 template <int S, int NK, int NMB, int NWV, int R, bool NT = false>
-int cs_launch(ConvStagedParams p, int dev, int n_cu, bool sg, hipStream_t stream, int* grid_out, int* lds_out) {
+int cs_launch(ConvStagedParams p, int n_cu, bool sg, hipStream_t stream, int* grid_out, int* lds_out) {
   constexpr int KB = 2 * NK, MP = 32 * NMB, ROWU = S == 2 ? 66 : 34, NDMA = (KB * ((R - 1) * S + 3) * ROWU + 63) / 64;
   p.tiles_per_row = cdiv(p.OW, 32);
   p.tiles_per_img = cdiv(p.OH, R) * p.tiles_per_row;
   p.ntiles = p.B * p.tiles_per_img;
-  p.m_tpr = cs_magic(p.tiles_per_row); p.m_tpi = cs_magic(p.tiles_per_img);
+  p.m_tpr = magic_u32(p.tiles_per_row); p.m_tpi = magic_u32(p.tiles_per_img);
   if (p.ntiles <= 0) return YOGO_OK;
   constexpr int lds = (9 * KB * MP + MP / 4 + NWV * MP / 4 + NWV * NDMA * 64) * 16;
   static_assert(lds <= 160 * 1024, "LDS");
   const int per_cu = max(1, min(16 / NWV, (160 * 1024) / lds));   // workgroups a CU holds
   const int t8 = cdiv(p.ntiles, 8);
   const int grid = 8 * max(1, min(cdiv(t8, NWV), per_cu * n_cu / 8));
-  if (lds > 64 * 1024) {   // more than 64 KB of dynamic LDS has to be asked for: once per device and instantiation
-    static std::mutex mu;
-    static bool done[64][2] = {};
-    std::lock_guard<std::mutex> lk(mu);
-    if (!done[dev][sg ? 1 : 0]) {
-      hipError_t e = sg ? hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_staged_kernel<S, NK, NMB, true, NWV, R, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)
-                        : hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_staged_kernel<S, NK, NMB, false, NWV, R, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) {
-        yogo_set_error("conv_bf16_staged: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return YOGO_ERR_HIP;
-      }
-      done[dev][sg ? 1 : 0] = true;
-    }
+  if (lds > 64 * 1024) {   // more than 64 KB of dynamic LDS has to be asked for
+    const void* kernel = sg ? reinterpret_cast<const void*>(&conv_bf16_staged_kernel<S, NK, NMB, true, NWV, R, NT>)
+                            : reinterpret_cast<const void*>(&conv_bf16_staged_kernel<S, NK, NMB, false, NWV, R, NT>);
+    if (int e = yogo_func_dynamic_lds(kernel, lds, "conv_bf16_staged")) return e;
   }
   if (sg) hipLaunchKernelGGL((conv_bf16_staged_kernel<S, NK, NMB, true, NWV, R, NT>), dim3(grid), dim3(64 * NWV), lds, stream, p);
   else hipLaunchKernelGGL((conv_bf16_staged_kernel<S, NK, NMB, false, NWV, R, NT>), dim3(grid), dim3(64 * NWV), lds, stream, p);
@@ -264,22 +253,8 @@ int cs_launch(ConvStagedParams p, int dev, int n_cu, bool sg, hipStream_t stream
 
 int launch_conv_bf16_staged(const void* in, const void* packed, const float* bias, void* out, void* signs, const float* chan_scale, int B, int K, int M, int IH,
                             int IW, int OH, int OW, int stride, int act, hipStream_t stream) {
-  static std::mutex mu;
-  static int n_cu_of[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-    yogo_set_error("conv_bf16_staged: hipGetDevice failed");
-    return YOGO_ERR_HIP;
-  }
   int n_cu;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    if (n_cu_of[dev] == 0) {
-      hipDeviceProp_t prop;
-      n_cu_of[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    n_cu = n_cu_of[dev];
-  }
+  if (int e = yogo_device_cus("conv_bf16_staged", &n_cu)) return e;
   ConvStagedParams p{};
   p.in = reinterpret_cast<const u32x4*>(in); p.wp = reinterpret_cast<const u32x4*>(packed); p.bias = bias; p.out = reinterpret_cast<u32x4*>(out);
   p.signs = reinterpret_cast<unsigned char*>(signs); p.chan_scale = chan_scale;
@@ -292,10 +267,10 @@ int launch_conv_bf16_staged(const void* in, const void* packed, const float* bia
   // stride 1 out of 16 into <= 32 channels (layer 1 forward): tiles of 8 rows and non-temporal stores (it writes twice what it reads): 7 - 9 % ahead of
   // the tiled kernel with the same stores (gpurun_out/r5_s1_ab1.log, r5_cs_ab4.log); with cached stores the two were equal, and layer 1's data
   // gradient (32 -> 16 channels: reads twice what it writes) came out equal either way (-2 ... +1 %): it stays with the tiled kernel, not instantiated
-  if (stride == 1) rc = cs_launch<1, 1, 1, 4, 8, true>(p, dev, n_cu, sg, stream, &grid, &lds);
+  if (stride == 1) rc = cs_launch<1, 1, 1, 4, 8, true>(p, n_cu, sg, stream, &grid, &lds);
   else
-  if (nk == 1) rc = nmb == 1 ? cs_launch<2, 1, 1, 4, 1>(p, dev, n_cu, sg, stream, &grid, &lds) : cs_launch<2, 1, 2, 4, 1>(p, dev, n_cu, sg, stream, &grid, &lds);
-  else rc = nmb == 1 ? cs_launch<2, 2, 1, 4, 1>(p, dev, n_cu, sg, stream, &grid, &lds) : cs_launch<2, 2, 2, 8, 1>(p, dev, n_cu, sg, stream, &grid, &lds);
+  if (nk == 1) rc = nmb == 1 ? cs_launch<2, 1, 1, 4, 1>(p, n_cu, sg, stream, &grid, &lds) : cs_launch<2, 1, 2, 4, 1>(p, n_cu, sg, stream, &grid, &lds);
+  else rc = nmb == 1 ? cs_launch<2, 2, 1, 4, 1>(p, n_cu, sg, stream, &grid, &lds) : cs_launch<2, 2, 2, 8, 1>(p, n_cu, sg, stream, &grid, &lds);
   if (rc != YOGO_OK) return rc;
   YOGO_CHECK_LAUNCH("conv_bf16_staged");
   return YOGO_OK;

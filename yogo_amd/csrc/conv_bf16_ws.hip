@@ -23,7 +23,6 @@
 //     One barrier per chunk orders everything: DMA landed (loaders wait vmcnt first), staging written (compute waits
 //     lgkmcnt), staging read, buffers free.
 #include "conv_bf16_ws.h"
-#include <mutex>
 #include <type_traits>
 #include <utility>
 
@@ -921,11 +920,10 @@ bool conv_bf16_ws_plan(ConvWsParams* p, int slots) {
   p->tiles_per_band = cdiv(OH * p->TW, WS_PT);
   p->gx = p->ncb * p->tiles_per_band;
   p->ntiles = p->B * p->gx;
-  auto magic = [](int d) -> unsigned { return d <= 1 ? 0xFFFFFFFFu : (unsigned)(((1ull << 32) + (unsigned)d - 1ull) / (unsigned)d); };
   const int bw_last = OW - (p->ncb - 1) * p->TW;
-  p->m_gx = magic(p->gx); p->m_tpb = magic(p->tiles_per_band);
-  p->m_bw = magic(p->TW); p->m_bwl = magic(bw_last);
-  p->m_lw = magic(p->TW + 2); p->m_lwl = magic(bw_last + 2);
+  p->m_gx = magic_u32(p->gx); p->m_tpb = magic_u32(p->tiles_per_band);
+  p->m_bw = magic_u32(p->TW); p->m_bwl = magic_u32(bw_last);
+  p->m_lw = magic_u32(p->TW + 2); p->m_lwl = magic_u32(bw_last + 2);
   p->nchunk = p->Kb / 2;
   // the kernels' divisions by multiplication: tile -> image / band / tile of the band, pixel -> row of its band, staged element -> row
   const int bw_l = OW - (p->ncb - 1) * p->TW;
@@ -936,32 +934,8 @@ bool conv_bf16_ws_plan(ConvWsParams* p, int slots) {
 }
 
 int launch_conv_bf16_ws(const ConvWsParams& p, hipStream_t stream) {
-  // per device, once: the dynamic-LDS attribute of every instantiation and the CU count (a second device in the process, or a
-  // first call from two host threads, must not see another device's state)
-  static std::mutex mu;
-  static int n_cu_of[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-    yogo_set_error("conv_bf16_ws: hipGetDevice failed");
-    return YOGO_ERR_HIP;
-  }
   int n_cu;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    if (n_cu_of[dev] == 0) {
-      hipError_t e = hipSuccess;
-#define WS_ATTR(M) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_ws_kernel<M>), hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS_BYTES);
-      WS_ATTR(0) WS_ATTR(1) WS_ATTR(3) WS_ATTR(4) WS_ATTR(5) WS_ATTR(7)
-#undef WS_ATTR
-      if (e != hipSuccess) {
-        yogo_set_error("conv_bf16_ws: hipFuncSetAttribute(MaxDynamicSharedMemorySize = %d) failed: %s", WS_LDS_BYTES, hipGetErrorString(e));
-        return YOGO_ERR_HIP;
-      }
-      hipDeviceProp_t prop;
-      n_cu_of[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    n_cu = n_cu_of[dev];
-  }
+  if (int e = yogo_device_cus("conv_bf16_ws", &n_cu)) return e;
   if (p.ntiles <= 0) return YOGO_OK;
   // one persistent workgroup per CU; a multiple of 8 so that a workgroup's tiles stay inside one XCD's run
   int grid = min(p.ntiles, n_cu);
@@ -972,7 +946,9 @@ int launch_conv_bf16_ws(const ConvWsParams& p, hipStream_t stream) {
     return YOGO_ERR_ARG;
   }
   const int mode = (leaky ? 1 : 0) | (sg ? 2 : 0) | (sc ? 4 : 0);
-#define WS_LAUNCH(M) case M: hipLaunchKernelGGL(conv_bf16_ws_kernel<M>, dim3(grid), dim3(512), WS_LDS_BYTES, stream, p); break;
+#define WS_LAUNCH(M) case M:                                                                                                    \
+    if (int e = yogo_func_dynamic_lds(reinterpret_cast<const void*>(&conv_bf16_ws_kernel<M>), WS_LDS_BYTES, "conv_bf16_ws")) return e; \
+    hipLaunchKernelGGL(conv_bf16_ws_kernel<M>, dim3(grid), dim3(512), WS_LDS_BYTES, stream, p); break;
   switch (mode) { WS_LAUNCH(0) WS_LAUNCH(1) WS_LAUNCH(3) WS_LAUNCH(4) WS_LAUNCH(5) WS_LAUNCH(7) }
 #undef WS_LAUNCH
   if (yogo_launch_log_enabled())

@@ -2,9 +2,10 @@
 // v_mfma_f32_16x16x32_bf16 -- the plain-epilogue member of the conv_bf16_ws family (layer 5's forward, the data gradients of
 // layers 5 / 6 of base_model: yogo/model_defns.py:54-65 and their autograd).
 //
-// Why a second member.  conv_bf16_ws_kernel runs its matrix pipes 0.755 busy at 1 627 MHz (profiles/r05_mfma_util.txt): it is limited by
-// the clock the chip holds under its power cap, and that clock depends on the MFMA shape (MI355X_MICROARCH.md "DVFS give-back" item 7).
-// Swapping the shape in situ at equal FLOPs and LDS reads (WS_ABL = 256, profiles/r06_ws_shape16_insitu_ab.log) gave -5.3 % on layer 5.
+// Why a second member.  Swapping the MFMA shape of conv_bf16_ws_kernel in situ at equal FLOPs and LDS reads (WS_ABL = 256,
+// profiles/r06_ws_shape16_insitu_ab.log) gave -5.3 % on layer 5.  What it buys is smaller than the clocks suggest:
+// the 16x16x32 shape does raise the clock (1 869 against 1 508 MHz) but the matrix pipes' busy fraction falls by half of that factor (0.705
+// against 0.785) -- the family is paced by its vector-memory stream, not by the clock the chip holds under its power cap as round 5 read it.
 // A 16x16x32 MFMA contracts 32 channels, so this kernel works on PAIRS of 16-channel chunks: lane l of a wavefront (column c16 = l & 15,
 // K group g = l >> 4) holds, per operand quad, the 8 channels of channel block g & 1 of chunk g >> 1 of the pair -- the packed weight
 // slices and the staged input tiles keep the 16-byte units of the family unchanged.  Both chunks of a pair have to be resident, which
@@ -33,7 +34,6 @@
 #ifndef W16_ABL
 #define W16_ABL 0
 #endif
-#include <mutex>
 #include <type_traits>
 #include <utility>
 
@@ -379,29 +379,8 @@ bool conv_bf16_ws16_eligible(int K, int M, int IH, int IW, int B) {
 }
 
 int launch_conv_bf16_ws16(const ConvWsParams& p, hipStream_t stream) {
-  static std::mutex mu;
-  static int n_cu_of[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-    yogo_set_error("conv_bf16_ws16: hipGetDevice failed");
-    return YOGO_ERR_HIP;
-  }
   int n_cu;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    if (n_cu_of[dev] == 0) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_ws16_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, W16_LDS_BYTES);
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_ws16_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, W16_LDS_BYTES);
-      if (e != hipSuccess) {
-        yogo_set_error("conv_bf16_ws16: hipFuncSetAttribute(MaxDynamicSharedMemorySize = %d) failed: %s", W16_LDS_BYTES, hipGetErrorString(e));
-        return YOGO_ERR_HIP;
-      }
-      hipDeviceProp_t prop;
-      n_cu_of[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    n_cu = n_cu_of[dev];
-  }
+  if (int e = yogo_device_cus("conv_bf16_ws16", &n_cu)) return e;
   if (p.ntiles <= 0) return YOGO_OK;
   if (p.act != ACT_NONE || p.signs != nullptr || p.chan_scale != nullptr || (p.nchunk & 3) != 0) {
     yogo_set_error("conv_bf16_ws16: plain epilogue and whole chunk-pair pairs only");
@@ -409,6 +388,8 @@ int launch_conv_bf16_ws16(const ConvWsParams& p, hipStream_t stream) {
   }
   int grid = min(p.ntiles, n_cu);
   if (grid >= 8) grid &= ~7;
+  const void* kernel = p.bias == nullptr ? reinterpret_cast<const void*>(&conv_bf16_ws16_kernel<false>) : reinterpret_cast<const void*>(&conv_bf16_ws16_kernel<true>);
+  if (int e = yogo_func_dynamic_lds(kernel, W16_LDS_BYTES, "conv_bf16_ws16")) return e;
   if (p.bias != nullptr) hipLaunchKernelGGL(conv_bf16_ws16_kernel<true>, dim3(grid), dim3(512), W16_LDS_BYTES, stream, p);
   else hipLaunchKernelGGL(conv_bf16_ws16_kernel<false>, dim3(grid), dim3(512), W16_LDS_BYTES, stream, p);
   if (yogo_launch_log_enabled())

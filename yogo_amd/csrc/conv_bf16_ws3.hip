@@ -13,7 +13,6 @@
 // an immediate of the ds_read.  Operands are requested two K steps ahead (conv_bf16_ws2.hip: an LDS read takes 200+ cycles beside
 // the LDS-DMA stream, a step's 4 MFMAs 128).
 #include "conv_bf16_ws3.h"
-#include <mutex>
 #include <type_traits>
 #include <utility>
 
@@ -529,10 +528,9 @@ bool conv_bf16_ws3_plan(ConvWs3Params* p) {
   p->tiles_per_band = cdiv(OH * p->TW, p->PT);
   p->gx = p->ncb * p->tiles_per_band;
   p->ntiles = p->B * p->gx;
-  auto magic = [](int d) -> unsigned { return d <= 1 ? 0xFFFFFFFFu : (unsigned)(((1ull << 32) + (unsigned)d - 1ull) / (unsigned)d); };
   const int bw_last = OW - (p->ncb - 1) * p->TW;
-  p->m_gx = magic(p->gx); p->m_tpb = magic(p->tiles_per_band);
-  p->m_bw = magic(p->TW); p->m_bwl = magic(bw_last);
+  p->m_gx = magic_u32(p->gx); p->m_tpb = magic_u32(p->tiles_per_band);
+  p->m_bw = magic_u32(p->TW); p->m_bwl = magic_u32(bw_last);
   p->nchunk = p->Kb / 2;
   // the kernel's divisions by multiplication: tile -> image / band / tile of the band, pixel -> row of its band
   if (!magic_div_exact((long long)p->ntiles - 1, p->gx) || !magic_div_exact(p->gx, p->tiles_per_band) || !magic_div_exact((long long)OH * p->TW, p->TW) ||
@@ -542,35 +540,15 @@ bool conv_bf16_ws3_plan(ConvWs3Params* p) {
 }
 
 int launch_conv_bf16_ws3(const ConvWs3Params& p, hipStream_t stream) {
-  static std::mutex mu;
-  static int n_cu_of[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-    yogo_set_error("conv_bf16_ws3: hipGetDevice failed");
-    return YOGO_ERR_HIP;
-  }
   int n_cu;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    if (n_cu_of[dev] == 0) {
-      hipError_t e = hipSuccess;
-#define W3_ATTR(M) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_ws3_kernel<M>), hipFuncAttributeMaxDynamicSharedMemorySize, W3_LDS_BYTES);
-      W3_ATTR(0) W3_ATTR(1) W3_ATTR(2) W3_ATTR(3) W3_ATTR(5) W3_ATTR(7)
-#undef W3_ATTR
-      if (e != hipSuccess) {
-        yogo_set_error("conv_bf16_ws3: hipFuncSetAttribute(MaxDynamicSharedMemorySize = %d) failed: %s", W3_LDS_BYTES, hipGetErrorString(e));
-        return YOGO_ERR_HIP;
-      }
-      hipDeviceProp_t prop;
-      n_cu_of[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    n_cu = n_cu_of[dev];
-  }
+  if (int e = yogo_device_cus("conv_bf16_ws3", &n_cu)) return e;
   if (p.ntiles <= 0) return YOGO_OK;
   int grid = min(p.ntiles, n_cu);
   if (grid >= 8) grid &= ~7;
   const int mode = (p.act == ACT_LEAKY ? 1 : 0) | (p.chan_scale != nullptr ? 2 : 0) | (p.signs != nullptr ? 4 : 0);   // (a sign map goes with LeakyReLU: the dispatch checks)
-#define W3_LAUNCH(M) case M: hipLaunchKernelGGL(conv_bf16_ws3_kernel<M>, dim3(grid), dim3(512), W3_LDS_BYTES, stream, p); break;
+#define W3_LAUNCH(M) case M:                                                                                                      \
+    if (int e = yogo_func_dynamic_lds(reinterpret_cast<const void*>(&conv_bf16_ws3_kernel<M>), W3_LDS_BYTES, "conv_bf16_ws3")) return e; \
+    hipLaunchKernelGGL(conv_bf16_ws3_kernel<M>, dim3(grid), dim3(512), W3_LDS_BYTES, stream, p); break;
   switch (mode) { W3_LAUNCH(0) W3_LAUNCH(1) W3_LAUNCH(2) W3_LAUNCH(3) W3_LAUNCH(5) W3_LAUNCH(7) }
 #undef W3_LAUNCH
   if (yogo_launch_log_enabled())

@@ -15,7 +15,6 @@
 // pair rounds 0.01 dy per element and sums in another order, so the two agree to fp32 rounding of sums over the whole batch, not bit for
 // bit (tests/test_gpu_first_fused_bwd.py: both against a CPU fp64 reference).
 #include "common.h"
-#include <mutex>
 #include <type_traits>
 #include <utility>
 
@@ -417,18 +416,6 @@ constexpr int df_lds_bytes(int R, int NWV, bool wg) {   // the wavefronts' piece
   return NWV * (((4 * (R + 2) * 34 + 63) / 64) * 1024 + (((2 * R + 1) * 18 + 63) / 64) * 256 + ((R * 16 + 63) / 64) * 256 + (wg ? R * 1024 : 0)) +
          2 * ((((2 * R + 1) * 72 + 15) / 16) * 16);
 }
-int df_n_cu() {
-  static std::mutex mu;
-  static int n_cu_of[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
-  std::lock_guard<std::mutex> lk(mu);
-  if (n_cu_of[dev] == 0) {
-    hipDeviceProp_t prop;
-    n_cu_of[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-  }
-  return n_cu_of[dev];
-}
 // the launch: workgroups, and the segment length -- short enough that the wavefronts of an XCD get equal shares, long enough that few tiles
 // re-read their upper halo from memory (cost = the busiest wavefront's tiles x (1 + the halo rows a segment's first tile fetches))
 struct DfPlan { int grid, seg; };
@@ -469,36 +456,19 @@ bool df_shape_ok(int Cmid, int Cout1, int H, int W, int B, int act0, bool wg) {
 
 template <bool WG>
 int df_launch(DgFirstParams p, int B, int H, int W, int act0, const char* what, hipStream_t stream) {
-  const int n_cu = df_n_cu();
-  if (n_cu < 0) {
-    yogo_set_error("%s: hipGetDevice failed", what);
-    return YOGO_ERR_HIP;
-  }
+  int n_cu;
+  if (int e = yogo_device_cus(what, &n_cu)) return e;
   constexpr int R = df_rows(WG);
   p.B = B; p.H = H; p.W = W; p.Mpad = 32; p.act = act0; p.ncol = DF_COUT * DF_PER + DF_NJ + DF_NJ * DF_NJ;
   const DfPlan pl = df_plan(B, H, W, n_cu, WG);
   p.tiles_per_row = cdiv(W, 32); p.tile_rows = cdiv(H, R); p.seg = pl.seg;
   p.segs_per_img = cdiv(p.tile_rows, pl.seg) * p.tiles_per_row; p.nsegs = B * p.segs_per_img;
-  auto magic = [](int d) -> unsigned { return d <= 1 ? 0xFFFFFFFFu : (unsigned)(((1ull << 32) + (unsigned)d - 1ull) / (unsigned)d); };
-  p.m_tpr = magic(p.tiles_per_row); p.m_spi = magic(p.segs_per_img);
+  p.m_tpr = magic_u32(p.tiles_per_row); p.m_spi = magic_u32(p.segs_per_img);
   const int grid = pl.grid;
   constexpr int lds = df_lds_bytes(R, DF_NWV, WG);
   static_assert(lds <= 160 * 1024, "LDS");
-  if (lds > 64 * 1024) {   // more than 64 KB of dynamic LDS has to be asked for: once per device and instantiation
-    static std::mutex mu;
-    static bool done[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(mu);
-    if (dev >= 0 && dev < 64 && !done[dev]) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_dgrad_first_bwd_kernel<R, DF_NWV, WG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) {
-        yogo_set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
-        return YOGO_ERR_HIP;
-      }
-      done[dev] = true;
-    }
-  }
+  if (lds > 64 * 1024)   // more than 64 KB of dynamic LDS has to be asked for
+    if (int e = yogo_func_dynamic_lds(reinterpret_cast<const void*>(&conv_bf16_dgrad_first_bwd_kernel<R, DF_NWV, WG>), lds, what)) return e;
   hipLaunchKernelGGL((conv_bf16_dgrad_first_bwd_kernel<R, DF_NWV, WG>), dim3(grid), dim3(64 * DF_NWV), lds, stream, p);
   if (yogo_launch_log_enabled())
     yogo_launch_log("conv_bf16_dgrad_first_bwd_kernel<%d, %d, %s> | K=32 M=16 at %dx%d segments=%d of %d tiles grid=%d lds=%d act0=%d", R, DF_NWV, WG ? "true" : "false", H, W,
@@ -524,11 +494,8 @@ extern "C" int yogo_conv2d_dgrad_first_bwd_supported(int Cmid, int Cout1, int H,
 // rows of the partial buffer (cols: yogo_conv_first_bn_wgrad_cols(1, Cmid)) on the current device; with_wgrad: of the _wgrad form below
 extern "C" int yogo_conv2d_dgrad_first_bwd_rows(int B, int H, int W, int with_wgrad, int* rows) {
   YOGO_CHECK_ARG(rows && B > 0 && H > 0 && W > 0, "conv2d_dgrad_first_bwd_rows: bad arguments");
-  const int n_cu = df_n_cu();
-  if (n_cu < 0) {
-    yogo_set_error("conv2d_dgrad_first_bwd_rows: hipGetDevice failed");
-    return YOGO_ERR_HIP;
-  }
+  int n_cu;
+  if (int e = yogo_device_cus("conv2d_dgrad_first_bwd_rows", &n_cu)) return e;
   *rows = df_plan(B, H, W, n_cu, with_wgrad != 0).grid * DF_NWV;
   return YOGO_OK;
 }
@@ -552,11 +519,8 @@ extern "C" int yogo_conv2d_dgrad_bf16_first_bwd(const void* g, const void* packe
 // them; workspace: yogo_conv2d_dgrad_wgrad_first_bwd_workspace_bytes; queue: NULL (reduce now) or a yogo_wgrad_reduce_queue (deferred)
 extern "C" int yogo_conv2d_dgrad_wgrad_first_bwd_workspace_bytes(int B, int H, int W, size_t* bytes) {
   YOGO_CHECK_ARG(bytes && B > 0 && H > 0 && W > 0, "conv2d_dgrad_wgrad_first_bwd_workspace_bytes: bad arguments");
-  const int n_cu = df_n_cu();
-  if (n_cu < 0) {
-    yogo_set_error("conv2d_dgrad_wgrad_first_bwd_workspace_bytes: hipGetDevice failed");
-    return YOGO_ERR_HIP;
-  }
+  int n_cu;
+  if (int e = yogo_device_cus("conv2d_dgrad_wgrad_first_bwd_workspace_bytes", &n_cu)) return e;
   *bytes = (size_t)df_plan(B, H, W, n_cu, true).grid * (9 * 32 * 16 + 32) * sizeof(float);
   return YOGO_OK;
 }
@@ -566,11 +530,8 @@ extern "C" int yogo_conv2d_dgrad_wgrad_bf16_first_bwd(const void* g, const void*
   YOGO_CHECK_ARG(g && packed && x && image && part && dw && workspace, "conv2d_dgrad_wgrad_bf16_first_bwd: null pointer");
   YOGO_CHECK_ARG(yogo_conv2d_dgrad_first_bwd_supported(Cmid, Cout1, H, W, B, act0), "conv2d_dgrad_wgrad_bf16_first_bwd: unsupported shape");
   YOGO_CHECK_ARG(signs != nullptr || act0 == ACT_NONE, "conv2d_dgrad_wgrad_bf16_first_bwd: LeakyReLU needs the sign map");
-  const int n_cu = df_n_cu();
-  if (n_cu < 0) {
-    yogo_set_error("conv2d_dgrad_wgrad_bf16_first_bwd: hipGetDevice failed");
-    return YOGO_ERR_HIP;
-  }
+  int n_cu;
+  if (int e = yogo_device_cus("conv2d_dgrad_wgrad_bf16_first_bwd", &n_cu)) return e;
   const int rows = df_plan(B, H, W, n_cu, true).grid;   // of the weight-gradient slab: one per workgroup
   DgFirstParams p{};
   p.g = reinterpret_cast<const u32x4*>(g); p.wp = reinterpret_cast<const u32x4*>(packed); p.img = reinterpret_cast<const unsigned char*>(image);

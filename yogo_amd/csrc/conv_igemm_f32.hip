@@ -550,12 +550,7 @@ int launch_igemm(const Geom& g, const float* in, const float* wp, const float* b
   if (g.B == 0 || g.OHt <= 0 || g.OWt <= 0) return YOGO_OK;
 #define LAUNCH(MW_, NW_, FU_)                                                                               \
   do {                                                                                                      \
-    static bool attr_set = false;                                                                           \
-    if (!attr_set) {                                                                                        \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_f32_kernel<MW_, NW_, FU_>),       \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);                          \
-      attr_set = true;                                                                                      \
-    }                                                                                                       \
+    if (int e = yogo_func_dynamic_lds(reinterpret_cast<const void*>(&conv_igemm_f32_kernel<MW_, NW_, FU_>), 128 * 1024, "conv_igemm_f32")) return e; \
     hipLaunchKernelGGL((conv_igemm_f32_kernel<MW_, NW_, FU_>), grid, dim3(256), tl.lds_bytes, stream, p);   \
     yogo_launch_log("conv_igemm_f32_kernel<" #MW_ ", " #NW_ ", " #FU_ "> | %s", plan_txt);                  \
   } while (0)

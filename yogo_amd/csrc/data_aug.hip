@@ -129,12 +129,7 @@ extern "C" int yogo_labels_rasterize(const float* labels, const int* offsets, fl
   const size_t lds = (size_t)Sx * Sy * sizeof(int);
   YOGO_CHECK_ARG(lds <= 160 * 1024, "labels_rasterize: grid of %d x %d cells does not fit the LDS", Sx, Sy);
   if (B == 0) return YOGO_OK;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&labels_rasterize_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    attr_set = true;
-  }
+  if (int e = yogo_func_dynamic_lds(reinterpret_cast<const void*>(&labels_rasterize_kernel), 160 * 1024, "labels_rasterize")) return e;
   hipLaunchKernelGGL(labels_rasterize_kernel, dim3(B), dim3(256), lds, stream, labels, offsets, out, status, Sx, Sy, box_format);
   YOGO_CHECK_LAUNCH("labels_rasterize");
   return YOGO_OK;

@@ -16,7 +16,6 @@
 #include "common.h"
 #include <cmath>
 #include <cstring>
-#include <mutex>
 
 #define MATCH_THREADS 1024
 #define MATCH_WAVES (MATCH_THREADS / 64)
@@ -43,26 +42,6 @@ struct MatchParams {
 // the host's workspace size
 __host__ __device__ inline size_t match_state_bytes(size_t nr, size_t nc, bool boxes) {
   return (boxes ? 16 * (nr + nc) : 0) + 8 * (nr + 2 * nc) + 4 * (2 * nr + 3 * nc);
-}
-
-// more than 64 KB of dynamic LDS has to be asked for: once per device and kernel (done[]: that kernel's flags), under one mutex
-static int allow_dynamic_lds(const void* kernel, int bytes, bool* done, const char* what) {
-  static std::mutex mu;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-    yogo_set_error("%s: hipGetDevice failed", what);
-    return YOGO_ERR_HIP;
-  }
-  std::lock_guard<std::mutex> lk(mu);
-  if (!done[dev]) {
-    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) {
-      yogo_set_error("%s: cannot reserve %d bytes of LDS: %s", what, bytes, hipGetErrorString(e));
-      return YOGO_ERR_HIP;
-    }
-    done[dev] = true;
-  }
-  return YOGO_OK;
 }
 
 template <bool WIDE>
@@ -642,9 +621,7 @@ extern "C" int yogo_match_preds_labels_batched(const float* rows, const int* cou
   p.ws = ws + ((16 - (reinterpret_cast<uintptr_t>(ws) & 15)) & 15);
   p.ws_per_image = (match_state_bytes((size_t)cap, (size_t)cap, false) + 15) & ~(size_t)15;
   p.B = B; p.P = P; p.cells = (int)cells; p.cap = cap;
-  static bool lds_allowed[64] = {false};
-  const int rc = allow_dynamic_lds(reinterpret_cast<const void*>(&match_kernel), MATCH_LDS_BYTES, lds_allowed, "match_preds_labels_batched");
-  if (rc != YOGO_OK) return rc;
+  if (int e = yogo_func_dynamic_lds(reinterpret_cast<const void*>(&match_kernel), MATCH_LDS_BYTES, "match_preds_labels_batched")) return e;
   yogo_launch_log("match_kernel | B=%d cells=%d P=%d lds=%d", B, (int)cells, P, MATCH_LDS_BYTES);
   hipLaunchKernelGGL(match_kernel, dim3(B), dim3(MATCH_THREADS), MATCH_LDS_BYTES, stream, p);
   YOGO_CHECK_LAUNCH("match_preds_labels_batched");
@@ -690,9 +667,7 @@ extern "C" int yogo_metrics_accumulate(const float* rows, const float* lab_out, 
   YOGO_CHECK_ARG(lds <= (size_t)ACC_LDS_MAX,
                  "metrics_accumulate: %d classes x %d thresholds x %d bins need %zu bytes of LDS, %d are available (at 500 thresholds and 30 bins: "
                  "up to 31 classes)", C, T, nbins, lds, ACC_LDS_MAX);
-  static bool lds_allowed[64] = {false};
-  const int rc = allow_dynamic_lds(reinterpret_cast<const void*>(&metrics_accumulate_kernel), ACC_LDS_MAX, lds_allowed, "metrics_accumulate");
-  if (rc != YOGO_OK) return rc;
+  if (int e = yogo_func_dynamic_lds(reinterpret_cast<const void*>(&metrics_accumulate_kernel), ACC_LDS_MAX, "metrics_accumulate")) return e;
   AccParams p{};
   p.rows = rows; p.lab_out = lab_out; p.meta = meta; p.pair_label = pair_label; p.pair_pred = pair_pred; p.un_label = un_label;
   p.un_pred = un_pred; p.roc_thr = roc_thresholds; p.cal_edges = cal_edges; p.acc = reinterpret_cast<unsigned long long*>(acc);

@@ -480,12 +480,7 @@ static int launch_format_preds(NmsParams p, void* workspace, double obj_thresh, 
   int npow2 = 64;
   while (npow2 < cells) npow2 <<= 1;
   const size_t lds = p.do_nms ? (size_t)npow2 * sizeof(unsigned long long) : 0;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nms_batched_kernel<DEC>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              NMS_MAX_CELLS * 8);
-    attr_set = true;
-  }
+  if (int e = yogo_func_dynamic_lds(reinterpret_cast<const void*>(&nms_batched_kernel<DEC>), NMS_MAX_CELLS * 8, what)) return e;
   yogo_launch_log("nms_batched_kernel<%s> | B=%d cells=%d P=%d nms=%d", DEC ? "true" : "false", B, cells, p.P, p.do_nms);
   hipLaunchKernelGGL(nms_batched_kernel<DEC>, dim3(B), dim3(NMS_THREADS), lds, stream, p);
   YOGO_CHECK_LAUNCH(what);

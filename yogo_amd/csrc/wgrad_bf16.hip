@@ -16,7 +16,6 @@
 // offsets (which the buffer unit writes as zeros).  One barrier per unit, up to two units in flight ahead of the MFMAs.  Split-K slabs + the fixed-order reduction of
 // wgrad_f32.hip (clamp, OIHW, bias) finish the gradient.
 #include "common.h"
-#include <mutex>
 #include <type_traits>
 #include <utility>
 
@@ -709,27 +708,8 @@ int wb_bias_rows(const WbPlan& pl, int T) {
 
 template <int MBW, int NBW, int NPW, int KS, int T, int S, int R, int MPW = 1, bool ROT = false, bool PACK2 = false, bool BLK4 = false>
 int wb_launch_one(const WgradBf16Params& p, const WbPlan& pl, hipStream_t stream) {
-  // per device, once per instantiation: the dynamic-LDS limit (a second device in the process, or a first call from two host threads,
-  // must not see another device's state)
-  static std::mutex mu;
-  static bool done[64] = {false};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-    yogo_set_error("wgrad_bf16: hipGetDevice failed");
-    return YOGO_ERR_HIP;
-  }
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    if (!done[dev]) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16_kernel<MBW, NBW, NPW, KS, T, S, R, MPW, ROT, PACK2, BLK4>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, WGB_LDS_MAX);
-      if (e != hipSuccess) {
-        yogo_set_error("wgrad_bf16: hipFuncSetAttribute(MaxDynamicSharedMemorySize = %d) failed: %s", WGB_LDS_MAX, hipGetErrorString(e));
-        return YOGO_ERR_HIP;
-      }
-      done[dev] = true;
-    }
-  }
+  if (int e = yogo_func_dynamic_lds(reinterpret_cast<const void*>(&wgrad_bf16_kernel<MBW, NBW, NPW, KS, T, S, R, MPW, ROT, PACK2, BLK4>), WGB_LDS_MAX, "wgrad_bf16"))
+    return e;
   hipLaunchKernelGGL((wgrad_bf16_kernel<MBW, NBW, NPW, KS, T, S, R, MPW, ROT, PACK2, BLK4>), pl.grid, dim3(64 * MBW * NBW * KS * (T == 1 ? 1 : 3)),
                      pl.lds_bytes, stream, p);
   yogo_launch_log("wgrad_bf16_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %s, %s, %s> | %s", MBW, NBW, NPW, KS, T, S, R, MPW, ROT ? "true" : "false",

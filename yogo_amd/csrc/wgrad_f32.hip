@@ -476,7 +476,8 @@ struct WgradPlan {
   dim3 grid;
 };
 
-unsigned magic_u32(int d) { return (unsigned)(((1ull << 32) + (unsigned long long)d - 1ull) / (unsigned long long)d); }
+// (not common.h's magic_u32: at d = 1 this one wraps to 0)
+unsigned wg_inv_u32(int d) { return (unsigned)(((1ull << 32) + (unsigned long long)d - 1ull) / (unsigned long long)d); }
 
 bool make_plan(int B, int N, int M, int IH, int IW, int ks, int stride, WgradPlan* pl) {
   const int pad = ks == 3 ? 1 : 0;
@@ -516,28 +517,23 @@ bool make_plan(int B, int N, int M, int IH, int IW, int ks, int stride, WgradPla
 }
 
 template <int MBW, int NBW, int KS, int T, int S, bool BF>
-void launch_one(const WgradParams& p, const WgradPlan& pl, hipStream_t stream) {
-  static bool s = false;
-  if (!s) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_f32_kernel<MBW, NBW, KS, T, S, BF>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, WGRAD_LDS_BUDGET);
-    s = true;
-  }
+int launch_one(const WgradParams& p, const WgradPlan& pl, hipStream_t stream) {
+  if (int e = yogo_func_dynamic_lds(reinterpret_cast<const void*>(&wgrad_f32_kernel<MBW, NBW, KS, T, S, BF>), WGRAD_LDS_BUDGET, "conv2d_wgrad")) return e;
   hipLaunchKernelGGL((wgrad_f32_kernel<MBW, NBW, KS, T, S, BF>), pl.grid, dim3(64 * MBW * NBW * KS * (T == 1 ? 1 : 3)), pl.lds_bytes,
                      stream, p);
+  return YOGO_OK;
 }
 
 template <int MBW, int NBW, int KS>
-void launch_wgrad(const WgradParams& p, const WgradPlan& pl, int T, int stride, bool bf, hipStream_t stream) {
+int launch_wgrad(const WgradParams& p, const WgradPlan& pl, int T, int stride, bool bf, hipStream_t stream) {
   if (bf) {
-    if (T == 1) launch_one<MBW, NBW, KS, 1, 1, true>(p, pl, stream);
-    else if (stride == 1) launch_one<MBW, NBW, KS, 9, 1, true>(p, pl, stream);
-    else launch_one<MBW, NBW, KS, 9, 2, true>(p, pl, stream);
-  } else {
-    if (T == 1) launch_one<MBW, NBW, KS, 1, 1, false>(p, pl, stream);
-    else if (stride == 1) launch_one<MBW, NBW, KS, 9, 1, false>(p, pl, stream);
-    else launch_one<MBW, NBW, KS, 9, 2, false>(p, pl, stream);
+    if (T == 1) return launch_one<MBW, NBW, KS, 1, 1, true>(p, pl, stream);
+    if (stride == 1) return launch_one<MBW, NBW, KS, 9, 1, true>(p, pl, stream);
+    return launch_one<MBW, NBW, KS, 9, 2, true>(p, pl, stream);
   }
+  if (T == 1) return launch_one<MBW, NBW, KS, 1, 1, false>(p, pl, stream);
+  if (stride == 1) return launch_one<MBW, NBW, KS, 9, 1, false>(p, pl, stream);
+  return launch_one<MBW, NBW, KS, 9, 2, false>(p, pl, stream);
 }
 
 }  // namespace
@@ -582,22 +578,24 @@ static int wgrad_impl(const void* x_, const void* g_, bool bf, float* dw, float*
   p.B = B; p.N = Cin; p.M = Cout; p.Npad = pl.Npad; p.Mpad = pl.Mpad; p.IH = IH; p.IW = IW;
   p.OH = (IH + 2 * pad - ks) / stride + 1; p.OW = (IW + 2 * pad - ks) / stride + 1; p.pad = pad;
   p.nchunk_w = pl.nchunk_w; p.base_w = pl.base_w; p.rem_w = pl.rem_w; p.wce = pl.wce; p.xw = pl.xw; p.per_ch = pl.per_ch;
-  p.inv_wce = magic_u32(pl.wce); p.inv_xw = magic_u32(pl.xw); p.inv_pc = magic_u32(pl.per_ch);
+  p.inv_wce = wg_inv_u32(pl.wce); p.inv_xw = wg_inv_u32(pl.xw); p.inv_pc = wg_inv_u32(pl.per_ch);
   p.units = pl.units; p.units_per_split = pl.units_per_split;
   p.gp = pl.gp; p.xp = pl.xp; p.x_off = pl.x_off; p.lds_dummy = pl.lds_dummy;
   p.Nb = ((Cin + 15) / 16) * 2; p.Mbk = ((Cout + 15) / 16) * 2;
   const int cfg = pl.MBW * 100 + pl.NBW * 10 + pl.KS;
+  int rc;
   switch (cfg) {
-    case 411: launch_wgrad<4, 1, 1>(p, pl, T, stride, bf, stream); break;
-    case 221: launch_wgrad<2, 2, 1>(p, pl, T, stride, bf, stream); break;
-    case 212: launch_wgrad<2, 1, 2>(p, pl, T, stride, bf, stream); break;
-    case 141: launch_wgrad<1, 4, 1>(p, pl, T, stride, bf, stream); break;
-    case 122: launch_wgrad<1, 2, 2>(p, pl, T, stride, bf, stream); break;
-    case 114: launch_wgrad<1, 1, 4>(p, pl, T, stride, bf, stream); break;
+    case 411: rc = launch_wgrad<4, 1, 1>(p, pl, T, stride, bf, stream); break;
+    case 221: rc = launch_wgrad<2, 2, 1>(p, pl, T, stride, bf, stream); break;
+    case 212: rc = launch_wgrad<2, 1, 2>(p, pl, T, stride, bf, stream); break;
+    case 141: rc = launch_wgrad<1, 4, 1>(p, pl, T, stride, bf, stream); break;
+    case 122: rc = launch_wgrad<1, 2, 2>(p, pl, T, stride, bf, stream); break;
+    case 114: rc = launch_wgrad<1, 1, 4>(p, pl, T, stride, bf, stream); break;
     default:
       yogo_set_error("wgrad: unsupported wave layout %d", cfg);
       return YOGO_ERR_ARG;
   }
+  if (rc != YOGO_OK) return rc;
   const int nw = (int)(((size_t)T * pl.Mpad * pl.Npad) / 64);
   hipLaunchKernelGGL(wgrad_reduce_kernel<4>, dim3(nw + (db ? cdiv(Cout, 256) : 0)), dim3(256), 0, stream, p.slab,
                      pl.nsplit * pl.KS, T, Cout, Cin, pl.Mpad, pl.Npad, clip, dw, p.bias_part, pl.nsplit, db);
