@@ -1,4 +1,4 @@
-"""Edge cases for the decode and loss kernels (yogo_amd/csrc/decode_loss.hip), their references and a numpy transcription.  Host only.
+"""Edge cases for the decode and loss kernels (yogo_amd/csrc/decode_loss.hip; their arithmetic: head_math.h), their references and a numpy transcription.  Host only.
 
 CASES.  Every box corner is dyadic (a multiple of 2^-6, scaled by 2^-k about a dyadic anchor), so corners, clamps and comparisons are
 exact in float32 AND float64: both precisions take the same branch at every `max` / `min` tie, clamp mask, `has` predicate and exp
@@ -12,8 +12,8 @@ F.cross_entropy, F.mse_loss, O.decode) per cell with torch autograd, in float64 
 imitates).  Nothing comes from the code under test.  Scale of a cell: s = max(max_c |ref32 - ref64|, ulp32(max_c |ref64|)); a kernel
 is held to |kernel - ref64| <= M s  (M: tests/_util.py LOSS_EDGE_M).
 
-TRANSCRIPTION.  `k_loss`, `k_decode`, `k_decode_bwd` restate the kernels' per-cell statements in numpy float32 (no fused multiply-add,
-as the translation unit is built with -ffp-contract=off).  `var` switches in the wrong variants that the host test must reject.
+TRANSCRIPTION.  `k_loss`, `k_decode`, `k_decode_bwd` restate the kernels' per-cell statements (the functions of head_math.h in the order
+the kernels call them) in numpy float32 (no fused multiply-add, as their translation units are built with -ffp-contract=off).  `var` switches in the wrong variants that the host test must reject.
 """
 import functools
 
@@ -159,7 +159,7 @@ _BOX = _xyxy_to_cell(np.asarray((10, 12, 30, 50)) / 64)
 _LAB = (np.asarray(G0) / 64).astype(F32)
 
 
-LSE_FOLD_MAX = F32(16)                                       # decode_loss.hip: the largest |max logit| whose log-sum-exp is folded
+LSE_FOLD_MAX = F32(16)                                       # head_math.h: the largest |max logit| whose log-sum-exp is folded
 _FOLD_UP = float(np.nextafter(LSE_FOLD_MAX, F32(np.inf)))
 
 
@@ -421,7 +421,7 @@ def _sig(x):
 
 
 def k_decode(raw, cxs, cys, inv_sx, inv_sy, anchors, inference):
-    """decode_fwd_kernel; raw [n, P], cxs / cys [n] (the cell's grid values)"""
+    """decode_fwd_kernel (head_math.h: hm_centre, hm_size, hm_sigmoid, hm_softmax_terms, hm_softmax); raw [n, P], cxs / cys [n] (the cell's grid values)"""
     r = np.asarray(raw, dtype=F32)
     aw, ah, wm, hm = (F32(v) for v in anchors)
     o = np.empty_like(r)
@@ -446,7 +446,7 @@ def k_decode(raw, cxs, cys, inv_sx, inv_sy, anchors, inference):
 
 
 def k_decode_bwd(raw, out, gout, inv_sx, inv_sy, inference, var=()):
-    """decode_bwd_kernel"""
+    """decode_bwd_kernel (head_math.h: hm_centre_bwd, hm_size_bwd, hm_obj_bwd, hm_softmax_bwd_dot, hm_softmax_bwd)"""
     r, o, g = (np.asarray(a, dtype=F32) for a in (raw, out, gout))
     one = F32(1)
     d = np.empty_like(r)
@@ -472,13 +472,13 @@ def k_decode_bwd(raw, out, gout, inv_sx, inv_sy, inference, var=()):
 
 
 def _logp(x, mx, lsum, var):
-    """log_softmax_ of decode_loss.hip: max + log(sum) folded into one constant while |max| <= LSE_FOLD_MAX, the shift first beyond"""
+    """log_softmax_ of head_math.h: max + log(sum) folded into one constant while |max| <= LSE_FOLD_MAX, the shift first beyond"""
     fold = np.ones_like(mx, dtype=bool) if "lse_always_folded" in var else np.abs(mx) <= LSE_FOLD_MAX
     return np.where(fold, x - (mx + lsum), (x - mx) - lsum)
 
 
 def k_loss(pred, label, w, inv_batch=1.0, var=()):
-    """yogo_loss_kernel, per cell: pred [n, P], label [n, 6] -> (val [3, n], grad [n, P]) float32"""
+    """yogo_loss_kernel (head_math.h: hm_obj_term, hm_ciou_cell, hm_ce_cell, hm_ce_grad), per cell: pred [n, P], label [n, 6] -> (val [3, n], grad [n, P]) float32"""
     pr, lb = np.asarray(pred, dtype=F32), np.asarray(label, dtype=F32)
     now, iw, cw, ls = (F32(v) for v in w)
     ib = F32(inv_batch)

@@ -7,10 +7,10 @@
 // -18.6 % (0.118 -> 0.096 ms, gpurun_out/r5_hd_ab2.log).  The head's DATA GRADIENT in the same form (1 load, 4 MFMAs, 8 stores per tile) was
 // 6 - 12 % slower than the tiled kernel (same log) and is not in the tree.
 //   DEC = true (round 6): the box decode of yogo/model.py:277-313 applied to the pixel's 5 + C outputs where they sit in registers (SURVEY.md 8b,
-//   head1x1_decode_fwd): sigmoid / exp / softmax and the grid offset with the expressions of decode_fwd_kernel (decode_loss.hip) in its order
-//   of operations -- this file is built with -ffp-contract=off like that one -- so `model(x)` in eval mode gets the bits the two launches gave
+//   head1x1_decode_fwd): sigmoid / exp / softmax and the grid offset are head_math.h's functions, the ones decode_fwd_kernel
+//   (decode_loss.hip) calls -- this file is built with -ffp-contract=off like that one -- so `model(x)` in eval mode gets the bits the two launches gave
 //   and the raw head output never goes through memory.
-#include "common.h"
+#include "head_math.h"
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -34,8 +34,6 @@ struct ConvHeadParams {
 namespace {
 __device__ __forceinline__ int ch_udivm1(int n, int d, unsigned m) { return d == 1 ? n : (int)__umulhi((unsigned)n, m); }
 }  // namespace
-
-__device__ __forceinline__ float ch_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }   // (decode_loss.hip: sigmoidf_)
 
 // NK: 16-channel steps of the contraction (K / 16, <= 8); M <= 32 (DEC: 6 <= M <= 16)
 template <int NK, bool DEC = false>
@@ -89,16 +87,16 @@ __global__ __launch_bounds__(256) void conv_bf16_1x1_f32_kernel(const ConvHeadPa
       for (int i = 0; i < 8; ++i) o[i] = v[i];
       const int pxc = ov ? px : 0;
       if (half == 0) {
-        o[0] = p.inv_sx * ch_sigmoid(v[0]) + p.cxs[pxc];
-        o[1] = p.inv_sy * ch_sigmoid(v[1]) + p.cys[pxc];
-        o[2] = p.anchor_w * expf(fminf(v[2], 80.f)) * p.wmul;
-        o[3] = p.anchor_h * expf(fminf(v[3], 80.f)) * p.hmul;
+        o[0] = hm_centre(p.inv_sx, v[0], p.cxs[pxc]);
+        o[1] = hm_centre(p.inv_sy, v[1], p.cys[pxc]);
+        o[2] = hm_size(p.anchor_w, v[2], p.wmul);
+        o[3] = hm_size(p.anchor_h, v[3], p.hmul);
       } else {
-        o[0] = ch_sigmoid(v[0]);
+        o[0] = hm_sigmoid(v[0]);
       }
       if (p.inference) {
-        // softmax over the class channels in decode_fwd_kernel's order: max over all, then sum += expf(v - mx) channel by channel -- the
-        // running sum crosses the half-wavefronts where the channel order does (5..7 | 8..11 | 12..15)
+        // softmax over the class channels in hm_softmax_terms' order (head_math.h): max over all, then sum += expf(v - mx) channel by channel
+        // -- the running sum crosses the half-wavefronts where the channel order does (5..7 | 8..11 | 12..15)
         const int i0 = half == 0 ? 4 : 1;   // this lane's first class slot (half 1: slots 1..3 = channels 5..7, slots 4..7 = 12..15)
         float mx = -INFINITY;
 #pragma unroll
@@ -134,7 +132,7 @@ __global__ __launch_bounds__(256) void conv_bf16_1x1_f32_kernel(const ConvHeadPa
         if (half == 0) sum = tot;
 #pragma unroll
         for (int i = 0; i < 8; ++i)
-          if (i >= i0) o[i] = e[i] / sum;
+          if (i >= i0) o[i] = hm_softmax(v[i], mx, sum);
       }
       if (ov) {
 #pragma unroll

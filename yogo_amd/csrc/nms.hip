@@ -18,10 +18,10 @@
 // objectness / class thresholds compared in float32 (torch casts the Python scalar to the tensor dtype).
 //
 // DEC = true (yogo_decode_format_preds_batched) takes the head's RAW output and decodes a value where it is loaded (the
-// arithmetic of decode_fwd_kernel, decode_loss.hip: same expressions, same -ffp-contract=off, so each value has the bits the
+// functions of head_math.h that decode_fwd_kernel calls, under the same -ffp-contract=off, so each value has the bits the
 // separate decode pass would have stored): the decoded [B, 5+C, Sy, Sx] tensor of `yogo infer` (yogo/model.py:277-313 ->
 // yogo/infer.py:45,73) is never written or read back, and the kept rows / cells / counts are identical.
-#include "common.h"
+#include "head_math.h"
 #include <cmath>
 #include <cstring>
 
@@ -55,21 +55,19 @@ struct NmsParams {
   int inference;          // class channels: softmax (1) or raw logits (0)
 };
 
-__device__ __forceinline__ float nms_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 // One image's prediction as the kernel sees it: the decoded tensor itself (DEC = false) or the raw head output decoded per load.
 template <bool DEC>
 struct PredView {
   const float* pred;   // [P][cells] of this image
   const NmsParams& p;
   __device__ __forceinline__ float at(int ch, int cell) const { return pred[(size_t)ch * p.cells + cell]; }
-  __device__ __forceinline__ float obj(int cell) const { return DEC ? nms_sigmoid(at(4, cell)) : at(4, cell); }
+  __device__ __forceinline__ float obj(int cell) const { return DEC ? hm_sigmoid(at(4, cell)) : at(4, cell); }
   __device__ __forceinline__ void box(int cell, float& cx, float& cy, float& w, float& h) const {
     if (DEC) {
-      cx = p.inv_sx * nms_sigmoid(at(0, cell)) + p.cxs[cell];
-      cy = p.inv_sy * nms_sigmoid(at(1, cell)) + p.cys[cell];
-      w = p.anchor_w * expf(fminf(at(2, cell), 80.f)) * p.wmul;
-      h = p.anchor_h * expf(fminf(at(3, cell), 80.f)) * p.hmul;
+      cx = hm_centre(p.inv_sx, at(0, cell), p.cxs[cell]);
+      cy = hm_centre(p.inv_sy, at(1, cell), p.cys[cell]);
+      w = hm_size(p.anchor_w, at(2, cell), p.wmul);
+      h = hm_size(p.anchor_h, at(3, cell), p.hmul);
     } else {
       cx = at(0, cell);
       cy = at(1, cell);
@@ -77,13 +75,9 @@ struct PredView {
       h = at(3, cell);
     }
   }
-  // softmax normalisation of the cell (decode_fwd_kernel's mx / sum), only for DEC && inference
+  // softmax normalisation of the cell, only for DEC && inference
   __device__ __forceinline__ void softmax_terms(int cell, float& mx, float& sum) const {
-    const int C = p.P - 5;
-    mx = -INFINITY;
-    for (int c = 0; c < C; ++c) mx = fmaxf(mx, at(5 + c, cell));
-    sum = 0.f;
-    for (int c = 0; c < C; ++c) sum += expf(at(5 + c, cell) - mx);
+    hm_softmax_terms(pred + cell, p.cells, p.P, mx, sum);
   }
   // NaN-propagating max over the class channels, like torch.max
   __device__ __forceinline__ float max_cls(int cell) const {
@@ -91,9 +85,9 @@ struct PredView {
     float smx = 0.f, ssum = 1.f;
     const bool sm = DEC && p.inference;
     if (sm) softmax_terms(cell, smx, ssum);
-    float mx = sm ? expf(at(5, cell) - smx) / ssum : at(5, cell);
+    float mx = sm ? hm_softmax(at(5, cell), smx, ssum) : at(5, cell);
     for (int c = 1; c < C; ++c) {
-      const float v = sm ? expf(at(5 + c, cell) - smx) / ssum : at(5 + c, cell);
+      const float v = sm ? hm_softmax(at(5 + c, cell), smx, ssum) : at(5 + c, cell);
       mx = (v > mx || v != v) ? v : mx;
       if (mx != mx) break;
     }
@@ -106,7 +100,7 @@ struct PredView {
     if (DEC && p.inference) {
       float smx, ssum;
       softmax_terms(cell, smx, ssum);
-      for (int c = 5; c < P; ++c) dst[c] = expf(at(c, cell) - smx) / ssum;
+      for (int c = 5; c < P; ++c) dst[c] = hm_softmax(at(c, cell), smx, ssum);
     } else {
       for (int c = 5; c < P; ++c) dst[c] = at(c, cell);
     }
@@ -195,7 +189,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_batched_kernel(const NmsParam
 #pragma unroll
     for (int k = 0; k < NMS_SLOTS; ++k) {
       const int cell = k * NMS_THREADS + tid;
-      const float o = DEC ? nms_sigmoid(ob[k]) : ob[k];
+      const float o = DEC ? hm_sigmoid(ob[k]) : ob[k];
       const bool f = (cell < cells) && (o > p.obj_thresh);
       const unsigned long long bal = __ballot(f);
       if (f) fire |= 1u << k;
