@@ -451,6 +451,17 @@ int yogo_image_cache_gather(const unsigned char* cache, int S, const int* slots,
 int yogo_zarr_unpack(const unsigned char* staged, long long staged_bytes, const long long* tile_off, const int* tile_k, int B, int gh,
                      int gw, int ch, int cw, int cn, int order_f, int fill, int H, int W, int top, int left, int OH, int OW, void* out,
                      int out_fp32, yogo_stream_t stream);
+/* The blocks of Blosc-compressed chunks (zarr's default compressor), decoded on the device in front of yogo_zarr_unpack
+ * (yogo_amd/blosc.py parses the chunk headers on the host).  src: src_bytes of device memory holding stored chunks as they came off
+ * the disk; table: [n][5] int64 device, one row { src_off, src_len, dst_off, dst_len, raw } per block: the block's bytes in src, where
+ * its decoded bytes belong in dst (dst_bytes of device memory, 16-byte aligned, not overlapping src: the `staged` of
+ * yogo_zarr_unpack), and whether they are copied (raw != 0, src_len == dst_len) or one LZ4 block.  One wavefront per row.
+ * status: [n] int32 device, per row 0 or the check that ended it: 1 a literal run passes the end of the source, 2 the source ends
+ * inside a sequence, 3 a match offset of 0 or beyond what the block has produced, 4 a copy would pass dst_len, 5 the block ends
+ * before dst_len, 6 the row does not lie inside src / dst.  No byte outside a row's two ranges is read or written, whatever
+ * the stored bytes say (the same checks, in the same order: yogo_amd.blosc.lz4_block_status). */
+int yogo_blosc_lz4_decode(const unsigned char* src, long long src_bytes, const long long* table, int n, unsigned char* dst,
+                          long long dst_bytes, int* status, yogo_stream_t stream);
 
 /* ---- optimiser: torch.optim.AdamW over one flat buffer, yogo/train.py:213-217,324 ---------------------------------------- */
 int yogo_adamw_step(float* p, const float* g, float* m, float* v, long long n, int step, double lr, double beta1,

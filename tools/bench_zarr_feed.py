@@ -1,23 +1,33 @@
-"""Zarr input for inference on one MI355X: the feed alone, the unpack kernel alone, and `predict` against a PNG directory.
+"""Zarr input for inference on one MI355X: the feed alone per compressor and decode route, the decode and unpack kernels alone,
+and `predict` from each store (optionally against a PNG directory).
 
-Input: 2048 seeded 772 x 1032 uint8 frames (a smooth background plus Gaussian noise of sigma 6, as tools/bench_loader.py), written
-once to a scratch file and from there into each store (tests/_zarr_write.py's layout rules) and into a PNG directory; everything
-lies in a temporary directory that is removed at the end.  Every measurement is a step in a child process of its own with its own
-time limit; a step that fails or runs out of time is recorded as such, and no further step is started.
+Input: seeded 772 x 1032 uint8 frames, written once to a scratch file and from there into each store (tests/_zarr_write.py's
+layout rules) and, with --png, into a PNG directory; everything lies in a temporary directory that is removed at the end.
+--content: `incompressible` = a smooth background plus Gaussian noise of sigma 6 (as tools/bench_loader.py; LZ4 does not shrink
+it: Blosc stores its blocks raw), `compressible` = the same with the lower third of every frame a flat field (LZ4 shrinks it to
+about two thirds).  --compressors: null, zlib (level 1), blosc (LZ4 blocks at --blocksize, framed here with the system's liblz4);
+--decode: for blosc, `device` (yogo_blosc_lz4_decode) and / or `host` (ZarrDeviceFeed(device_decode=False)).  Every measurement
+is a step in a child process of its own with its own time limit; a step that fails or runs out of time is recorded as such, and
+no further step is started.  The lines are APPENDED to --out.
 
-  (a) feed     ZarrDeviceFeed alone, batch 256, images/s on the host clock up to the final device synchronise (one warm-up
-               pass, then the timed passes): (H, W, 1) raw zip, (H, W, 1) zlib zip, (H, W, 16) raw zip (deinterleave)
-  (b) kernel   yogo_zarr_unpack alone from device events, B = 256, against the bytes it has to move (frame bytes read + output
-               bytes written) as a share of 8 TB/s
-  (c) predict  predict(count_predictions=True, half=True, batch_size=256) from the raw zip and from the same frames as a PNG
-               directory (16 workers), alternated in one process, host clock around the whole call
+  feed     ZarrDeviceFeed alone, batch 256, images/s on the host clock up to the final device synchronise (one warm-up pass,
+           then the timed passes), (H, W, 1) chunks in a zip store of stored members
+  decode   (blosc, device) yogo_blosc_lz4_decode alone on the first batch's blocks, device events around each of 20 launches,
+           and the share of blocks stored raw
+  predict  predict(count_predictions=True, half=True, device_outputs=True, batch_size=256), host clock around the whole call
+  --unpack-kernel  yogo_zarr_unpack alone from device events, B = 256, against the bytes it has to move as a share of 8 TB/s
+  --png            predict from the null store against the same frames as a PNG directory (16 workers), alternated
 
-  python tools/bench_zarr_feed.py [--frames 2048] [--out profiles/zarr_feed.log]
+  python tools/bench_zarr_feed.py [--frames 1024] [--content incompressible,compressible] [--compressors null,zlib,blosc]
+                                  [--decode device,host] [--out profiles/zarr_feed.log]
 """
 import argparse
+import ctypes
+import ctypes.util
 import json
 import os
 import shutil
+import struct
 import subprocess
 import sys
 import tempfile
@@ -36,12 +46,44 @@ HBM_PEAK = 8.0e12
 CLASSES = ["you", "only", "glance", "once"]
 
 
-def _frame(k: int) -> np.ndarray:
+def _frame(k: int, content: str = "incompressible") -> np.ndarray:
     rng = np.random.default_rng(k)
     y, x = np.mgrid[0:H, 0:W].astype(np.float32)
     a, b, c = rng.uniform(0.5, 2.0, 3)
     smooth = 150 + 40 * np.sin(x / W * np.pi * a + c) * np.cos(y / H * np.pi * b)
-    return np.clip(smooth + rng.normal(0, 6, size=(H, W)), 0, 255).astype(np.uint8)
+    f = np.clip(smooth + rng.normal(0, 6, size=(H, W)), 0, 255).astype(np.uint8)
+    if content == "compressible":
+        f[2 * H // 3:] = int(f.mean())
+    return f
+
+
+def _lz4():
+    name = ctypes.util.find_library("lz4")
+    if not name:
+        raise RuntimeError("the blosc stores of this tool are written with the system's liblz4, which is not installed")
+    return ctypes.CDLL(name)
+
+
+def blosc_lz4_frame(raw: bytes, blocksize: int) -> bytes:
+    """one Blosc 1 chunk of uint8 data (yogo_amd/blosc.py describes the layout): LZ4 blocks, a block stored raw when LZ4 does not
+    shrink it, the whole chunk memcpyed when the framing would make it longer than the data plus the header (as c-blosc does)"""
+    L = _lz4()
+    n = len(raw)
+    nblocks = -(-n // blocksize)
+    cap = L.LZ4_compressBound(blocksize)
+    buf = ctypes.create_string_buffer(cap)
+    body, bstarts, pos = bytearray(), [], 16 + 4 * nblocks
+    for b in range(nblocks):
+        block = raw[b * blocksize:(b + 1) * blocksize]
+        got = L.LZ4_compress_default(block, buf, len(block), cap)
+        enc = buf.raw[:got] if 0 < got < len(block) else block
+        bstarts.append(pos)
+        body += struct.pack("<i", len(enc)) + enc
+        pos += 4 + len(enc)
+    flags = 0x01 | (1 << 5)
+    if pos > n + 16:
+        return struct.pack("<BBBBIII", 2, 1, flags | 0x02, 1, n, blocksize, n + 16) + raw
+    return struct.pack("<BBBBIII", 2, 1, flags, 1, n, blocksize, pos) + struct.pack(f"<{nblocks}i", *bstarts) + bytes(body)
 
 
 def _frames(d: str, n: int) -> np.ndarray:
@@ -49,10 +91,10 @@ def _frames(d: str, n: int) -> np.ndarray:
 
 
 def _gen(args):
-    d, n, lo, hi = args
+    d, n, lo, hi, content = args
     m = np.memmap(os.path.join(d, "frames.u8"), dtype=np.uint8, mode="r+", shape=(n, H, W))
     for k in range(lo, hi):
-        m[k] = _frame(k)
+        m[k] = _frame(k, content)
     m.flush()
 
 
@@ -66,14 +108,16 @@ def _png(args):
 
 
 def _chunk(args):
-    d, n, t, cn, compress = args
+    d, n, t, cn, compress, blocksize = args
     m = _frames(d, n)
     block = np.zeros((H, W, cn), dtype=np.uint8)
     for j in range(cn):
         if t * cn + j < n:
             block[:, :, j] = m[t * cn + j]
     raw = block.tobytes()
-    return t, (zlib.compress(raw, 1) if compress else raw)
+    if compress == "blosc":
+        return t, blosc_lz4_frame(raw, blocksize)
+    return t, (zlib.compress(raw, 1) if compress == "zlib" else raw)
 
 
 def _spans(n, parts):
@@ -81,21 +125,25 @@ def _spans(n, parts):
     return [(lo, min(lo + step, n)) for lo in range(0, n, step)]
 
 
-def write_store(d: str, n: int, name: str, cn: int, compress: bool) -> str:
-    """an [H, W, n] array in (H, W, cn) chunks as a zip store of stored members"""
+COMPRESSOR_DOCS = {"null": None, "zlib": {"id": "zlib", "level": 1},
+                   "blosc": {"id": "blosc", "cname": "lz4", "clevel": 5, "shuffle": 1, "blocksize": 0}}
+
+
+def write_store(d: str, n: int, name: str, cn: int, compress: str, blocksize: int = 131072) -> str:
+    """an [H, W, n] array in (H, W, cn) chunks as a zip store of stored members; compress: null, zlib or blosc"""
     p = os.path.join(d, name)
     meta = {"zarr_format": 2, "shape": [H, W, n], "chunks": [H, W, cn], "dtype": "|u1", "order": "C", "fill_value": 0, "filters": None,
-            "compressor": {"id": "zlib", "level": 1} if compress else None, "dimension_separator": "."}
+            "compressor": COMPRESSOR_DOCS[compress], "dimension_separator": "."}
     with zipfile.ZipFile(p, "w", zipfile.ZIP_STORED) as zf, ProcessPoolExecutor(WORKERS) as ex:
         zf.writestr(".zarray", json.dumps(meta))
-        for t, data in ex.map(_chunk, [(d, n, t, cn, compress) for t in range(-(-n // cn))], chunksize=2):
+        for t, data in ex.map(_chunk, [(d, n, t, cn, compress, blocksize) for t in range(-(-n // cn))], chunksize=2):
             zf.writestr(f"0.0.{t}", data)
     return p
 
 
 # ---- the steps (child processes) ------------------------------------------------------------------------------------------
 
-def step_feed(store: str, n: int, passes: int = 2) -> dict:
+def step_feed(store: str, n: int, device_decode: bool = True, passes: int = 2) -> dict:
     import torch
 
     from yogo_amd.image_path_dataset import ZarrDataset
@@ -105,7 +153,7 @@ def step_feed(store: str, n: int, passes: int = 2) -> dict:
     rates, setup = [], []
     for p in range(passes + 1):
         t0 = time.perf_counter()
-        feed = ZarrDeviceFeed(ds, B, "cuda", num_frames=n)   # allocates the pinned and the device buffers
+        feed = ZarrDeviceFeed(ds, B, "cuda", num_frames=n, device_decode=device_decode)   # allocates the pinned and the device buffers
         torch.cuda.synchronize()
         setup.append(time.perf_counter() - t0)
         t0 = time.perf_counter()
@@ -119,7 +167,41 @@ def step_feed(store: str, n: int, passes: int = 2) -> dict:
         assert seen == n, (seen, n)
         if p:
             rates.append(n / dt)
-    return {"images_per_s": rates, "setup_s": setup[1:], "bytes_on_disk": os.path.getsize(store), "last_pixel": acc}
+    return {"images_per_s": rates, "setup_s": setup[1:], "bytes_on_disk": os.path.getsize(store), "last_pixel": acc,
+            "device_decode": bool(feed.device_decode)}
+
+
+def step_decode(store: str, n: int) -> dict:
+    """yogo_blosc_lz4_decode alone on the blocks of the first batch"""
+    import torch
+
+    from yogo_amd.zarr_feed import ChunkStager, FrameSource, decode_blocks, plan_batch
+    from yogo_amd.zarr_store import open_zarr
+
+    src = FrameSource(open_zarr(store))
+    plan = plan_batch(src, 0, min(B, n))
+    stager = ChunkStager(src)
+    buf = np.zeros(len(plan.keys) * src.stored_stride, np.uint8)
+    try:
+        table = stager.stage_stored(plan, buf)
+    finally:
+        stager.close()
+    stored = torch.from_numpy(buf).cuda()
+    table_dev = torch.from_numpy(table).cuda()
+    out = torch.empty(plan.nbytes, dtype=torch.uint8, device="cuda")
+    status = torch.empty(len(table), dtype=torch.int32, device="cuda")
+    for _ in range(3):
+        decode_blocks(stored, table_dev, out, status)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(21)]
+    ev[0].record()
+    for i in range(20):
+        decode_blocks(stored, table_dev, out, status)
+        ev[i + 1].record()
+    torch.cuda.synchronize()
+    us = sorted(ev[i].elapsed_time(ev[i + 1]) * 1e3 for i in range(20))
+    return {"median_us": us[10], "min_us": us[0], "blocks": int(len(table)), "raw_blocks": int(table[:, 4].sum()),
+            "stored_bytes": int(table[:, 1].sum()), "decoded_bytes": int(table[:, 3].sum()), "all_ok": not bool(status.any()),
+            "frames": int(plan.hi - plan.lo)}
 
 
 def step_kernel() -> list:
@@ -162,6 +244,36 @@ def step_kernel() -> list:
             out.append({"kernel": name, "cn": cn, "median_us": us[10], "min_us": us[0], "bytes_moved": moved,
                         "share_of_8TBps": moved / (us[10] * 1e-6) / HBM_PEAK, "matches_host": ok})
     return out
+
+
+def step_predict_store(d: str, store: str, n: int) -> dict:
+    """predict --count --device-outputs from one store, twice"""
+    import contextlib
+    import io
+
+    import torch
+
+    from yogo_amd.infer import predict
+    from yogo_amd.model import YOGO
+
+    torch.manual_seed(3)
+    net = YOGO((H, W), 0.0425, 0.0555, 4).cuda().eval()
+    pth = os.path.join(d, "m.pth")
+    torch.save({"epoch": 0, "step": 7, "normalize_images": False, "classes": CLASSES, "model_name": "bench",
+                "model_state_dict": {k: v.cpu() for k, v in net.state_dict().items()}, "model_version": "base_model"}, pth)
+    del net
+    res = {"s": [], "counts": []}
+    for rep in range(2):
+        buf = io.StringIO()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with contextlib.redirect_stdout(buf):
+            predict(pth, path_to_zarr=store, count_predictions=True, half=True, batch_size=B, class_names=CLASSES, device_outputs=True)
+        torch.cuda.synchronize()
+        res["s"].append(time.perf_counter() - t0)
+        res["counts"].append(buf.getvalue().strip().splitlines()[-1])
+    res["counts"] = res["counts"][0] if len(set(res["counts"])) == 1 else res["counts"]
+    return res
 
 
 def step_predict(d: str, store: str, n: int) -> dict:
@@ -219,77 +331,104 @@ def run_step(log, name: str, limit: int, args: list):
 
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=2048)
+    ap.add_argument("--frames", type=int, default=1024)
+    ap.add_argument("--content", default="incompressible,compressible")
+    ap.add_argument("--compressors", default="null,zlib,blosc")
+    ap.add_argument("--decode", default="device,host", help="for blosc stores: device and / or host")
+    ap.add_argument("--blocksize", type=int, default=131072, help="Blosc block size (c-blosc's choice for 1-byte items at clevel 5)")
+    ap.add_argument("--no-predict", action="store_true")
+    ap.add_argument("--unpack-kernel", action="store_true")
+    ap.add_argument("--png", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "zarr_feed.log"))
     ap.add_argument("--step", default=None)
     ap.add_argument("rest", nargs="*")
     a = ap.parse_args()
     if a.step:
         if a.step == "feed":
-            res = step_feed(a.rest[0], int(a.rest[1]))
+            res = step_feed(a.rest[0], int(a.rest[1]), a.rest[2] == "device")
+        elif a.step == "decode":
+            res = step_decode(a.rest[0], int(a.rest[1]))
         elif a.step == "kernel":
             res = step_kernel()
+        elif a.step == "predict_store":
+            res = step_predict_store(a.rest[0], a.rest[1], int(a.rest[2]))
         else:
             res = step_predict(a.rest[0], a.rest[1], int(a.rest[2]))
         print("RESULT " + json.dumps(res), flush=True)
         return 0
 
     n = a.frames
-    lines = []
 
     def log(s=""):
         print(s, flush=True)
-        lines.append(s)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        with open(a.out, "a") as f:
+            f.write(s + "\n")
 
     d = tempfile.mkdtemp(prefix="zarr_bench_")
     try:
-        log(f"tools/bench_zarr_feed.py --frames {n} on one MI355X; {n} seeded {H}x{W} uint8 frames (smooth background + Gaussian noise "
-            f"sigma 6), batch {B}")
-        np.memmap(os.path.join(d, "frames.u8"), dtype=np.uint8, mode="w+", shape=(n, H, W)).flush()
-        with ProcessPoolExecutor(WORKERS) as ex:
-            list(ex.map(_gen, [(d, n, lo, hi) for lo, hi in _spans(n, WORKERS * 4)]))
         log()
-        log("(a) ZarrDeviceFeed alone: read -> pinned staging -> upload -> unpack, images/s on the host clock, timed passes after a warm-up pass;")
-        log("    the stores were written just before: reads come from the page cache, not from a disk")
+        log(f"tools/bench_zarr_feed.py --frames {n} --content {a.content} --compressors {a.compressors} --decode {a.decode} "
+            f"--blocksize {a.blocksize} on one MI355X ({time.strftime('%Y-%m-%d')}); seeded {H}x{W} uint8 frames, batch {B}, (H, W, 1) chunks, "
+            "zip stores written just before (reads come from the page cache, not from a disk)")
+        log("feed = ZarrDeviceFeed alone, images/s on the host clock, timed passes after a warm-up pass; predict = predict(count_predictions, "
+            "half, device_outputs), host clock around the whole call (model load included); decode = yogo_blosc_lz4_decode alone on the first "
+            "batch, device events, median / min of 20")
         ok = True
-        raw_store = None
-        for label, name, cn, compress in (("(H, W, 1) raw zip ", "raw1.zip", 1, False), ("(H, W, 1) zlib zip", "zlib1.zip", 1, True),
-                                          ("(H, W, 16) raw zip", "raw16.zip", 16, False)):
-            store = write_store(d, n, name, cn, compress)
-            r = run_step(log, "feed", 240, [store, n])
-            if r is None:
-                ok = False
+        for content in a.content.split(","):
+            np.memmap(os.path.join(d, "frames.u8"), dtype=np.uint8, mode="w+", shape=(n, H, W)).flush()
+            with ProcessPoolExecutor(WORKERS) as ex:
+                list(ex.map(_gen, [(d, n, lo, hi, content) for lo, hi in _spans(n, WORKERS * 4)]))
+            log(f"content {content}:")
+            for comp in a.compressors.split(","):
+                store = write_store(d, n, f"{content}_{comp}.zip", 1, comp, a.blocksize)
+                share = os.path.getsize(store) / n / (H * W) * 100
+                for route in (a.decode.split(",") if comp == "blosc" else ["host"]):
+                    label = f"  {comp:<5s} {('decode on the ' + route) if comp == 'blosc' else '':<20s}"
+                    r = run_step(log, "feed", 300, [store, n, route])
+                    if r is None:
+                        ok = False
+                        break
+                    log(f"{label} feed     " + "  ".join(f"{v:9.0f} img/s" for v in r["images_per_s"]) +
+                        f"   ({share:.1f} % of raw on disk; device_decode={r['device_decode']})")
+                    if comp == "blosc" and route == "device":
+                        k = run_step(log, "decode", 180, [store, n])
+                        if k is None:
+                            ok = False
+                            break
+                        log(f"{label} decode   {k['median_us']:9.1f} us / {k['min_us']:9.1f} us per batch of {k['frames']} frames: {k['blocks']} blocks, "
+                            f"{k['raw_blocks']} of them raw ({100 * k['raw_blocks'] / max(k['blocks'], 1):.1f} %), {k['stored_bytes'] / 1e6:.1f} MB stored -> "
+                            f"{k['decoded_bytes'] / 1e6:.1f} MB decoded = {k['decoded_bytes'] / (k['median_us'] * 1e-6) / 1e9:.0f} GB/s out; every status 0: {k['all_ok']}")
+                    if not a.no_predict and (comp != "blosc" or route == "device"):
+                        r = run_step(log, "predict_store", 420, [d, store, n])
+                        if r is None:
+                            ok = False
+                            break
+                        log(f"{label} predict  " + "  ".join(f"{t:7.2f} s = {n / t:8.0f} img/s" for t in r["s"]) + f"   {r['counts']}")
+                if comp != "null" or not a.png or not ok:
+                    os.remove(store)
+                if not ok:
+                    break
+            if not ok:
                 break
-            log(f"  {label}  " + "  ".join(f"{v:9.0f} img/s" for v in r["images_per_s"]) + f"   ({r['bytes_on_disk'] / n / (H * W) * 100:.1f} % "
-                f"of raw on disk; buffers allocated in {max(r['setup_s']):.2f} s before each pass, not counted)")
-            if name == "raw1.zip":
-                raw_store = store
-            else:
-                os.remove(store)
-        if ok:
-            log()
-            log(f"(b) yogo_zarr_unpack alone, B = {B}, device events around each of 20 launches (median / min), bytes = frames read + output written")
-            r = run_step(log, "kernel", 180, [])
-            ok = r is not None
-            for k in r or []:
+            if a.png:
+                raw_store = os.path.join(d, f"{content}_null.zip")
+                if os.path.exists(raw_store):
+                    os.makedirs(os.path.join(d, "png"), exist_ok=True)
+                    with ProcessPoolExecutor(WORKERS) as ex:
+                        list(ex.map(_png, [(d, n, lo, hi) for lo, hi in _spans(n, WORKERS * 4)]))
+                    r = run_step(log, "predict", 420, [d, raw_store, n])
+                    if r is not None:
+                        for kind, label in (("zarr", "(H, W, 1) raw zip"), ("png", "PNG directory    ")):
+                            log(f"  predict(count_predictions, half), alternated: {label}  " + "  ".join(f"{t:7.2f} s = {n / t:8.0f} img/s" for t in r[kind + "_s"]))
+                        log(f"  the four runs print the same counts: {r['same_counts']}   {r['counts']}")
+                    os.remove(raw_store)
+        if ok and a.unpack_kernel:
+            log(f"yogo_zarr_unpack alone, B = {B}, device events around each of 20 launches (median / min), bytes = frames read + output written")
+            for k in run_step(log, "kernel", 180, []) or []:
                 log(f"  {k['kernel']:<42s} cn={k['cn']:<3d} {k['median_us']:8.1f} us / {k['min_us']:8.1f} us   {k['bytes_moved'] / 1e6:7.1f} MB   "
                     f"{k['bytes_moved'] / (k['median_us'] * 1e-6) / 1e12:5.2f} TB/s = {k['share_of_8TBps'] * 100:4.1f} % of 8 TB/s"
                     f"   equals the host's slicing: {k['matches_host']}")
-        if ok:
-            os.makedirs(os.path.join(d, "png"))
-            with ProcessPoolExecutor(WORKERS) as ex:
-                list(ex.map(_png, [(d, n, lo, hi) for lo, hi in _spans(n, WORKERS * 4)]))
-            log()
-            log(f"(c) predict(count_predictions=True, half=True, batch_size={B}) over the {n} frames, host clock around the whole call (model load "
-                "included), zarr and PNG alternated twice in one process; PNG directory read by 16 DataLoader workers")
-            r = run_step(log, "predict", 420, [d, raw_store, n])
-            if r is not None:
-                for kind, label in (("zarr", "(H, W, 1) raw zip"), ("png", "PNG directory    ")):
-                    log(f"  {label}  " + "  ".join(f"{s:7.2f} s = {n / s:8.0f} img/s" for s in r[kind + "_s"]))
-                log(f"  the four runs print the same counts: {r['same_counts']}   {r['counts']}")
-        return 0
+        return 0 if ok else 1
     finally:
         shutil.rmtree(d, ignore_errors=True)
 

@@ -7,6 +7,13 @@ copy), uploads the buffer on a side stream and launches ``yogo_zarr_unpack`` (yo
 behind an event: de-interleave / crop / optional ``/ 255`` happen there.  Two staging and two device buffers: the reading and the
 upload of batch n+1 overlap whatever the caller does with batch n.  A chunk that two consecutive batches share (more than one
 frame per chunk, batch size no multiple of it) is read and decoded once and copied from the previous staging buffer.
+
+Blosc-compressed stacks with LZ4 blocks (zarr's default compressor) are decoded on the device (``device_decode=True``, the
+default): the stager reads the STORED bytes into a second pair of pinned buffers and parses each chunk's header into one table
+entry per block (yogo_amd/blosc.py), the loader uploads bytes and table, launches ``yogo_blosc_lz4_decode``
+(yogo_amd/csrc/blosc_lz4.hip) on the side stream into the slot's device buffer -- the layout ``yogo_zarr_unpack`` reads -- and
+waits for the per-block status.  A chunk the device cannot decode (zlib inside, bit-shuffle) is decoded on the host and enters
+the table as one raw entry.
 """
 from __future__ import annotations
 
@@ -20,11 +27,12 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from yogo_amd import _hip
-from yogo_amd.zarr_store import ZarrArray, ZarrGroup
+from yogo_amd import _hip, blosc
+from yogo_amd.zarr_store import ChunkTooLong, ZarrArray, ZarrGroup
 
 ALIGN = 256          # every staged chunk starts on a multiple of this (the kernel asks for 16)
 MAX_THREADS = 16
+RAW_PIECE = 1 << 16  # bytes of a raw block one wavefront of the device decoder copies (longer raw entries are cut up)
 
 
 def center_crop_origin(H: int, W: int, OH: int, OW: int) -> Tuple[int, int]:
@@ -60,6 +68,10 @@ class FrameSource:
         self.fill = first.fill_value
         self.chunk_nbytes = first.chunk_nbytes
         self.chunk_stride = -(-self.chunk_nbytes // ALIGN) * ALIGN
+        # room for one chunk's STORED bytes when they go to the device decoder: header, block starts and sizes of blocks of 64
+        # bytes or more.  c-blosc writes no chunk above chunk_nbytes + 16 (it falls back to memcpyed); a longer one from
+        # another writer (all blocks raw at a tiny blocksize) is decoded on the host instead.
+        self.stored_stride = -(-(self.chunk_nbytes + blosc.HEADER + 8 * -(-self.chunk_nbytes // 64)) // ALIGN) * ALIGN
 
     def locate(self, idx: int) -> Tuple[ZarrArray, Optional[int], int]:
         """-> (array, its chunk coordinate on the frame axis or None for a 2-D member, position inside the chunk)"""
@@ -90,6 +102,9 @@ class BatchPlan:
     tile_off: np.ndarray                  # int64 [B, gh, gw], -1 where the key is absent from the store
     tile_k: np.ndarray                    # int32 [B]
     nbytes: int                           # bytes of the staging buffer in use
+    stored: Optional[Dict[str, Tuple[int, List[Tuple[int, int, int, int, int]]]]] = None   # device decode: key -> (stored bytes,
+    #                                       its block entries relative to the chunk's stored / decoded start)
+    row_chunk: Optional[List[int]] = None  # device decode: per row of the decoder's table, the index of its chunk in `keys`
 
 
 def plan_batch(src: FrameSource, lo: int, hi: int) -> BatchPlan:
@@ -140,12 +155,17 @@ class ChunkStager:
                 s.close()
             self._stores.clear()
 
-    def _read(self, arr: ZarrArray, coords: Tuple[int, ...], out: np.ndarray) -> None:
+    def _store(self, arr: ZarrArray):
+        """this thread's handle of the store"""
         store = getattr(self._local, "store", None)
         if store is None:
             store = self._local.store = arr.store.clone()
             with self._lock:
                 self._stores.append(store)
+        return store
+
+    def _read(self, arr: ZarrArray, coords: Tuple[int, ...], out: np.ndarray) -> None:
+        store = self._store(arr)
         try:
             arr.with_store(store).read_chunk_into(coords, out)
         except KeyError:
@@ -171,6 +191,88 @@ class ChunkStager:
                 err = e
         if err is not None:
             raise err
+
+    def _read_stored(self, arr: ZarrArray, coords: Tuple[int, ...], out: np.ndarray):
+        """the stored bytes of one chunk into ``out`` (stored_stride bytes) -> (bytes in use, block entries relative to the chunk).
+        What the device cannot decode is decoded here and becomes one raw entry."""
+        n = self.src.chunk_nbytes
+        key = arr.chunk_key(coords)
+        store = self._store(arr)
+        a = arr.with_store(store)
+        try:
+            if a.device_decodable:
+                try:
+                    got = a.read_stored_into(coords, out)
+                    flags, entries = blosc.parse_chunk(out[:got], n)
+                    if blosc.device_decodable(flags):
+                        return got, entries
+                except (ChunkTooLong, NotImplementedError):
+                    pass
+                except ValueError as e:
+                    raise RuntimeError(f"zarr store {arr.where}: chunk {key!r} could not be decoded ({type(e).__name__}: {e})") from e
+            a.read_chunk_into(coords, out[:n])
+            return n, [(0, n, 0, n, 1)]
+        except KeyError:
+            raise RuntimeError(f"zarr store {arr.where}: chunk {key!r} disappeared from the store") from None
+
+    def stage_stored(self, plan: BatchPlan, buf: np.ndarray, prev: Optional[Tuple[BatchPlan, np.ndarray]] = None) -> np.ndarray:
+        """(device decode) the STORED bytes of every chunk of ``plan`` at ``i * stored_stride`` in ``buf``; fills ``plan.stored``
+        and returns the decoder's table, int64 [blocks, 5]: (src_off, src_len, dst_off, dst_len, raw) with dst_off in the layout of
+        ``plan.offsets``.  Chunks that ``prev`` holds are copied from there; errors as in ``stage``."""
+        stride = self.src.stored_stride
+        plan.stored = {}
+        futures: List[Tuple[str, Future]] = []
+        for i, (key, (arr, coords)) in enumerate(zip(plan.keys, plan.chunks)):
+            soff = i * stride
+            if prev is not None and prev[0].stored and key in prev[0].stored:
+                used, entries = prev[0].stored[key]
+                poff = prev[0].keys.index(key) * stride
+                buf[soff:soff + used] = prev[1][poff:poff + used]
+                plan.stored[key] = (used, entries)
+                continue
+            self.reads[key] += 1
+            futures.append((key, self._pool.submit(self._read_stored, arr, coords, buf[soff:soff + stride])))
+        err: Optional[BaseException] = None
+        for key, f in futures:
+            e = f.exception()
+            if e is None:
+                plan.stored[key] = f.result()
+            elif err is None:
+                err = e
+        if err is not None:
+            raise err
+        rows, owner = [], []
+        for i, key in enumerate(plan.keys):
+            for so, sl, do, dl, raw in plan.stored[key][1]:
+                # a long raw entry (a memcpyed chunk, a chunk decoded on the host) goes to several wavefronts
+                for at in (range(0, sl, RAW_PIECE) if raw else (0,)):
+                    ln = min(RAW_PIECE, sl - at) if raw else sl
+                    rows.append((i * stride + so + at, ln, plan.offsets[key] + do + at, ln if raw else dl, raw))
+                    owner.append(i)
+        plan.row_chunk = owner
+        return np.asarray(rows, dtype=np.int64).reshape(-1, 5)
+
+
+def decode_blocks(stored: torch.Tensor, table: torch.Tensor, out: torch.Tensor, status: torch.Tensor) -> None:
+    """One ``yogo_blosc_lz4_decode`` launch on the current stream.  stored / out: 1-D uint8 device tensors (stored chunk bytes, decoded
+    staging buffer); table: int64 [n, 5] device, rows (src_off, src_len, dst_off, dst_len, raw); status: int32 [n] device.  The
+    kernel holds every row to the two buffers itself."""
+    for t, what in ((stored, "the stored chunk bytes"), (table, "the block table"), (out, "the decoded chunks"), (status, "the status")):
+        _hip.require_cuda(t, what)
+    if stored.dtype != torch.uint8 or out.dtype != torch.uint8 or stored.ndim != 1 or out.ndim != 1 or not stored.is_contiguous() \
+            or not out.is_contiguous() or stored.numel() == 0 or out.numel() == 0:
+        raise ValueError("decode_blocks: stored and out must be non-empty contiguous 1-D uint8 tensors")
+    n = int(table.shape[0])
+    if table.dtype != torch.int64 or table.ndim != 2 or table.shape[1] != 5 or not table.is_contiguous():
+        raise ValueError(f"decode_blocks: the table must be a contiguous int64 [n, 5] tensor, got {tuple(table.shape)} {table.dtype}")
+    if status.dtype != torch.int32 or tuple(status.shape) != (n,) or not status.is_contiguous():
+        raise ValueError(f"decode_blocks: the status must be a contiguous int32 [{n}] tensor, got {tuple(status.shape)} {status.dtype}")
+    if len({stored.device, table.device, out.device, status.device}) != 1:
+        raise ValueError("decode_blocks: the tensors live on different devices")
+    if n == 0:
+        return
+    with torch.cuda.device(out.device):
+        _hip.call("yogo_blosc_lz4_decode", stored, stored.numel(), table, n, out, out.numel(), status, _hip.stream_ptr())
 
 
 def unpack(staged: torch.Tensor, tile_off: np.ndarray, tile_k: np.ndarray, *, chunks: Sequence[int], order_f: bool, fill: int,
@@ -218,10 +320,11 @@ class ZarrDeviceFeed:
     generator: when a batch raises RuntimeError (an unreadable chunk), the next ``next()`` goes on with the following batch.
     ``crop``: (OH, OW) of a centre crop done in the kernel; ``normalize``: fp32 ``/ 255`` in the kernel, else uint8.
     ``num_frames``: how many frames to walk (default: ``len(dataset)``, as the reference's DataLoader does, and never more
-    than the stack holds)."""
+    than the stack holds).  ``device_decode``: a Blosc stack with LZ4 blocks is decoded on the device (module docstring); False
+    takes the host route (A/B runs); every other source takes the host route whatever it says."""
 
     def __init__(self, dataset, batch_size: int, device, crop: Optional[Tuple[int, int]] = None, normalize: bool = False,
-                 num_frames: Optional[int] = None):
+                 num_frames: Optional[int] = None, device_decode: bool = True):
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError(f"yogo_amd: the zarr feed unpacks on an MI355X device (got {dev}); there is no CPU fallback")
@@ -240,6 +343,13 @@ class ZarrDeviceFeed:
         self._pinned = [torch.empty(cap, dtype=torch.uint8).pin_memory() for _ in range(2)]
         self._host = [p.numpy() for p in self._pinned]
         self._dev = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.device_decode = bool(device_decode) and src.first.device_decodable
+        if self.device_decode:
+            scap = src.max_chunks(self.batch_size) * src.stored_stride
+            self._spinned = [torch.empty(scap, dtype=torch.uint8).pin_memory() for _ in range(2)]
+            self._shost = [p.numpy() for p in self._spinned]
+            self._sdev = [torch.empty(scap, dtype=torch.uint8, device=dev) for _ in range(2)]
+            self._slast: Optional[Tuple[int, BatchPlan, np.ndarray]] = None
         self._side = torch.cuda.Stream(dev)
         self._uploaded: List[Optional[torch.cuda.Event]] = [None, None]   # slot's pinned buffer may be overwritten after this
         self._consumed: List[Optional[torch.cuda.Event]] = [None, None]   # slot's device buffer may be overwritten after this
@@ -262,8 +372,59 @@ class ZarrDeviceFeed:
         self._pending.clear()
         self.stager.close()
 
+    def _upload_stored(self, plan: BatchPlan, slot: int) -> None:
+        """(side stream) the stored bytes in use; neighbours whose gap is under a quarter of a chunk's room travel in one copy"""
+        stride = self.src.stored_stride
+        runs: List[List[int]] = []
+        for i, key in enumerate(plan.keys):
+            a, b = i * stride, i * stride + plan.stored[key][0]
+            if runs and a - runs[-1][1] <= stride // 4:
+                runs[-1][1] = b
+            else:
+                runs.append([a, b])
+        for a, b in runs:
+            self._sdev[slot][a:b].copy_(self._spinned[slot][a:b], non_blocking=True)
+
+    def _load_decoded(self, n: int):
+        """(loader thread) batch n through the device decoder: stored bytes and block table up, one decode launch on the side
+        stream into the slot's device buffer, then the per-block status back -- RuntimeError naming the first bad chunk"""
+        slot = n % 2
+        lo, hi = self.batches[n]
+        plan = plan_batch(self.src, lo, hi)
+        if self._uploaded[slot] is not None:
+            self._uploaded[slot].synchronize()
+        prev = (self._slast[1], self._slast[2]) if self._slast is not None and self._slast[0] == n - 1 else None
+        self._slast = None
+        table = self.stager.stage_stored(plan, self._shost[slot], prev)
+        self._slast = (n, plan, self._shost[slot])
+        with torch.cuda.device(self.device), torch.cuda.stream(self._side):
+            if self._consumed[slot] is not None:
+                self._side.wait_event(self._consumed[slot])
+            toff = torch.from_numpy(plan.tile_off).to(self.device)
+            tk = torch.from_numpy(plan.tile_k).to(self.device)
+            status = None
+            if len(table):
+                self._upload_stored(plan, slot)
+                table_dev = torch.from_numpy(table).to(self.device)
+                status = torch.empty(len(table), dtype=torch.int32, device=self.device)
+                decode_blocks(self._sdev[slot], table_dev, self._dev[slot], status)
+            ev = torch.cuda.Event()
+            ev.record(self._side)
+            bad = status.cpu() if status is not None else None   # waits for the decode: this thread overlaps the consumer already
+        self._uploaded[slot] = ev
+        if bad is not None and bool(bad.any()):
+            self._slast = None   # what a bad chunk left in the device buffer is not handed on
+            first = int(torch.nonzero(bad)[0])
+            which = plan.row_chunk[first]
+            key, code = plan.keys[which], int(bad[first])
+            raise RuntimeError(f"zarr store {plan.chunks[which][0].where}: chunk {key!r} could not be decoded on the device "
+                               f"({blosc.LZ4_STATUS.get(code, 'unknown status')}: status {code})")
+        return plan, toff, tk, ev
+
     def _load(self, n: int):
         """(loader thread) stage batch n and start its upload on the side stream"""
+        if self.device_decode:
+            return self._load_decoded(n)
         slot = n % 2
         lo, hi = self.batches[n]
         plan = plan_batch(self.src, lo, hi)

@@ -11,7 +11,9 @@ after the compressor.  What `yogo infer --path-to-zarr` needs of it (yogo/data/i
 * stores: a directory, or a ``.zip`` file (members stored or deflated; of two members with one name the last one wins).
 
 ``dtype`` must be ``|u1``; ``filters`` must be null; the compressors ``null`` / ``zlib`` / ``gzip`` / ``bz2`` come from the standard
-library, any other id goes through ``numcodecs.get_codec`` when numcodecs imports and raises ``NotImplementedError`` otherwise.
+library, any other id goes through ``numcodecs.get_codec`` when numcodecs imports; without it ``blosc`` (zarr's default) is decoded
+by yogo_amd/blosc.py when its document is complete (``cname``, ``clevel``, ``shuffle``, ``blocksize``: what numcodecs writes)
+and everything else raises ``NotImplementedError``.
 A chunk that cannot be read or decoded raises ``RuntimeError`` naming its key -- the class `predict`'s loop tolerates.
 """
 from __future__ import annotations
@@ -58,6 +60,13 @@ class DirectoryStore:
         try:
             with open(self._file(key), "rb") as f:
                 return f.read()
+        except FileNotFoundError:
+            raise KeyError(key) from None
+
+    def nbytes(self, key: str) -> int:
+        """the stored size of the value of ``key``"""
+        try:
+            return os.path.getsize(self._file(key))
         except FileNotFoundError:
             raise KeyError(key) from None
 
@@ -118,6 +127,12 @@ class ZipStore:
             raise KeyError(key)
         return self._zf.read(info)   # inflates a deflated member; checks length and CRC
 
+    def nbytes(self, key: str) -> int:
+        info = self._info.get(key)
+        if info is None:
+            raise KeyError(key)
+        return info.file_size
+
     def readinto(self, key: str, out: memoryview) -> int:
         info = self._info.get(key)
         if info is None:
@@ -163,7 +178,13 @@ def _open_store(path: Union[str, Path]) -> Store:
     raise ValueError(f"{p} is neither a directory store nor a zip store")
 
 
-def _decoder(compressor: Optional[dict], where: str) -> Optional[Callable[[bytes], bytes]]:
+def _blosc_document(compressor: Optional[dict]) -> bool:
+    """a Blosc compressor document as numcodecs writes it, every key of its configuration present (zarr never writes less).
+    Only such a one is read here without numcodecs: the defaults of a shorter document are numcodecs' to choose."""
+    return bool(compressor) and compressor.get("id") == "blosc" and all(k in compressor for k in ("cname", "clevel", "shuffle", "blocksize"))
+
+
+def _decoder(compressor: Optional[dict], where: str, chunk_nbytes: int) -> Optional[Callable[[bytes], bytes]]:
     """compressed chunk bytes -> decoded bytes for a ``compressor`` document of .zarray (None: the chunk is stored raw)"""
     if compressor is None:
         return None
@@ -177,6 +198,10 @@ def _decoder(compressor: Optional[dict], where: str) -> Optional[Callable[[bytes
     try:
         import numcodecs
     except ImportError:
+        if _blosc_document(compressor):
+            from yogo_amd import blosc
+
+            return lambda data: blosc.decompress(data, chunk_nbytes)
         raise NotImplementedError(f"zarr store {where}: compressor {cid!r} needs the numcodecs package, which is not installed "
                                   "(null, zlib, gzip and bz2 are read without it)") from None
     codec = numcodecs.get_codec(dict(compressor))
@@ -184,6 +209,10 @@ def _decoder(compressor: Optional[dict], where: str) -> Optional[Callable[[bytes
 
 
 _READ_ERRORS = (zlib.error, OSError, EOFError, zipfile.BadZipFile, ValueError)
+
+
+class ChunkTooLong(Exception):
+    """ZarrArray.read_stored_into: the stored chunk is longer than the caller's buffer"""
 
 
 class ZarrArray:
@@ -219,9 +248,9 @@ class ZarrArray:
         if self.separator not in (".", "/"):
             raise ValueError(f"zarr store {self.where}: dimension_separator {self.separator!r}")
         self.compressor = meta.get("compressor")
-        self._decode = _decoder(self.compressor, self.where)
-        self.grid = tuple(-(-s // c) for s, c in zip(self.shape, self.chunks))
         self.chunk_nbytes = int(np.prod(self.chunks, dtype=np.int64))
+        self._decode = _decoder(self.compressor, self.where, self.chunk_nbytes)
+        self.grid = tuple(-(-s // c) for s, c in zip(self.shape, self.chunks))
         sep = re.escape(self.separator)
         self._key_re = re.compile(re.escape(prefix) + r"\d+(?:" + sep + r"\d+){" + str(self.ndim - 1) + r"}$")
 
@@ -236,6 +265,12 @@ class ZarrArray:
     def raw(self) -> bool:
         """chunks are stored as they are (no compressor)"""
         return self._decode is None
+
+    @property
+    def device_decodable(self) -> bool:
+        """the stored chunks may be handed to the device decoder (yogo_amd/zarr_feed.py): Blosc with LZ4 blocks, not bit-shuffled"""
+        c = self.compressor
+        return _blosc_document(c) and c.get("cname") in ("lz4", "lz4hc") and c.get("shuffle") in (0, 1)
 
     def chunk_key(self, coords: Sequence[int]) -> str:
         return self.prefix + self.separator.join(str(int(c)) for c in coords)
@@ -275,6 +310,22 @@ class ZarrArray:
             raise RuntimeError(f"zarr store {self.where}: chunk {key!r} could not be read ({type(e).__name__}: {e})") from e
         except Exception as e:   # a numcodecs codec raises its own classes
             raise RuntimeError(f"zarr store {self.where}: chunk {key!r} could not be decoded ({type(e).__name__}: {e})") from e
+
+    def read_stored_into(self, coords: Sequence[int], out) -> int:
+        """the stored bytes of one chunk as they are (before the compressor) into the front of the writable buffer ``out`` ->
+        how many.  KeyError when the key is absent; ChunkTooLong when ``out`` is too short; RuntimeError naming the key when the
+        chunk cannot be read."""
+        key = self.chunk_key(coords)
+        mv = memoryview(out).cast("B")
+        try:
+            stored = self.store.nbytes(key)
+            if stored > len(mv):
+                raise ChunkTooLong(f"zarr store {self.where}: chunk {key!r} holds {stored} bytes, the buffer {len(mv)}")
+            return self.store.readinto(key, mv[:stored])
+        except (KeyError, ChunkTooLong):
+            raise
+        except _READ_ERRORS as e:
+            raise RuntimeError(f"zarr store {self.where}: chunk {key!r} could not be read ({type(e).__name__}: {e})") from e
 
     def read_chunk(self, coords: Sequence[int]) -> Optional[np.ndarray]:
         """one chunk as an array of the chunk shape, or None when its key is absent"""
