@@ -462,6 +462,34 @@ int yogo_zarr_unpack(const unsigned char* staged, long long staged_bytes, const 
  * the stored bytes say (the same checks, in the same order: yogo_amd.blosc.lz4_block_status). */
 int yogo_blosc_lz4_decode(const unsigned char* src, long long src_bytes, const long long* table, int n, unsigned char* dst,
                           long long dst_bytes, int* status, yogo_stream_t stream);
+/* The chunks of a zarr stack under the `zlib` codec, inflated on the device in front of yogo_zarr_unpack (yogo_amd/inflate.py takes
+ * the zlib wrapper off on the host: split_zlib).  src: src_bytes of device memory holding stored chunks as they came off the disk;
+ * table: [n][5] int64 device, one row { src_off, src_len, dst_off, dst_len, adler32 } per stream: its raw DEFLATE bytes in src
+ * (between the 2-byte header and the 4-byte trailer), where exactly dst_len inflated bytes belong in dst (dst_bytes of device
+ * memory, 16-byte aligned, not overlapping src), and the trailer's Adler-32.  One wavefront per row; stored, fixed and dynamic
+ * blocks, code-length sets held to zlib's rule.  status: [n] int32 device, per row 0 or the check that ended it: 1 the row does not
+ * lie inside src / dst, 2 block type 3, 3 a stored block's LEN / NLEN do not match, 4 the source ends inside a token, 5 invalid
+ * code lengths in a dynamic header, 6 a code or symbol the format does not define (a pattern without a code, literal / length
+ * symbol 286 / 287, distance code 30 / 31), 7 a distance beyond what the stream has produced, 8 the stream would pass dst_len,
+ * 9 it ends before dst_len, 10 dst_len bytes came out and their Adler-32 is not the trailer's.  No byte outside a row's two
+ * ranges is read or written, whatever the stored bytes say (the same checks, in the same order: yogo_amd.inflate.inflate_status). */
+int yogo_inflate_zlib(const unsigned char* src, long long src_bytes, const long long* table, int n, unsigned char* dst,
+                      long long dst_bytes, int* status, yogo_stream_t stream);
+
+/* ---- PNG directories for inference (yogo_amd/png_feed.py, `yogo infer --path-to-images --device-image-decode`) ---------------
+ * The scanlines of 8-bit greyscale, non-interlaced PNG files as yogo_inflate_zlib leaves them (the IDAT payloads of a file are one
+ * zlib stream; yogo_amd/png.py parses the chunks on the host) -> a batch: the PNG filters reversed, CenterCrop and the optional
+ * / 255 in one launch.  scan: scan_bytes of device memory; table: [B][2] int64 device, one row { off, raw } per image: where it
+ * lies in scan, and whether it is H scanlines of 1 + W bytes with the filter-type byte first (raw = 0) or H x W pixels as they are
+ * (raw != 0: an image the host decoded).  Filter types 0 .. 4 with one byte per pixel, the row above row 0 zeros, arithmetic
+ * mod 256, the Paeth predictor's ties in the order left, above, upper-left.  scan is WRITTEN: the last row of every band of 64 rows
+ * is unfiltered in place (the next band reads it), the rest is left as it was.  out: [B][1][OH][OW] uint8 (out_fp32 = 0) or fp32
+ * x / 255 bit-identical to torch's CPU uint8_tensor / 255 (out_fp32 = 1): out[b][0][oy][ox] = image_b[top + oy][left + ox],
+ * 1 <= OH <= H - top, 1 <= OW <= W - left.  status: [B] int32 device, per image 0, 1 (a filter-type byte above 4: its rows from
+ * that band on are not written) or 2 (the image does not lie inside scan: nothing of it is read).  One wavefront per image,
+ * 64 rows at a time, skewed by one pixel per row.  B <= 65535, H, W <= 65535. */
+int yogo_png_unpack(unsigned char* scan, long long scan_bytes, const long long* table, int B, int H, int W, int top, int left, int OH,
+                    int OW, void* out, int out_fp32, int* status, yogo_stream_t stream);
 
 /* ---- optimiser: torch.optim.AdamW over one flat buffer, yogo/train.py:213-217,324 ---------------------------------------- */
 int yogo_adamw_step(float* p, const float* g, float* m, float* v, long long n, int step, double lr, double beta1,

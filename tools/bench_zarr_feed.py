@@ -6,14 +6,15 @@ layout rules) and, with --png, into a PNG directory; everything lies in a tempor
 --content: `incompressible` = a smooth background plus Gaussian noise of sigma 6 (as tools/bench_loader.py; LZ4 does not shrink
 it: Blosc stores its blocks raw), `compressible` = the same with the lower third of every frame a flat field (LZ4 shrinks it to
 about two thirds).  --compressors: null, zlib (level 1), blosc (LZ4 blocks at --blocksize, framed here with the system's liblz4);
---decode: for blosc, `device` (yogo_blosc_lz4_decode) and / or `host` (ZarrDeviceFeed(device_decode=False)).  Every measurement
+--decode: for blosc and zlib, `device` (yogo_blosc_lz4_decode / yogo_inflate_zlib) and / or `host` (ZarrDeviceFeed(device_decode=False);
+for predict, zarr_feed.DEVICE_DECODE_ZLIB = False).  Every measurement
 is a step in a child process of its own with its own time limit; a step that fails or runs out of time is recorded as such, and
 no further step is started.  The lines are APPENDED to --out.
 
   feed     ZarrDeviceFeed alone, batch 256, images/s on the host clock up to the final device synchronise (one warm-up pass,
            then the timed passes), (H, W, 1) chunks in a zip store of stored members
-  decode   (blosc, device) yogo_blosc_lz4_decode alone on the first batch's blocks, device events around each of 20 launches,
-           and the share of blocks stored raw
+  decode   (blosc / zlib, device) yogo_blosc_lz4_decode / yogo_inflate_zlib alone on the first batch's rows, device events around
+           each of 20 launches (zlib: 5), and the share of blocks stored raw
   predict  predict(count_predictions=True, half=True, device_outputs=True, batch_size=256), host clock around the whole call
   --unpack-kernel  yogo_zarr_unpack alone from device events, B = 256, against the bytes it has to move as a share of 8 TB/s
   --png            predict from the null store against the same frames as a PNG directory (16 workers), alternated
@@ -172,13 +173,16 @@ def step_feed(store: str, n: int, device_decode: bool = True, passes: int = 2) -
 
 
 def step_decode(store: str, n: int) -> dict:
-    """yogo_blosc_lz4_decode alone on the blocks of the first batch"""
+    """yogo_blosc_lz4_decode (a zlib store: yogo_inflate_zlib) alone on the rows of the first batch"""
     import torch
 
-    from yogo_amd.zarr_feed import ChunkStager, FrameSource, decode_blocks, plan_batch
+    from yogo_amd.zarr_feed import ChunkStager, FrameSource, decode_blocks, inflate_streams, plan_batch
     from yogo_amd.zarr_store import open_zarr
 
     src = FrameSource(open_zarr(store))
+    zlib_store = src.first.device_codec == "zlib"
+    launches = 5 if zlib_store else 20
+    launch = inflate_streams if zlib_store else decode_blocks   # (zlib: one row per chunk, the fifth field its Adler-32)
     plan = plan_batch(src, 0, min(B, n))
     stager = ChunkStager(src)
     buf = np.zeros(len(plan.keys) * src.stored_stride, np.uint8)
@@ -186,20 +190,22 @@ def step_decode(store: str, n: int) -> dict:
         table = stager.stage_stored(plan, buf)
     finally:
         stager.close()
+    if zlib_store:
+        table = table[table[:, 4] >= 0]   # (a chunk that went the host way is no stream for the inflater)
     stored = torch.from_numpy(buf).cuda()
     table_dev = torch.from_numpy(table).cuda()
     out = torch.empty(plan.nbytes, dtype=torch.uint8, device="cuda")
     status = torch.empty(len(table), dtype=torch.int32, device="cuda")
-    for _ in range(3):
-        decode_blocks(stored, table_dev, out, status)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(21)]
+    for _ in range(1 if zlib_store else 3):
+        launch(stored, table_dev, out, status)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(launches + 1)]
     ev[0].record()
-    for i in range(20):
-        decode_blocks(stored, table_dev, out, status)
+    for i in range(launches):
+        launch(stored, table_dev, out, status)
         ev[i + 1].record()
     torch.cuda.synchronize()
-    us = sorted(ev[i].elapsed_time(ev[i + 1]) * 1e3 for i in range(20))
-    return {"median_us": us[10], "min_us": us[0], "blocks": int(len(table)), "raw_blocks": int(table[:, 4].sum()),
+    us = sorted(ev[i].elapsed_time(ev[i + 1]) * 1e3 for i in range(launches))
+    return {"median_us": us[launches // 2], "min_us": us[0], "blocks": int(len(table)), "raw_blocks": 0 if zlib_store else int(table[:, 4].sum()),
             "stored_bytes": int(table[:, 1].sum()), "decoded_bytes": int(table[:, 3].sum()), "all_ok": not bool(status.any()),
             "frames": int(plan.hi - plan.lo)}
 
@@ -246,15 +252,18 @@ def step_kernel() -> list:
     return out
 
 
-def step_predict_store(d: str, store: str, n: int) -> dict:
-    """predict --count --device-outputs from one store, twice"""
+def step_predict_store(d: str, store: str, n: int, route: str = "device") -> dict:
+    """predict --count --device-outputs from one store, twice; route host: a zlib store is inflated on the host"""
     import contextlib
     import io
 
     import torch
 
+    from yogo_amd import zarr_feed
     from yogo_amd.infer import predict
     from yogo_amd.model import YOGO
+
+    zarr_feed.DEVICE_DECODE_ZLIB = route == "device"
 
     torch.manual_seed(3)
     net = YOGO((H, W), 0.0425, 0.0555, 4).cuda().eval()
@@ -334,7 +343,7 @@ def main() -> int:
     ap.add_argument("--frames", type=int, default=1024)
     ap.add_argument("--content", default="incompressible,compressible")
     ap.add_argument("--compressors", default="null,zlib,blosc")
-    ap.add_argument("--decode", default="device,host", help="for blosc stores: device and / or host")
+    ap.add_argument("--decode", default="device,host", help="for blosc and zlib stores: device and / or host")
     ap.add_argument("--blocksize", type=int, default=131072, help="Blosc block size (c-blosc's choice for 1-byte items at clevel 5)")
     ap.add_argument("--no-predict", action="store_true")
     ap.add_argument("--unpack-kernel", action="store_true")
@@ -351,7 +360,7 @@ def main() -> int:
         elif a.step == "kernel":
             res = step_kernel()
         elif a.step == "predict_store":
-            res = step_predict_store(a.rest[0], a.rest[1], int(a.rest[2]))
+            res = step_predict_store(a.rest[0], a.rest[1], int(a.rest[2]), *a.rest[3:4])
         else:
             res = step_predict(a.rest[0], a.rest[1], int(a.rest[2]))
         print("RESULT " + json.dumps(res), flush=True)
@@ -371,8 +380,8 @@ def main() -> int:
             f"--blocksize {a.blocksize} on one MI355X ({time.strftime('%Y-%m-%d')}); seeded {H}x{W} uint8 frames, batch {B}, (H, W, 1) chunks, "
             "zip stores written just before (reads come from the page cache, not from a disk)")
         log("feed = ZarrDeviceFeed alone, images/s on the host clock, timed passes after a warm-up pass; predict = predict(count_predictions, "
-            "half, device_outputs), host clock around the whole call (model load included); decode = yogo_blosc_lz4_decode alone on the first "
-            "batch, device events, median / min of 20")
+            "half, device_outputs), host clock around the whole call (model load included); decode = the device decoder alone on the first "
+            "batch, device events, median / min of 20 launches (zlib: 5)")
         ok = True
         for content in a.content.split(","):
             np.memmap(os.path.join(d, "frames.u8"), dtype=np.uint8, mode="w+", shape=(n, H, W)).flush()
@@ -382,15 +391,16 @@ def main() -> int:
             for comp in a.compressors.split(","):
                 store = write_store(d, n, f"{content}_{comp}.zip", 1, comp, a.blocksize)
                 share = os.path.getsize(store) / n / (H * W) * 100
-                for route in (a.decode.split(",") if comp == "blosc" else ["host"]):
-                    label = f"  {comp:<5s} {('decode on the ' + route) if comp == 'blosc' else '':<20s}"
+                routed = comp in ("blosc", "zlib")
+                for route in (a.decode.split(",") if routed else ["host"]):
+                    label = f"  {comp:<5s} {('decode on the ' + route) if routed else '':<20s}"
                     r = run_step(log, "feed", 300, [store, n, route])
                     if r is None:
                         ok = False
                         break
                     log(f"{label} feed     " + "  ".join(f"{v:9.0f} img/s" for v in r["images_per_s"]) +
                         f"   ({share:.1f} % of raw on disk; device_decode={r['device_decode']})")
-                    if comp == "blosc" and route == "device":
+                    if routed and route == "device":
                         k = run_step(log, "decode", 180, [store, n])
                         if k is None:
                             ok = False
@@ -399,7 +409,7 @@ def main() -> int:
                             f"{k['raw_blocks']} of them raw ({100 * k['raw_blocks'] / max(k['blocks'], 1):.1f} %), {k['stored_bytes'] / 1e6:.1f} MB stored -> "
                             f"{k['decoded_bytes'] / 1e6:.1f} MB decoded = {k['decoded_bytes'] / (k['median_us'] * 1e-6) / 1e9:.0f} GB/s out; every status 0: {k['all_ok']}")
                     if not a.no_predict and (comp != "blosc" or route == "device"):
-                        r = run_step(log, "predict_store", 420, [d, store, n])
+                        r = run_step(log, "predict_store", 420, [d, store, n, route])
                         if r is None:
                             ok = False
                             break

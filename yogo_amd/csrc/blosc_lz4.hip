@@ -25,38 +25,14 @@
 // workgroup scope asks for here.  It costs no LDS; a 64 KiB history window in LDS would hold two blocks per CU, and this loop,
 // latency-bound per sequence, wants many wavefronts per CU.
 #include "common.h"
+#include "wave_copy.h"
 
 namespace {
 
-constexpr int WAVE = 64;
+using yogo_wave::WAVE;
+using yogo_wave::wave_copy;
 enum : int { ST_OK = 0, ST_LITERALS_PAST_SOURCE = 1, ST_SOURCE_ENDS_IN_SEQUENCE = 2, ST_BAD_OFFSET = 3, ST_PAST_DESTINATION = 4,
              ST_ENDS_EARLY = 5, ST_BAD_ENTRY = 6 };
-
-// n bytes from s to d by the whole wave; the ranges do not overlap.  Aligned 16-byte stores, 16-byte loads at the source's alignment.
-__device__ __forceinline__ void wave_copy(unsigned char* d, const unsigned char* s, long long n, int lane) {
-  if (n < 4 * WAVE) {
-    for (long long i = lane; i < n; i += WAVE) d[i] = s[i];
-    return;
-  }
-  const long long head = (16 - (reinterpret_cast<uintptr_t>(d) & 15)) & 15;   // < n
-  const long long pieces = (n - head) >> 4;
-  if (lane < head) d[lane] = s[lane];
-  long long p = lane;
-  for (; p + 3 * WAVE < pieces; p += 4 * WAVE) {   // four loads in flight before the first store (d may alias s for the compiler)
-    uint4 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) __builtin_memcpy(&v[u], s + head + 16 * (p + u * WAVE), 16);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) *reinterpret_cast<uint4*>(d + head + 16 * (p + u * WAVE)) = v[u];
-  }
-  for (; p < pieces; p += WAVE) {
-    uint4 v;
-    __builtin_memcpy(&v, s + head + 16 * p, 16);
-    *reinterpret_cast<uint4*>(d + head + 16 * p) = v;
-  }
-  const long long done = head + 16 * pieces;
-  if (done + lane < n) d[done + lane] = s[done + lane];   // < 16 bytes are left
-}
 
 // the source byte at p (0 <= p < n, wave-uniform) out of the wave's 64-byte window, which is refilled when p lies outside it
 __device__ __forceinline__ unsigned src_byte(const unsigned char* s, long long n, long long p, long long& wbase, unsigned& w, int lane) {
@@ -121,18 +97,10 @@ __global__ __launch_bounds__(WAVE) void blosc_lz4_decode_kernel(const unsigned c
       if (off == 0 || off > dp) { st = ST_BAD_OFFSET; break; }
       if (ml > dst_len - dp) { st = ST_PAST_DESTINATION; break; }
       __syncthreads();   // everything stored so far (these literals, every earlier sequence) is visible to the loads below
-      const unsigned char* m = d + dp - off;
       if (off >= ml) {
-        wave_copy(d + dp, m, ml, lane);
+        wave_copy(d + dp, d + dp - off, ml, lane);
       } else {
-        // lane i serves bytes i, i + 64, ... of the match: byte j comes from m[j % off]; r follows j % off without a division per trip
-        const int o = (int)off, step = WAVE % o;
-        int r = lane % o;
-        for (long long j = lane; j < ml; j += WAVE) {
-          d[dp + j] = m[r];
-          r += step;
-          if (r >= o) r -= o;
-        }
+        yogo_wave::wave_copy_periodic(d + dp, off, ml, lane);
       }
       dp += ml;   // (the next sequence's barrier stands between these stores and its loads)
     }

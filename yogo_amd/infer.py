@@ -11,6 +11,10 @@ the model is already a fixed sequence of hand-written kernels.
 requested output (yogo_amd/pred_sink.py) compacts and counts the kept rows in HBM, and the host reads them when a sink is drained --
 after the loop, or when ``flush_rows`` records have piled up -- instead of copying the padded rows of every batch.  Same files, same
 counts.
+
+``device_image_decode=True`` (``yogo infer --path-to-images DIR --device-image-decode``) replaces the DataLoader and its PIL-decoding
+workers by a ``PngDeviceFeed`` (yogo_amd/png_feed.py): the files' zlib streams are inflated and their PNG filters reversed on the
+device, crop and ``/ 255`` included.  Same batches and names; ``ValueError`` with ``path_to_zarr`` and for an RGB model.
 """
 from __future__ import annotations
 
@@ -67,6 +71,7 @@ def predict(
     half: bool = False,
     return_full_predictions: bool = False,
     device_outputs: bool = False,
+    device_image_decode: bool = False,
 ) -> Optional[torch.Tensor]:
     if save_preds and draw_boxes:
         raise ValueError("cannot save predictions in YOGO format and draw_boxes at the same time")
@@ -79,6 +84,8 @@ def predict(
     elif output_img_ftype not in [".png", ".tif", ".tiff"]:
         raise ValueError(f"only .png, .tif, and .tiff are supported for output img filetype; got {output_img_ftype}")
 
+    if device_image_decode and path_to_zarr is not None:
+        raise ValueError("device_image_decode decodes the PNG files of path_to_images; a zarr stack has its own device route")
     device = torch.device(device or choose_device())
     if device.type != "cuda":
         raise RuntimeError(f"yogo_amd: inference runs on an MI355X (got device {device}); there is no CPU compute path")
@@ -94,6 +101,8 @@ def predict(
         model.resize_model(crop_px)
         img_h = crop_px
     assert model.img_size.numel() == 2, f"YOGO model must be 2D, is {model.img_size}"
+    if device_image_decode and bool(model.is_rgb):
+        raise ValueError("device_image_decode reads 8-bit greyscale images; this model takes RGB input")
     num_classes = int(model.num_classes)
     if class_names is not None and len(class_names) != num_classes:
         raise ValueError(f"expected {num_classes} class names, got {len(class_names)}")
@@ -108,6 +117,13 @@ def predict(
         with torch.cuda.device(device):
             loader = ZarrDeviceFeed(image_dataset, batch_size, device, crop=(img_h, img_w) if vertical_crop_height else None,
                                     normalize=bool(model.normalize_images))
+    elif device_image_decode:
+        # the files' zlib streams are inflated and unfiltered on the device, crop and / 255 included (yogo_amd/png_feed.py)
+        from yogo_amd.png_feed import PngDeviceFeed
+
+        with torch.cuda.device(device):
+            loader = PngDeviceFeed(image_dataset, batch_size, device, crop=(img_h, img_w) if vertical_crop_height else None,
+                                   normalize=bool(model.normalize_images))
     else:
         num_workers = choose_dataloader_num_workers(len(image_dataset), requested_num_workers=requested_num_workers)
         loader = DataLoader(image_dataset, batch_size=batch_size, shuffle=False, drop_last=False, pin_memory=True, collate_fn=collate_fn,
@@ -149,7 +165,7 @@ def predict(
             continue
         x = img_batch.to(device, non_blocking=True)
         if draw_boxes and img_batch.is_cuda:
-            img_batch = img_batch.cpu()   # (zarr feed) drawing is host work
+            img_batch = img_batch.cpu()   # (zarr / PNG feed) drawing is host work
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=bool(half)):
             # the decoded tensor itself is only needed for drawing and for return_full_predictions; every other output goes
             # through the threshold + NMS kernel, which decodes the head's raw output as it loads it
@@ -235,4 +251,5 @@ def do_infer(args) -> None:
         obj_thresh=args.obj_thresh, iou_thresh=args.iou_thresh, batch_size=args.batch_size, device=args.device, use_tqdm=args.use_tqdm,
         vertical_crop_height=args.crop_height, count_predictions=args.count, output_img_ftype=args.output_img_filetype,
         min_class_confidence_threshold=args.min_class_confidence_threshold, half=args.half, device_outputs=args.device_outputs,
+        device_image_decode=args.device_image_decode,
     )

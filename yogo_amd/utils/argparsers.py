@@ -175,6 +175,9 @@ def infer_parser(parser=None):
     parser.add_argument("--device-outputs", default=False, action=boolean_action,
                         help="compact and count the kept predictions of --save-preds / --save-npy / --count on the GPU and read them once "
                              "instead of copying every batch's padded rows to the host; same files and counts (default: False)")
+    parser.add_argument("--device-image-decode", default=False, action=boolean_action,
+                        help="with --path-to-images: inflate and unfilter 8-bit greyscale PNG files on the GPU instead of decoding them "
+                             "in DataLoader workers; other files are decoded on the host; same outputs (default: False)")
     parser.add_argument("--output-dir", type=Path, default=None,
                         help="path to directory for results, either --draw-boxes or --save-preds")
     parser.add_argument("--class-names", help="list of class names - will default to integers if not provided", nargs="*", type=str, default=None)

@@ -14,6 +14,12 @@ entry per block (yogo_amd/blosc.py), the loader uploads bytes and table, launche
 (yogo_amd/csrc/blosc_lz4.hip) on the side stream into the slot's device buffer -- the layout ``yogo_zarr_unpack`` reads -- and
 waits for the per-block status.  A chunk the device cannot decode (zlib inside, bit-shuffle) is decoded on the host and enters
 the table as one raw entry.
+
+Stacks under zarr's ``zlib`` codec take the same route with another decoder: one table row per chunk -- the raw DEFLATE bytes
+between the zlib header and trailer, and the trailer's Adler-32 (yogo_amd/inflate.py) -- and one ``yogo_inflate_zlib`` launch
+(yogo_amd/csrc/inflate.hip).  A chunk whose wrapper is not a plain zlib one is decoded on the host and copied as a raw row by
+``yogo_blosc_lz4_decode``.  ``DEVICE_DECODE_ZLIB`` switches the route for this codec; it is off, because the
+host route measured faster (profiles/zarr_feed.log).
 """
 from __future__ import annotations
 
@@ -27,12 +33,15 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from yogo_amd import _hip, blosc
+from yogo_amd import _hip, blosc, inflate
 from yogo_amd.zarr_store import ChunkTooLong, ZarrArray, ZarrGroup
 
 ALIGN = 256          # every staged chunk starts on a multiple of this (the kernel asks for 16)
 MAX_THREADS = 16
 RAW_PIECE = 1 << 16  # bytes of a raw block one wavefront of the device decoder copies (longer raw entries are cut up)
+DEVICE_DECODE_ZLIB = False  # True: stacks under the zlib codec are inflated on the device.  Off: at batch 256 the device route feeds
+#                             1.0-1.5 k img/s where the host's 16 threads feed 2.5-3.4 k (profiles/zarr_feed.log); PNG files do gain
+ZLIB_RAW = -1        # fifth field of a zlib store's entry that holds host-decoded bytes (an Adler-32 is never negative)
 
 
 def center_crop_origin(H: int, W: int, OH: int, OW: int) -> Tuple[int, int]:
@@ -199,27 +208,37 @@ class ChunkStager:
         key = arr.chunk_key(coords)
         store = self._store(arr)
         a = arr.with_store(store)
-        try:
-            if a.device_decodable:
+        codec = self.src.first.device_codec   # the table's fifth field is read by the STORE's codec: a group member under
+        try:                                   # another compressor than member 0's is decoded on the host, as before
+            if codec is not None and a.device_codec == codec:
                 try:
                     got = a.read_stored_into(coords, out)
-                    flags, entries = blosc.parse_chunk(out[:got], n)
-                    if blosc.device_decodable(flags):
-                        return got, entries
+                    if codec == "zlib":
+                        try:
+                            off, ln, adler = inflate.split_zlib(out[:got])
+                            return got, [(off, ln, 0, n, adler)]
+                        except ValueError:
+                            pass   # not a plain zlib wrapper: the host's to decode (or to refuse)
+                    else:
+                        flags, entries = blosc.parse_chunk(out[:got], n)
+                        if blosc.device_decodable(flags):
+                            return got, entries
                 except (ChunkTooLong, NotImplementedError):
                     pass
                 except ValueError as e:
                     raise RuntimeError(f"zarr store {arr.where}: chunk {key!r} could not be decoded ({type(e).__name__}: {e})") from e
             a.read_chunk_into(coords, out[:n])
-            return n, [(0, n, 0, n, 1)]
+            return n, [(0, n, 0, n, ZLIB_RAW if codec == "zlib" else 1)]
         except KeyError:
             raise RuntimeError(f"zarr store {arr.where}: chunk {key!r} disappeared from the store") from None
 
     def stage_stored(self, plan: BatchPlan, buf: np.ndarray, prev: Optional[Tuple[BatchPlan, np.ndarray]] = None) -> np.ndarray:
         """(device decode) the STORED bytes of every chunk of ``plan`` at ``i * stored_stride`` in ``buf``; fills ``plan.stored``
         and returns the decoder's table, int64 [blocks, 5]: (src_off, src_len, dst_off, dst_len, raw) with dst_off in the layout of
-        ``plan.offsets``.  Chunks that ``prev`` holds are copied from there; errors as in ``stage``."""
+        ``plan.offsets`` (a zlib store: one row per chunk, the fifth field its Adler-32, or ZLIB_RAW for host-decoded bytes).
+        Chunks that ``prev`` holds are copied from there; errors as in ``stage``."""
         stride = self.src.stored_stride
+        zlib_store = self.src.first.device_codec == "zlib"
         plan.stored = {}
         futures: List[Tuple[str, Future]] = []
         for i, (key, (arr, coords)) in enumerate(zip(plan.keys, plan.chunks)):
@@ -243,36 +262,49 @@ class ChunkStager:
             raise err
         rows, owner = [], []
         for i, key in enumerate(plan.keys):
-            for so, sl, do, dl, raw in plan.stored[key][1]:
+            for so, sl, do, dl, fifth in plan.stored[key][1]:
+                raw = fifth == ZLIB_RAW if zlib_store else fifth
                 # a long raw entry (a memcpyed chunk, a chunk decoded on the host) goes to several wavefronts
                 for at in (range(0, sl, RAW_PIECE) if raw else (0,)):
                     ln = min(RAW_PIECE, sl - at) if raw else sl
-                    rows.append((i * stride + so + at, ln, plan.offsets[key] + do + at, ln if raw else dl, raw))
+                    rows.append((i * stride + so + at, ln, plan.offsets[key] + do + at, ln if raw else dl, fifth))
                     owner.append(i)
         plan.row_chunk = owner
         return np.asarray(rows, dtype=np.int64).reshape(-1, 5)
+
+
+def _decode_rows(symbol: str, stored: torch.Tensor, table: torch.Tensor, out: torch.Tensor, status: torch.Tensor) -> None:
+    """one launch of a device decoder (`symbol`) on the current stream: the checks the two share"""
+    what = symbol[len("yogo_"):]
+    for t, name in ((stored, "the stored chunk bytes"), (table, "the table"), (out, "the decoded chunks"), (status, "the status")):
+        _hip.require_cuda(t, name)
+    if stored.dtype != torch.uint8 or out.dtype != torch.uint8 or stored.ndim != 1 or out.ndim != 1 or not stored.is_contiguous() \
+            or not out.is_contiguous() or stored.numel() == 0 or out.numel() == 0:
+        raise ValueError(f"{what}: stored and out must be non-empty contiguous 1-D uint8 tensors")
+    n = int(table.shape[0])
+    if table.dtype != torch.int64 or table.ndim != 2 or table.shape[1] != 5 or not table.is_contiguous():
+        raise ValueError(f"{what}: the table must be a contiguous int64 [n, 5] tensor, got {tuple(table.shape)} {table.dtype}")
+    if status.dtype != torch.int32 or tuple(status.shape) != (n,) or not status.is_contiguous():
+        raise ValueError(f"{what}: the status must be a contiguous int32 [{n}] tensor, got {tuple(status.shape)} {status.dtype}")
+    if len({stored.device, table.device, out.device, status.device}) != 1:
+        raise ValueError(f"{what}: the tensors live on different devices")
+    if n == 0:
+        return
+    with torch.cuda.device(out.device):
+        _hip.call(symbol, stored, stored.numel(), table, n, out, out.numel(), status, _hip.stream_ptr())
 
 
 def decode_blocks(stored: torch.Tensor, table: torch.Tensor, out: torch.Tensor, status: torch.Tensor) -> None:
     """One ``yogo_blosc_lz4_decode`` launch on the current stream.  stored / out: 1-D uint8 device tensors (stored chunk bytes, decoded
     staging buffer); table: int64 [n, 5] device, rows (src_off, src_len, dst_off, dst_len, raw); status: int32 [n] device.  The
     kernel holds every row to the two buffers itself."""
-    for t, what in ((stored, "the stored chunk bytes"), (table, "the block table"), (out, "the decoded chunks"), (status, "the status")):
-        _hip.require_cuda(t, what)
-    if stored.dtype != torch.uint8 or out.dtype != torch.uint8 or stored.ndim != 1 or out.ndim != 1 or not stored.is_contiguous() \
-            or not out.is_contiguous() or stored.numel() == 0 or out.numel() == 0:
-        raise ValueError("decode_blocks: stored and out must be non-empty contiguous 1-D uint8 tensors")
-    n = int(table.shape[0])
-    if table.dtype != torch.int64 or table.ndim != 2 or table.shape[1] != 5 or not table.is_contiguous():
-        raise ValueError(f"decode_blocks: the table must be a contiguous int64 [n, 5] tensor, got {tuple(table.shape)} {table.dtype}")
-    if status.dtype != torch.int32 or tuple(status.shape) != (n,) or not status.is_contiguous():
-        raise ValueError(f"decode_blocks: the status must be a contiguous int32 [{n}] tensor, got {tuple(status.shape)} {status.dtype}")
-    if len({stored.device, table.device, out.device, status.device}) != 1:
-        raise ValueError("decode_blocks: the tensors live on different devices")
-    if n == 0:
-        return
-    with torch.cuda.device(out.device):
-        _hip.call("yogo_blosc_lz4_decode", stored, stored.numel(), table, n, out, out.numel(), status, _hip.stream_ptr())
+    _decode_rows("yogo_blosc_lz4_decode", stored, table, out, status)
+
+
+def inflate_streams(stored: torch.Tensor, table: torch.Tensor, out: torch.Tensor, status: torch.Tensor) -> None:
+    """One ``yogo_inflate_zlib`` launch on the current stream; as decode_blocks, rows (src_off, src_len, dst_off, dst_len, adler32):
+    the raw DEFLATE bytes of one zlib stream each (yogo_amd.inflate.split_zlib)."""
+    _decode_rows("yogo_inflate_zlib", stored, table, out, status)
 
 
 def unpack(staged: torch.Tensor, tile_off: np.ndarray, tile_k: np.ndarray, *, chunks: Sequence[int], order_f: bool, fill: int,
@@ -320,8 +352,8 @@ class ZarrDeviceFeed:
     generator: when a batch raises RuntimeError (an unreadable chunk), the next ``next()`` goes on with the following batch.
     ``crop``: (OH, OW) of a centre crop done in the kernel; ``normalize``: fp32 ``/ 255`` in the kernel, else uint8.
     ``num_frames``: how many frames to walk (default: ``len(dataset)``, as the reference's DataLoader does, and never more
-    than the stack holds).  ``device_decode``: a Blosc stack with LZ4 blocks is decoded on the device (module docstring); False
-    takes the host route (A/B runs); every other source takes the host route whatever it says."""
+    than the stack holds).  ``device_decode``: a Blosc stack with LZ4 blocks (and, with DEVICE_DECODE_ZLIB set, a zlib stack) is decoded on the device
+    (module docstring); False takes the host route (A/B runs); every other source takes the host route whatever it says."""
 
     def __init__(self, dataset, batch_size: int, device, crop: Optional[Tuple[int, int]] = None, normalize: bool = False,
                  num_frames: Optional[int] = None, device_decode: bool = True):
@@ -343,7 +375,8 @@ class ZarrDeviceFeed:
         self._pinned = [torch.empty(cap, dtype=torch.uint8).pin_memory() for _ in range(2)]
         self._host = [p.numpy() for p in self._pinned]
         self._dev = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(2)]
-        self.device_decode = bool(device_decode) and src.first.device_decodable
+        self.codec = src.first.device_codec
+        self.device_decode = bool(device_decode) and self.codec is not None and (self.codec != "zlib" or DEVICE_DECODE_ZLIB)
         if self.device_decode:
             scap = src.max_chunks(self.batch_size) * src.stored_stride
             self._spinned = [torch.empty(scap, dtype=torch.uint8).pin_memory() for _ in range(2)]
@@ -386,8 +419,9 @@ class ZarrDeviceFeed:
             self._sdev[slot][a:b].copy_(self._spinned[slot][a:b], non_blocking=True)
 
     def _load_decoded(self, n: int):
-        """(loader thread) batch n through the device decoder: stored bytes and block table up, one decode launch on the side
-        stream into the slot's device buffer, then the per-block status back -- RuntimeError naming the first bad chunk"""
+        """(loader thread) batch n through the device decoder: stored bytes and table up, one decode launch on the side stream
+        into the slot's device buffer (a zlib stack: one inflate launch, and one of raw rows where a chunk was decoded on the
+        host), then the per-row status back -- RuntimeError naming the first bad chunk"""
         slot = n % 2
         lo, hi = self.batches[n]
         plan = plan_batch(self.src, lo, hi)
@@ -402,12 +436,21 @@ class ZarrDeviceFeed:
                 self._side.wait_event(self._consumed[slot])
             toff = torch.from_numpy(plan.tile_off).to(self.device)
             tk = torch.from_numpy(plan.tile_k).to(self.device)
-            status = None
+            status, n_inflate = None, 0
             if len(table):
                 self._upload_stored(plan, slot)
+                if self.codec == "zlib":   # host-decoded chunks are copied by the Blosc decoder's raw rows, behind the inflate rows
+                    raw = table[:, 4] == ZLIB_RAW
+                    order = np.argsort(raw, kind="stable")
+                    table, n_inflate = table[order], int((~raw).sum())
+                    table[n_inflate:, 4] = 1
+                    plan.row_chunk = [plan.row_chunk[i] for i in order]
                 table_dev = torch.from_numpy(table).to(self.device)
                 status = torch.empty(len(table), dtype=torch.int32, device=self.device)
-                decode_blocks(self._sdev[slot], table_dev, self._dev[slot], status)
+                if n_inflate:
+                    inflate_streams(self._sdev[slot], table_dev[:n_inflate], self._dev[slot], status[:n_inflate])
+                if n_inflate < len(table):
+                    decode_blocks(self._sdev[slot], table_dev[n_inflate:], self._dev[slot], status[n_inflate:])
             ev = torch.cuda.Event()
             ev.record(self._side)
             bad = status.cpu() if status is not None else None   # waits for the decode: this thread overlaps the consumer already
@@ -417,8 +460,9 @@ class ZarrDeviceFeed:
             first = int(torch.nonzero(bad)[0])
             which = plan.row_chunk[first]
             key, code = plan.keys[which], int(bad[first])
+            texts = inflate.INF_STATUS if first < n_inflate else blosc.LZ4_STATUS
             raise RuntimeError(f"zarr store {plan.chunks[which][0].where}: chunk {key!r} could not be decoded on the device "
-                               f"({blosc.LZ4_STATUS.get(code, 'unknown status')}: status {code})")
+                               f"({texts.get(code, 'unknown status')}: status {code})")
         return plan, toff, tk, ev
 
     def _load(self, n: int):

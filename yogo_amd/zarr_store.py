@@ -268,9 +268,20 @@ class ZarrArray:
 
     @property
     def device_decodable(self) -> bool:
-        """the stored chunks may be handed to the device decoder (yogo_amd/zarr_feed.py): Blosc with LZ4 blocks, not bit-shuffled"""
+        """Blosc only: the stored chunks may be handed to yogo_blosc_lz4_decode (Blosc with LZ4 blocks, not bit-shuffled).  The
+        feed asks ``device_codec``, which also knows the zlib codec's device route."""
         c = self.compressor
         return _blosc_document(c) and c.get("cname") in ("lz4", "lz4hc") and c.get("shuffle") in (0, 1)
+
+    @property
+    def device_codec(self) -> Optional[str]:
+        """which device decoder the feed hands the stored chunks to: "blosc" (device_decodable), "zlib" (the zlib codec: one
+        stream per chunk for yogo_inflate_zlib), or None"""
+        if self.device_decodable:
+            return "blosc"
+        if self.compressor and self.compressor.get("id") == "zlib":
+            return "zlib"
+        return None
 
     def chunk_key(self, coords: Sequence[int]) -> str:
         return self.prefix + self.separator.join(str(int(c)) for c in coords)
