@@ -491,6 +491,21 @@ int yogo_inflate_zlib(const unsigned char* src, long long src_bytes, const long 
 int yogo_png_unpack(unsigned char* scan, long long scan_bytes, const long long* table, int B, int H, int W, int top, int left, int OH,
                     int OW, void* out, int out_fp32, int* status, yogo_stream_t stream);
 
+/* ---- PNG files into the device image cache (yogo_amd/png_prefill.py, `yogo train --device-image-cache GIB --device-image-decode`)
+ * yogo_png_unpack for full frames of 1 or 3 planes, from 8-bit greyscale AND 8-bit RGB files: same scan buffer, same [B][2] int64
+ * table { off, kind }, kind 0: H scanlines of 1 + W bytes (grey); kind 2: H scanlines of 1 + 3 W bytes (RGB, the filters at 3 bytes
+ * per pixel: a byte's left neighbour is the same channel of the pixel to the left); kind 1: C_out x H x W planar pixels as they
+ * are (an image the host decoded).  out: [B][C_out][H][W] uint8 (any alignment: a view into the cache), C_out 1 or 3, no crop and
+ * no / 255; the file's channels become the cache's as yogo_amd.yogo_dataset.read_image(path, rgb) does it: grey -> 1 plane as it
+ * is, grey -> 3 planes the plane three times, RGB -> 3 planes de-interleaved, RGB -> 1 plane
+ * L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16.  scan is WRITTEN as by yogo_png_unpack (the last row of every band of 64).
+ * status: [B] int32 device, per image 0, 1 (a filter-type byte above 4: its rows from that band on are not written) or 2 (a kind
+ * outside 0 .. 2, or the image does not lie inside scan: nothing of it is read).  One wavefront per image, 64 rows at a time,
+ * skewed by one pixel per row, a 3-byte pixel in one register.  For kind 0 and C_out = 1 the output is yogo_png_unpack's, bit for
+ * bit.  B <= 65535, H, W <= 65535. */
+int yogo_png_unpack_planes(unsigned char* scan, long long scan_bytes, const long long* table, int B, int H, int W, int C_out,
+                           unsigned char* out, int* status, yogo_stream_t stream);
+
 /* ---- optimiser: torch.optim.AdamW over one flat buffer, yogo/train.py:213-217,324 ---------------------------------------- */
 int yogo_adamw_step(float* p, const float* g, float* m, float* v, long long n, int step, double lr, double beta1,
                     double beta2, double eps, double weight_decay, double grad_scale, yogo_stream_t stream);

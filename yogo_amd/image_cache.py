@@ -14,6 +14,11 @@ persistent, its own generator so that torch's global RNG -- and with it every la
 ``(index, uint8 image after resize_image, label rows)`` per sample.  A sample unreadable at prefill is not made resident and
 stays with the workers, which retry it every epoch as before.
 
+``device_decode=True`` (``yogo train --device-image-decode``) fills the cache without that pool: threads read the PNG files, the
+device inflates and unfilters them in chunks of ``decode_batch`` images straight into their slots (yogo_amd/png_prefill.py), and
+whatever the device does not take goes through ``image_uint8`` as above.  Its scratch (pinned slots, stored streams, scanlines) is
+dropped when the prefill returns and is not part of the budget.  Everything after the fill is the same code on both routes.
+
 The one deliberate difference to the uncached path: a resident image is a snapshot taken at prefill, so a file changed or
 removed later is still served.  Otherwise pixels and labels are bit-identical.
 """
@@ -28,11 +33,13 @@ import numpy as np
 import torch
 from torch.utils.data import ConcatDataset, DataLoader, Dataset, SequentialSampler, Subset
 
-from yogo_amd import _hip
+from yogo_amd import _hip, png_prefill
+from yogo_amd.png_prefill import DEFAULT_DECODE_BATCH
 from yogo_amd.yogo_dataset import ObjectDetectionDataset
 
 GIB = 2 ** 30
 FLAG = "--device-image-cache"
+DECODE_FLAG = "--device-image-decode"
 
 
 def check_budget_gib(gib: float) -> float:
@@ -189,7 +196,8 @@ class ImageCache:
     in its real part, are cached)."""
 
     def __init__(self, split: Dataset, S: int, image_shape: Tuple[int, int, int], normalize_images: bool, device=None,
-                 num_workers: int = 0, batch_size: int = 64, name: str = "train", log: bool = False):
+                 num_workers: int = 0, batch_size: int = 64, name: str = "train", log: bool = False, device_decode: bool = False,
+                 decode_batch: int = DEFAULT_DECODE_BATCH):
         if not torch.cuda.is_available():
             raise RuntimeError(f"yogo_amd: {FLAG} keeps images on an MI355X device; there is no CPU fallback")
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -204,6 +212,8 @@ class ImageCache:
             raise ValueError(f"ImageCache: S = {S} outside [1, {self.split_len}]")
         self.normalize_images, self.device = bool(normalize_images), dev
         self.num_workers, self.batch_size, self.name, self.log = int(num_workers), max(1, int(batch_size)), name, log
+        self.device_decode, self.decode_batch = bool(device_decode), png_prefill.check_decode_batch(decode_batch)
+        self.decode_stats: dict = {}   # what png_prefill.fill reports of a device prefill (chunk times, scratch bytes); empty otherwise
         self.nbytes = self.S * C * H * W
         try:
             self.images = torch.empty((self.S, C, H, W), dtype=torch.uint8, device=dev)
@@ -230,22 +240,11 @@ class ImageCache:
         if self.prefilled:
             return
         t0 = time.perf_counter()
-        items = _PrefillItems(self.split, self.S)
-        nw = self.num_workers
-        loader = DataLoader(items, batch_size=self.batch_size, sampler=SequentialSampler(items), num_workers=nw, persistent_workers=False,
-                            pin_memory=True, collate_fn=_collate_prefill, generator=torch.Generator().manual_seed(0),
-                            multiprocessing_context="spawn" if nw > 0 else None)
-        rows: List[Optional[torch.Tensor]] = [None] * self.S
         with torch.cuda.device(self.device):
-            for idx, imgs, rws in loader:
-                if not idx:
-                    continue
-                slots = torch.tensor(idx, dtype=torch.long).to(self.device, non_blocking=True)
-                self.images.index_copy_(0, slots, imgs.to(self.device, non_blocking=True))
-                for i, r in zip(idx, rws):
-                    rows[i] = r.reshape(-1, 5).to(torch.float32)
-                    self.resident[i] = True
+            rows = self._fill_on_device() if self.device_decode else self._fill_from_workers()
             torch.cuda.synchronize(self.device)
+        for i, r in enumerate(rows):
+            self.resident[i] = r is not None
         counts = np.array([0 if r is None else int(r.shape[0]) for r in rows], dtype=np.int64)
         self.row_offsets = np.zeros(self.S + 1, dtype=np.int64)
         self.row_offsets[1:] = np.cumsum(counts)
@@ -257,3 +256,24 @@ class ImageCache:
         if self.log:
             print(f"yogo_amd: device image cache ({self.name}): {n} of {self.split_len} images resident, {self.nbytes} bytes of HBM; "
                   f"prefill {dt:.2f} s ({n / max(dt, 1e-9):.0f} images/s)", flush=True)
+
+    def _fill_from_workers(self) -> List[Optional[torch.Tensor]]:
+        """the host route: a one-off DataLoader decodes, the pixels are copied up -> per slot its label rows, None = not resident"""
+        items = _PrefillItems(self.split, self.S)
+        nw = self.num_workers
+        loader = DataLoader(items, batch_size=self.batch_size, sampler=SequentialSampler(items), num_workers=nw, persistent_workers=False,
+                            pin_memory=True, collate_fn=_collate_prefill, generator=torch.Generator().manual_seed(0),
+                            multiprocessing_context="spawn" if nw > 0 else None)
+        rows: List[Optional[torch.Tensor]] = [None] * self.S
+        for idx, imgs, rws in loader:
+            if not idx:
+                continue
+            slots = torch.tensor(idx, dtype=torch.long).to(self.device, non_blocking=True)
+            self.images.index_copy_(0, slots, imgs.to(self.device, non_blocking=True))
+            for i, r in zip(idx, rws):
+                rows[i] = r.reshape(-1, 5).to(torch.float32)
+        return rows
+
+    def _fill_on_device(self) -> List[Optional[torch.Tensor]]:
+        """the device route (yogo_amd/png_prefill.py): the same result, the PNG files inflated and unfiltered on the device"""
+        return png_prefill.fill(self.images, [resolve_sample(self.split, i) for i in range(self.S)], self.decode_batch, self.decode_stats)

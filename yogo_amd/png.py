@@ -6,7 +6,9 @@ concatenated are ONE zlib stream of the filtered scanlines (``height`` rows of o
 last.  ``parse_png`` lists what yogo_amd/png_feed.py needs: the header fields and where the IDAT payloads lie, so that they are
 copied back to back into the staging buffer and the device sees one zlib stream (csrc/inflate.hip), whose inflated rows
 csrc/png_unpack.hip unfilters.  Only 8-bit greyscale, non-interlaced files without transparency go that way
-(``PngInfo.device_decodable``); everything else is read by ``yogo_amd.yogo_dataset.read_image`` on the host.
+(``PngInfo.device_decodable``); everything else is read by ``yogo_amd.yogo_dataset.read_image`` on the host.  The prefill of the
+device image cache (yogo_amd/png_prefill.py, csrc/png_unpack_planes.hip) parses files the same way and also takes 8-bit RGB ones
+(``PngInfo.prefill_decodable``, ``PngInfo.bytes_per_pixel``).
 """
 from __future__ import annotations
 
@@ -36,6 +38,17 @@ class PngInfo:
     def device_decodable(self) -> bool:
         """8-bit greyscale, not interlaced, no tRNS: the scanlines are 1 + width bytes and a pixel is a byte"""
         return self.bit_depth == 8 and self.color_type == 0 and self.interlace == 0 and not self.has_trns
+
+    @property
+    def prefill_decodable(self) -> bool:
+        """8-bit greyscale or 8-bit RGB, not interlaced, no tRNS: what csrc/png_unpack_planes.hip unfilters for the device image
+        cache (yogo_amd/png_prefill.py) -- scanlines of 1 + width * bytes_per_pixel bytes"""
+        return self.bit_depth == 8 and self.color_type in (0, 2) and self.interlace == 0 and not self.has_trns
+
+    @property
+    def bytes_per_pixel(self) -> int:
+        """of an 8-bit file: 1 (grey), 3 (RGB); the other colour types are not decoded on the device"""
+        return 3 if self.color_type == 2 else 1
 
     @property
     def idat_bytes(self) -> int:

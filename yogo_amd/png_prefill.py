@@ -1,0 +1,281 @@
+"""The device image cache filled from PNG files decoded on the device (``yogo train --device-image-cache GIB --device-image-decode``).
+
+``ImageCache.prefill`` PIL-decodes the resident set once in a one-off pool of DataLoader workers.  ``fill`` here takes its place:
+no worker processes, a pool of threads that only READ.  The N samples go in chunks of ``decode_batch``; per chunk the threads read
+and parse every file (yogo_amd/png.py), copy its IDAT payloads back to back -- one zlib stream per image -- into a pinned slot and
+parse the sample's label rows; then, on a side stream: the slot goes up, ONE ``yogo_inflate_zlib`` launch (csrc/inflate.hip, one
+wavefront per stream) inflates every image's scanlines, ONE ``yogo_png_unpack_planes`` launch (csrc/png_unpack_planes.hip) reverses
+the filters and writes the planes straight into ``images[lo:hi]``, and the per-image statuses come back.  Two pinned slots: chunk
+n + 1 is read while chunk n decodes.  The chunk is independent of the training batch, so thousands of streams share a launch.
+
+A slot is sized from the files' sizes, known by ``stat`` before anything is read (an IDAT payload is shorter than its file): every
+file has room at a multiple of ``ALIGN``, whatever the sizes of the files before it.
+
+What the device takes: 8-bit greyscale and 8-bit RGB, not interlaced, no tRNS, of exactly ``image_hw``; the kernel converts to the
+cache's channel count as ``read_image(path, rgb)`` does.  Everything else goes through ``ds.image_uint8(j)`` (PIL, its retries,
+``resize_image``) and enters the unpack launch as planar pixels (kind 1): other bit depths and colour types, interlace, tRNS, a
+file that is not a PNG under its name or does not parse, a file of another size than ``image_hw``, and a file whose inflate or unpack
+status is not 0.  If that returns None the sample is not made resident, exactly as on the host route.
+
+One divergence: a file that PIL rejects but this route accepts (a defect in a chunk that only PIL checks) is resident here and
+not on the host route, where it stays with the workers.  Files both accept give the same bytes.
+
+The scratch -- two pinned slots, the stored streams and the scanlines on the device -- lives only while ``fill`` runs and is NOT
+part of the cache budget: per chunk the files' bytes twice pinned, once on the device, and ``H * (1 + bpp * W)`` bytes of scanlines
+per image (``stats["scratch_device_bytes"]``, ``stats["scratch_pinned_bytes"]``).  torch's global RNG is not touched.
+"""
+from __future__ import annotations
+
+import os
+from concurrent.futures import ThreadPoolExecutor
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from yogo_amd import _hip, inflate, png
+from yogo_amd.zarr_feed import ALIGN, MAX_THREADS, inflate_streams
+
+# images per decode chunk, from tools/bench_prefill.py's sweep (profiles/prefill_decode.log: 772 x 1032 frames, three runs per size):
+# every run at 1 024 beat every run at 256 on the noise frames; against 2 048 and 4 096 the prefill times lie inside their scatter
+# (the host threads bound it) and the scratch decides: 1.45 GiB device + 1.38 GiB pinned at 1 024, 2.90 + 2.75 GiB at 2 048
+DEFAULT_DECODE_BATCH = 1024
+MAX_DECODE_BATCH = 65535
+KIND_GREY, KIND_PLANAR, KIND_RGB = 0, 1, 2
+SCAN_ALIGN = 16   # yogo_inflate_zlib asks for 16-byte aligned destinations
+
+
+def check_decode_batch(decode_batch: int) -> int:
+    n = int(decode_batch)
+    if not 1 <= n <= MAX_DECODE_BATCH:
+        raise ValueError(f"decode_batch {decode_batch} outside [1, {MAX_DECODE_BATCH}]")
+    return n
+
+
+def slot_layout(sizes: Sequence[int]) -> Tuple[np.ndarray, int]:
+    """file sizes -> (where each file's room starts in a slot, the bytes the chunk takes): room i holds ``sizes[i]`` bytes and
+    starts on a multiple of ALIGN, the rooms in order and without overlap"""
+    rooms = (np.asarray(sizes, dtype=np.int64).reshape(-1) + (ALIGN - 1)) // ALIGN * ALIGN
+    offsets = np.zeros(len(rooms), dtype=np.int64)
+    if len(rooms) > 1:
+        offsets[1:] = np.cumsum(rooms[:-1])
+    return offsets, int(rooms.sum())
+
+
+def png_unpack_planes(scan: torch.Tensor, table: torch.Tensor, image_hw: Tuple[int, int], out: torch.Tensor, status: torch.Tensor) -> torch.Tensor:
+    """One ``yogo_png_unpack_planes`` launch on the current stream.  scan: 1-D uint8 device tensor (written: the kernel unfilters one
+    row of every 64 in place); table: int64 [B, 2] device, rows (offset, kind); out: contiguous uint8 [B, C, H, W], C 1 or 3;
+    status: int32 [B].  The kernel holds every image to ``scan`` itself."""
+    for t, what in ((scan, "the scanlines"), (table, "the image table"), (out, "the unpack output"), (status, "the status")):
+        _hip.require_cuda(t, what)
+    H, W = (int(v) for v in image_hw)
+    if scan.dtype != torch.uint8 or scan.ndim != 1 or not scan.is_contiguous() or scan.numel() == 0:
+        raise ValueError(f"png_unpack_planes: scan must be a non-empty contiguous 1-D uint8 tensor, got {tuple(scan.shape)} {scan.dtype}")
+    if out.dtype != torch.uint8 or out.ndim != 4 or out.shape[1] not in (1, 3) or tuple(out.shape[2:]) != (H, W) or not out.is_contiguous():
+        raise ValueError(f"png_unpack_planes: out must be a contiguous uint8 [B, 1 or 3, {H}, {W}] tensor, got {tuple(out.shape)} {out.dtype}")
+    B, C = int(out.shape[0]), int(out.shape[1])
+    if table.dtype != torch.int64 or tuple(table.shape) != (B, 2) or not table.is_contiguous():
+        raise ValueError(f"png_unpack_planes: the table must be a contiguous int64 [{B}, 2] tensor, got {tuple(table.shape)} {table.dtype}")
+    if status.dtype != torch.int32 or tuple(status.shape) != (B,) or not status.is_contiguous():
+        raise ValueError(f"png_unpack_planes: the status must be a contiguous int32 [{B}] tensor, got {tuple(status.shape)} {status.dtype}")
+    if len({scan.device, table.device, out.device, status.device}) != 1:
+        raise ValueError("png_unpack_planes: the tensors live on different devices")
+    if B == 0:
+        return out
+    with torch.cuda.device(out.device):
+        _hip.call("yogo_png_unpack_planes", scan, scan.numel(), table, B, H, W, C, out, status, _hip.stream_ptr())
+    return out
+
+
+class _Sample:
+    """what one sample of a chunk turned out to be: a zlib stream for the device (``stored`` bytes at the start of its room, the
+    DEFLATE range and Adler-32 inside them, ``bpp`` bytes per pixel) or a sample for the host decoder (``host``: ``pixels`` is what
+    ``image_uint8`` gave, None when the file is unreadable).  ``rows``: the label rows, or the exception their parsing raised."""
+    __slots__ = ("host", "stored", "deflate", "adler", "bpp", "pixels", "rows")
+
+    def __init__(self):
+        self.host, self.stored, self.deflate, self.adler, self.bpp, self.pixels, self.rows = False, 0, (0, 0), 0, 1, None, None
+
+
+def _label_rows(ds, j: int):
+    try:
+        return ds.label_rows(j).reshape(-1, 5).to(torch.float32)
+    except Exception as e:   # raised when (and only if) the sample becomes resident, as on the host route
+        return e
+
+
+def _host_sample(s: _Sample, ds, j: int) -> _Sample:
+    s.host = True
+    s.pixels = ds.image_uint8(j)
+    if s.pixels is not None and s.rows is None:
+        s.rows = _label_rows(ds, j)
+    return s
+
+
+def _read(ds, j: int, room: np.ndarray, image_hw: Tuple[int, int]) -> _Sample:
+    """(pool thread) one sample: its file's zlib stream into ``room`` (its bytes of the pinned slot) and its label rows, or its
+    pixels from the host decoder"""
+    s = _Sample()
+    try:
+        with open(str(ds._image_paths[j]), "rb") as f:
+            data = f.read()
+        info = png.parse_png(data)
+    except (OSError, ValueError):   # unreadable, another format under its name (png.NotPng), a PNG that does not parse
+        return _host_sample(s, ds, j)
+    if not info.prefill_decodable or (info.height, info.width) != tuple(image_hw) or info.idat_bytes > len(room):
+        return _host_sample(s, ds, j)   # (longer than its room: the file grew after its size was taken)
+    at = 0
+    for o, n in info.idat:
+        room[at:at + n] = np.frombuffer(data, dtype=np.uint8, count=n, offset=o)
+        at += n
+    try:
+        off, ln, adler = inflate.split_zlib(room[:at])
+    except ValueError:
+        return _host_sample(s, ds, j)
+    s.stored, s.deflate, s.adler, s.bpp = at, (off, ln), adler, info.bytes_per_pixel
+    s.rows = _label_rows(ds, j)
+    return s
+
+
+def _file_size(path: str) -> int:
+    try:
+        return os.stat(path).st_size
+    except OSError:
+        return 0
+
+
+def fill(images: torch.Tensor, samples: Sequence[Tuple[object, int]], decode_batch: int = DEFAULT_DECODE_BATCH,
+         stats: Optional[Dict] = None) -> List[Optional[torch.Tensor]]:
+    """images[i] = the uint8 image of samples[i] = (ObjectDetectionDataset, index in it), what ``ds.image_uint8(index)`` gives, for
+    every sample that can be read.  images: contiguous uint8 [N, C, H, W] on an MI355X device (a view of the cache), C 1 or 3.
+    -> per sample its fp32 [n, 5] label rows, or None for a sample nothing could decode (its image is left as it was).  Returns after
+    the device has finished.  stats (optional dict) receives ``scratch_device_bytes``, ``scratch_pinned_bytes``, ``host_decoded`` and
+    per chunk the device-event times ``inflate_ms`` / ``unpack_ms``."""
+    _hip.require_cuda(images, "the image cache")
+    if images.dtype != torch.uint8 or images.ndim != 4 or images.shape[1] not in (1, 3) or not images.is_contiguous():
+        raise ValueError(f"fill: images must be a contiguous uint8 [N, 1 or 3, H, W] tensor, got {tuple(images.shape)} {images.dtype}")
+    N, C, H, W = (int(v) for v in images.shape)
+    if len(samples) != N:
+        raise ValueError(f"fill: {len(samples)} samples for {N} images")
+    decode_batch = check_decode_batch(decode_batch)
+    dev = images.device
+    out: List[Optional[torch.Tensor]] = [None] * N
+    if stats is not None:
+        stats.update(scratch_device_bytes=0, scratch_pinned_bytes=0, host_decoded=0, inflate_ms=[], unpack_ms=[])
+    if N == 0:
+        return out
+    chunks = [(lo, min(lo + decode_batch, N)) for lo in range(0, N, decode_batch)]
+    pool = ThreadPoolExecutor(max_workers=max(1, min(MAX_THREADS, os.cpu_count() or 1)), thread_name_prefix="png-prefill")
+    stager = ThreadPoolExecutor(max_workers=1, thread_name_prefix="png-prefill-stage")   # chunk n + 1 is read while n decodes
+    try:
+        sizes = list(pool.map(_file_size, [str(ds._image_paths[j]) for ds, j in samples]))
+        layouts = [slot_layout(sizes[lo:hi]) for lo, hi in chunks]
+        slot_bytes = max(1, max(total for _, total in layouts))
+        pinned = [torch.empty(slot_bytes, dtype=torch.uint8).pin_memory() for _ in range(min(2, len(chunks)))]
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        images.record_stream(side)
+
+        def stage(n: int) -> List[_Sample]:
+            (lo, hi), (offsets, _) = chunks[n], layouts[n]
+            host = pinned[n % 2].numpy()
+            futures = [pool.submit(_read, *samples[i], host[int(offsets[i - lo]):int(offsets[i - lo]) + sizes[i]], (H, W)) for i in range(lo, hi)]
+            return [f.result() for f in futures]
+
+        with torch.cuda.device(dev), torch.cuda.stream(side):
+            sdev = torch.empty(slot_bytes, dtype=torch.uint8, device=dev)
+            scan: Optional[torch.Tensor] = None
+            pending = stager.submit(stage, 0)
+            for n, (lo, hi) in enumerate(chunks):
+                chunk = pending.result()
+                if n + 1 < len(chunks):
+                    pending = stager.submit(stage, n + 1)
+                scan = _decode(chunk, samples[lo:hi], layouts[n], pinned[n % 2], sdev, scan, images[lo:hi], stats)
+                for i, s in enumerate(chunk):
+                    if s.host and s.pixels is None:
+                        continue
+                    if isinstance(s.rows, BaseException):
+                        raise s.rows
+                    out[lo + i] = s.rows
+            side.synchronize()
+        if stats is not None:
+            stats["scratch_device_bytes"] = slot_bytes + (scan.numel() if scan is not None else 0)
+            stats["scratch_pinned_bytes"] = slot_bytes * len(pinned)
+    finally:
+        stager.shutdown(wait=True)
+        pool.shutdown(wait=True)
+    return out
+
+
+def _decode(chunk: List[_Sample], samples, layout, pinned: torch.Tensor, sdev: torch.Tensor, scan: Optional[torch.Tensor],
+            out: torch.Tensor, stats: Optional[Dict]) -> torch.Tensor:
+    """one chunk on the current (side) stream: upload, inflate, unpack into ``out``, the statuses back; then whatever the device
+    refused through the host decoder.  -> the scanline buffer (grown when this chunk needed more)"""
+    offsets, _ = layout
+    B, C, H, W = (int(v) for v in out.shape)
+    dev = out.device
+    need = [C * H * W if s.host else H * (1 + s.bpp * W) for s in chunk]
+    at = np.zeros(B + 1, dtype=np.int64)
+    at[1:] = np.cumsum([-(-v // SCAN_ALIGN) * SCAN_ALIGN for v in need])
+    if scan is None or scan.numel() < int(at[B]):
+        scan = None   # (the smaller buffer goes back to the allocator first)
+        scan = torch.empty(int(at[B]), dtype=torch.uint8, device=dev)
+    device_rows = [i for i, s in enumerate(chunk) if not s.host]
+    kept = [i for i, s in enumerate(chunk) if not (s.host and s.pixels is None)]
+    if not kept:
+        return scan
+    timed = stats is not None
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timed else None
+    inflate_status = None
+    if device_rows:
+        last = device_rows[-1]
+        used = int(offsets[last]) + chunk[last].stored
+        sdev[:used].copy_(pinned[:used], non_blocking=True)
+        rows = np.asarray([(int(offsets[i]) + chunk[i].deflate[0], chunk[i].deflate[1], int(at[i]), need[i], chunk[i].adler)
+                           for i in device_rows], dtype=np.int64).reshape(-1, 5)
+        inflate_status = torch.empty(len(device_rows), dtype=torch.int32, device=dev)
+        if timed:
+            ev[0].record()
+        inflate_streams(sdev, torch.from_numpy(rows).to(dev), scan, inflate_status)
+        if timed:
+            ev[1].record()
+    for i, s in enumerate(chunk):
+        if s.host and s.pixels is not None:   # (rare: a pageable copy per image)
+            if tuple(s.pixels.shape) != (C, H, W):
+                raise ValueError(f"fill: {samples[i][0]._image_paths[samples[i][1]]} decodes to {tuple(s.pixels.shape)}, the cache holds {(C, H, W)}")
+            scan[int(at[i]):int(at[i]) + need[i]].copy_(s.pixels.contiguous().reshape(-1))
+    # a sample nothing could decode keeps its place in the launch as an entry the kernel refuses before it reads anything
+    table = np.asarray([(int(at[i]), -1 if (s.host and s.pixels is None) else KIND_PLANAR if s.host else KIND_RGB if s.bpp == 3 else KIND_GREY)
+                        for i, s in enumerate(chunk)], dtype=np.int64).reshape(-1, 2)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    table_dev = torch.from_numpy(table).to(dev)
+    if timed:
+        ev[2].record()
+    png_unpack_planes(scan, table_dev, (H, W), out, status)
+    if timed:
+        ev[3].record()
+    bad = status.cpu().numpy().copy()   # waits for the launches
+    if inflate_status is not None:
+        bad[np.asarray(device_rows)[inflate_status.cpu().numpy() != 0]] = 1
+    if timed:
+        if device_rows:
+            stats["inflate_ms"].append(ev[0].elapsed_time(ev[1]))
+        stats["unpack_ms"].append(ev[2].elapsed_time(ev[3]))
+        stats["host_decoded"] += sum(1 for s in chunk if s.host)
+    # what the device refused: the host decoder's turn (the kernel may have written part of the image: it is overwritten or,
+    # where the host cannot read the file either, not resident)
+    for i in device_rows:
+        if not bad[i]:
+            continue
+        s = _host_sample(chunk[i], *samples[i])
+        if timed:
+            stats["host_decoded"] += 1
+        if s.pixels is None:
+            continue
+        px = s.pixels.contiguous().reshape(-1).to(dev)
+        one = torch.tensor([[0, KIND_PLANAR]], dtype=torch.int64).to(dev)
+        st = torch.empty(1, dtype=torch.int32, device=dev)
+        png_unpack_planes(px, one, (H, W), out[i:i + 1], st)
+        if int(st.cpu()[0]) != 0:
+            raise RuntimeError(f"yogo_amd: the host-decoded image of {samples[i][0]._image_paths[samples[i][1]]} was refused by the unpack kernel")
+    return scan

@@ -72,9 +72,32 @@ class SplitFractionsAction(argparse.Action):
             parser.error(str(e))
 
 
+class CheckedParser(argparse.ArgumentParser):
+    """ArgumentParser that, after parsing, runs the checks registered on it (``checks``: namespace -> an error message or None):
+    the place for a condition that spans two flags of one sub-command.  A parser runs its own checks only."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.checks = []
+
+    def parse_known_args(self, args=None, namespace=None):
+        ns, rest = super().parse_known_args(args, namespace)
+        for check in self.checks:
+            message = check(ns)
+            if message:
+                self.error(message)
+        return ns, rest
+
+
+def _decode_needs_cache(ns):
+    if ns.device_image_decode and ns.device_image_cache is None:
+        return "--device-image-decode fills the device image cache: it needs --device-image-cache GIB"
+    return None
+
+
 def global_parser():
     parser = argparse.ArgumentParser(description="what can yogo do for you today?", allow_abbrev=False)
-    sub = parser.add_subparsers(help="here is what you can do", dest="task")
+    sub = parser.add_subparsers(help="here is what you can do", dest="task", parser_class=CheckedParser)
     train_parser(parser=sub.add_parser("train", help="train a model", allow_abbrev=False))
     test_parser(parser=sub.add_parser("test", help="test a model", allow_abbrev=False))
     export_parser(parser=sub.add_parser("export", help="export a model", allow_abbrev=False))
@@ -87,7 +110,7 @@ def train_parser(parser=None):
     from yogo_amd.utils.default_hyperparams import DefaultHyperparams as df
 
     if parser is None:
-        parser = argparse.ArgumentParser(description="commence a training run", allow_abbrev=False)
+        parser = CheckedParser(description="commence a training run", allow_abbrev=False)
     parser.add_argument("dataset_descriptor_file", type=str, help="path to yml dataset descriptor file")
     parser.add_argument("--from-pretrained", type=Path, help="start training from the provided pth file", default=None)
     parser.add_argument("--dataset-split-override", action=SplitFractionsAction, nargs=3,
@@ -113,6 +136,11 @@ def train_parser(parser=None):
     parser.add_argument("--device-image-cache", default=None, type=positive_gib, metavar="GIB",
                         help="keep decoded images resident in GPU memory within this many GiB per rank: the train split first, the val "
                              "split gets what is left (default: off)")
+    parser.add_argument("--device-image-decode", default=False, action=boolean_action,
+                        help="with --device-image-cache: fill the cache from PNG files inflated and unfiltered on the GPU (8-bit greyscale "
+                             "and RGB) instead of a pool of PIL workers; other files are decoded on the host; same batches.  Its scratch "
+                             "memory (pinned staging, stored streams, scanlines) is freed after the prefill and is not counted in the "
+                             "GIB budget (default: False)")
     parser.add_argument("--device-metrics", default=False, action=boolean_action,
                         help="match predictions to labels and accumulate the test metrics on the GPU instead of per image on the host; "
                              "same results (default: False)")
@@ -122,6 +150,7 @@ def train_parser(parser=None):
     parser.add_argument("--tags", default=None, type=str, nargs="*", help="tags for the run (e.g. '--tags test fine-tune')")
     parser.add_argument("--wandb-entity", type=str, default=os.getenv("wandb_entity"), help="wandb entity - defaults to the environment variable wandb_entity")
     parser.add_argument("--wandb-project", type=str, default=os.getenv("wandb_project"), help="wandb project name - defaults to the environment variable wandb_project")
+    parser.checks.append(_decode_needs_cache)
     return parser
 
 
