@@ -452,7 +452,7 @@ int yogo_zarr_unpack(const unsigned char* staged, long long staged_bytes, const 
                      int gw, int ch, int cw, int cn, int order_f, int fill, int H, int W, int top, int left, int OH, int OW, void* out,
                      int out_fp32, yogo_stream_t stream);
 /* The blocks of Blosc-compressed chunks (zarr's default compressor), decoded on the device in front of yogo_zarr_unpack
- * (yogo_amd/blosc.py parses the chunk headers on the host).  src: src_bytes of device memory holding stored chunks as they came off
+ * (yogo_amd/blosc.py parses the chunk headers on the host; launched from yogo_amd/device_decode.py, as yogo_inflate_zlib is).  src: src_bytes of device memory holding stored chunks as they came off
  * the disk; table: [n][5] int64 device, one row { src_off, src_len, dst_off, dst_len, raw } per block: the block's bytes in src, where
  * its decoded bytes belong in dst (dst_bytes of device memory, 16-byte aligned, not overlapping src: the `staged` of
  * yogo_zarr_unpack), and whether they are copied (raw != 0, src_len == dst_len) or one LZ4 block.  One wavefront per row.
@@ -487,7 +487,8 @@ int yogo_inflate_zlib(const unsigned char* src, long long src_bytes, const long 
  * x / 255 bit-identical to torch's CPU uint8_tensor / 255 (out_fp32 = 1): out[b][0][oy][ox] = image_b[top + oy][left + ox],
  * 1 <= OH <= H - top, 1 <= OW <= W - left.  status: [B] int32 device, per image 0, 1 (a filter-type byte above 4: its rows from
  * that band on are not written) or 2 (the image does not lie inside scan: nothing of it is read).  One wavefront per image,
- * 64 rows at a time, skewed by one pixel per row.  B <= 65535, H, W <= 65535. */
+ * 64 rows at a time, skewed by one pixel per row (csrc/png_unfilter.h: the loop yogo_png_unpack_planes runs too; the launch wrappers
+ * of both are in yogo_amd/device_decode.py).  B <= 65535, H, W <= 65535. */
 int yogo_png_unpack(unsigned char* scan, long long scan_bytes, const long long* table, int B, int H, int W, int top, int left, int OH,
                     int OW, void* out, int out_fp32, int* status, yogo_stream_t stream);
 
@@ -501,8 +502,8 @@ int yogo_png_unpack(unsigned char* scan, long long scan_bytes, const long long* 
  * L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16.  scan is WRITTEN as by yogo_png_unpack (the last row of every band of 64).
  * status: [B] int32 device, per image 0, 1 (a filter-type byte above 4: its rows from that band on are not written) or 2 (a kind
  * outside 0 .. 2, or the image does not lie inside scan: nothing of it is read).  One wavefront per image, 64 rows at a time,
- * skewed by one pixel per row, a 3-byte pixel in one register.  For kind 0 and C_out = 1 the output is yogo_png_unpack's, bit for
- * bit.  B <= 65535, H, W <= 65535. */
+ * skewed by one pixel per row, a 3-byte pixel in one register: csrc/png_unfilter.h's loop, so for kind 0 and C_out = 1 the output
+ * is yogo_png_unpack's, bit for bit.  B <= 65535, H, W <= 65535. */
 int yogo_png_unpack_planes(unsigned char* scan, long long scan_bytes, const long long* table, int B, int H, int W, int C_out,
                            unsigned char* out, int* status, yogo_stream_t stream);
 

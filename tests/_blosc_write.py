@@ -186,7 +186,7 @@ def decode_on_device(entries):
     import numpy as np
     import torch
 
-    from yogo_amd.zarr_feed import decode_blocks
+    from yogo_amd.device_decode import decode_blocks
 
     rows, src, spos, dpos = [], bytearray(), 0, 16
     for i, (data, dst_len, raw) in enumerate(entries):

@@ -440,7 +440,7 @@ def inflate_on_device(entries):
     import numpy as np
     import torch
 
-    from yogo_amd.zarr_feed import inflate_streams
+    from yogo_amd.device_decode import inflate_streams
 
     rows, src, dpos = [], bytearray(), 16
     for i, (data, dst_len, adler) in enumerate(entries):

@@ -1,8 +1,11 @@
 """A small PNG writer for the tests, after the PNG specification (nothing but numpy and the standard library): a file from given
 pixel rows with a chosen filter type per row, any split of the zlib stream over IDAT chunks, any IHDR fields and ancillary chunks
-before and after the IDAT chunks; `filter_rows` / `unfilter_rows` are numpy restatements of the five filters at one byte per pixel.
+before and after the IDAT chunks; 8-bit greyscale from an [H, W] image, 8-bit RGB from an [H, W, 3] one.  `filter_rows` is the numpy
+restatement of the five filters at 1 or 3 bytes per pixel -- they act on BYTES: the byte to the left of a byte is the one ``bpp``
+bytes before it, the same channel of the pixel to the left -- and `unfilter_rows` their reverse at one byte per pixel.
 
-The decoders under test (yogo_amd/png.py, csrc/png_unpack.hip) and this writer share an author; PIL reads the files it writes."""
+The decoders under test (yogo_amd/png.py, csrc/png_unfilter.h behind csrc/png_unpack.hip and csrc/png_unpack_planes.hip) and this
+writer share an author; PIL reads the files it writes (tests/test_png_host.py, tests/test_png_write_planes.py)."""
 import struct
 import zlib
 
@@ -21,18 +24,28 @@ def paeth(a, b, c):
     return np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, b, c))
 
 
-def filter_rows(img, types):
-    """uint8 [H, W] pixels -> uint8 [H, 1 + W] scanlines, row y under filter types[y] (0 .. 4), one byte per pixel"""
+def _as_rows(img):
+    """uint8 [H, W] or [H, W, 3] -> (uint8 [H, W * bpp] row bytes, bpp)"""
     img = np.asarray(img, dtype=np.uint8)
-    H, W = img.shape
-    out = np.zeros((H, 1 + W), dtype=np.uint8)
+    if img.ndim == 2:
+        return img, 1
+    if img.ndim == 3 and img.shape[2] == 3:
+        return img.reshape(img.shape[0], -1), 3
+    raise ValueError(f"an [H, W] or [H, W, 3] image is expected, got {img.shape}")
+
+
+def filter_rows(img, types):
+    """uint8 [H, W] / [H, W, 3] pixels -> uint8 [H, 1 + W * bpp] scanlines, row y under filter types[y] (0 .. 4)"""
+    rows, bpp = _as_rows(img)
+    H, n = rows.shape
+    out = np.zeros((H, 1 + n), dtype=np.uint8)
     for y in range(H):
-        cur = img[y].astype(np.int64)
-        up = img[y - 1].astype(np.int64) if y else np.zeros(W, np.int64)
-        left = np.concatenate(([0], cur[:-1]))
-        upleft = np.concatenate(([0], up[:-1]))
+        cur = rows[y].astype(np.int64)
+        up = rows[y - 1].astype(np.int64) if y else np.zeros(n, np.int64)
+        left = np.concatenate((np.zeros(bpp, np.int64), cur[:-bpp]))[:n]
+        upleft = np.concatenate((np.zeros(bpp, np.int64), up[:-bpp]))[:n]
         t = int(types[y])
-        pred = {0: np.zeros(W, np.int64), 1: left, 2: up, 3: (left + up) // 2, 4: paeth(left, up, upleft)}[t]
+        pred = {0: np.zeros(n, np.int64), 1: left, 2: up, 3: (left + up) // 2, 4: paeth(left, up, upleft)}[t]
         out[y, 0] = t
         out[y, 1:] = (cur - pred) & 255
     return out
@@ -74,13 +87,13 @@ def adam7_scan(img):
 
 
 def png_bytes(img, types=None, *, idat_sizes=None, level=6, ihdr=None, before=(), after=(), scan=None, stream=None):
-    """One file.  img: uint8 [H, W]; types: filter type per row (default 0); idat_sizes: lengths of the IDAT payloads (the last
+    """One file.  img: uint8 [H, W] (colour type 0) or [H, W, 3] (colour type 2); types: filter type per row (default 0); idat_sizes: lengths of the IDAT payloads (the last
     chunk takes the rest; default one chunk); ihdr: (width, height, bit depth, colour type, compression, filter, interlace) when
     it is to differ from the image; before / after: ancillary chunks [(type, data)] between IHDR and the first IDAT / between the
     last IDAT and IEND (IDAT chunks are consecutive by the specification); scan: the scanline bytes to compress instead of the
     filtered image; stream: the zlib stream itself."""
-    img = np.asarray(img, dtype=np.uint8)
-    H, W = img.shape
+    rows, bpp = _as_rows(img)
+    H, W = rows.shape[0], rows.shape[1] // bpp
     scan = filter_rows(img, [0] * H if types is None else types).tobytes() if scan is None else scan
     z = zlib.compress(scan, level) if stream is None else stream
     parts, at = [], 0
@@ -88,6 +101,6 @@ def png_bytes(img, types=None, *, idat_sizes=None, level=6, ihdr=None, before=()
         parts.append(z[at:at + n])
         at += n
     parts.append(z[at:])
-    out = SIGNATURE + chunk(b"IHDR", struct.pack(">IIBBBBB", *(ihdr or (W, H, 8, 0, 0, 0, 0))))
+    out = SIGNATURE + chunk(b"IHDR", struct.pack(">IIBBBBB", *(ihdr or (W, H, 8, 0 if bpp == 1 else 2, 0, 0, 0))))
     out += b"".join(chunk(*c) for c in before) + b"".join(chunk(b"IDAT", p) for p in parts) + b"".join(chunk(*c) for c in after)
     return out + chunk(b"IEND", b"")

@@ -7,7 +7,6 @@ import numpy as np
 import pytest
 
 from _png_write import chunk, png_bytes
-from _png_write_planes import png_planes_bytes
 
 
 def test_train_parser_stores_the_flag():
@@ -60,16 +59,16 @@ def test_trns_is_not_prefill_decodable():
     from yogo_amd import png
 
     rgb = np.zeros((3, 4, 3), np.uint8)
-    assert png.parse_png(png_planes_bytes(rgb)).prefill_decodable is True
-    assert png.parse_png(png_planes_bytes(rgb, before=[(b"tRNS", struct.pack(">HHH", 1, 2, 3))])).prefill_decodable is False
-    assert png.parse_png(png_planes_bytes(rgb[..., 0], before=[(b"tRNS", struct.pack(">H", 7))])).prefill_decodable is False
-    assert png.parse_png(png_planes_bytes(rgb, before=[(b"gAMA", struct.pack(">I", 45455))])).prefill_decodable is True
-    assert chunk(b"IEND", b"")[-4:] == png_planes_bytes(rgb)[-4:]
+    assert png.parse_png(png_bytes(rgb)).prefill_decodable is True
+    assert png.parse_png(png_bytes(rgb, before=[(b"tRNS", struct.pack(">HHH", 1, 2, 3))])).prefill_decodable is False
+    assert png.parse_png(png_bytes(rgb[..., 0], before=[(b"tRNS", struct.pack(">H", 7))])).prefill_decodable is False
+    assert png.parse_png(png_bytes(rgb, before=[(b"gAMA", struct.pack(">I", 45455))])).prefill_decodable is True
+    assert chunk(b"IEND", b"")[-4:] == png_bytes(rgb)[-4:]
 
 
 def test_slot_layout_packs_without_overlap_at_align():
     from yogo_amd.png_prefill import slot_layout
-    from yogo_amd.zarr_feed import ALIGN
+    from yogo_amd.device_decode import ALIGN
 
     rng = np.random.default_rng(2)
     for sizes in ([1], [0, 5, 0], [ALIGN, ALIGN + 1, ALIGN - 1], list(rng.integers(0, 900_000, size=300)), [900_000, 10, 2_000_000, 3]):

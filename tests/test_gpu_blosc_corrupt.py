@@ -35,7 +35,7 @@ def test_one_defect_ends_in_its_status(defect, code):
 def test_rows_outside_the_buffers_are_refused_before_any_access():
     import torch
 
-    from yogo_amd.zarr_feed import decode_blocks
+    from yogo_amd.device_decode import decode_blocks
 
     src = torch.full((64,), 7, dtype=torch.uint8, device="cuda")
     dst = torch.full((96,), BW.CANARY, dtype=torch.uint8, device="cuda")

@@ -114,7 +114,7 @@ def test_300_entries_in_one_launch():
 def test_entry_point_refuses_bad_arguments():
     import torch
 
-    from yogo_amd.zarr_feed import decode_blocks
+    from yogo_amd.device_decode import decode_blocks
 
     src = torch.zeros(64, dtype=torch.uint8, device="cuda")
     dst = torch.zeros(80, dtype=torch.uint8, device="cuda")

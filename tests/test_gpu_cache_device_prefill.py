@@ -18,7 +18,6 @@ import torch
 
 from _image_cache_data import write_defn
 from _png_write import adam7_scan, png_bytes
-from _png_write_planes import png_planes_bytes
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
@@ -48,11 +47,11 @@ def _dataset(root: Path):
         return [int(t) for t in rng.integers(0, 5, size=H)]
 
     files = [
-        png_planes_bytes(grey(), mixed()),
-        png_planes_bytes(rgb(), mixed(), idat_sizes=[100, 333]),
-        png_planes_bytes(grey(), mixed(), idat_sizes=[1, 2, 3]),
-        png_planes_bytes(rgb(), mixed()),
-        png_planes_bytes(grey(), [4] * H, level=0),
+        png_bytes(grey(), mixed()),
+        png_bytes(rgb(), mixed(), idat_sizes=[100, 333]),
+        png_bytes(grey(), mixed(), idat_sizes=[1, 2, 3]),
+        png_bytes(rgb(), mixed()),
+        png_bytes(grey(), [4] * H, level=0),
     ]
     lace = grey()
     files.append(png_bytes(lace, scan=adam7_scan(lace), ihdr=(W, H, 8, 0, 0, 0, 1)))                      # interlaced
@@ -60,9 +59,9 @@ def _dataset(root: Path):
         (img_dir / f"img_{k:04d}.png").write_bytes(data)
     Image.fromarray(rng.integers(0, 65536, size=HW, dtype=np.uint16)).save(img_dir / "img_0006.png")       # 16-bit
     Image.fromarray(grey()).convert("P").save(img_dir / "img_0007.png")                                    # palette
-    (img_dir / "img_0008.png").write_bytes(png_planes_bytes(grey((35, 20)), [int(t) for t in rng.integers(0, 5, size=35)]))   # resized
+    (img_dir / "img_0008.png").write_bytes(png_bytes(grey((35, 20)), [int(t) for t in rng.integers(0, 5, size=35)]))   # resized
     Image.fromarray(rgb()).save(img_dir / "img_0009.png", format="JPEG")                                   # a JPEG under a .png name
-    whole = png_planes_bytes(grey(), mixed())
+    whole = png_bytes(grey(), mixed())
     (img_dir / "img_0010.png").write_bytes(whole[:len(whole) // 2])                                        # truncated
     for k in range(N):
         m = (0, 1, 4, 2, 0, 3, 1, 5, 2, 1, 3)[k]

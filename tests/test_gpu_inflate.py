@@ -89,7 +89,7 @@ def test_defective_streams():
 def test_rows_outside_the_buffers():
     import torch
 
-    from yogo_amd.zarr_feed import inflate_streams
+    from yogo_amd.device_decode import inflate_streams
 
     raw, data = DW.CASES["fixed-len3"]
     src = torch.frombuffer(bytearray(raw + bytes(16)), dtype=torch.uint8).cuda()
@@ -109,7 +109,7 @@ def test_rows_outside_the_buffers():
 def test_entry_point_refuses_bad_arguments():
     import torch
 
-    from yogo_amd.zarr_feed import inflate_streams
+    from yogo_amd.device_decode import inflate_streams
 
     src = torch.zeros(64, dtype=torch.uint8, device="cuda")
     dst = torch.zeros(80, dtype=torch.uint8, device="cuda")

@@ -18,8 +18,7 @@ CLASSES = ["you", "only", "glance", "once"]
 
 def _unpack(scans, raws, H, W, crop=None, fp32=False, flags=None):
     """one launch over the images `scans` (uint8 [H, 1 + W] scanlines, or [H, W] pixels where raws[i]) -> (batch on the host, status)"""
-    from yogo_amd.png_feed import png_unpack
-    from yogo_amd.zarr_feed import center_crop_origin
+    from yogo_amd.device_decode import center_crop_origin, png_unpack
 
     buf, table = bytearray(b"\xEE" * 16), []
     for s, raw in zip(scans, raws):
@@ -73,7 +72,7 @@ def test_unpack_centre_crop(H, W, crop):
 
 
 def test_unpack_bad_filter_byte_and_bad_image():
-    from yogo_amd.png_feed import png_unpack
+    from yogo_amd.device_decode import png_unpack
 
     H, W = 70, 20
     imgs = [_image(H, W, s) for s in range(3)]

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from _png_write_planes import filter_rows_bpp, png_planes_bytes
+from _png_write import filter_rows, png_bytes
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
@@ -47,7 +47,7 @@ def _pack(blobs):
 
 
 def _launch(scan_np, table, hw, C, B, fill=0xA5):
-    from yogo_amd.png_prefill import png_unpack_planes
+    from yogo_amd.device_decode import png_unpack_planes
 
     scan = torch.from_numpy(scan_np.copy()).to(DEV)   # (the kernel writes into the scanlines: every launch has its own)
     out = torch.full((B, C, *hw), fill, dtype=torch.uint8, device=DEV)
@@ -61,16 +61,16 @@ def _launch(scan_np, table, hw, C, B, fill=0xA5):
 @pytest.mark.parametrize("W", WS)
 @pytest.mark.parametrize("H", HS)
 def test_planes_equal_read_image(tmp_path, H, W, C):
-    from yogo_amd.png_feed import png_unpack
+    from yogo_amd.device_decode import png_unpack
     from yogo_amd.yogo_dataset import read_image
 
     images = _images(H, W)
     want, blobs, kinds = [], [], []
     for name, px, types in images:
         p = tmp_path / f"{name}.png"
-        p.write_bytes(png_planes_bytes(px, types))
+        p.write_bytes(png_bytes(px, types))
         want.append(read_image(p, rgb=C == 3))
-        blobs.append(filter_rows_bpp(px, types).tobytes())
+        blobs.append(filter_rows(px, types).tobytes())
         kinds.append(2 if px.ndim == 3 else 0)
     planar = np.random.default_rng(7).integers(0, 256, size=(C, H, W), dtype=np.uint8)   # an image the host decoded
     want.append(torch.from_numpy(planar))
@@ -98,7 +98,7 @@ def test_filter_byte_above_4_is_that_images_status(bad, C):
     grey = rng.integers(0, 256, size=(H, W), dtype=np.uint8)
     rgb = rng.integers(0, 256, size=(H, W, 3), dtype=np.uint8)
     types = [int(t) for t in rng.integers(0, 5, size=H)]
-    blobs = [filter_rows_bpp(grey, types), filter_rows_bpp(rgb, types), filter_rows_bpp(grey, types), filter_rows_bpp(rgb, types)]
+    blobs = [filter_rows(grey, types), filter_rows(rgb, types), filter_rows(grey, types), filter_rows(rgb, types)]
     victim = 2 if bad == "grey" else 1
     blobs[victim] = blobs[victim].copy()
     blobs[victim][70, 0] = 5   # in the second band: the first band's rows are still written
@@ -122,7 +122,7 @@ def test_an_image_outside_the_scanlines_is_status_2(C):
     grey = rng.integers(0, 256, size=(H, W), dtype=np.uint8)
     rgb = rng.integers(0, 256, size=(H, W, 3), dtype=np.uint8)
     types = [int(t) for t in rng.integers(0, 5, size=H)]
-    scan, offs = _pack([filter_rows_bpp(grey, types).tobytes(), filter_rows_bpp(rgb, types).tobytes()])
+    scan, offs = _pack([filter_rows(grey, types).tobytes(), filter_rows(rgb, types).tobytes()])
     n = len(scan)
     # past the end, ending one byte after the end (an RGB image at the grey one's distance from the end), negative, an unknown kind
     table = [(offs[0], 0), (n + 4096, 0), (offs[1], 2), (n - H * (W + 1), 2), (-16, 1), (offs[0], 3), (n - H * (W + 1) + 1, 0)]
@@ -145,7 +145,7 @@ def test_rgb_to_one_plane_is_pils_luma(tmp_path):
     H, W = 65, 65 * 65
     img = lattice.reshape(H, W, 3)
     p = tmp_path / "lattice.png"
-    p.write_bytes(png_planes_bytes(img))
-    scan, offs = _pack([filter_rows_bpp(img, [0] * H).tobytes()])
+    p.write_bytes(png_bytes(img))
+    scan, offs = _pack([filter_rows(img, [0] * H).tobytes()])
     out, status = _launch(scan, [(offs[0], 2)], (H, W), 1, 1)
     assert status.tolist() == [0] and torch.equal(out[0], read_image(p, rgb=False))

@@ -19,7 +19,8 @@ def _unpack_case(tmp_path, shape, chunks, order, idxs, crop=None, skip=()):
     """write the stack, stage what frames `idxs` (consecutive) need as the feed does, unpack in both dtypes ->
     ({dtype: device result}, {dtype: expectation}, launch log lines)"""
     from yogo_amd import _hip
-    from yogo_amd.zarr_feed import ChunkStager, FrameSource, center_crop_origin, plan_batch, unpack
+    from yogo_amd.device_decode import center_crop_origin
+    from yogo_amd.zarr_feed import ChunkStager, FrameSource, plan_batch, unpack
 
     H, W, N = shape
     stack = np.random.default_rng(sum(shape) + sum(chunks)).integers(0, 256, size=shape, dtype=np.uint8)

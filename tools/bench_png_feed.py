@@ -106,10 +106,9 @@ def step_kernels(d: str) -> dict:
     import torch
 
     from yogo_amd import inflate, png
+    from yogo_amd.device_decode import inflate_streams, png_unpack
     from yogo_amd.image_path_dataset import ImagePathDataset
-    from yogo_amd.png_feed import png_unpack
     from yogo_amd.yogo_dataset import read_image
-    from yogo_amd.zarr_feed import inflate_streams
 
     paths = [str(p) for p in ImagePathDataset(d).image_paths[:B]]
     stored, rows, table = bytearray(), [], []

@@ -176,7 +176,8 @@ def step_decode(store: str, n: int) -> dict:
     """yogo_blosc_lz4_decode (a zlib store: yogo_inflate_zlib) alone on the rows of the first batch"""
     import torch
 
-    from yogo_amd.zarr_feed import ChunkStager, FrameSource, decode_blocks, inflate_streams, plan_batch
+    from yogo_amd.device_decode import decode_blocks, inflate_streams
+    from yogo_amd.zarr_feed import ChunkStager, FrameSource, plan_batch
     from yogo_amd.zarr_store import open_zarr
 
     src = FrameSource(open_zarr(store))
@@ -214,7 +215,8 @@ def step_kernel() -> list:
     import torch
 
     from yogo_amd import _hip
-    from yogo_amd.zarr_feed import ALIGN, unpack
+    from yogo_amd.device_decode import ALIGN
+    from yogo_amd.zarr_feed import unpack
 
     out = []
     g = torch.Generator(device="cuda").manual_seed(0)

@@ -6,22 +6,13 @@
 // uint8_tensor / 255: build.sh compiles with correctly rounded division), out[b][0][oy][ox] = image_b[top + oy][left + ox].
 // status[b] = 0, 1 (a filter-type byte above 4) or 2 (the image does not lie inside scan: nothing of it was read).
 //
-// Filters (bytes per pixel = 1, the row above row 0 is zeros, arithmetic mod 256): 0 None, 1 Sub (+ left), 2 Up (+ above),
-// 3 Average (+ floor((left + above) / 2)), 4 Paeth (+ whichever of left, above, upper-left is nearest left + above - upper-left,
-// ties in that order).  Sub, Average and Paeth are serial along a row, Up, Average and Paeth need the row above: one wavefront
-// per image takes 64 consecutive rows at a time, lane r on row r, skewed by one pixel per row -- at step t lane r makes pixel
-// t - r of its row, so that the pixel above it is what lane r - 1 made one step earlier (one DPP-style shuffle) and the
-// upper-left one is what that shuffle brought the step before.  Every mix of filter types keeps the 64 lanes busy; a band of 64
-// rows costs W + 63 steps.  Lane 0's row above is the last row of the band before: lane 63 writes its unfiltered pixels back to
-// `scan` IN PLACE (only that row of each band is written back; `scan` is not left whole), and the wave reads them 64 at a time.
-// __syncthreads() between two bands orders those stores before the loads, as in blosc_lz4.hip.  The filtered bytes of a row are
-// fetched four pixels per lane at a time, one fetch ahead of their use.
-#include "common.h"
+// The filters are reversed by csrc/png_unfilter.h's loop at one byte per pixel (one wavefront per image, 64 rows at a time; `scan` is
+// WRITTEN: the last row of every band of 64 is unfiltered in place); this file says where a pixel goes: crop and put.
+#include "png_unfilter.h"
 
 namespace {
 
-constexpr int WAVE = 64;
-enum : int { ST_OK = 0, ST_BAD_FILTER = 1, ST_BAD_IMAGE = 2 };
+using namespace yogo_png;
 
 template <bool FP32>
 __device__ __forceinline__ void put(void* out, long long i, unsigned v) {
@@ -29,18 +20,22 @@ __device__ __forceinline__ void put(void* out, long long i, unsigned v) {
   else static_cast<unsigned char*>(out)[i] = (unsigned char)v;
 }
 
-// pixels x0 .. x0 + 3 of the row at p (W bytes), one per byte of the result; zero outside the row
-__device__ __forceinline__ unsigned fetch4(const unsigned char* p, int x0, int W, bool active) {
-  unsigned w = 0;
-  if (!active || x0 >= W || x0 + 3 < 0) return 0;
-  if (x0 >= 0 && x0 + 4 <= W) {
-    __builtin_memcpy(&w, p + x0, 4);
-  } else {
-    for (int k = 0; k < 4; ++k)
-      if (x0 + k >= 0 && x0 + k < W) w |= (unsigned)p[x0 + k] << (8 * k);
+// a pixel of the image into the crop: out[oy][ox] = image[top + oy][left + ox]
+template <bool FP32>
+struct CropSink {
+  void* out;
+  long long obase;
+  int top, left, OH, OW, oy;
+  bool row_out;
+  __device__ __forceinline__ void row(int y, bool active) {
+    oy = y - top;
+    row_out = active && oy >= 0 && oy < OH;
   }
-  return w;
-}
+  __device__ __forceinline__ void pixel(int x, unsigned v) const {
+    const int ox = x - left;
+    if (row_out && ox >= 0 && ox < OW) put<FP32>(out, obase + (long long)oy * OW + ox, v);
+  }
+};
 
 template <bool FP32>
 __global__ __launch_bounds__(WAVE) void png_unpack_kernel(unsigned char* scan, long long scan_bytes, const long long* __restrict__ table,
@@ -63,54 +58,7 @@ __global__ __launch_bounds__(WAVE) void png_unpack_kernel(unsigned char* scan, l
     if (lane == 0) status[b] = ST_OK;
     return;
   }
-  const int stride = W + 1;
-  int st = ST_OK;
-  for (int band = 0; band < H; band += WAVE) {
-    const int y = band + lane;
-    const bool active = y < H;
-    unsigned char* rowp = scan + off + (long long)(active ? y : 0) * stride + 1;
-    const int ft = active ? rowp[-1] : 0;
-    if (__ballot(ft > 4)) {
-      st = ST_BAD_FILTER;
-      break;
-    }
-    const unsigned char* abovep = band ? scan + off + (long long)(band - 1) * stride + 1 : nullptr;
-    const int oy = y - top;
-    const bool row_out = active && oy >= 0 && oy < OH;
-    unsigned cur = 0, upleft = 0, abv = 0;   // what this lane made last step; what the shuffle brought last step; lane 0's row above
-    unsigned next = fetch4(rowp, -lane, W, active);
-    for (int t0 = 0; t0 < W + WAVE - 1; t0 += 4) {
-      if ((t0 & (WAVE - 1)) == 0) abv = abovep && t0 + lane < W ? abovep[t0 + lane] : 0u;
-      const unsigned w = next;
-      next = fetch4(rowp, t0 + 4 - lane, W, active);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int t = t0 + k, x = t - lane;
-        unsigned up = (unsigned)__shfl_up((int)cur, 1);
-        const unsigned first_up = (unsigned)__builtin_amdgcn_readlane((int)abv, t & (WAVE - 1));
-        if (lane == 0) up = first_up;
-        const bool valid = active && x >= 0 && x < W;
-        const int a = (int)cur, bb = (int)up, c = (int)upleft;
-        int pred = 0;
-        if (ft == 1) pred = a;
-        else if (ft == 2) pred = bb;
-        else if (ft == 3) pred = (a + bb) >> 1;
-        else if (ft == 4) {
-          const int pa = abs(bb - c), pb = abs(a - c), pc = abs(a + bb - 2 * c);
-          pred = (pa <= pb && pa <= pc) ? a : (pb <= pc ? bb : c);
-        }
-        const unsigned val = (((w >> (8 * k)) & 255u) + (unsigned)pred) & 255u;
-        upleft = up;
-        cur = valid ? val : 0u;
-        if (valid) {
-          if (lane == WAVE - 1) rowp[x] = (unsigned char)val;
-          const int ox = x - left;
-          if (row_out && ox >= 0 && ox < OW) put<FP32>(out, obase + (long long)oy * OW + ox, val);
-        }
-      }
-    }
-    __syncthreads();   // lane 63's row is visible to the loads of the next band
-  }
+  const int st = unfilter<1>(scan + off, H, W, CropSink<FP32>{out, obase, top, left, OH, OW, 0, false}, lane);
   if (lane == 0) status[b] = st;
 }
 

@@ -1,0 +1,189 @@
+"""What the routes that decode stored bytes on the device share -- zarr stacks (yogo_amd/zarr_feed.py), PNG directories for inference
+(yogo_amd/png_feed.py), the PNG prefill of the device image cache (yogo_amd/png_prefill.py): the launch wrappers of
+``yogo_blosc_lz4_decode``, ``yogo_inflate_zlib``, ``yogo_png_unpack`` and ``yogo_png_unpack_planes`` with their tensor checks,
+``gather`` (a pool's futures), ``raise_first_bad`` (a status vector -> RuntimeError), ``png_stream_into`` (one PNG file -> one zlib
+stream in its room of a pinned slot) and ``PrefetchFeed`` (the iterator that loads batch n + 1 while the caller works on batch n)."""
+from __future__ import annotations
+
+from concurrent.futures import Future, ThreadPoolExecutor
+from typing import Callable, Dict, Mapping, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from yogo_amd import _hip, inflate
+
+ALIGN = 256          # every staged chunk / stored stream starts on a multiple of this (the kernels ask for 16)
+MAX_THREADS = 16
+
+
+def center_crop_origin(H: int, W: int, OH: int, OW: int) -> Tuple[int, int]:
+    """(top, left) of torchvision's CenterCrop((OH, OW)) on an H x W image (yogo_amd.image_path_dataset.CenterCrop)"""
+    if OH > H or OW > W or OH < 1 or OW < 1:
+        raise ValueError(f"crop {(OH, OW)} does not fit the image {(H, W)}")
+    return int(round((H - OH) / 2.0)), int(round((W - OW) / 2.0))
+
+
+def require_bytes(who: str, what: str, *tensors: torch.Tensor) -> None:
+    """(the launch wrappers' tensor checks: ``who`` is the wrapper's name in the message)  every tensor a non-empty contiguous 1-D uint8
+    one; ``what`` names it (them)"""
+    for t in tensors:
+        if t.dtype != torch.uint8 or t.ndim != 1 or not t.is_contiguous() or t.numel() == 0:
+            if len(tensors) > 1:
+                raise ValueError(f"{who}: {what} must be non-empty contiguous 1-D uint8 tensors")
+            raise ValueError(f"{who}: {what} must be a non-empty contiguous 1-D uint8 tensor, got {tuple(t.shape)} {t.dtype}")
+
+
+def require_table(who: str, table: torch.Tensor, k: int, n: Optional[int] = None) -> None:
+    """a contiguous int64 [n, k] table; n None: any number of rows"""
+    if table.dtype != torch.int64 or table.ndim != 2 or table.shape[1] != k or n not in (None, table.shape[0]) or not table.is_contiguous():
+        raise ValueError(f"{who}: the table must be a contiguous int64 [{'n' if n is None else n}, {k}] tensor, got {tuple(table.shape)} {table.dtype}")
+
+
+def require_status(who: str, status: torch.Tensor, n: int) -> None:
+    if status.dtype != torch.int32 or tuple(status.shape) != (n,) or not status.is_contiguous():
+        raise ValueError(f"{who}: the status must be a contiguous int32 [{n}] tensor, got {tuple(status.shape)} {status.dtype}")
+
+
+def require_same_device(who: str, *tensors: torch.Tensor) -> None:
+    if len({t.device for t in tensors}) != 1:
+        raise ValueError(f"{who}: the tensors live on different devices")
+
+
+def _decode_rows(symbol: str, stored: torch.Tensor, table: torch.Tensor, out: torch.Tensor, status: torch.Tensor) -> None:
+    """one launch of a device decoder (`symbol`): the checks the two share"""
+    what = symbol[len("yogo_"):]
+    for t, name in ((stored, "the stored chunk bytes"), (table, "the table"), (out, "the decoded chunks"), (status, "the status")):
+        _hip.require_cuda(t, name)
+    require_bytes(what, "stored and out", stored, out)
+    n = int(table.shape[0])
+    require_table(what, table, 5)
+    require_status(what, status, n)
+    require_same_device(what, stored, table, out, status)
+    if n == 0:
+        return
+    with torch.cuda.device(out.device):
+        _hip.call(symbol, stored, stored.numel(), table, n, out, out.numel(), status, _hip.stream_ptr())
+
+
+def decode_blocks(stored: torch.Tensor, table: torch.Tensor, out: torch.Tensor, status: torch.Tensor) -> None:
+    """One ``yogo_blosc_lz4_decode`` launch on the current stream.  stored / out: 1-D uint8 device tensors (stored chunk bytes, decoded
+    staging buffer); table: int64 [n, 5] device, rows (src_off, src_len, dst_off, dst_len, raw); status: int32 [n] device.  The
+    kernel holds every row to the two buffers itself."""
+    _decode_rows("yogo_blosc_lz4_decode", stored, table, out, status)
+
+
+def inflate_streams(stored: torch.Tensor, table: torch.Tensor, out: torch.Tensor, status: torch.Tensor) -> None:
+    """One ``yogo_inflate_zlib`` launch on the current stream; as decode_blocks, rows (src_off, src_len, dst_off, dst_len, adler32):
+    the raw DEFLATE bytes of one zlib stream each (yogo_amd.inflate.split_zlib)."""
+    _decode_rows("yogo_inflate_zlib", stored, table, out, status)
+
+
+def png_unpack(scan: torch.Tensor, table: torch.Tensor, image_hw: Tuple[int, int], out: torch.Tensor, status: torch.Tensor,
+               top: int = 0, left: int = 0) -> torch.Tensor:
+    """One ``yogo_png_unpack`` launch on the current stream.  scan: 1-D uint8 device tensor of inflated scanlines (written: the
+    kernel unfilters one row of every 64 in place); table: int64 [B, 2] device, rows (offset, raw); out: contiguous [B, 1, OH, OW]
+    uint8 or float32; status: int32 [B].  The kernel holds every image to ``scan`` itself."""
+    for t, what in ((scan, "the scanlines"), (table, "the image table"), (out, "the unpack output"), (status, "the status")):
+        _hip.require_cuda(t, what)
+    H, W = (int(v) for v in image_hw)
+    require_bytes("png_unpack", "scan", scan)
+    if out.dtype not in (torch.uint8, torch.float32) or out.ndim != 4 or out.shape[1] != 1 or not out.is_contiguous():
+        raise ValueError(f"png_unpack: out must be a contiguous [B, 1, OH, OW] uint8 or float32 tensor, got {tuple(out.shape)} {out.dtype}")
+    B, _, OH, OW = (int(v) for v in out.shape)
+    require_table("png_unpack", table, 2, B)
+    require_status("png_unpack", status, B)
+    require_same_device("png_unpack", scan, table, out, status)
+    if B == 0:
+        return out
+    with torch.cuda.device(out.device):
+        _hip.call("yogo_png_unpack", scan, scan.numel(), table, B, H, W, int(top), int(left), OH, OW, out,
+                  1 if out.dtype == torch.float32 else 0, status, _hip.stream_ptr())
+    return out
+
+
+def png_unpack_planes(scan: torch.Tensor, table: torch.Tensor, image_hw: Tuple[int, int], out: torch.Tensor, status: torch.Tensor) -> torch.Tensor:
+    """One ``yogo_png_unpack_planes`` launch on the current stream.  scan: 1-D uint8 device tensor (written: the kernel unfilters one
+    row of every 64 in place); table: int64 [B, 2] device, rows (offset, kind); out: contiguous uint8 [B, C, H, W], C 1 or 3;
+    status: int32 [B].  The kernel holds every image to ``scan`` itself."""
+    for t, what in ((scan, "the scanlines"), (table, "the image table"), (out, "the unpack output"), (status, "the status")):
+        _hip.require_cuda(t, what)
+    H, W = (int(v) for v in image_hw)
+    require_bytes("png_unpack_planes", "scan", scan)
+    if out.dtype != torch.uint8 or out.ndim != 4 or out.shape[1] not in (1, 3) or tuple(out.shape[2:]) != (H, W) or not out.is_contiguous():
+        raise ValueError(f"png_unpack_planes: out must be a contiguous uint8 [B, 1 or 3, {H}, {W}] tensor, got {tuple(out.shape)} {out.dtype}")
+    B, C = int(out.shape[0]), int(out.shape[1])
+    require_table("png_unpack_planes", table, 2, B)
+    require_status("png_unpack_planes", status, B)
+    require_same_device("png_unpack_planes", scan, table, out, status)
+    if B == 0:
+        return out
+    with torch.cuda.device(out.device):
+        _hip.call("yogo_png_unpack_planes", scan, scan.numel(), table, B, H, W, C, out, status, _hip.stream_ptr())
+    return out
+
+
+def gather(futures: Sequence[Future]) -> list:
+    """every future's result, in order -- or, after every future has ended, the first one's exception"""
+    for e in [f.exception() for f in futures]:   # (the list: every future has ended before the first error is raised)
+        if e is not None:
+            raise e
+    return [f.result() for f in futures]
+
+
+def raise_first_bad(status: Optional[torch.Tensor], texts: Mapping[int, str], name_of_row: Callable[[int], str]) -> None:
+    """status: what a decode launch left per row, on the host (None: there was no launch).  The first non-zero entry becomes the
+    RuntimeError naming its row (``name_of_row(i)``: a file, a chunk of a store) and the status' words from ``texts``"""
+    if status is None or not bool(status.any()):
+        return
+    first = int(torch.nonzero(status)[0])
+    code = int(status[first])
+    raise RuntimeError(f"{name_of_row(first)} could not be decoded on the device ({texts.get(code, 'unknown status')}: status {code})")
+
+
+def png_stream_into(data: bytes, info, room: np.ndarray) -> Tuple[int, int, int, int]:
+    """The IDAT payloads of one parsed PNG file (``info = png.parse_png(data)``) back to back at the start of ``room`` -- one zlib stream
+    -- and the wrapper taken off: -> (stored bytes, where the raw DEFLATE bytes start in them, how many, the Adler-32).  The caller has
+    made sure that ``info.idat_bytes`` fit; ValueError (yogo_amd.inflate.split_zlib) for a wrapper that is no plain zlib one."""
+    at = 0
+    for o, n in info.idat:
+        room[at:at + n] = np.frombuffer(data, dtype=np.uint8, count=n, offset=o)
+        at += n
+    off, ln, adler = inflate.split_zlib(room[:at])
+    return at, off, ln, adler
+
+
+class PrefetchFeed:
+    """Iterator over ``self.batches`` ([lo, hi) of ``count`` items, ``batch_size`` at a time) that has batch n + 1 loading while the
+    caller works on batch n.  A subclass gives ``_load(n)`` (on the one loader thread: loads run one after the other) and
+    ``_deliver(n, loaded)`` (on the caller's thread: what ``next()`` returns).  An object, not a generator: when a batch raises
+    RuntimeError, the next ``next()`` goes on with the following batch.  ``close()`` runs when the batches are used up."""
+
+    def __init__(self, count: int, batch_size: int, thread_name: str):
+        self.batches = [(lo, min(lo + batch_size, count)) for lo in range(0, count, batch_size)]
+        self._loader = ThreadPoolExecutor(max_workers=1, thread_name_prefix=thread_name)
+        self._pending: Dict[int, Future] = {}
+        self._pos = 0
+
+    def __len__(self) -> int:
+        return len(self.batches)
+
+    def __iter__(self):
+        return self
+
+    def close(self) -> None:
+        for f in self._pending.values():
+            f.cancel()
+        self._loader.shutdown(wait=True)
+        self._pending.clear()
+
+    def __next__(self):
+        if self._pos >= len(self.batches):
+            self.close()
+            raise StopIteration
+        n = self._pos
+        self._pos += 1
+        fut = self._pending.pop(n, None) or self._loader.submit(self._load, n)
+        if n + 1 < len(self.batches):
+            self._pending[n + 1] = self._loader.submit(self._load, n + 1)
+        return self._deliver(n, fut.result())

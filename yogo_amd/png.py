@@ -5,7 +5,7 @@ and data.  IHDR comes first (width, height, bit depth, colour type, compression,
 concatenated are ONE zlib stream of the filtered scanlines (``height`` rows of one filter-type byte and the row's bytes), IEND is
 last.  ``parse_png`` lists what yogo_amd/png_feed.py needs: the header fields and where the IDAT payloads lie, so that they are
 copied back to back into the staging buffer and the device sees one zlib stream (csrc/inflate.hip), whose inflated rows
-csrc/png_unpack.hip unfilters.  Only 8-bit greyscale, non-interlaced files without transparency go that way
+csrc/png_unpack.hip unfilters (csrc/png_unfilter.h).  Only 8-bit greyscale, non-interlaced files without transparency go that way
 (``PngInfo.device_decodable``); everything else is read by ``yogo_amd.yogo_dataset.read_image`` on the host.  The prefill of the
 device image cache (yogo_amd/png_prefill.py, csrc/png_unpack_planes.hip) parses files the same way and also takes 8-bit RGB ones
 (``PngInfo.prefill_decodable``, ``PngInfo.bytes_per_pixel``).

@@ -1,12 +1,12 @@
 """Inference batches from a directory of PNG files, decoded on the device (``yogo infer --path-to-images --device-image-decode``).
 
 The reference's DataLoader workers decode every file with torchvision / PIL on the host.  Here a ``PngDeviceFeed`` takes the
-DataLoader's place, built like yogo_amd/zarr_feed.py's ZarrDeviceFeed: per batch a thread pool reads the files and parses their
+DataLoader's place, a yogo_amd/device_decode.py PrefetchFeed as ZarrDeviceFeed is: per batch a thread pool reads the files and parses their
 chunks (yogo_amd/png.py: signature, IHDR, CRC-32 of IHDR and of every IDAT chunk), the IDAT payloads of a file are copied back to
 back into a pinned buffer -- one zlib stream per image -- and go up on a side stream as they came off the disk;
 ``yogo_inflate_zlib`` (csrc/inflate.hip) inflates every image's scanlines, one wavefront each, and ``yogo_png_unpack``
-(csrc/png_unpack.hip) reverses the PNG filters, crops and optionally divides by 255 into the batch.  Two slots: the loader thread
-reads and decodes batch n+1 while the caller works on batch n.
+(csrc/png_unpack.hip, the loop of csrc/png_unfilter.h) reverses the PNG filters, crops and optionally divides by 255 into the
+batch.  Two slots: the loader thread reads and decodes batch n+1 while the caller works on batch n.
 
 What the device does not take -- anything but 8-bit greyscale without interlace or transparency, a file that does not parse as PNG,
 a file larger than the room a slot has per image -- is decoded by ``read_image`` on the host and enters the unpack launch as a raw
@@ -16,44 +16,18 @@ costs exactly its batch, the class ``predict`` warns on and goes on.
 from __future__ import annotations
 
 import os
-from concurrent.futures import Future, ThreadPoolExecutor
-from typing import Dict, List, Optional, Tuple
+from concurrent.futures import ThreadPoolExecutor
+from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
 
-from yogo_amd import _hip, inflate, png
+from yogo_amd import inflate, png
+from yogo_amd.device_decode import ALIGN, MAX_THREADS, PrefetchFeed, center_crop_origin, gather, inflate_streams, png_stream_into, \
+    png_unpack, raise_first_bad
 from yogo_amd.yogo_dataset import read_image
-from yogo_amd.zarr_feed import ALIGN, MAX_THREADS, center_crop_origin, inflate_streams
 
 UNPACK_STATUS = {1: "a filter-type byte above 4", 2: "the image lies outside the scanline buffer"}
-
-
-def png_unpack(scan: torch.Tensor, table: torch.Tensor, image_hw: Tuple[int, int], out: torch.Tensor, status: torch.Tensor,
-               top: int = 0, left: int = 0) -> torch.Tensor:
-    """One ``yogo_png_unpack`` launch on the current stream.  scan: 1-D uint8 device tensor of inflated scanlines (written: the
-    kernel unfilters one row of every 64 in place); table: int64 [B, 2] device, rows (offset, raw); out: contiguous [B, 1, OH, OW]
-    uint8 or float32; status: int32 [B].  The kernel holds every image to ``scan`` itself."""
-    for t, what in ((scan, "the scanlines"), (table, "the image table"), (out, "the unpack output"), (status, "the status")):
-        _hip.require_cuda(t, what)
-    H, W = (int(v) for v in image_hw)
-    if scan.dtype != torch.uint8 or scan.ndim != 1 or not scan.is_contiguous() or scan.numel() == 0:
-        raise ValueError(f"png_unpack: scan must be a non-empty contiguous 1-D uint8 tensor, got {tuple(scan.shape)} {scan.dtype}")
-    if out.dtype not in (torch.uint8, torch.float32) or out.ndim != 4 or out.shape[1] != 1 or not out.is_contiguous():
-        raise ValueError(f"png_unpack: out must be a contiguous [B, 1, OH, OW] uint8 or float32 tensor, got {tuple(out.shape)} {out.dtype}")
-    B, _, OH, OW = (int(v) for v in out.shape)
-    if table.dtype != torch.int64 or tuple(table.shape) != (B, 2) or not table.is_contiguous():
-        raise ValueError(f"png_unpack: the table must be a contiguous int64 [{B}, 2] tensor, got {tuple(table.shape)} {table.dtype}")
-    if status.dtype != torch.int32 or tuple(status.shape) != (B,) or not status.is_contiguous():
-        raise ValueError(f"png_unpack: the status must be a contiguous int32 [{B}] tensor, got {tuple(status.shape)} {status.dtype}")
-    if len({scan.device, table.device, out.device, status.device}) != 1:
-        raise ValueError("png_unpack: the tensors live on different devices")
-    if B == 0:
-        return out
-    with torch.cuda.device(out.device):
-        _hip.call("yogo_png_unpack", scan, scan.numel(), table, B, H, W, int(top), int(left), OH, OW, out,
-                  1 if out.dtype == torch.float32 else 0, status, _hip.stream_ptr())
-    return out
 
 
 class _Image:
@@ -66,10 +40,10 @@ class _Image:
         self.hw, self.stored, self.deflate, self.adler, self.pixels, self.stream = hw, stored, deflate, adler, pixels, stream
 
 
-class PngDeviceFeed:
-    """Iterator over ``(device batch [B, 1, OH, OW], tuple of paths)`` in the dataset's order; the last batch may be partial.  An
-    object, not a generator: when a batch raises RuntimeError, the next ``next()`` goes on with the following batch.
-    ``crop``: (OH, OW) of a centre crop done in the kernel; ``normalize``: fp32 ``/ 255`` in the kernel, else uint8."""
+class PngDeviceFeed(PrefetchFeed):
+    """Iterator over ``(device batch [B, 1, OH, OW], tuple of paths)`` in the dataset's order; the last batch may be partial; a batch
+    that raises RuntimeError costs that batch alone (device_decode.PrefetchFeed).  ``crop``: (OH, OW) of a centre crop done in the
+    kernel; ``normalize``: fp32 ``/ 255`` in the kernel, else uint8."""
 
     def __init__(self, dataset, batch_size: int, device, crop: Optional[Tuple[int, int]] = None, normalize: bool = False):
         dev = torch.device(device)
@@ -83,29 +57,17 @@ class PngDeviceFeed:
         self.crop = None if crop is None else (int(crop[0]), int(crop[1]))
         self.paths = [str(p) for p in dataset.image_paths]
         n = len(self.paths)
-        self.batches = [(lo, min(lo + self.batch_size, n)) for lo in range(0, n, self.batch_size)]
         self.room = 0   # bytes a slot has per image for its stored zlib stream; sized from the first batch
         self._pinned: List[Optional[torch.Tensor]] = [None, None]
         self._sdev: List[Optional[torch.Tensor]] = [None, None]
         self._scan: List[Optional[torch.Tensor]] = [None, None]
         self._side = torch.cuda.Stream(dev)
         self._pool = ThreadPoolExecutor(max_workers=max(1, min(MAX_THREADS, os.cpu_count() or 1)), thread_name_prefix="png-read")
-        self._loader = ThreadPoolExecutor(max_workers=1, thread_name_prefix="png-feed")   # loads run one after the other
-        self._pending: Dict[int, Future] = {}
-        self._pos = 0
         self.host_decoded = 0   # images that went through read_image
-
-    def __len__(self) -> int:
-        return len(self.batches)
-
-    def __iter__(self) -> "PngDeviceFeed":
-        return self
+        super().__init__(n, self.batch_size, "png-feed")
 
     def close(self) -> None:
-        for f in self._pending.values():
-            f.cancel()
-        self._loader.shutdown(wait=True)
-        self._pending.clear()
+        super().close()
         self._pool.shutdown(wait=True)
 
     @staticmethod
@@ -132,30 +94,16 @@ class PngDeviceFeed:
             raise RuntimeError(f"{path} could not be decoded ({e})") from e
         if not info.device_decodable or (room is not None and info.idat_bytes > len(room)):
             return self._host_image(path)
-        stream = b"".join(data[o:o + n] for o, n in info.idat) if room is None else None
-        if room is not None:
-            at = 0
-            for o, n in info.idat:
-                room[at:at + n] = np.frombuffer(data, dtype=np.uint8, count=n, offset=o)
-                at += n
+        stream = None
         try:
-            off, ln, adler = inflate.split_zlib(stream if room is None else room[:info.idat_bytes])
+            if room is None:
+                stream = b"".join(data[o:o + n] for o, n in info.idat)
+                stored, (off, ln, adler) = len(stream), inflate.split_zlib(stream)
+            else:
+                stored, off, ln, adler = png_stream_into(data, info, room)
         except ValueError as e:
             raise RuntimeError(f"{path} could not be decoded ({e})") from e
-        return _Image((info.height, info.width), info.idat_bytes, (off, ln), adler, stream=stream)
-
-    def _gather(self, futures: List[Future]) -> List[_Image]:
-        """every result, or the first file's RuntimeError after every read has ended"""
-        err: Optional[BaseException] = None
-        out = []
-        for f in futures:
-            e = f.exception()
-            if e is not None and err is None:
-                err = e
-            out.append(None if e is not None else f.result())
-        if err is not None:
-            raise err
-        return out
+        return _Image((info.height, info.width), stored, (off, ln), adler, stream=stream)
 
     def _size_slots(self, streams: List[int], B: int) -> None:
         """the room per image from the longest stream of the first batch, with a quarter and 4 KiB to spare"""
@@ -172,7 +120,7 @@ class PngDeviceFeed:
         B = len(paths)
         if self.room == 0:
             # the first batch sizes the slots: its streams come back as bytes and are copied in here
-            images = self._gather([self._pool.submit(self._read, p, None) for p in paths])
+            images = gather([self._pool.submit(self._read, p, None) for p in paths])
             self._size_slots([im.stored for im in images], self.batch_size)
             host = self._pinned[slot].numpy()
             for i, im in enumerate(images):
@@ -181,7 +129,7 @@ class PngDeviceFeed:
                     im.stream = None
         else:
             host = self._pinned[slot].numpy()
-            images = self._gather([self._pool.submit(self._read, p, host[i * self.room:(i + 1) * self.room]) for i, p in enumerate(paths)])
+            images = gather([self._pool.submit(self._read, p, host[i * self.room:(i + 1) * self.room]) for i, p in enumerate(paths)])
         H, W = images[0].hw
         for p, im in zip(paths, images):
             if im.hw != (H, W):
@@ -217,27 +165,13 @@ class PngDeviceFeed:
             ev.record(self._side)
             bad_inflate = inflate_status.cpu() if inflate_status is not None else None   # waits for the launches
             bad = status.cpu()
-        if bad_inflate is not None and bool(bad_inflate.any()):
-            first = int(torch.nonzero(bad_inflate)[0])
-            code = int(bad_inflate[first])
-            raise RuntimeError(f"{paths[device_rows[first]]} could not be decoded on the device "
-                               f"({inflate.INF_STATUS.get(code, 'unknown status')}: status {code})")
-        if bool(bad.any()):
-            first = int(torch.nonzero(bad)[0])
-            code = int(bad[first])
-            raise RuntimeError(f"{paths[first]} could not be decoded on the device ({UNPACK_STATUS.get(code, 'unknown status')}: status {code})")
+        raise_first_bad(bad_inflate, inflate.INF_STATUS, lambda row: paths[device_rows[row]])
+        raise_first_bad(bad, UNPACK_STATUS, lambda row: paths[row])
         return out, tuple(paths), ev
 
-    def __next__(self) -> Tuple[torch.Tensor, Tuple[str, ...]]:
-        if self._pos >= len(self.batches):
-            self.close()
-            raise StopIteration
-        n = self._pos
-        self._pos += 1
-        fut = self._pending.pop(n, None) or self._loader.submit(self._load, n)
-        if n + 1 < len(self.batches):
-            self._pending[n + 1] = self._loader.submit(self._load, n + 1)
-        out, paths, ev = fut.result()
+    def _deliver(self, n: int, loaded) -> Tuple[torch.Tensor, Tuple[str, ...]]:
+        """(caller's thread) the batch behind the side stream's work"""
+        out, paths, ev = loaded
         with torch.cuda.device(self.device):
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(ev)

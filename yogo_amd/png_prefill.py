@@ -4,7 +4,7 @@
 no worker processes, a pool of threads that only READ.  The N samples go in chunks of ``decode_batch``; per chunk the threads read
 and parse every file (yogo_amd/png.py), copy its IDAT payloads back to back -- one zlib stream per image -- into a pinned slot and
 parse the sample's label rows; then, on a side stream: the slot goes up, ONE ``yogo_inflate_zlib`` launch (csrc/inflate.hip, one
-wavefront per stream) inflates every image's scanlines, ONE ``yogo_png_unpack_planes`` launch (csrc/png_unpack_planes.hip) reverses
+wavefront per stream) inflates every image's scanlines, ONE ``yogo_png_unpack_planes`` launch (csrc/png_unpack_planes.hip on csrc/png_unfilter.h) reverses
 the filters and writes the planes straight into ``images[lo:hi]``, and the per-image statuses come back.  Two pinned slots: chunk
 n + 1 is read while chunk n decodes.  The chunk is independent of the training batch, so thousands of streams share a launch.
 
@@ -33,8 +33,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from yogo_amd import _hip, inflate, png
-from yogo_amd.zarr_feed import ALIGN, MAX_THREADS, inflate_streams
+from yogo_amd import _hip, png
+from yogo_amd.device_decode import ALIGN, MAX_THREADS, inflate_streams, png_stream_into, png_unpack_planes
 
 # images per decode chunk, from tools/bench_prefill.py's sweep (profiles/prefill_decode.log: 772 x 1032 frames, three runs per size):
 # every run at 1 024 beat every run at 256 on the noise frames; against 2 048 and 4 096 the prefill times lie inside their scatter
@@ -60,31 +60,6 @@ def slot_layout(sizes: Sequence[int]) -> Tuple[np.ndarray, int]:
     if len(rooms) > 1:
         offsets[1:] = np.cumsum(rooms[:-1])
     return offsets, int(rooms.sum())
-
-
-def png_unpack_planes(scan: torch.Tensor, table: torch.Tensor, image_hw: Tuple[int, int], out: torch.Tensor, status: torch.Tensor) -> torch.Tensor:
-    """One ``yogo_png_unpack_planes`` launch on the current stream.  scan: 1-D uint8 device tensor (written: the kernel unfilters one
-    row of every 64 in place); table: int64 [B, 2] device, rows (offset, kind); out: contiguous uint8 [B, C, H, W], C 1 or 3;
-    status: int32 [B].  The kernel holds every image to ``scan`` itself."""
-    for t, what in ((scan, "the scanlines"), (table, "the image table"), (out, "the unpack output"), (status, "the status")):
-        _hip.require_cuda(t, what)
-    H, W = (int(v) for v in image_hw)
-    if scan.dtype != torch.uint8 or scan.ndim != 1 or not scan.is_contiguous() or scan.numel() == 0:
-        raise ValueError(f"png_unpack_planes: scan must be a non-empty contiguous 1-D uint8 tensor, got {tuple(scan.shape)} {scan.dtype}")
-    if out.dtype != torch.uint8 or out.ndim != 4 or out.shape[1] not in (1, 3) or tuple(out.shape[2:]) != (H, W) or not out.is_contiguous():
-        raise ValueError(f"png_unpack_planes: out must be a contiguous uint8 [B, 1 or 3, {H}, {W}] tensor, got {tuple(out.shape)} {out.dtype}")
-    B, C = int(out.shape[0]), int(out.shape[1])
-    if table.dtype != torch.int64 or tuple(table.shape) != (B, 2) or not table.is_contiguous():
-        raise ValueError(f"png_unpack_planes: the table must be a contiguous int64 [{B}, 2] tensor, got {tuple(table.shape)} {table.dtype}")
-    if status.dtype != torch.int32 or tuple(status.shape) != (B,) or not status.is_contiguous():
-        raise ValueError(f"png_unpack_planes: the status must be a contiguous int32 [{B}] tensor, got {tuple(status.shape)} {status.dtype}")
-    if len({scan.device, table.device, out.device, status.device}) != 1:
-        raise ValueError("png_unpack_planes: the tensors live on different devices")
-    if B == 0:
-        return out
-    with torch.cuda.device(out.device):
-        _hip.call("yogo_png_unpack_planes", scan, scan.numel(), table, B, H, W, C, out, status, _hip.stream_ptr())
-    return out
 
 
 class _Sample:
@@ -124,15 +99,11 @@ def _read(ds, j: int, room: np.ndarray, image_hw: Tuple[int, int]) -> _Sample:
         return _host_sample(s, ds, j)
     if not info.prefill_decodable or (info.height, info.width) != tuple(image_hw) or info.idat_bytes > len(room):
         return _host_sample(s, ds, j)   # (longer than its room: the file grew after its size was taken)
-    at = 0
-    for o, n in info.idat:
-        room[at:at + n] = np.frombuffer(data, dtype=np.uint8, count=n, offset=o)
-        at += n
     try:
-        off, ln, adler = inflate.split_zlib(room[:at])
+        s.stored, off, ln, s.adler = png_stream_into(data, info, room)
     except ValueError:
         return _host_sample(s, ds, j)
-    s.stored, s.deflate, s.adler, s.bpp = at, (off, ln), adler, info.bytes_per_pixel
+    s.deflate, s.bpp = (off, ln), info.bytes_per_pixel
     s.rows = _label_rows(ds, j)
     return s
 

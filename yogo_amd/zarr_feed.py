@@ -18,8 +18,8 @@ the table as one raw entry.
 Stacks under zarr's ``zlib`` codec take the same route with another decoder: one table row per chunk -- the raw DEFLATE bytes
 between the zlib header and trailer, and the trailer's Adler-32 (yogo_amd/inflate.py) -- and one ``yogo_inflate_zlib`` launch
 (yogo_amd/csrc/inflate.hip).  A chunk whose wrapper is not a plain zlib one is decoded on the host and copied as a raw row by
-``yogo_blosc_lz4_decode``.  ``DEVICE_DECODE_ZLIB`` switches the route for this codec; it is off, because the
-host route measured faster (profiles/zarr_feed.log).
+``yogo_blosc_lz4_decode``.  ``DEVICE_DECODE_ZLIB`` switches the route for this codec; it is off, because the host route measured
+faster (profiles/zarr_feed.log).  The decoders' launch wrappers and the iterator's skeleton are yogo_amd/device_decode.py's.
 """
 from __future__ import annotations
 
@@ -34,21 +34,14 @@ import numpy as np
 import torch
 
 from yogo_amd import _hip, blosc, inflate
+from yogo_amd.device_decode import ALIGN, MAX_THREADS, PrefetchFeed, center_crop_origin, decode_blocks, gather, inflate_streams, \
+    raise_first_bad, require_bytes
 from yogo_amd.zarr_store import ChunkTooLong, ZarrArray, ZarrGroup
 
-ALIGN = 256          # every staged chunk starts on a multiple of this (the kernel asks for 16)
-MAX_THREADS = 16
 RAW_PIECE = 1 << 16  # bytes of a raw block one wavefront of the device decoder copies (longer raw entries are cut up)
 DEVICE_DECODE_ZLIB = False  # True: stacks under the zlib codec are inflated on the device.  Off: at batch 256 the device route feeds
 #                             1.0-1.5 k img/s where the host's 16 threads feed 2.5-3.4 k (profiles/zarr_feed.log); PNG files do gain
 ZLIB_RAW = -1        # fifth field of a zlib store's entry that holds host-decoded bytes (an Adler-32 is never negative)
-
-
-def center_crop_origin(H: int, W: int, OH: int, OW: int) -> Tuple[int, int]:
-    """(top, left) of torchvision's CenterCrop((OH, OW)) on an H x W image (yogo_amd.image_path_dataset.CenterCrop)"""
-    if OH > H or OW > W or OH < 1 or OW < 1:
-        raise ValueError(f"crop {(OH, OW)} does not fit the image {(H, W)}")
-    return int(round((H - OH) / 2.0)), int(round((W - OW) / 2.0))
 
 
 class FrameSource:
@@ -193,13 +186,7 @@ class ChunkStager:
                 continue
             self.reads[key] += 1
             futures.append(self._pool.submit(self._read, arr, coords, buf[off:off + n]))
-        err: Optional[BaseException] = None
-        for f in futures:
-            e = f.exception()
-            if e is not None and err is None:
-                err = e
-        if err is not None:
-            raise err
+        gather(futures)
 
     def _read_stored(self, arr: ZarrArray, coords: Tuple[int, ...], out: np.ndarray):
         """the stored bytes of one chunk into ``out`` (stored_stride bytes) -> (bytes in use, block entries relative to the chunk).
@@ -240,7 +227,7 @@ class ChunkStager:
         stride = self.src.stored_stride
         zlib_store = self.src.first.device_codec == "zlib"
         plan.stored = {}
-        futures: List[Tuple[str, Future]] = []
+        pending: Dict[str, Future] = {}
         for i, (key, (arr, coords)) in enumerate(zip(plan.keys, plan.chunks)):
             soff = i * stride
             if prev is not None and prev[0].stored and key in prev[0].stored:
@@ -250,16 +237,8 @@ class ChunkStager:
                 plan.stored[key] = (used, entries)
                 continue
             self.reads[key] += 1
-            futures.append((key, self._pool.submit(self._read_stored, arr, coords, buf[soff:soff + stride])))
-        err: Optional[BaseException] = None
-        for key, f in futures:
-            e = f.exception()
-            if e is None:
-                plan.stored[key] = f.result()
-            elif err is None:
-                err = e
-        if err is not None:
-            raise err
+            pending[key] = self._pool.submit(self._read_stored, arr, coords, buf[soff:soff + stride])
+        plan.stored.update(zip(pending, gather(list(pending.values()))))
         rows, owner = [], []
         for i, key in enumerate(plan.keys):
             for so, sl, do, dl, fifth in plan.stored[key][1]:
@@ -273,40 +252,6 @@ class ChunkStager:
         return np.asarray(rows, dtype=np.int64).reshape(-1, 5)
 
 
-def _decode_rows(symbol: str, stored: torch.Tensor, table: torch.Tensor, out: torch.Tensor, status: torch.Tensor) -> None:
-    """one launch of a device decoder (`symbol`) on the current stream: the checks the two share"""
-    what = symbol[len("yogo_"):]
-    for t, name in ((stored, "the stored chunk bytes"), (table, "the table"), (out, "the decoded chunks"), (status, "the status")):
-        _hip.require_cuda(t, name)
-    if stored.dtype != torch.uint8 or out.dtype != torch.uint8 or stored.ndim != 1 or out.ndim != 1 or not stored.is_contiguous() \
-            or not out.is_contiguous() or stored.numel() == 0 or out.numel() == 0:
-        raise ValueError(f"{what}: stored and out must be non-empty contiguous 1-D uint8 tensors")
-    n = int(table.shape[0])
-    if table.dtype != torch.int64 or table.ndim != 2 or table.shape[1] != 5 or not table.is_contiguous():
-        raise ValueError(f"{what}: the table must be a contiguous int64 [n, 5] tensor, got {tuple(table.shape)} {table.dtype}")
-    if status.dtype != torch.int32 or tuple(status.shape) != (n,) or not status.is_contiguous():
-        raise ValueError(f"{what}: the status must be a contiguous int32 [{n}] tensor, got {tuple(status.shape)} {status.dtype}")
-    if len({stored.device, table.device, out.device, status.device}) != 1:
-        raise ValueError(f"{what}: the tensors live on different devices")
-    if n == 0:
-        return
-    with torch.cuda.device(out.device):
-        _hip.call(symbol, stored, stored.numel(), table, n, out, out.numel(), status, _hip.stream_ptr())
-
-
-def decode_blocks(stored: torch.Tensor, table: torch.Tensor, out: torch.Tensor, status: torch.Tensor) -> None:
-    """One ``yogo_blosc_lz4_decode`` launch on the current stream.  stored / out: 1-D uint8 device tensors (stored chunk bytes, decoded
-    staging buffer); table: int64 [n, 5] device, rows (src_off, src_len, dst_off, dst_len, raw); status: int32 [n] device.  The
-    kernel holds every row to the two buffers itself."""
-    _decode_rows("yogo_blosc_lz4_decode", stored, table, out, status)
-
-
-def inflate_streams(stored: torch.Tensor, table: torch.Tensor, out: torch.Tensor, status: torch.Tensor) -> None:
-    """One ``yogo_inflate_zlib`` launch on the current stream; as decode_blocks, rows (src_off, src_len, dst_off, dst_len, adler32):
-    the raw DEFLATE bytes of one zlib stream each (yogo_amd.inflate.split_zlib)."""
-    _decode_rows("yogo_inflate_zlib", stored, table, out, status)
-
-
 def unpack(staged: torch.Tensor, tile_off: np.ndarray, tile_k: np.ndarray, *, chunks: Sequence[int], order_f: bool, fill: int,
            frame_shape: Tuple[int, int], out: torch.Tensor, top: int = 0, left: int = 0,
            tile_off_dev: Optional[torch.Tensor] = None, tile_k_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -317,8 +262,7 @@ def unpack(staged: torch.Tensor, tile_off: np.ndarray, tile_k: np.ndarray, *, ch
     _hip.require_cuda(out, "the unpack output")
     ch, cw, cn = (int(v) for v in chunks)
     H, W = (int(v) for v in frame_shape)
-    if staged.dtype != torch.uint8 or staged.ndim != 1 or not staged.is_contiguous() or staged.numel() == 0:
-        raise ValueError(f"unpack: staged must be a non-empty contiguous 1-D uint8 tensor, got {tuple(staged.shape)} {staged.dtype}")
+    require_bytes("unpack", "staged", staged)
     if out.dtype not in (torch.uint8, torch.float32) or out.ndim != 4 or out.shape[1] != 1 or not out.is_contiguous():
         raise ValueError(f"unpack: out must be a contiguous [B, 1, OH, OW] uint8 or float32 tensor, got {tuple(out.shape)} {out.dtype}")
     if out.device != staged.device:
@@ -347,10 +291,10 @@ def unpack(staged: torch.Tensor, tile_off: np.ndarray, tile_k: np.ndarray, *, ch
     return out
 
 
-class ZarrDeviceFeed:
-    """Iterator over ``(device batch [B, 1, OH, OW], names)`` in index order; the last batch may be partial.  An object, not a
-    generator: when a batch raises RuntimeError (an unreadable chunk), the next ``next()`` goes on with the following batch.
-    ``crop``: (OH, OW) of a centre crop done in the kernel; ``normalize``: fp32 ``/ 255`` in the kernel, else uint8.
+class ZarrDeviceFeed(PrefetchFeed):
+    """Iterator over ``(device batch [B, 1, OH, OW], names)`` in index order; the last batch may be partial; a batch that raises
+    RuntimeError (an unreadable chunk) costs that batch alone (device_decode.PrefetchFeed).  ``crop``: (OH, OW) of a centre crop
+    done in the kernel; ``normalize``: fp32 ``/ 255`` in the kernel, else uint8.
     ``num_frames``: how many frames to walk (default: ``len(dataset)``, as the reference's DataLoader does, and never more
     than the stack holds).  ``device_decode``: a Blosc stack with LZ4 blocks (and, with DEVICE_DECODE_ZLIB set, a zlib stack) is decoded on the device
     (module docstring); False takes the host route (A/B runs); every other source takes the host route whatever it says."""
@@ -368,7 +312,6 @@ class ZarrDeviceFeed:
         self.src = src = FrameSource(dataset.zarr_store)
         n = min(len(dataset) if num_frames is None else int(num_frames), src.num_frames)
         self.num_frames = n
-        self.batches = [(lo, min(lo + self.batch_size, n)) for lo in range(0, n, self.batch_size)]
         self.OH, self.OW = (src.H, src.W) if crop is None else (int(crop[0]), int(crop[1]))
         self.top, self.left = center_crop_origin(src.H, src.W, self.OH, self.OW)
         cap = max(ALIGN, src.max_chunks(self.batch_size) * src.chunk_stride)
@@ -382,27 +325,15 @@ class ZarrDeviceFeed:
             self._spinned = [torch.empty(scap, dtype=torch.uint8).pin_memory() for _ in range(2)]
             self._shost = [p.numpy() for p in self._spinned]
             self._sdev = [torch.empty(scap, dtype=torch.uint8, device=dev) for _ in range(2)]
-            self._slast: Optional[Tuple[int, BatchPlan, np.ndarray]] = None
         self._side = torch.cuda.Stream(dev)
         self._uploaded: List[Optional[torch.cuda.Event]] = [None, None]   # slot's pinned buffer may be overwritten after this
         self._consumed: List[Optional[torch.cuda.Event]] = [None, None]   # slot's device buffer may be overwritten after this
-        self._last: Optional[Tuple[int, BatchPlan, np.ndarray]] = None
+        self._last: Optional[Tuple[int, BatchPlan, np.ndarray]] = None   # the batch staged last, its plan and its filled host buffer
         self.stager = ChunkStager(src)
-        self._loader = ThreadPoolExecutor(max_workers=1, thread_name_prefix="zarr-feed")   # loads run one after the other
-        self._pending: Dict[int, Future] = {}
-        self._pos = 0
-
-    def __len__(self) -> int:
-        return len(self.batches)
-
-    def __iter__(self) -> "ZarrDeviceFeed":
-        return self
+        super().__init__(n, self.batch_size, "zarr-feed")
 
     def close(self) -> None:
-        for f in self._pending.values():
-            f.cancel()
-        self._loader.shutdown(wait=True)
-        self._pending.clear()
+        super().close()
         self.stager.close()
 
     def _upload_stored(self, plan: BatchPlan, slot: int) -> None:
@@ -418,87 +349,64 @@ class ZarrDeviceFeed:
         for a, b in runs:
             self._sdev[slot][a:b].copy_(self._spinned[slot][a:b], non_blocking=True)
 
-    def _load_decoded(self, n: int):
-        """(loader thread) batch n through the device decoder: stored bytes and table up, one decode launch on the side stream
-        into the slot's device buffer (a zlib stack: one inflate launch, and one of raw rows where a chunk was decoded on the
-        host), then the per-row status back -- RuntimeError naming the first bad chunk"""
+    def _decode(self, plan: BatchPlan, table: np.ndarray, slot: int) -> Tuple[Optional[torch.Tensor], int]:
+        """(side stream) stored bytes and table up, one decode launch into the slot's device buffer (a zlib stack: one inflate launch,
+        and one of raw rows where a chunk was decoded on the host) -> (the per-row status, None without a launch; its inflate rows)"""
+        if not len(table):
+            return None, 0
+        n_inflate = 0
+        self._upload_stored(plan, slot)
+        if self.codec == "zlib":   # host-decoded chunks are copied by the Blosc decoder's raw rows, behind the inflate rows
+            raw = table[:, 4] == ZLIB_RAW
+            order = np.argsort(raw, kind="stable")
+            table, n_inflate = table[order], int((~raw).sum())
+            table[n_inflate:, 4] = 1
+            plan.row_chunk = [plan.row_chunk[i] for i in order]
+        table_dev = torch.from_numpy(table).to(self.device)
+        status = torch.empty(len(table), dtype=torch.int32, device=self.device)
+        if n_inflate:
+            inflate_streams(self._sdev[slot], table_dev[:n_inflate], self._dev[slot], status[:n_inflate])
+        if n_inflate < len(table):
+            decode_blocks(self._sdev[slot], table_dev[n_inflate:], self._dev[slot], status[n_inflate:])
+        return status, n_inflate
+
+    def _load(self, n: int):
+        """(loader thread) stage batch n and start its upload on the side stream; through the device decoder: the stored bytes are
+        staged and decoded there, then the per-row status comes back -- RuntimeError naming the first bad chunk"""
         slot = n % 2
         lo, hi = self.batches[n]
         plan = plan_batch(self.src, lo, hi)
         if self._uploaded[slot] is not None:
             self._uploaded[slot].synchronize()
-        prev = (self._slast[1], self._slast[2]) if self._slast is not None and self._slast[0] == n - 1 else None
-        self._slast = None
-        table = self.stager.stage_stored(plan, self._shost[slot], prev)
-        self._slast = (n, plan, self._shost[slot])
+        host = (self._shost if self.device_decode else self._host)[slot]
+        prev = (self._last[1], self._last[2]) if self._last is not None and self._last[0] == n - 1 else None
+        self._last = None
+        table = self.stager.stage_stored(plan, host, prev) if self.device_decode else self.stager.stage(plan, host, prev)
+        self._last = (n, plan, host)
         with torch.cuda.device(self.device), torch.cuda.stream(self._side):
             if self._consumed[slot] is not None:
                 self._side.wait_event(self._consumed[slot])
             toff = torch.from_numpy(plan.tile_off).to(self.device)
             tk = torch.from_numpy(plan.tile_k).to(self.device)
-            status, n_inflate = None, 0
-            if len(table):
-                self._upload_stored(plan, slot)
-                if self.codec == "zlib":   # host-decoded chunks are copied by the Blosc decoder's raw rows, behind the inflate rows
-                    raw = table[:, 4] == ZLIB_RAW
-                    order = np.argsort(raw, kind="stable")
-                    table, n_inflate = table[order], int((~raw).sum())
-                    table[n_inflate:, 4] = 1
-                    plan.row_chunk = [plan.row_chunk[i] for i in order]
-                table_dev = torch.from_numpy(table).to(self.device)
-                status = torch.empty(len(table), dtype=torch.int32, device=self.device)
-                if n_inflate:
-                    inflate_streams(self._sdev[slot], table_dev[:n_inflate], self._dev[slot], status[:n_inflate])
-                if n_inflate < len(table):
-                    decode_blocks(self._sdev[slot], table_dev[n_inflate:], self._dev[slot], status[n_inflate:])
+            if self.device_decode:
+                status, n_inflate = self._decode(plan, table, slot)
+            else:
+                status, n_inflate = None, 0
+                self._dev[slot][:plan.nbytes].copy_(self._pinned[slot][:plan.nbytes], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self._side)
             bad = status.cpu() if status is not None else None   # waits for the decode: this thread overlaps the consumer already
         self._uploaded[slot] = ev
         if bad is not None and bool(bad.any()):
-            self._slast = None   # what a bad chunk left in the device buffer is not handed on
-            first = int(torch.nonzero(bad)[0])
-            which = plan.row_chunk[first]
-            key, code = plan.keys[which], int(bad[first])
-            texts = inflate.INF_STATUS if first < n_inflate else blosc.LZ4_STATUS
-            raise RuntimeError(f"zarr store {plan.chunks[which][0].where}: chunk {key!r} could not be decoded on the device "
-                               f"({texts.get(code, 'unknown status')}: status {code})")
+            self._last = None   # what a bad chunk left in the device buffer is not handed on
+            names = [f"zarr store {plan.chunks[i][0].where}: chunk {plan.keys[i]!r}" for i in plan.row_chunk]
+            raise_first_bad(bad[:n_inflate], inflate.INF_STATUS, names.__getitem__)
+            raise_first_bad(bad[n_inflate:], blosc.LZ4_STATUS, names[n_inflate:].__getitem__)
         return plan, toff, tk, ev
 
-    def _load(self, n: int):
-        """(loader thread) stage batch n and start its upload on the side stream"""
-        if self.device_decode:
-            return self._load_decoded(n)
-        slot = n % 2
-        lo, hi = self.batches[n]
-        plan = plan_batch(self.src, lo, hi)
-        if self._uploaded[slot] is not None:
-            self._uploaded[slot].synchronize()
-        prev = (self._last[1], self._last[2]) if self._last is not None and self._last[0] == n - 1 else None
-        self._last = None
-        self.stager.stage(plan, self._host[slot], prev)
-        self._last = (n, plan, self._host[slot])
-        with torch.cuda.device(self.device), torch.cuda.stream(self._side):
-            if self._consumed[slot] is not None:
-                self._side.wait_event(self._consumed[slot])
-            self._dev[slot][:plan.nbytes].copy_(self._pinned[slot][:plan.nbytes], non_blocking=True)
-            toff = torch.from_numpy(plan.tile_off).to(self.device)
-            tk = torch.from_numpy(plan.tile_k).to(self.device)
-            ev = torch.cuda.Event()
-            ev.record(self._side)
-        self._uploaded[slot] = ev
-        return plan, toff, tk, ev
-
-    def __next__(self) -> Tuple[torch.Tensor, Tuple[str, ...]]:
-        if self._pos >= len(self.batches):
-            self.close()
-            raise StopIteration
-        n = self._pos
-        self._pos += 1
-        fut = self._pending.pop(n, None) or self._loader.submit(self._load, n)
-        if n + 1 < len(self.batches):
-            self._pending[n + 1] = self._loader.submit(self._load, n + 1)
-        plan, toff, tk, ev = fut.result()
+    def _deliver(self, n: int, loaded) -> Tuple[torch.Tensor, Tuple[str, ...]]:
+        """(caller's thread) the unpack launch on the current stream, behind the upload"""
+        plan, toff, tk, ev = loaded
         slot = n % 2
         with torch.cuda.device(self.device):
             cur = torch.cuda.current_stream(self.device)
