@@ -198,6 +198,23 @@ int yogo_pred_sink_workspace_bytes(int B, size_t* bytes);
 int yogo_pred_sink_append(const float* rows, const int* counts, int B, int cap, int P, int mode, int count_classes,
                           long long first_img_id, int img_h, int img_w, long long* state, float* arena, long long arena_cap,
                           int* img_counts, long long img_cap, void* workspace, yogo_stream_t stream);
+/* The prediction files of --save-preds (yogo/infer.py:52-55) as text, written on the device.  The definition is
+ * prediction_rows_to_text (yogo_amd/utils/prediction_formatting.py): per row "<class> <cx> <cy> <w> <h>" -- class =
+ * max(range(C), key=scores.__getitem__) (the first maximum under ">": a NaN never displaces the current best), the four numbers as
+ * repr(float(numpy.float32(v))), shortest round-trip decimals (yogo_amd/csrc/float_text.h) -- the rows of an image joined by "\n" with
+ * no trailing newline, an image without rows an empty text.  records [n][P] fp32 in image order and img_counts [images] int32 = what a
+ * mode-1 sink holds at drain time.  text [text_cap] receives the images' texts back to back, img_offsets [images + 1] (int64) where each
+ * starts (image k is text[img_offsets[k] : img_offsets[k + 1]]), total (ONE device int64) the byte count NEEDED: the text is complete
+ * iff 0 <= total <= text_cap, and nothing is ever stored at or past text_cap (text may be null when text_cap is 0: a measuring run).
+ * img_counts is not trusted: a negative entry or a sum other than n gives total = -1, and text / img_offsets are not written.
+ * n = 0 launches nothing (offsets and total become 0 by stream-ordered memsets; img_counts is not read); n > 0 with images = 0 is an
+ * argument error.  n, images <= INT_MAX.  workspace: 8-byte aligned, yogo_pred_text_bound's workspace_bytes. */
+/* HOST pointers: text_bytes = a capacity that no records of n_records rows with P - 5 class scores can exceed (at most 1 + the digits
+ * of C - 1 + 4 * 25 bytes per row), workspace_bytes = the scratch of yogo_pred_text_format (one byte per record, 8 per image and per
+ * 256 records) */
+int yogo_pred_text_bound(long long n_records, long long images, int P, size_t* text_bytes, size_t* workspace_bytes);
+int yogo_pred_text_format(const float* records, long long n, int P, const int* img_counts, long long images, char* text,
+                          long long text_cap, long long* img_offsets, long long* total, void* workspace, yogo_stream_t stream);
 
 /* ---- bf16 path: the bf16-autocast forward of `yogo infer` (yogo/infer.py:313-317) and half-precision training
  * (yogo/train.py:315-318, --half) -------------------------------------------------------------------------------------------

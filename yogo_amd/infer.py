@@ -9,7 +9,8 @@ the model is already a fixed sequence of hand-written kernels.
 
 ``device_outputs=True`` (``yogo infer --device-outputs``) keeps what those launches leave on the device: a ``PredictionSink`` per
 requested output (yogo_amd/pred_sink.py) compacts and counts the kept rows in HBM, and the host reads them when a sink is drained --
-after the loop, or when ``flush_rows`` records have piled up -- instead of copying the padded rows of every batch.  Same files, same
+after the loop, or when ``flush_rows`` records have piled up -- instead of copying the padded rows of every batch.  The text of
+``save_preds`` is formatted on the device too (yogo_amd/csrc/pred_text.hip): the host writes ready byte ranges.  Same files, same
 counts.
 
 ``device_image_decode=True`` (``yogo infer --path-to-images DIR --device-image-decode``) replaces the DataLoader and its PIL-decoding
@@ -30,9 +31,9 @@ from torch.utils.data import DataLoader
 
 from yogo_amd.image_path_dataset import CenterCrop, ZarrDataset, collate_fn, get_dataset
 from yogo_amd.model import YOGO
-from yogo_amd.pred_sink import PredictionSink, npy_columns, split_records
+from yogo_amd.pred_sink import PredictionSink, npy_columns
 from yogo_amd.utils import format_to_numpy_batched, get_prediction_class_counts, save_predictions  # noqa: F401
-from yogo_amd.utils.prediction_formatting import format_preds_batched, prediction_rows_to_text
+from yogo_amd.utils.prediction_formatting import format_preds_batched, prediction_rows_to_text  # noqa: F401  (the text's definition; the host path calls it in save_predictions)
 from yogo_amd.utils.utils import choose_device, draw_yogo_prediction
 from yogo_amd.yogo_dataloader import choose_dataloader_num_workers
 
@@ -146,11 +147,13 @@ def predict(
     npy_chunks: list = []   # (records, per-image counts) per drain
 
     def drain_txt() -> None:
-        records, per_image = txt_sink.drain()
-        assert len(per_image) == len(txt_names), f"{len(per_image)} images drained, {len(txt_names)} file names held"
-        for fname, r in zip(txt_names, split_records(records, per_image)):
-            with open(fname, "w") as f:
-                f.write(prediction_rows_to_text(torch.from_numpy(r)))
+        # the files' bytes come ready from the device (PredictionSink.drain_text: what prediction_rows_to_text gives, byte for byte)
+        text, offsets = txt_sink.drain_text()
+        assert len(offsets) - 1 == len(txt_names), f"{len(offsets) - 1} images drained, {len(txt_names)} file names held"
+        data = memoryview(text)
+        for k, fname in enumerate(txt_names):
+            with open(fname, "wb") as f:
+                f.write(data[offsets[k]: offsets[k + 1]])
         txt_names.clear()
 
     file_iterator = enumerate(loader)

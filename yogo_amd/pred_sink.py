@@ -7,7 +7,10 @@ them, per batch.  A sink instead hands ``rows`` / ``counts`` of ``format_preds_b
 per-image counts and adds to a class histogram; the host reads the arena once per ``drain()`` -- at the end of a run, or when
 ``should_flush()`` says that ``flush_rows`` records have piled up.  What comes out is bit for bit what the host path computes.
 
-Text formatting and file writing stay on the host (``split_records`` gives them their per-image views).
+The text of ``--save-preds`` is written on the device as well: ``drain_text()`` hands the arena of a "rows" sink to
+``yogo_pred_text_format`` (yogo_amd/csrc/pred_text.hip), which prints every row as ``prediction_rows_to_text`` does -- shortest
+round-trip decimals, byte for byte what Python's ``repr`` gives -- and the host reads the finished bytes of all images and their
+offsets.  Only the file writes stay on the host (``split_records`` gives ``drain()``'s callers their per-image views).
 """
 from __future__ import annotations
 
@@ -61,7 +64,7 @@ def npy_columns(chunks, num_classes: int) -> np.ndarray:
 
 class PredictionSink:
     """Kept rows of many batches, compacted and counted in HBM.  ``mode`` "npy" (needs ``img_hw``) or "rows"; ``append`` and
-    ``add_counts`` launch and return, ``drain`` is the one read."""
+    ``add_counts`` launch and return, ``drain`` (or ``drain_text``) is the one read."""
 
     def __init__(self, device: Union[str, torch.device], num_classes: int, mode: Union[str, int], img_hw: Optional[Tuple[int, int]] = None,
                  flush_rows: int = DEFAULT_FLUSH_ROWS) -> None:
@@ -170,9 +173,8 @@ class PredictionSink:
         return self._rows_known > self.flush_rows
 
     # -- read-out ----------------------------------------------------------------------------------------------------------------
-    def drain(self) -> Tuple[np.ndarray, np.ndarray]:
-        """(records float32 [N, reclen], per_image_counts int32 [images]) of everything appended since the last drain, in order;
-        the totals start again at zero, ``class_counts`` go on.  Raises if anything was dropped for lack of room."""
+    def _take(self) -> Tuple[int, int]:
+        """(records, images) appended since the last drain; the totals start again at zero.  Raises if anything was dropped."""
         head = self.state[: self.off_counts].cpu()
         n, images = int(head[self.off_rows]), int(head[self.off_images])
         dropped, dropped_images = int(head[self.off_dropped]), int(head[self.off_dropped_images])
@@ -182,6 +184,12 @@ class PredictionSink:
         if dropped or dropped_images:
             raise RuntimeError(f"yogo_amd: the prediction sink dropped {dropped} records and {dropped_images} image entries for lack of "
                                f"room (kept {n} records of {images} images)")
+        return n, images
+
+    def drain(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(records float32 [N, reclen], per_image_counts int32 [images]) of everything appended since the last drain, in order;
+        the totals start again at zero, ``class_counts`` go on.  Raises if anything was dropped for lack of room."""
+        n, images = self._take()
         if self.arena is None or n == 0:
             records = np.zeros((0, self.reclen), dtype=np.float32)
         else:
@@ -191,6 +199,31 @@ class PredictionSink:
         else:
             per_image = self.img_counts[:images].cpu().numpy()
         return records, per_image
+
+    def drain_text(self) -> Tuple[np.ndarray, np.ndarray]:
+        """``drain()`` of a "rows" sink as text: (text uint8 [total], offsets int64 [images + 1]); ``text[offsets[k]: offsets[k + 1]]``
+        are the bytes of ``prediction_rows_to_text`` of image k's rows.  The rows are formatted on the device
+        (``yogo_pred_text_format``); the host reads ``total`` bytes and the offsets, not the records."""
+        if self.mode != MODE_ROWS:
+            raise ValueError("drain_text: prediction text is made of the kept rows; this sink holds npy records")
+        n, images = self._take()
+        if images == 0:
+            return np.zeros((0,), dtype=np.uint8), np.zeros((1,), dtype=np.int64)
+        with torch.cuda.device(self.device):
+            text_bytes, ws_bytes = ctypes.c_size_t(0), ctypes.c_size_t(0)
+            _hip.call("yogo_pred_text_bound", n, images, self.reclen, ctypes.addressof(text_bytes), ctypes.addressof(ws_bytes))
+            text = torch.empty(max(int(text_bytes.value), 1), dtype=torch.uint8, device=self.device)
+            ws = torch.empty(max(int(ws_bytes.value), 8), dtype=torch.uint8, device=self.device)
+            out = torch.empty(images + 2, dtype=torch.int64, device=self.device)   # the offsets, then the total: one copy
+            _hip.call("yogo_pred_text_format", self.arena if n else None, n, self.reclen, self.img_counts, images, text, text.shape[0],
+                      out, out[images + 1:], ws, _hip.stream_ptr())
+            out_h = out.cpu().numpy()
+            total = int(out_h[images + 1])
+            if total < 0:
+                raise RuntimeError(f"yogo_amd: the sink's per-image counts do not add up to its {n} records")
+            if total > text.shape[0]:
+                raise RuntimeError(f"yogo_amd: the prediction text needs {total} bytes, more than the bound of {text.shape[0]}")
+            return text[:total].cpu().numpy(), out_h[: images + 1].copy()
 
     def class_counts(self) -> torch.Tensor:
         return self.state[self.off_counts: self.off_counts + self.C].cpu()
