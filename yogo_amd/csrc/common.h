@@ -52,6 +52,12 @@ static inline bool magic_div_exact(long long nmax, int d) {
 }
 // the multiplier m of magic_div_exact as the kernel-argument structs carry it (d <= 1, where m does not fit 32 bits: all ones)
 static inline unsigned magic_u32(int d) { return d <= 1 ? 0xFFFFFFFFu : (unsigned)(((1ull << 32) + (unsigned)d - 1ull) / (unsigned)d); }
+// grid of a persistent kernel (workgroups walk tiles lin = blockIdx.x + k * gridDim.x): one workgroup per CU, none without a tile; a
+// multiple of 8 so that a workgroup's tiles stay inside one XCD's contiguous run (bf16_dev.h, xcd_remap)
+static inline int persistent_grid(int ntiles, int n_cu) {
+  const int g = ntiles < n_cu ? ntiles : n_cu;
+  return g >= 8 ? g & ~7 : g;
+}
 
 #define ACT_NONE 0
 #define ACT_LEAKY 1

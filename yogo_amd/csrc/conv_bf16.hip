@@ -13,22 +13,12 @@
 //     bytes per store instruction).
 // At bf16 every layer of the network is HBM-bound on MI355X (ridge ~312 FLOP/B, the widest layer offers ~230), so the
 // kernel is built around few, wide memory operations rather than around MFMA issue.
-#include "common.h"
+#include "bf16_dev.h"
 #include "conv_bf16_ws.h"
 #include "conv_bf16_ws16.h"
 #include "conv_bf16_ws3.h"
-#include <type_traits>
-#include <utility>
 #include <cstdlib>
 #include <vector>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-// native vector types (HIP's u32x4/u32x2 are structs and get spilled to scratch when selected/stored through pointers)
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x16 __attribute__((ext_vector_type(16)));
 
 #define BF_MAX_TAPS 9
 #define BF_LDS_BUDGET (80 * 1024)      // two 4-wavefront workgroups per CU
@@ -99,23 +89,14 @@ __device__ __forceinline__ float half_wave_sum(float v) {
   return v;
 }
 
-// n / d through the precomputed magic number m = ceil(2^32 / d) (d = 1: m does not fit, n is returned)
-__device__ __forceinline__ int udivm(int n, int d, unsigned m) { return d == 1 ? n : (int)__umulhi((unsigned)n, m); }
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-// raw buffer descriptor of `bytes` bytes at `ptr`
-__device__ __forceinline__ i32x4 bf_make_rsrc(const void* ptr, int bytes) {
-  const unsigned long long a = reinterpret_cast<unsigned long long>(ptr);
-  return i32x4{(int)(unsigned)a, (int)((unsigned)(a >> 32) & 0xFFFFu), bytes, 0x00020000};
-}
 // One LDS-DMA piece from inline asm (invisible to hipcc's waitcnt bookkeeping; retired by explicit s_waitcnt vmcnt): 64 lanes x
 // 16 bytes from (descriptor, per-lane byte offset + scalar offset) to LDS bytes [lds_addr, lds_addr + 1024).  The dynamic LDS
 // block of this kernel starts at LDS address 0 (no static __shared__ objects).
-__device__ __forceinline__ void bf_dma16(i32x4 rsrc, unsigned lds_addr, int voff, int soff) {
+__device__ __forceinline__ void bf_dma16(i32x4 rs, unsigned lds_addr, int voff, int soff) {
   unsigned keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
                : "=&s"(keep)
-               : "v"(voff), "s"(lds_addr), "s"(rsrc), "s"(soff)
+               : "v"(voff), "s"(lds_addr), "s"(rs), "s"(soff)
                : "memory");
 }
 
@@ -123,7 +104,7 @@ __device__ __forceinline__ void bf_dma16(i32x4 rsrc, unsigned lds_addr, int voff
 // issues an instruction only every ~10 cycles, so the request sequence is kept to 3 instructions per piece): LDS destinations
 // lds_addr + k * STRIDE (M0 is stepped in place), per-lane source offsets v0..v4, common scalar offset.
 template <int STRIDE>
-__device__ __forceinline__ void bf_dma16x5(i32x4 rsrc, unsigned lds_addr, int soff, int v0, int v1, int v2, int v3, int v4) {
+__device__ __forceinline__ void bf_dma16x5(i32x4 rs, unsigned lds_addr, int soff, int v0, int v1, int v2, int v3, int v4) {
   unsigned keep;
   asm volatile(
       "s_mov_b32 %0, m0\n\t"
@@ -144,7 +125,7 @@ __device__ __forceinline__ void bf_dma16x5(i32x4 rsrc, unsigned lds_addr, int so
       "buffer_load_dwordx4 %5, %6, %8 offen lds\n\t"
       "s_mov_b32 m0, %0"
       : "=&s"(keep)
-      : "v"(v0), "v"(v1), "v"(v2), "v"(v3), "v"(v4), "s"(rsrc), "s"(lds_addr), "s"(soff), "i"(STRIDE)
+      : "v"(v0), "v"(v1), "v"(v2), "v"(v3), "v"(v4), "s"(rs), "s"(lds_addr), "s"(soff), "i"(STRIDE)
       : "memory", "scc");
 }
 
@@ -174,12 +155,6 @@ __device__ __forceinline__ void bf_dma16_2p3(i32x4 ra, i32x4 rb, unsigned lds_ad
       : "=&s"(keep)
       : "v"(v0), "v"(v1), "v"(v2), "v"(v3), "v"(v4), "s"(ra), "s"(rb), "s"(lds_addr), "s"(sa), "s"(sb), "i"(STRIDE)
       : "memory", "scc");
-}
-
-// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a compile-time unrolled loop whose index can feed constexpr
-template <class F, int... I>
-__device__ __forceinline__ void bf_static_for(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
 }
 
 // NWV wavefronts per workgroup, each owning NW 32-pixel groups x all MW channel blocks: NWV = 8 shares one staged weight
@@ -224,17 +199,16 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv_bf16_kernel(const ConvBf16Pa
   // XCD-aware bijective remap: contiguous runs of (image, tile) per XCD so halo rows hit the same L2
   const unsigned nwg = gridDim.x * gridDim.y * gridDim.z;
   const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-  const unsigned xq = nwg >> 3, xr = nwg & 7, xcd = lin & 7;
-  const unsigned widx = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (lin >> 3);
+  const unsigned widx = xcd_remap(lin, nwg);
   const int gx = gridDim.x, gy = gridDim.y;
-  const int b = udivm((int)widx, gx * gy, p.m_gxy);
+  const int b = udivm1((int)widx, gx * gy, p.m_gxy);
   const int rem_ = (int)widx - b * gx * gy;
   // stride-2 data gradient with <= 64 rows: the two row parities of a tile are NEIGHBOURS in the walk -- they stage the same gradient
   // tile, and 195 tiles apart (parity-major) the second fetch no longer finds it in the XCD's L2 (FETCH 2.2x the tensor).  Layer 2's data
   // gradient -6 % in the same-box A/B (gpurun_out/r4_abpair.log); the 128-row tile (layer 4, not bound by memory) loses 4 % and keeps
   // the parity-major order.
   constexpr bool PAIR = S2D && MW < 4;
-  const int mb_ = udivm(PAIR ? (rem_ >> 1) : rem_, gx, p.m_gx);
+  const int mb_ = udivm1(PAIR ? (rem_ >> 1) : rem_, gx, p.m_gx);
   const int by = PAIR ? 2 * mb_ + (rem_ & 1) : mb_;
   const int bx = (PAIR ? (rem_ >> 1) : rem_) - mb_ * gx;
   const int py = S2D ? (by & 1) : 0;
@@ -246,7 +220,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv_bf16_kernel(const ConvBf16Pa
   const int tbase = S2D ? 3 * py : 0;       // first weight slice
   const int ntap = S2D ? 3 + 3 * py : p.T;  // weight slices this workgroup uses
   const int n0tap = S2D ? 1 + py : ntap;    // ... of which belong to column parity 0
-  const int cb = udivm(bx, p.tiles_per_band, p.m_tpb);
+  const int cb = udivm1(bx, p.tiles_per_band, p.m_tpb);
   const int tb = bx - cb * p.tiles_per_band;
   const int j0 = cb * p.TW;
   const int bw = min(p.TW, OWt - j0);
@@ -269,7 +243,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv_bf16_kernel(const ConvBf16Pa
   const int p1 = min(p0 + PT, NPb);
   const bool lastband = cb == p.ncb - 1;
   const unsigned m_bw = lastband ? p.m_bwl : p.m_bw;
-  const int i_lo = udivm(p0, bw, m_bw), i_hi = udivm(p1 - 1, bw, m_bw);
+  const int i_lo = udivm1(p0, bw, m_bw), i_hi = udivm1(p1 - 1, bw, m_bw);
   const int rows_in = (i_hi - i_lo) * p.a + span_y;
   const int iy0 = i_lo * p.a + p.dy_min;
   const int ix0 = j0 * p.a + p.dx_min;
@@ -283,7 +257,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv_bf16_kernel(const ConvBf16Pa
     const int pp = p0 + (wave * NW + n) * 32 + l31;
     pvalid[n] = pp < p1;
     const int pc = pvalid[n] ? pp : (p1 - 1);
-    const int i = udivm(pc, bw, m_bw), j = pc - i * bw;
+    const int i = udivm1(pc, bw, m_bw), j = pc - i * bw;
     boff[n] = ((i - i_lo) * p.a) * lw + j * p.a;
     if constexpr (S2D) {
       opix[n] = (2 * i + py) * p.OW + 2 * (j0 + j);
@@ -437,7 +411,6 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv_bf16_kernel(const ConvBf16Pa
     // source byte offset of each is decoded ONCE; image borders, tile tails and unused slices become out-of-range offsets,
     // which the buffer unit turns into zeros written to LDS.  A chunk then costs one `buffer_load_dwordx4 ... lds` per slot
     // with the chunk's base in the scalar offset.
-    constexpr unsigned OOB = 0x80000000u;
     const int ni = p.ni_slots, ns = p.n_slots;
     const int wtotal = total - itotal;
     i32x16 voffv = {};  // the slot offsets: a register vector, so that a slot can also be picked at run time (relative indexing)
@@ -483,7 +456,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv_bf16_kernel(const ConvBf16Pa
           voffv[i] = wok ? wi_ * 16 : (int)OOB;
         }
         if (!BF_DBG(4))
-          bf_dma16x5<NT * 16>(bf_make_rsrc(p.wp, p.T * p.Kb * p.Mpad * 16), (unsigned)(wave * 64 * 16) + (unsigned)(5 * NT * 16), 0, voffv[5], voffv[6],
+          bf_dma16x5<NT * 16>(rsrc(p.wp, p.T * p.Kb * p.Mpad * 16), (unsigned)(wave * 64 * 16) + (unsigned)(5 * NT * 16), 0, voffv[5], voffv[6],
                               voffv[7], voffv[8], voffv[9]);
       }
 #pragma unroll
@@ -509,8 +482,8 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv_bf16_kernel(const ConvBf16Pa
     }
     const int ibytes = p.Kb * p.IH * p.IW * 16, wbytes = p.T * p.Kb * p.Mpad * 16;
     const int so_i = p.CKb * p.IH * p.IW * 16, so_w = p.CKb * p.Mpad * 16;
-    const auto rs_i = __builtin_amdgcn_make_buffer_rsrc((void*)inb, (short)0, ibytes, 0x00020000);
-    const auto rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.wp, (short)0, wbytes, 0x00020000);
+    const auto rs_i = __builtin_amdgcn_make_buffer_rsrc((void*)inb, (short)0, ibytes, RSRC_WORD3);
+    const auto rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.wp, (short)0, wbytes, RSRC_WORD3);
 #if defined(__HIP_DEVICE_COMPILE__)  // LDS address space and the DMA builtin exist in the device pass only
     typedef __attribute__((address_space(3))) void* lds_ptr_t;
 #define DMA_ISSUE(C)                                                                                                   \
@@ -550,7 +523,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv_bf16_kernel(const ConvBf16Pa
   {                                                                                                                    \
     const int i_ = (I);                                                                                                \
     const bool isw_ = i_ >= ni;                                                                                        \
-    const auto rs_ = __builtin_amdgcn_make_buffer_rsrc(isw_ ? (void*)p.wp : (void*)inb, (short)0, isw_ ? wbytes : ibytes, 0x00020000); \
+    const auto rs_ = __builtin_amdgcn_make_buffer_rsrc(isw_ ? (void*)p.wp : (void*)inb, (short)0, isw_ ? wbytes : ibytes, RSRC_WORD3); \
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_, (lds_ptr_t)(smem4 + ((C) & 1) * p.bufs + wave * 64 + i_ * NT), 16, voffv[i_],   \
                                              (C) * (isw_ ? so_w : so_i), 0, 0);                                        \
   }
@@ -570,7 +543,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv_bf16_kernel(const ConvBf16Pa
       static_assert(NWV == 8 && !S2D, "ping-pong needs two wavefronts per SIMD");
       constexpr int PS = 3;
       const int grp = wave >> 2;                 // 0: waves 0-3 (lead), 1: waves 4-7 (one phase behind) -- scalar
-      const i32x4 rsi = bf_make_rsrc(inb, ibytes), rsw = bf_make_rsrc(p.wp, wbytes);
+      const i32x4 rsi = rsrc(inb, ibytes), rsw = rsrc(p.wp, wbytes);
       const unsigned bufbytes = (unsigned)p.bufs * 16u;
       const unsigned a_b0 = (unsigned)(p.ldsw_off + a_vu) * 16u;
       unsigned b_b0[NW][3];
@@ -686,7 +659,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv_bf16_kernel(const ConvBf16Pa
       if (p.ring) {
         ring_done = true;
         constexpr int NB = 4, D = 3;  // buffers, chunks in flight (5 DMA pieces per chunk and wavefront: the counted waits below)
-        const i32x4 rsi = bf_make_rsrc(inb, ibytes), rsw = bf_make_rsrc(p.wp, wbytes);
+        const i32x4 rsi = rsrc(inb, ibytes), rsw = rsrc(p.wp, wbytes);
         const unsigned bufbytes = (unsigned)p.bufs * 16u;
         const unsigned la0 = (unsigned)(wave * 64 * 16);
         const unsigned char* lds_b = reinterpret_cast<const unsigned char*>(smem4);
@@ -752,7 +725,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv_bf16_kernel(const ConvBf16Pa
               __builtin_amdgcn_sched_barrier(0);
             };
             __builtin_amdgcn_sched_barrier(0);
-            bf_static_for(step, std::make_integer_sequence<int, NTAP>{});
+            static_for(step, std::make_integer_sequence<int, NTAP>{});
           }
         };
         if (py) chunks(std::integral_constant<int, 1>{});
@@ -920,7 +893,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv_bf16_kernel(const ConvBf16Pa
   const bool write_signs = (REF == 3 || (SIGN_OUT && p.signs != nullptr)) && !BF_DBG(512);  // uniform  (diagnostic bit 512: no sign map)
   unsigned sg[(REF == 2 || SIGN_OUT) ? NC : 1][NW][SW];
   if constexpr (REF == 2) {
-    const auto rs_s = __builtin_amdgcn_make_buffer_rsrc((void*)(p.signs + (size_t)b * plane * 2 * sq), (short)0, (int)plane * 2 * sq, 0x00020000);
+    const auto rs_s = __builtin_amdgcn_make_buffer_rsrc((void*)(p.signs + (size_t)b * plane * 2 * sq), (short)0, (int)plane * 2 * sq, RSRC_WORD3);
 #pragma unroll
     for (int c = 0; c < NC; ++c)
 #pragma unroll
@@ -979,7 +952,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv_bf16_kernel(const ConvBf16Pa
     constexpr bool has_ref = REF == 1 || REF == 2;  // act'(ref) epilogue (training data gradient into a block without BatchNorm)
     constexpr bool sign_ref = REF == 2;  // ... with the LeakyReLU sign map in place of the bf16 reference
     const int plane16 = (int)plane * 16;
-    const auto rs_o = __builtin_amdgcn_make_buffer_rsrc((void*)(p.out + (size_t)b * p.Mb * plane * 2), (short)0, p.Mb * plane16, 0x00020000);
+    const auto rs_o = __builtin_amdgcn_make_buffer_rsrc((void*)(p.out + (size_t)b * p.Mb * plane * 2), (short)0, p.Mb * plane16, RSRC_WORD3);
     // cache policy of the bf16 output stores: non-temporal for the sign-writing forward of the 4-wavefront tiles (layer 1 forward: 1.8 GB out per
     // 0.8 GB in, -5.3 % in the same-box A/B gpurun_out/r5_nt_ab3.log); everywhere else it made no difference or lost (head data gradient +43 %)
 #ifndef BF_NT_L1
@@ -1009,7 +982,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv_bf16_kernel(const ConvBf16Pa
     constexpr bool RF_PER_GP = MW == 1;
     u32x2 rf[REF == 1 ? MW : 1][RF_PER_GP ? 1 : 2][NC][NW][2];
     if constexpr (REF == 1 && !RF_PER_GP) {
-      const auto rs_r = __builtin_amdgcn_make_buffer_rsrc((void*)(p.act_ref + (size_t)b * p.Mb * plane * 2), (short)0, p.Mb * plane16, 0x00020000);
+      const auto rs_r = __builtin_amdgcn_make_buffer_rsrc((void*)(p.act_ref + (size_t)b * p.Mb * plane * 2), (short)0, p.Mb * plane16, RSRC_WORD3);
 #pragma unroll
       for (int mb = 0; mb < MW; ++mb)
 #pragma unroll
@@ -1054,7 +1027,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv_bf16_kernel(const ConvBf16Pa
 #include "conv_bf16_epi_groups.inc"
     }
     if constexpr (SIGN_OUT) if (write_signs) {  // the sign bytes of a pixel go out together
-      const auto rs_s = __builtin_amdgcn_make_buffer_rsrc((void*)(p.signs + (size_t)b * plane * 2 * sq), (short)0, (int)plane * 2 * sq, 0x00020000);
+      const auto rs_s = __builtin_amdgcn_make_buffer_rsrc((void*)(p.signs + (size_t)b * plane * 2 * sq), (short)0, (int)plane * 2 * sq, RSRC_WORD3);
 #pragma unroll
       for (int c = 0; c < NC; ++c)
 #pragma unroll

@@ -14,7 +14,7 @@
 // kx = px + 1 (mod 2): 1 + 2 + 2 + 4 tap-GEMMs per 2x2 output quad).  A tile = 32 consecutive quads (= dy pixels) of an image: 4 accumulator
 // tiles (py, px), per 16-channel step four pixel operands (the quad's dy pixel and its right / lower / diagonal neighbours) serve the nine
 // taps.  Epilogue as the tiled kernel: x channel scale [x LeakyReLU'(sign bit)], bf16, half-wave exchange, 16-byte stores.
-#include "common.h"
+#include "bf16_dev.h"
 // cache policy of the output stores: 2 = nt (non-temporal).  The 1.6 GB a launch writes are read again by a later kernel, long after they
 // left the 4 MB L2: stored as ordinary lines they push the gradient rows the tiles of the next quad row (and the partner pass) are about
 // to read out of it.  Same-box A/B (gpurun_out/r5_nt_ab1.log, r5_nt_ab2.log): L4 -8.5 ... -10 %, L2 -5 % (A/B variant builds: 0 = cached)
@@ -25,9 +25,6 @@
 #ifndef DD_ABL
 #define DD_ABL 0   // (ablation variant builds: 1 = no stores, 2 = no MFMAs, 4 = no operand loads, 8 = no weight reads)
 #endif
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct ConvDirectS2dParams {
   const u32x4* in;    // dy: bf16 NCHW8c [B][Kb][IH][IW] units
@@ -41,9 +38,6 @@ struct ConvDirectS2dParams {
   unsigned m_iw, m_tpi;         // ceil(2^32 / d) magic numbers of IW and tiles_per_img
 };
 
-namespace {
-__device__ __forceinline__ int dd_udivm1(int n, int d, unsigned m) { return d == 1 ? n : (int)__umulhi((unsigned)n, m); }
-}  // namespace
 
 // NK: 16-channel steps of the contraction (K / 16); NMB: 32-channel blocks of dx per wavefront tile (1: 4 wavefronts per workgroup, four
 // workgroups per CU; 2: 8 wavefronts, ONE workgroup per CU whose 147 KB of LDS hold the nine slices of 64 of the 128 channels -- the other
@@ -53,7 +47,6 @@ template <int NK, int NMB, bool SIGNS>
 __global__ __launch_bounds__(256 * NMB) __attribute__((amdgpu_waves_per_eu(NMB == 1 ? 4 : 2, NMB == 1 ? 4 : 2))) void conv_bf16_s2d_direct_kernel(
     const ConvDirectS2dParams p) {
   extern __shared__ __attribute__((aligned(16))) u32x4 lds_w[];   // [9][2 NK][32 NMB] units, then [wavefronts][32 NMB] fp32 channel scales
-  constexpr int OOB = (int)0x80000000u;
   constexpr int KB = 2 * NK, MP = 32 * NMB, NT = 256 * NMB, NWV = 4 * NMB;
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, half = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -86,24 +79,24 @@ __global__ __launch_bounds__(256 * NMB) __attribute__((amdgpu_waves_per_eu(NMB =
   };
   auto geo_of = [&](int tile) __attribute__((always_inline)) {
     Geo g;
-    g.b = dd_udivm1(tile, p.tiles_per_img, p.m_tpi);
+    g.b = udivm1(tile, p.tiles_per_img, p.m_tpi);
     const int t = tile - g.b * p.tiles_per_img;
     const int q = t * 32 + l31;
     g.qv = q < nq;
     const int qc = g.qv ? q : nq - 1;
-    const int a = dd_udivm1(qc, IW, p.m_iw), c = qc - a * IW;
+    const int a = udivm1(qc, IW, p.m_iw), c = qc - a * IW;
     const bool cx = c + 1 < IW, cy = a + 1 < IH;   // the right / lower dy neighbour exists
     g.vx = 2 * c + 1 < OW; g.vy = 2 * a + 1 < OH;
     const int v00 = (a * IW + c) * 16 + half * kcb;
-    g.vsh[0] = v00; g.vsh[1] = cx ? v00 + 16 : OOB; g.vsh[2] = cy ? v00 + IW * 16 : OOB; g.vsh[3] = (cx && cy) ? v00 + IW * 16 + 16 : OOB;
+    g.vsh[0] = v00; g.vsh[1] = cx ? v00 + 16 : (int)OOB; g.vsh[2] = cy ? v00 + IW * 16 : (int)OOB; g.vsh[3] = (cx && cy) ? v00 + IW * 16 + 16 : (int)OOB;
     g.pix = 2 * a * OW + 2 * c;
     return g;
   };
   u32x4 Bq[2][4];
   auto load_step = [&](const Geo& g, int kc, u32x4 (&dst)[4]) __attribute__((always_inline)) {
-    const auto rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + (size_t)g.b * KB * IH * IW), (short)0, KB * kcb, 0x00020000);
+    const auto rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + (size_t)g.b * KB * IH * IW), (short)0, KB * kcb, RSRC_WORD3);
 #pragma unroll
-    for (int s = 0; s < 4; ++s) dst[s] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, (DD_ABL & 4) ? OOB : g.vsh[s], (2 * kc) * kcb, 0));
+    for (int s = 0; s < 4; ++s) dst[s] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, (DD_ABL & 4) ? (int)OOB : g.vsh[s], (2 * kc) * kcb, 0));
   };
   static_assert(NK % 2 == 0, "the first operand set of the NEXT tile is requested while the last step still reads the second");
   const int tstep = nslot * NWV;
@@ -113,19 +106,19 @@ __global__ __launch_bounds__(256 * NMB) __attribute__((amdgpu_waves_per_eu(NMB =
   for (; tile < t_end; tile += tstep) {
     const int b = G.b, pix = G.pix;
     const bool qv = G.qv, vx = G.vx, vy = G.vy;
-    const auto rs_o = __builtin_amdgcn_make_buffer_rsrc((void*)(p.out + (size_t)b * p.Mb * plane), (short)0, p.Mb * plane16, 0x00020000);
+    const auto rs_o = __builtin_amdgcn_make_buffer_rsrc((void*)(p.out + (size_t)b * p.Mb * plane), (short)0, p.Mb * plane16, RSRC_WORD3);
     // the epilogue's small inputs first (they are older than the operand loads: landed when the MFMAs are through)
     float my_s = 0.f;   // lanes < MP: the scale of channel ch0 + lane (1 without a scale, 0 for the padding channels)
     if (lane < MP) my_s = ch0 + lane < p.M ? (p.chan_scale != nullptr ? p.chan_scale[(size_t)b * p.M + ch0 + lane] : 1.f) : 0.f;
     unsigned sg[2][2] = {{0u, 0u}, {0u, 0u}};   // byte j = the lane's sign bits of channel group 2 pass NMB + j
     if constexpr (SIGNS) {
-      const auto rs_s = __builtin_amdgcn_make_buffer_rsrc((void*)(p.signs + (size_t)b * plane * 2 * sq), (short)0, plane * 2 * sq, 0x00020000);
+      const auto rs_s = __builtin_amdgcn_make_buffer_rsrc((void*)(p.signs + (size_t)b * plane * 2 * sq), (short)0, plane * 2 * sq, RSRC_WORD3);
 #pragma unroll
       for (int py = 0; py < 2; ++py)
 #pragma unroll
         for (int px = 0; px < 2; ++px) {
           const bool ok = qv && (px == 0 || vx) && (py == 0 || vy);
-          const int vs = ok ? (half * plane + pix + py * OW + px) * sq + pass * 2 * NMB : OOB;
+          const int vs = ok ? (half * plane + pix + py * OW + px) * sq + pass * 2 * NMB : (int)OOB;
           if constexpr (NMB == 2) sg[py][px] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rs_s, vs, 0, 0);
           else sg[py][px] = (unsigned)__builtin_amdgcn_raw_buffer_load_b16(rs_s, vs, 0, 0);
         }
@@ -200,13 +193,7 @@ __global__ __launch_bounds__(256 * NMB) __attribute__((amdgpu_waves_per_eu(NMB =
 #pragma unroll
             for (int i = 0; i < 8; ++i) v[i] = fmaf(acc[mb][py][px][8 * gp + i], sa[i], 0.f * sa[i]);
           }
-          bf16x8 o;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) o[i] = (__bf16)v[i];
-          const u32x4 w = __builtin_bit_cast(u32x4, o);
-          const auto r0 = __builtin_amdgcn_permlane32_swap(w.x, w.z, false, false);
-          const auto r1 = __builtin_amdgcn_permlane32_swap(w.y, w.w, false, false);
-          un[px] = u32x4{r0[0], r1[0], r0[1], r1[1]};
+          un[px] = pack_unit_swap(v);
         }
         // a second exchange makes every store a CONTIGUOUS kilobyte: lanes 0-31 the even pixel, lanes 32-63 the odd pixel of ONE channel
         // block (un[0]'s upper half-wave = (px 0, block cb + 1) trades places with un[1]'s lower half-wave = (px 1, block cb))
@@ -223,7 +210,7 @@ __global__ __launch_bounds__(256 * NMB) __attribute__((amdgpu_waves_per_eu(NMB =
         const bool okp = qv && (half == 0 || vx) && (py == 0 || vy);
 #pragma unroll
         for (int e = 0; e < 2; ++e)
-          __builtin_amdgcn_raw_buffer_store_b128(se[e], rs_o, (okp && cb + e < p.Mb && !(DD_ABL & 1)) ? (pix + py * OW + half) * 16 + (cb + e) * plane16 : OOB, 0, YOGO_ST_AUX);
+          __builtin_amdgcn_raw_buffer_store_b128(se[e], rs_o, (okp && cb + e < p.Mb && !(DD_ABL & 1)) ? (pix + py * OW + half) * 16 + (cb + e) * plane16 : (int)OOB, 0, YOGO_ST_AUX);
       }
     }
   }

@@ -7,7 +7,7 @@
         const int cb = (m0 >> 3) + mb * 4 + 2 * gp;  // channel block the lower half-wave stores (uniform); Mb is even
         if (cb >= p.Mb) continue;
         if constexpr (REF == 1 && RF_PER_GP) {
-          const auto rs_r = __builtin_amdgcn_make_buffer_rsrc((void*)(p.act_ref + (size_t)b * p.Mb * plane * 2), (short)0, p.Mb * plane16, 0x00020000);
+          const auto rs_r = __builtin_amdgcn_make_buffer_rsrc((void*)(p.act_ref + (size_t)b * p.Mb * plane * 2), (short)0, p.Mb * plane16, RSRC_WORD3);
 #pragma unroll
           for (int c = 0; c < NC; ++c)
 #pragma unroll
@@ -59,14 +59,14 @@
                 }
               }
               if (p.out_pre != nullptr) {  // the pre-activation goes out through the same 16-byte-unit exchange
-                bf16x8 po;
+                bf16x8 po;   // (bf16_dev.h's pack_unit_swap, open-coded here and below: through the call hipcc orders these epilogues' arithmetic differently)
 #pragma unroll
                 for (int i = 0; i < 8; ++i) po[i] = (__bf16)v[i];
                 const u32x4 pw = __builtin_bit_cast(u32x4, po);
                 const auto q0 = __builtin_amdgcn_permlane32_swap(pw.x, pw.z, false, false);
                 const auto q1 = __builtin_amdgcn_permlane32_swap(pw.y, pw.w, false, false);
                 const u32x4 pst = {q0[0], q1[0], q0[1], q1[1]};
-                const auto rs_p = __builtin_amdgcn_make_buffer_rsrc((void*)(p.out_pre + (size_t)b * p.Mb * plane * 2), (short)0, p.Mb * plane16, 0x00020000);
+                const auto rs_p = __builtin_amdgcn_make_buffer_rsrc((void*)(p.out_pre + (size_t)b * p.Mb * plane * 2), (short)0, p.Mb * plane16, RSRC_WORD3);
                 __builtin_amdgcn_raw_buffer_store_b128(pst, rs_p, vo[c][n] + cb * plane16, 0, 0);
               }
               if constexpr (sign_ref) {  // (the launcher only takes the sign map for LeakyReLU)
@@ -129,8 +129,7 @@
               } else if (leaky) {  // max(v, 0.01 v) as a bare v_max_f32 (fmaxf would first quiet both operands: two more instructions per value)
 #pragma unroll
                 for (int i = 0; i < 8; i += 2) {
-                  typedef float f32x2_t __attribute__((ext_vector_type(2)));
-                  const f32x2_t sv = (f32x2_t){v[i], v[i + 1]} * (f32x2_t){LEAKY_SLOPE, LEAKY_SLOPE};  // one v_pk_mul_f32
+                  const f32x2 sv = (f32x2){v[i], v[i + 1]} * (f32x2){LEAKY_SLOPE, LEAKY_SLOPE};  // one v_pk_mul_f32
                   asm("v_max_f32 %0, %1, %2" : "=v"(v[i]) : "v"(v[i]), "v"(sv.x));
                   asm("v_max_f32 %0, %1, %2" : "=v"(v[i + 1]) : "v"(v[i + 1]), "v"(sv.y));
                 }
@@ -141,6 +140,7 @@
               // byte = sum of (v[i] > 0) << i: the compare leaves its result in vcc and an add-with-carry shifts it into the
               // byte (m = 2 m + carry), values taken from 7 down to 0 -- two vector instructions per value where the compare /
               // select / shift-or form takes three (these tiles are bound by vector-instruction issue)
+              // (bf16_dev.h's sign_byte, one statement per value here: hipcc schedules between them)
               unsigned mA = 0;
               constexpr unsigned mB = 0;
 #pragma unroll

@@ -11,10 +11,7 @@
 //   (decode_loss.hip) calls -- this file is built with -ffp-contract=off like that one -- so `model(x)` in eval mode gets the bits the two launches gave
 //   and the raw head output never goes through memory.
 #include "head_math.h"
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "bf16_dev.h"
 
 struct ConvHeadParams {
   const u32x4* in;     // bf16 NCHW8c [B][Kb][plane] units
@@ -31,14 +28,10 @@ struct ConvHeadParams {
   int inference;       // class channels: softmax (1) or raw logits (0)
 };
 
-namespace {
-__device__ __forceinline__ int ch_udivm1(int n, int d, unsigned m) { return d == 1 ? n : (int)__umulhi((unsigned)n, m); }
-}  // namespace
 
 // NK: 16-channel steps of the contraction (K / 16, <= 8); M <= 32 (DEC: 6 <= M <= 16)
 template <int NK, bool DEC = false>
 __global__ __launch_bounds__(256) void conv_bf16_1x1_f32_kernel(const ConvHeadParams p) {
-  constexpr int OOB = (int)0x80000000u;
   constexpr int KB = 2 * NK;
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, half = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -60,11 +53,11 @@ __global__ __launch_bounds__(256) void conv_bf16_1x1_f32_kernel(const ConvHeadPa
   }
   const int nwaves = gridDim.x * 4;
   for (int tile = blockIdx.x * 4 + wave; tile < p.ntiles; tile += nwaves) {
-    const int b = ch_udivm1(tile, p.tiles_per_img, p.m_tpi);
+    const int b = udivm1(tile, p.tiles_per_img, p.m_tpi);
     const int px = (tile - b * p.tiles_per_img) * 32 + l31;
     const bool ov = px < plane;
-    const auto rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + (size_t)b * KB * plane), (short)0, KB * plane16, 0x00020000);
-    const int v0 = ov ? (half * plane + px) * 16 : OOB;
+    const auto rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + (size_t)b * KB * plane), (short)0, KB * plane16, RSRC_WORD3);
+    const int v0 = ov ? (half * plane + px) * 16 : (int)OOB;
     u32x4 Bq[NK];
 #pragma unroll
     for (int kc = 0; kc < NK; ++kc) Bq[kc] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, v0, (2 * kc) * plane16, 0));

@@ -14,12 +14,7 @@
 // row apart ([33 even | 33 odd]) so that a tap's 32 pixels read 32 consecutive units (conv_bf16_ws3.h).  Products accumulate chunk-major /
 // tap-minor as conv_bf16_kernel with 16-channel chunks does (bit-identical); the epilogue is its lean form: fma(acc, scale, bias * scale),
 // LeakyReLU as max(v, 0.01 v), the sign map of the result, bf16, half-wave exchange, 512 contiguous bytes per half-wave and store.
-#include "common.h"
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "bf16_dev.h"
 
 #define CS_MAXDMA 16   // LDS-DMA pieces of a tile: ceil(2 NK x 3 x ROWU / 64)
 
@@ -36,25 +31,18 @@ struct ConvStagedParams {
 };
 
 namespace {
-__device__ __forceinline__ int cs_udivm1(int n, int d, unsigned m) { return d == 1 ? n : (int)__umulhi((unsigned)n, m); }
-__device__ __forceinline__ unsigned cs_u(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
 // One LDS-DMA piece: 64 lanes x 16 bytes from (descriptor, per-lane byte offset) to LDS bytes [lds_addr, lds_addr + 1024).  From inline asm:
 // hipcc would make every later LDS read wait for all of its own LDS-DMA loads AND stores (vmcnt(0)) wherever it liked; cs_wait_dma() below
 // is the one place this kernel waits.
 __device__ __forceinline__ void cs_dma16(i32x4 rs, unsigned lds_addr, int voff) {
   unsigned keep;
-  rs = i32x4{(int)cs_u((unsigned)rs.x), (int)cs_u((unsigned)rs.y), (int)cs_u((unsigned)rs.z), (int)cs_u((unsigned)rs.w)};
-  lds_addr = cs_u(lds_addr);
+  rs = uniform4(rs); lds_addr = uniform(lds_addr);
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
                : "=&s"(keep)
                : "v"(voff), "s"(lds_addr), "s"(rs)
                : "memory");
 }
 __device__ __forceinline__ void cs_wait_dma() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ i32x4 cs_rsrc(const void* ptr, unsigned bytes) {
-  const unsigned long long a = reinterpret_cast<unsigned long long>(ptr);
-  return i32x4{(int)(unsigned)a, (int)((unsigned)(a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
 }  // namespace
 
 // S: stride; NK: 16-channel steps of the contraction (1 or 2); NMB: 32-channel blocks of the output (1 or 2); NWV: wavefronts per workgroup;
@@ -63,7 +51,6 @@ __device__ __forceinline__ i32x4 cs_rsrc(const void* ptr, unsigned bytes) {
 template <int S, int NK, int NMB, bool SIGN_OUT, int NWV, int R, bool NTS>
 __global__ __launch_bounds__(64 * NWV) void conv_bf16_staged_kernel(const ConvStagedParams p) {
   extern __shared__ __attribute__((aligned(16))) u32x4 lds_u[];   // (the dynamic block starts at LDS address 0: LDS-DMA takes addresses, not pointers)
-  constexpr int OOB = (int)0x80000000u;
   constexpr int KB = 2 * NK, MP = 32 * NMB, WU = 9 * KB * MP, NT = 64 * NWV;
   constexpr int PW = 33;                       // stride 2: units of a column-parity plane of a staged row
   constexpr int ROWU = S == 2 ? 2 * PW : 34;   // units of a staged row
@@ -103,20 +90,20 @@ __global__ __launch_bounds__(64 * NWV) void conv_bf16_staged_kernel(const ConvSt
   const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslot = gridDim.x >> 3;
   const int t8 = (p.ntiles + 7) >> 3, t_end = min(p.ntiles, (xcd + 1) * t8);
   for (int tile = xcd * t8 + slot * NWV + wave; tile < t_end; tile += nslot * NWV) {
-    const int b = cs_udivm1(tile, p.tiles_per_img, p.m_tpi);
+    const int b = udivm1(tile, p.tiles_per_img, p.m_tpi);
     const int t = tile - b * p.tiles_per_img;
-    const int ty = cs_udivm1(t, p.tiles_per_row, p.m_tpr), ox0 = (t - ty * p.tiles_per_row) * 32;
+    const int ty = udivm1(t, p.tiles_per_row, p.m_tpr), ox0 = (t - ty * p.tiles_per_row) * 32;
     const int oy0 = ty * R;
     const int iy0 = oy0 * S - 1, ix0 = ox0 * S - 1;
     // ---- stage the tile image (zeros where the padding or the image border is: out-of-range offsets)
     {
-      const i32x4 rs_in = cs_rsrc(p.in + (size_t)b * KB * IH * IW, (unsigned)(KB * kcb));
+      const i32x4 rs_in = rsrc(p.in + (size_t)b * KB * IH * IW, (unsigned)(KB * kcb));
       const int base = (iy0 * IW + ix0) * 16;
 #pragma unroll
       for (int i = 0; i < NDMA; ++i) {
         const int r = (int)(rc[i] >> 16), c = (int)(rc[i] & 0xFFFFu);
         const bool ok = ((unsigned)(iy0 + r) < (unsigned)IH) && ((unsigned)(ix0 + c) < (unsigned)IW);   // (all ones: r = 65535 fails the row test)
-        cs_dma16(rs_in, my_tile_addr + (unsigned)i * 1024u, ok ? rel[i] + base : OOB);
+        cs_dma16(rs_in, my_tile_addr + (unsigned)i * 1024u, ok ? rel[i] + base : (int)OOB);
       }
     }
     // the tile's channel scales ride along (lanes < MP: the scale of channel `lane`; 1 without a scale, 0 for the padding channels)
@@ -155,7 +142,7 @@ __global__ __launch_bounds__(64 * NWV) void conv_bf16_staged_kernel(const ConvSt
       }
     __builtin_amdgcn_sched_barrier(0);
     // ---- epilogue: (mb, gp) -> one 16-byte store per lane: lanes 0-31 channel block 4 mb + 2 gp, lanes 32-63 the next one
-    const auto rs_o = __builtin_amdgcn_make_buffer_rsrc((void*)(p.out + (size_t)b * p.Mb * plane), (short)0, p.Mb * plane16, 0x00020000);
+    const auto rs_o = __builtin_amdgcn_make_buffer_rsrc((void*)(p.out + (size_t)b * p.Mb * plane), (short)0, p.Mb * plane16, RSRC_WORD3);
 #pragma unroll
     for (int rr = 0; rr < R; ++rr) {
     const bool ov = ox0 + l31 < OW && oy0 + rr < p.OH;
@@ -177,31 +164,30 @@ __global__ __launch_bounds__(64 * NWV) void conv_bf16_staged_kernel(const ConvSt
         if (leaky) {   // max(v, 0.01 v) as a bare v_max_f32 (conv_bf16_epi_groups.inc)
 #pragma unroll
           for (int i = 0; i < 8; i += 2) {
-            typedef float f32x2_t __attribute__((ext_vector_type(2)));
-            const f32x2_t sv = (f32x2_t){v[i], v[i + 1]} * (f32x2_t){LEAKY_SLOPE, LEAKY_SLOPE};
+            const f32x2 sv = (f32x2){v[i], v[i + 1]} * (f32x2){LEAKY_SLOPE, LEAKY_SLOPE};
             asm("v_max_f32 %0, %1, %2" : "=v"(v[i]) : "v"(v[i]), "v"(sv.x));
             asm("v_max_f32 %0, %1, %2" : "=v"(v[i + 1]) : "v"(v[i + 1]), "v"(sv.y));
           }
         }
-        if constexpr (SIGN_OUT) {   // byte = sum of (v[i] > 0) << i (compare into vcc, add-with-carry shifts it in: values 7 down to 0)
+        if constexpr (SIGN_OUT) {   // bf16_dev.h's sign_byte as eight statements (hipcc schedules between them; as one statement the ISA differs)
           unsigned m = 0;
 #pragma unroll
           for (int i = 7; i >= 0; --i) asm("v_cmp_lt_f32_e32 vcc, 0, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc" : "+v"(m) : "v"(v[i]) : "vcc");
           sg |= m << (8 * (2 * mb + gp));
         }
-        bf16x8 ob;
+        bf16x8 ob;   // (bf16_dev.h's pack_unit_swap, kept open-coded: through the call hipcc interleaves it differently with the sign statements)
 #pragma unroll
         for (int i = 0; i < 8; ++i) ob[i] = (__bf16)v[i];
         const u32x4 w = __builtin_bit_cast(u32x4, ob);
         const auto r0 = __builtin_amdgcn_permlane32_swap(w.x, w.z, false, false);
         const auto r1 = __builtin_amdgcn_permlane32_swap(w.y, w.w, false, false);
         const u32x4 st = {r0[0], r1[0], r0[1], r1[1]};
-        __builtin_amdgcn_raw_buffer_store_b128(st, rs_o, (ov && cb + half < p.Mb) ? o * 16 + (cb + half) * plane16 : OOB, 0, NTS ? 2 : 0);
+        __builtin_amdgcn_raw_buffer_store_b128(st, rs_o, (ov && cb + half < p.Mb) ? o * 16 + (cb + half) * plane16 : (int)OOB, 0, NTS ? 2 : 0);
       }
     if constexpr (SIGN_OUT) {
       constexpr int sq = 2 * NMB;   // sign bytes per (pixel, half-wave)
-      const auto rs_s = __builtin_amdgcn_make_buffer_rsrc((void*)(p.signs + (size_t)b * plane * 2 * sq), (short)0, plane * 2 * sq, 0x00020000);
-      const int vs = ov ? (half * plane + o) * sq : OOB;
+      const auto rs_s = __builtin_amdgcn_make_buffer_rsrc((void*)(p.signs + (size_t)b * plane * 2 * sq), (short)0, plane * 2 * sq, RSRC_WORD3);
+      const int vs = ov ? (half * plane + o) * sq : (int)OOB;
       if constexpr (NMB == 2) __builtin_amdgcn_raw_buffer_store_b32(sg, rs_s, vs, 0, 0);
       else __builtin_amdgcn_raw_buffer_store_b16((unsigned short)sg, rs_s, vs, 0, 0);
     }

@@ -23,13 +23,7 @@
 //     One barrier per chunk orders everything: DMA landed (loaders wait vmcnt first), staging written (compute waits
 //     lgkmcnt), staging read, buffers free.
 #include "conv_bf16_ws.h"
-#include <type_traits>
-#include <utility>
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "bf16_dev.h"
 
 // The eight 32x32 accumulator tiles of a compute wavefront are a[0:127], OWNED BY THE ASM STATEMENTS: named literally and listed
 // as clobbers, so the kernel descriptor allocates them.  A clobber does not reserve a register, though: in the seam hipcc may park
@@ -39,7 +33,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 // (sched_barrier between its groups), and build.sh AUDITS the assembly of this file: no compiler v_accvgpr_* outside the asm
 // statements, .vgpr_spill_count 0, no scratch (cdna_hip_programming.md 5.7 item 4).
 // accumulator tile (mb, n) = a[16 * (2 mb + n) : +15]
-#define WS_ACC_CLOBBER "a0","a1","a2","a3","a4","a5","a6","a7","a8","a9","a10","a11","a12","a13","a14","a15","a16","a17","a18","a19","a20","a21","a22","a23","a24","a25","a26","a27","a28","a29","a30","a31","a32","a33","a34","a35","a36","a37","a38","a39","a40","a41","a42","a43","a44","a45","a46","a47","a48","a49","a50","a51","a52","a53","a54","a55","a56","a57","a58","a59","a60","a61","a62","a63","a64","a65","a66","a67","a68","a69","a70","a71","a72","a73","a74","a75","a76","a77","a78","a79","a80","a81","a82","a83","a84","a85","a86","a87","a88","a89","a90","a91","a92","a93","a94","a95","a96","a97","a98","a99","a100","a101","a102","a103","a104","a105","a106","a107","a108","a109","a110","a111","a112","a113","a114","a115","a116","a117","a118","a119","a120","a121","a122","a123","a124","a125","a126","a127"
+#define WS_ACC_CLOBBER ACC_A0_63, ACC_A64_127
 // compile-time ablations (build.sh variant TAG conv_bf16_ws -DWS_ABL=bits; timings only, the results are wrong): see WS_ABLATE below;
 // 256 = every 32x32x16 MFMA becomes two 16x16x32 MFMAs on eight of its sixteen accumulator registers (same operand registers, same
 // FLOPs, same LDS reads: the in-situ test of the clock the other MFMA shape holds, MI355X_MICROARCH.md "DVFS give-back" item 7)
@@ -63,31 +57,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
-__device__ __forceinline__ int ws_udivm(int n, unsigned m) { return (int)__umulhi((unsigned)n, m); }   // n / d, m = ceil(2^32 / d), d > 1
-__device__ __forceinline__ int ws_udivm1(int n, int d, unsigned m) { return d == 1 ? n : (int)__umulhi((unsigned)n, m); }
-// lane index, re-derived at every use (volatile: never merged with an earlier copy that would have to stay live or be spilled)
-__device__ __forceinline__ int ws_lane() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
-__device__ __forceinline__ i32x4 ws_rsrc(const void* ptr, unsigned bytes) {
-  const unsigned long long a = reinterpret_cast<unsigned long long>(ptr);
-  return i32x4{(int)(unsigned)a, (int)((unsigned)(a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-// one LDS-DMA piece (64 lanes x 16 bytes -> LDS bytes [lds, lds + 1024))
-__device__ __forceinline__ void ws_dma1(i32x4 rs, unsigned lds, int voff, unsigned soff) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 4\n\tbuffer_load_dwordx4 %0, %2, %3 offen lds" ::"v"(voff), "s"(lds), "s"(rs), "s"(soff) : "memory");
-}
-// four pieces of one descriptor with one scalar offset: LDS destinations lds + k * 4 KB (the input slots of a chunk)
-__device__ __forceinline__ void ws_dma4(i32x4 rs, unsigned lds, int v0, int v1, int v2, int v3, unsigned soff) {
-  asm volatile(
-      "s_mov_b32 m0, %5\n\ts_nop 4\n\tbuffer_load_dwordx4 %0, %4, %6 offen lds\n\t"
-      "s_add_u32 m0, m0, 4096\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %4, %6 offen lds\n\t"
-      "s_add_u32 m0, m0, 4096\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %4, %6 offen lds\n\t"
-      "s_add_u32 m0, m0, 4096\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %4, %6 offen lds"
-      ::"v"(v0), "v"(v1), "v"(v2), "v"(v3), "s"(rs), "s"(lds), "s"(soff) : "memory", "scc");
-}
 // nine pieces of one descriptor with one per-lane offset: LDS destinations lds + j * 4 KB, scalar offsets soff + j * step (the
 // weight slices of the nine taps): three scalar instructions per piece -- a loader beside an MFMA-saturating partner issues
 // about one instruction per 10 cycles, whatever its kind
@@ -100,19 +69,6 @@ __device__ __forceinline__ void ws_dma9(i32x4 rs, unsigned lds, int voff, unsign
                : "memory", "scc");
 #undef WS_P9
 }
-// 64 lanes x 4 bytes -> LDS bytes [lds, lds + 256)
-__device__ __forceinline__ void ws_dma_dword(i32x4 rs, unsigned lds, int voff, unsigned soff) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 4\n\tbuffer_load_dword %0, %2, %3 offen lds" ::"v"(voff), "s"(lds), "s"(rs), "s"(soff) : "memory");
-}
-__device__ __forceinline__ void ws_store16(u32x4 data, int voff, i32x4 rs, unsigned soff) {
-  asm volatile("s_nop 4\n\tbuffer_store_dwordx4 %0, %1, %2, %3 offen" ::"v"(data), "v"(voff), "s"(rs), "s"(soff) : "memory");   // (s_nop: descriptor from v_readfirstlane)
-}
-
-template <class F, int... I>
-__device__ __forceinline__ void ws_static_for(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-
 // ---- the asm statements of a K step (tap) of a compute wavefront ---------------------------------------------------------
 // first half: accumulator rows mb = 0, 1 (4 MFMAs) with the 6 operand reads of the NEXT step in their gaps.  The reads are
 // retired by the lgkmcnt(0) that ends the second half (ws_sb), which names their destinations "+v".
@@ -178,18 +134,6 @@ __device__ __forceinline__ void ws_y8_last(const u32x4& a1, const u32x4& a2, con
                : [a1] "v"(a1), [a2] "v"(a2), [a3] "v"(a3), [b0] "v"(b0), [b1] "v"(b1)
                : "memory", WS_ACC_CLOBBER);
 }
-// eight consecutive accumulator registers -> VGPRs in ONE statement (hipcc pads every asm statement with a wait state).  The
-// statement also CLOBBERS every accumulator register: hipcc then cannot keep a value of its own in an AGPR across any part of the
-// seam (a clobbered register holds nothing live across the statement)
-template <int R>
-__device__ __forceinline__ void ws_acc_read8(float (&r)[8]) {
-  asm volatile(
-      "v_accvgpr_read_b32 %0, a[%8]\n\tv_accvgpr_read_b32 %1, a[%8+1]\n\tv_accvgpr_read_b32 %2, a[%8+2]\n\tv_accvgpr_read_b32 %3, a[%8+3]\n\t"
-      "v_accvgpr_read_b32 %4, a[%8+4]\n\tv_accvgpr_read_b32 %5, a[%8+5]\n\tv_accvgpr_read_b32 %6, a[%8+6]\n\tv_accvgpr_read_b32 %7, a[%8+7]"
-      : "=v"(r[0]), "=v"(r[1]), "=v"(r[2]), "=v"(r[3]), "=v"(r[4]), "=v"(r[5]), "=v"(r[6]), "=v"(r[7])
-      : "n"(R)
-      : WS_ACC_CLOBBER);
-}
 
 // ---- group-major K steps (the first and the last chunk of a tile): ONE MFMA per statement, so that C++ code placed between the
 // statements -- the epilogue of the other half of the accumulators -- lands in the MFMA gaps.  Accumulator rows mb = 0, 1 are
@@ -247,7 +191,8 @@ __device__ __forceinline__ void ws_prefetch4(u32x4& an0, u32x4& an1, u32x4& bn0,
                : [pa] "v"(pa), [pb0] "v"(pb0), [pb1] "v"(pb1)
                : "memory");
 }
-// four consecutive accumulator registers -> VGPRs (see ws_acc_read8: the statement clobbers every accumulator register)
+// four consecutive accumulator registers -> VGPRs (the statement clobbers every accumulator register: hipcc then cannot keep a value
+// of its own in an AGPR across any part of the seam -- bf16_dev.h, acc_read8)
 template <int R>
 __device__ __forceinline__ void ws_acc_read4(float& r0, float& r1, float& r2, float& r3) {
 #if defined(WS_ABL) && (WS_ABL & 64)
@@ -299,7 +244,6 @@ template <int N> using WsIC = std::integral_constant<int, N>;
 template <int MODE>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_bf16_ws_kernel(const ConvWsParams p) {
   extern __shared__ __attribute__((aligned(16))) u32x4 smem4[];
-  constexpr unsigned OOB = 0x80000000u;
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int team = wave >> 2, tw = wave & 3;   // team 0 computes, team 1 loads; wavefronts tw and tw + 4 share a SIMD
@@ -318,11 +262,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (;; ++k) {
       const unsigned lin = slot + k * G;
       if (lin >= NV) return false;
-      const unsigned xcd = lin & 7;
+      const unsigned xcd = lin & 7;   // (bf16_dev.h's xcd_remap, kept open-coded: through the call hipcc numbers this kernel's SGPRs differently)
       const int widx = (int)((xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (lin >> 3));
-      const int b = ws_udivm1(widx, p.gx, p.m_gx);
+      const int b = udivm1(widx, p.gx, p.m_gx);
       const int bx = widx - b * p.gx;
-      const int cb = ws_udivm1(bx, p.tiles_per_band, p.m_tpb);
+      const int cb = udivm1(bx, p.tiles_per_band, p.m_tpb);
       const int tb = bx - cb * p.tiles_per_band;
       const int j0 = cb * p.TW;
       const int bw = min(p.TW, OW - j0);
@@ -337,11 +281,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   auto decode_pix = [&](const TileS& t, unsigned (&pbr)[2], int (&vo)[2], unsigned& lw16) {
     // (the lane's constants are re-derived from v_mbcnt: kept live across the tile loop -- or derived from threadIdx.x, which then
     //  has to stay live -- they cost registers the 256-register instantiations do not have and end up in scratch)
-    const int ln_ = ws_lane();
+    const int ln_ = lane_id();
     const int l31 = ln_ & 31, half = ln_ >> 5;
     const unsigned m_bw = t.lastband ? p.m_bwl : p.m_bw;
     const int bw = t.bw;   // >= 2 (planner)
-    const int i_lo = ws_udivm(t.p0, m_bw), i_hi = ws_udivm(t.p1 - 1, m_bw);
+    const int i_lo = udivm(t.p0, m_bw), i_hi = udivm(t.p1 - 1, m_bw);
     const int rows_in = i_hi - i_lo + 3;
     const int lw = bw + 2;
     const int per_kb = rows_in * lw;
@@ -351,7 +295,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       const int pp = t.p0 + (tw * 2 + n) * 32 + l31;
       const bool pv = pp < t.p1;
       const int pc = pv ? pp : (t.p1 - 1);
-      const int i = ws_udivm(pc, m_bw), j = pc - i * bw;
+      const int i = udivm(pc, m_bw), j = pc - i * bw;
       pbr[n] = (unsigned)((i - i_lo) * lw + j + half * per_kb) * 16u;
       vo[n] = pv ? (i * OW + t.j0 + j) * 16 + half * plane16 : (int)OOB;
     }
@@ -374,7 +318,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   if (team == 1) {
     // (lane indices are re-derived inside each role: a value of the prologue that both roles use stays live across the other
     //  role's code in hipcc's layout and is spilled there)
-    const int lane = ws_lane();
+    const int lane = lane_id();
     const int ttid = tw * 64 + lane;   // thread index inside the team
     if (WS_PRIO_LOADER) __builtin_amdgcn_s_setprio(WS_PRIO_LOADER);
     // =====================================================================================================================
@@ -385,14 +329,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const unsigned ibytes = (unsigned)p.Kb * kcb, obytes = 16u * plane16, wbytes = 9u * p.Kb * 2048u;
     const unsigned so_i = 2u * kcb;                  // bytes between the 16-channel chunks of an image
     const unsigned wstep = (unsigned)p.Kb * 2048u;   // bytes between the taps of the packed weights
-    const i32x4 rs_w = ws_rsrc(p.wp, wbytes);
+    const i32x4 rs_w = rsrc(p.wp, wbytes);
     const int lane16 = WS_DBG(4) ? (int)OOB : lane * 16;
     const int kbw = tw >> 1, colh = tw & 1;          // this wavefront's weight pieces: channel block of the chunk, column half
     const bool has_scale = p.chan_scale != nullptr;
-    const i32x4 rs_sc = ws_rsrc(p.chan_scale, has_scale ? (unsigned)p.B * 512u : 0u);
+    const i32x4 rs_sc = rsrc(p.chan_scale, has_scale ? (unsigned)p.B * 512u : 0u);
     auto issue_scale = [&](int b, int par) {   // [128] channel scale of image b -> es[par] (loaders 0 and 1, 64 floats each)
       if (has_scale && tw < 2)
-        ws_dma_dword(rs_sc, (unsigned)__builtin_amdgcn_readfirstlane(WS_ES + par * 512 + tw * 256), lane * 4,
+        dma_dword(rs_sc, (unsigned)__builtin_amdgcn_readfirstlane(WS_ES + par * 512 + tw * 256), lane * 4,
                      (unsigned)__builtin_amdgcn_readfirstlane((b * 128 + tw * 64) * 4));
     };
     // DMA source offsets of the 4 input slots: element ttid + i * 256 of the flattened [2][rows_in][lw] tile -> (channel
@@ -400,20 +344,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     auto decode_slots = [&](const TileS& t, int (&voff)[WS_NI]) {
       const unsigned m_bw = t.lastband ? p.m_bwl : p.m_bw;
       const int bw = t.bw;
-      const int i_lo = ws_udivm(t.p0, m_bw), i_hi = ws_udivm(t.p1 - 1, m_bw);
+      const int i_lo = udivm(t.p0, m_bw), i_hi = udivm(t.p1 - 1, m_bw);
       const int rows_in = i_hi - i_lo + 3;
       const int iy0 = i_lo - 1, ix0 = t.j0 - 1;
       const int lw = bw + 2;
       const int per_kb = rows_in * lw;
       const unsigned inv_lw = t.lastband ? p.m_lwl : p.m_lw;
       const unsigned inv_perkb = 0xFFFFFFFFu / (unsigned)per_kb + 1u;
-      const int skc = ws_udivm(WS_NT, inv_perkb);
+      const int skc = udivm(WS_NT, inv_perkb);
       const int srm = WS_NT - skc * per_kb;
-      const int sr = ws_udivm(srm, inv_lw);
+      const int sr = udivm(srm, inv_lw);
       const int sx = srm - sr * lw;
-      int kc_ = ws_udivm(ttid, inv_perkb);
+      int kc_ = udivm(ttid, inv_perkb);
       const int rm0 = ttid - kc_ * per_kb;
-      int r_ = ws_udivm(rm0, inv_lw);
+      int r_ = udivm(rm0, inv_lw);
       int x_ = rm0 - r_ * lw;
 #pragma unroll
       for (int i = 0; i < WS_NI; ++i) {
@@ -425,7 +369,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         if (r_ >= rows_in) { r_ -= rows_in; ++kc_; }
       }
     };
-    static_assert(WS_NI == 4, "ws_dma4 issues the four input slots");
+    static_assert(WS_NI == 4, "dma4 issues the four input slots");
     // weight slices of chunk cn (9 pieces of this wavefront) -> weight buffer cn & 1 (nchunk is even)
     auto req_w = [&](int cn) {
       const unsigned wb = (unsigned)(((2 * cn + kbw) * 128 + colh * 64) * 16);
@@ -433,7 +377,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     };
     // input tile of chunk cn of the tile described by (rs, voff) (4 pieces of this wavefront) -> input buffer ib
     auto req_i = [&](i32x4 rs, const int (&voff)[WS_NI], int cn, int ib) {
-      ws_dma4(rs, (unsigned)(WS_I0 + ib * WS_IB + tw * 64 * 16), voff[0], voff[1], voff[2], voff[3], (unsigned)cn * so_i);
+      dma4(rs, (unsigned)(WS_I0 + ib * WS_IB + tw * 64 * 16), voff[0], voff[1], voff[2], voff[3], (unsigned)cn * so_i);
     };
     // Output hand-over.  The 8 staged units of compute wavefront tw (units U0 .. U0 + 7; unit = 2 q + n, q = 2 mb + gp: channel
     // block 2 q, pixel group n) are read into registers in periods 1 and 3 and stored FOUR PER PERIOD (periods 1, 2, 3 and 0 of
@@ -442,7 +386,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const unsigned stg_rd = (unsigned)(WS_STG + tw * 4096 + lane * 16);
     u32x4 fifo[8];
     int f_vo[2] = {(int)OOB, (int)OOB};   // output offsets / descriptor / first unit of the tile the FIFO holds
-    i32x4 f_rs = ws_rsrc(p.out, 0u);
+    i32x4 f_rs = rsrc(p.out, 0u);
     int f_u0 = 0;
     auto fifo_fill = [&](int U0, const int (&vop)[2], i32x4 rs_o) {
       const unsigned char* base = reinterpret_cast<const unsigned char*>(smem4) + stg_rd;
@@ -453,13 +397,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     auto fifo_store4 = [&](auto h_tag) {   // units 4 h .. 4 h + 3 of the FIFO
       constexpr int Hh = decltype(h_tag)::value;
       // (the descriptor and the unit base travel through assignments hipcc cannot prove uniform)
-      const i32x4 rs = {__builtin_amdgcn_readfirstlane(f_rs.x), __builtin_amdgcn_readfirstlane(f_rs.y), __builtin_amdgcn_readfirstlane(f_rs.z),
-                        __builtin_amdgcn_readfirstlane(f_rs.w)};
+      const i32x4 rs = uniform4(f_rs);
       const int u0 = __builtin_amdgcn_readfirstlane(f_u0);
 #pragma unroll
       for (int u = 4 * Hh; u < 4 * Hh + 4; ++u) {
         const int q = (u0 + u) >> 1;
-        ws_store16(fifo[u], (u & 1) ? f_vo[1] : f_vo[0], rs, (unsigned)(2 * q) * (unsigned)plane16);
+        store16(fifo[u], (u & 1) ? f_vo[1] : f_vo[0], rs, (unsigned)(2 * q) * (unsigned)plane16);
       }
     };
 
@@ -468,9 +411,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     int vo[2], vo_prev[2] = {(int)OOB, (int)OOB};
     decode_slots(T, voff);
     decode_pix(T, pbr_, vo, lw16_);
-    i32x4 rs_in = ws_rsrc(reinterpret_cast<const unsigned char*>(p.in) + (size_t)T.b * ibytes, ibytes);
-    i32x4 rs_out = ws_rsrc(reinterpret_cast<unsigned char*>(p.out) + (size_t)T.b * obytes, obytes);
-    i32x4 rs_out_prev = ws_rsrc(p.out, 0u);
+    i32x4 rs_in = rsrc(reinterpret_cast<const unsigned char*>(p.in) + (size_t)T.b * ibytes, ibytes);
+    i32x4 rs_out = rsrc(reinterpret_cast<unsigned char*>(p.out) + (size_t)T.b * obytes, obytes);
+    i32x4 rs_out_prev = rsrc(p.out, 0u);
     int tpar = 0;
     issue_scale(T.b, 0);
     req_i(rs_in, voff, 0, 0);
@@ -537,8 +480,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
               for (int i = 0; i < WS_NI; ++i) asm volatile("" : : "v"(v2[i]));
             }
             decode_pix(Tn, pbr_, vo_n, lw16_);
-            rs_in_n = ws_rsrc(reinterpret_cast<const unsigned char*>(p.in) + (size_t)Tn.b * ibytes, ibytes);
-            rs_out_n = ws_rsrc(reinterpret_cast<unsigned char*>(p.out) + (size_t)Tn.b * obytes, obytes);
+            rs_in_n = rsrc(reinterpret_cast<const unsigned char*>(p.in) + (size_t)Tn.b * ibytes, ibytes);
+            rs_out_n = rsrc(reinterpret_cast<unsigned char*>(p.out) + (size_t)Tn.b * obytes, obytes);
           }
         }
         // the NEXT tile's geometry for the partner compute wavefront (same lanes, same pixels): written in period 1 -- the compute
@@ -598,7 +541,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // COMPUTE
   // =======================================================================================================================
   if (WS_PRIO_COMPUTE) __builtin_amdgcn_s_setprio(WS_PRIO_COMPUTE);
-  const int lane = ws_lane(), l31 = lane & 31, half = lane >> 5;
+  const int lane = lane_id(), l31 = lane & 31, half = lane >> 5;
   const unsigned a_b0 = (unsigned)(half * 128 + l31) * 16u;
   // staging address of this lane's 8 bytes of a unit's lower channel block (the upper block's are 512 B above)
   const unsigned stg_wr = (unsigned)(WS_STG + tw * 4096 + l31 * 16 + half * 8);
@@ -667,16 +610,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
               : "+v"(e_v[0]), "+v"(e_v[1]), "+v"(e_v[2]), "+v"(e_v[3]), "+v"(e_v[4]), "+v"(e_v[5]), "+v"(e_v[6]), "+v"(e_v[7])
               : "v"(sv[0]), "v"(sv[1]), "v"(sv[2]), "v"(sv[3]), "v"(sv[4]), "v"(sv[5]), "v"(sv[6]), "v"(sv[7]));
         }
-        if constexpr (write_signs) {   // byte = sum of (v[i] > 0) << i: compare into vcc, add-with-carry shifts it in (values 7 down to 0)
-          unsigned mA = 0;
-#define WS_SGN(I) "v_cmp_lt_f32_e32 vcc, 0, %" #I "\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-          asm(WS_SGN(8) WS_SGN(7) WS_SGN(6) WS_SGN(5) WS_SGN(4) WS_SGN(3) WS_SGN(2) "v_cmp_lt_f32_e32 vcc, 0, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc"
-              : "+v"(mA)
-              : "v"(e_v[0]), "v"(e_v[1]), "v"(e_v[2]), "v"(e_v[3]), "v"(e_v[4]), "v"(e_v[5]), "v"(e_v[6]), "v"(e_v[7])
-              : "vcc");
-#undef WS_SGN
-          sg[N][Q >> 2] |= mA << (8 * (Q & 3));
-        }
+        if constexpr (write_signs) sg[N][Q >> 2] |= sign_byte(e_v) << (8 * (Q & 3));
       } else {
         bf16x8 o;
 #pragma unroll
@@ -696,7 +630,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   };
   auto store_signs = [&]() {   // the 8 sign bytes of a pixel (this lane's half of the 128 channels) go out together
     if constexpr (write_signs) {
-      const auto rs_s = __builtin_amdgcn_make_buffer_rsrc((void*)(p.signs + (size_t)b_e * plane * 16), (short)0, plane * 16, 0x00020000);
+      const auto rs_s = __builtin_amdgcn_make_buffer_rsrc((void*)(p.signs + (size_t)b_e * plane * 16), (short)0, plane * 16, RSRC_WORD3);
 #pragma unroll
       for (int n = 0; n < 2; ++n) {
         const int vs = vo_e[n] < 0 ? (int)OOB : (vo_e[n] >> 4) * 8;
@@ -735,7 +669,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         ws_y8(Ac[1], Ac[2], Ac[3], Bc[0], Bc[1], An[0], An[1], An[2], An[3], Bn[0], Bn[1], a_b0 + (1 - P) * WS_WB, pbr[0] + ibn, pbr[1] + ibn);
       }
     };
-    ws_static_for(one, std::make_integer_sequence<int, 9>{});
+    static_for(one, std::make_integer_sequence<int, 9>{});
     ibo = ibn;
   };
   // a GROUP-MAJOR chunk: the 9 taps of accumulator rows 0, 1 (group 0), then those of rows 2, 3 (group 1), one MFMA per statement
@@ -807,7 +741,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
       }
     };
-    ws_static_for(one, std::make_integer_sequence<int, 18>{});
+    static_for(one, std::make_integer_sequence<int, 18>{});
     ibo = ibn;
   };
   using TT = std::true_type;
@@ -851,7 +785,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
   // ---- the last tile: group 1's epilogue on its own, then the parked half's hand-over
   asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // (the last MFMAs' results are in the accumulator file)
-  ws_static_for([&](auto u_tag) {
+  static_for([&](auto u_tag) {
     epi(WsIC<1>{}, u_tag, WsIC<0>{}); epi(WsIC<1>{}, u_tag, WsIC<1>{}); epi(WsIC<1>{}, u_tag, WsIC<2>{}); epi(WsIC<1>{}, u_tag, WsIC<3>{});
     epi(WsIC<1>{}, u_tag, WsIC<4>{});
   }, std::make_integer_sequence<int, 8>{});
@@ -861,7 +795,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   {
     // (the staging address is re-derived from v_mbcnt: live across the tile loop it costs a register the 256-register
     //  instantiations do not have)
-    const int ln_ = ws_lane();
+    const int ln_ = lane_id();
     const unsigned stg2 = (unsigned)(WS_STG + tw * 4096 + (ln_ & 31) * 16 + (ln_ >> 5) * 8);
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -937,9 +871,7 @@ int launch_conv_bf16_ws(const ConvWsParams& p, hipStream_t stream) {
   int n_cu;
   if (int e = yogo_device_cus("conv_bf16_ws", &n_cu)) return e;
   if (p.ntiles <= 0) return YOGO_OK;
-  // one persistent workgroup per CU; a multiple of 8 so that a workgroup's tiles stay inside one XCD's run
-  int grid = min(p.ntiles, n_cu);
-  if (grid >= 8) grid &= ~7;
+  const int grid = persistent_grid(p.ntiles, n_cu);
   const bool leaky = p.act == ACT_LEAKY, sc = p.chan_scale != nullptr, sg = p.signs != nullptr;
   if (sg && !leaky) {
     yogo_set_error("conv_bf16_ws: a sign map goes with LeakyReLU");

@@ -34,41 +34,17 @@
 #ifndef W16_ABL
 #define W16_ABL 0
 #endif
-#include <type_traits>
-#include <utility>
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+#include "bf16_dev.h"
 
 // the accumulators a[0:127], the bias a[128:159] and the arch registers v16..v95 are named literally by the generated statement (its inputs
 // live in v0..v15: the kernel is held to 96 arch VGPRs so that 160 accumulator registers fit a wavefront's 256)
 #define W16_CLOBBER \
   "memory", "scc", "s87", "s88", "s89", "s90", "s91", "s92", "s93", "s94", "s95", \
   "v16", "v17", "v18", "v19", "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63", "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71", "v72", "v73", "v74", "v75", "v76", "v77", "v78", "v79", "v80", "v81", "v82", "v83", "v84", "v85", "v86", "v87", "v88", "v89", "v90", "v91", "v92", "v93", "v94", "v95", \
-  "a0","a1","a2","a3","a4","a5","a6","a7","a8","a9","a10","a11","a12","a13","a14","a15","a16","a17","a18","a19","a20","a21","a22","a23","a24","a25","a26","a27","a28","a29","a30","a31","a32","a33","a34","a35","a36","a37","a38","a39","a40","a41","a42","a43","a44","a45","a46","a47","a48","a49","a50","a51","a52","a53","a54","a55","a56","a57","a58","a59","a60","a61","a62","a63","a64","a65","a66","a67","a68","a69","a70","a71","a72","a73","a74","a75","a76","a77","a78","a79","a80","a81","a82","a83","a84","a85","a86","a87","a88","a89","a90","a91","a92","a93","a94","a95","a96","a97","a98","a99","a100","a101","a102","a103","a104","a105","a106","a107","a108","a109","a110","a111","a112","a113","a114","a115","a116","a117","a118","a119","a120","a121","a122","a123","a124","a125","a126","a127","a128","a129","a130","a131","a132","a133","a134","a135","a136","a137","a138","a139","a140","a141","a142","a143","a144","a145","a146","a147","a148","a149","a150","a151","a152","a153","a154","a155","a156","a157","a158","a159"
+  ACC_A0_63, ACC_A64_127, ACC_A128_159
 
 namespace {
 
-__device__ __forceinline__ int w16_udivm(int n, unsigned m) { return (int)__umulhi((unsigned)n, m); }   // n / d, m = ceil(2^32 / d), d > 1
-__device__ __forceinline__ int w16_udivm1(int n, int d, unsigned m) { return d == 1 ? n : (int)__umulhi((unsigned)n, m); }
-__device__ __forceinline__ int w16_lane() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
-__device__ __forceinline__ i32x4 w16_rsrc(const void* ptr, unsigned bytes) {
-  const unsigned long long a = reinterpret_cast<unsigned long long>(ptr);
-  return i32x4{(int)(unsigned)a, (int)((unsigned)(a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-// four LDS-DMA pieces (64 lanes x 16 bytes each) of one descriptor with one scalar offset: LDS destinations lds + k * 4 KB
-__device__ __forceinline__ void w16_dma4(i32x4 rs, unsigned lds, int v0, int v1, int v2, int v3, unsigned soff) {
-  asm volatile(
-      "s_mov_b32 m0, %5\n\ts_nop 4\n\tbuffer_load_dwordx4 %0, %4, %6 offen lds\n\t"
-      "s_add_u32 m0, m0, 4096\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %4, %6 offen lds\n\t"
-      "s_add_u32 m0, m0, 4096\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %4, %6 offen lds\n\t"
-      "s_add_u32 m0, m0, 4096\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %4, %6 offen lds"
-      ::"v"(v0), "v"(v1), "v"(v2), "v"(v3), "s"(rs), "s"(lds), "s"(soff) : "memory", "scc");
-}
 // six pieces of one descriptor with one per-lane offset: LDS destinations lds + k * 4 KB, scalar offsets soff, + sj, + sk, + sj, + sk, + sj
 // (the weight slices [3 kx][2 chunks] of a period for this wavefront's channel block and column half)
 __device__ __forceinline__ void w16_dma6(i32x4 rs, unsigned lds, int voff, unsigned soff, unsigned sj, unsigned sk) {
@@ -82,16 +58,12 @@ __device__ __forceinline__ void w16_dma6(i32x4 rs, unsigned lds, int voff, unsig
 #undef W16_PJ
 #undef W16_PK
 }
-__device__ __forceinline__ void w16_store16(u32x4 data, int voff, i32x4 rs, unsigned soff) {
-  asm volatile("s_nop 4\n\tbuffer_store_dwordx4 %0, %1, %2, %3 offen" ::"v"(data), "v"(voff), "s"(rs), "s"(soff) : "memory");
-}
 
 }  // namespace
 
 template <bool BIAS>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2), amdgpu_num_vgpr(96))) void conv_bf16_ws16_kernel(const ConvWsParams p) {
   extern __shared__ __attribute__((aligned(16))) u32x4 smem4[];
-  constexpr unsigned OOB = 0x80000000u;
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int team = wave >> 2, tw = wave & 3;   // team 0 computes, team 1 loads; wavefronts tw and tw + 4 share a SIMD
@@ -104,17 +76,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2), amdg
 
   // ---- tile walk (conv_bf16_ws_kernel's): virtual block lin = slot + k * G, an XCD's workgroups share a contiguous run of tiles
   const unsigned NV = (unsigned)p.ntiles, G = gridDim.x, slot = blockIdx.x;
-  const unsigned xq = NV >> 3, xr = NV & 7;
   struct TileS { int b, j0, bw, p0, p1, lastband; };
   auto find_tile = [&](unsigned& k, TileS& t) -> bool {   // (uniform) next non-empty tile of this workgroup from ordinal k on
     for (;; ++k) {
       const unsigned lin = slot + k * G;
       if (lin >= NV) return false;
-      const unsigned xcd = lin & 7;
-      const int widx = (int)((xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (lin >> 3));
-      const int b = w16_udivm1(widx, p.gx, p.m_gx);
+      const int widx = (int)xcd_remap(lin, NV);
+      const int b = udivm1(widx, p.gx, p.m_gx);
       const int bx = widx - b * p.gx;
-      const int cb = w16_udivm1(bx, p.tiles_per_band, p.m_tpb);
+      const int cb = udivm1(bx, p.tiles_per_band, p.m_tpb);
       const int tb = bx - cb * p.tiles_per_band;
       const int j0 = cb * p.TW;
       const int bw = min(p.TW, OW - j0);
@@ -129,17 +99,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2), amdg
   auto pix_geom = [&](const TileS& t, int q, unsigned& pbase, int& vo) {
     const unsigned m_bw = t.lastband ? p.m_bwl : p.m_bw;
     const int bw = t.bw;   // >= 2 (planner)
-    const int i_lo = w16_udivm(t.p0, m_bw);
+    const int i_lo = udivm(t.p0, m_bw);
     const int pp = t.p0 + q;
     const bool pv = pp < t.p1;
     const int pc = pv ? pp : (t.p1 - 1);
-    const int i = w16_udivm(pc, m_bw), j = pc - i * bw;
+    const int i = udivm(pc, m_bw), j = pc - i * bw;
     pbase = (unsigned)((i - i_lo) * (bw + 2) + j) * 16u;
     vo = pv ? (i * OW + t.j0 + j) * 16 : (int)OOB;
   };
   auto tile_pitch = [&](const TileS& t, unsigned& lw16, unsigned& perkb16) {   // (uniform) staged row pitch, bytes of a channel block of the staged tile
     const unsigned m_bw = t.lastband ? p.m_bwl : p.m_bw;
-    const int i_lo = w16_udivm(t.p0, m_bw), i_hi = w16_udivm(t.p1 - 1, m_bw);
+    const int i_lo = udivm(t.p0, m_bw), i_hi = udivm(t.p1 - 1, m_bw);
     lw16 = (unsigned)(t.bw + 2) * 16u;
     perkb16 = (unsigned)(i_hi - i_lo + 3) * lw16;
   };
@@ -162,33 +132,33 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2), amdg
     // slices (6 pieces per wavefront), chunk r of the NEXT pair's input tiles in the pair's periods r = 0, 1 (4 pieces), four output
     // stores in each of the periods 0..3, [period 0: next-tile lookup + decode; period 1: the mailbox], counted vmcnt, barrier.
     // =====================================================================================================================
-    const int lane = w16_lane();
+    const int lane = lane_id();
     const int ttid = tw * 64 + lane;
     const int rowb = p.IW * 16, kcb = p.IH * p.IW * 16;
     const unsigned ibytes = (unsigned)p.Kb * kcb, obytes = 16u * plane16, wbytes = 9u * p.Kb * 2048u;
     const unsigned so_i = 2u * kcb;                  // bytes between the 16-channel chunks of an image
     const unsigned wstep = (unsigned)p.Kb * 2048u;   // bytes between the taps of the packed weights
-    const i32x4 rs_w = w16_rsrc(p.wp, wbytes);
+    const i32x4 rs_w = rsrc(p.wp, wbytes);
     const int lane16 = lane * 16;
     const int kbw = tw >> 1, colh = tw & 1;          // this wavefront's weight pieces: channel block of the chunk, column half
     // DMA source offsets of the 4 input slots: element ttid + i * 256 of the flattened [2][rows_in][lw] tile -> (channel block, row, column)
     auto decode_slots = [&](const TileS& t, int (&voff)[WS_NI]) {
       const unsigned m_bw = t.lastband ? p.m_bwl : p.m_bw;
       const int bw = t.bw;
-      const int i_lo = w16_udivm(t.p0, m_bw), i_hi = w16_udivm(t.p1 - 1, m_bw);
+      const int i_lo = udivm(t.p0, m_bw), i_hi = udivm(t.p1 - 1, m_bw);
       const int rows_in = i_hi - i_lo + 3;
       const int iy0 = i_lo - 1, ix0 = t.j0 - 1;
       const int lw = bw + 2;
       const int per_kb = rows_in * lw;
       const unsigned inv_lw = t.lastband ? p.m_lwl : p.m_lw;
       const unsigned inv_perkb = 0xFFFFFFFFu / (unsigned)per_kb + 1u;
-      const int skc = w16_udivm(WS_NT, inv_perkb);
+      const int skc = udivm(WS_NT, inv_perkb);
       const int srm = WS_NT - skc * per_kb;
-      const int sr = w16_udivm(srm, inv_lw);
+      const int sr = udivm(srm, inv_lw);
       const int sx = srm - sr * lw;
-      int kc_ = w16_udivm(ttid, inv_perkb);
+      int kc_ = udivm(ttid, inv_perkb);
       const int rm0 = ttid - kc_ * per_kb;
-      int r_ = w16_udivm(rm0, inv_lw);
+      int r_ = udivm(rm0, inv_lw);
       int x_ = rm0 - r_ * lw;
 #pragma unroll
       for (int i = 0; i < WS_NI; ++i) {
@@ -200,7 +170,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2), amdg
         if (r_ >= rows_in) { r_ -= rows_in; ++kc_; }
       }
     };
-    static_assert(WS_NI == 4, "w16_dma4 issues the four input slots");
+    static_assert(WS_NI == 4, "dma4 issues the four input slots");
     // weight slices of period cn (pair cn / 3, kernel row cn % 3) -> weight slot cn & 1
     auto req_w = [&](int P, int r, int par) {
       const unsigned soff = (unsigned)(((3 * r) * p.Kb + 4 * P + kbw) * 2048 + colh * 1024);
@@ -208,13 +178,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2), amdg
     };
     // input tile of chunk cn of the image behind (rs, voff) -> pair slot ps, chunk half j
     auto req_i = [&](i32x4 rs, const int (&voff)[WS_NI], int cn, int ps, int j) {
-      w16_dma4(rs, (unsigned)(W16_I0 + ps * W16_ISLOT + j * WS_IB + tw * 64 * 16), voff[0], voff[1], voff[2], voff[3], (unsigned)cn * so_i);
+      dma4(rs, (unsigned)(W16_I0 + ps * W16_ISLOT + j * WS_IB + tw * 64 * 16), voff[0], voff[1], voff[2], voff[3], (unsigned)cn * so_i);
     };
     // Output hand-over: the staged half (8 channel blocks x this wavefront's 64 pixels) -> registers, four stores per period
     const unsigned stg_rd = (unsigned)(W16_STG + tw * 8192 + lane * 16);
     u32x4 fifo[8];
     int f_vo = (int)OOB;
-    i32x4 f_rs = w16_rsrc(p.out, 0u);
+    i32x4 f_rs = rsrc(p.out, 0u);
     int f_cb0 = 0;
     auto fifo_fill = [&](int cb0, int vop, i32x4 rs_o) {
 #pragma unroll
@@ -223,11 +193,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2), amdg
     };
     auto fifo_store4 = [&](auto h_tag) {   // units 4 h .. 4 h + 3 of the FIFO
       constexpr int Hh = decltype(h_tag)::value;
-      const i32x4 rs = {__builtin_amdgcn_readfirstlane(f_rs.x), __builtin_amdgcn_readfirstlane(f_rs.y), __builtin_amdgcn_readfirstlane(f_rs.z),
-                        __builtin_amdgcn_readfirstlane(f_rs.w)};
+      const i32x4 rs = uniform4(f_rs);
       const int cb0 = __builtin_amdgcn_readfirstlane(f_cb0);
 #pragma unroll
-      for (int u = 4 * Hh; u < 4 * Hh + 4; ++u) w16_store16(fifo[u], (W16_ABL & 2) ? (int)OOB : f_vo, rs, (unsigned)(cb0 + u) * (unsigned)plane16);
+      for (int u = 4 * Hh; u < 4 * Hh + 4; ++u) store16(fifo[u], (W16_ABL & 2) ? (int)OOB : f_vo, rs, (unsigned)(cb0 + u) * (unsigned)plane16);
     };
     using IC0 = std::integral_constant<int, 0>;
     using IC1 = std::integral_constant<int, 1>;
@@ -237,9 +206,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2), amdg
     unsigned pbase_ = 0, lw16_ = 0, perkb16_ = 0;
     int vo = (int)OOB, vo_prev = (int)OOB;
     pix_geom(T, ttid, pbase_, vo);
-    i32x4 rs_in = w16_rsrc(reinterpret_cast<const unsigned char*>(p.in) + (size_t)T.b * ibytes, ibytes);
-    i32x4 rs_out = w16_rsrc(reinterpret_cast<unsigned char*>(p.out) + (size_t)T.b * obytes, obytes);
-    i32x4 rs_out_prev = w16_rsrc(p.out, 0u);
+    i32x4 rs_in = rsrc(reinterpret_cast<const unsigned char*>(p.in) + (size_t)T.b * ibytes, ibytes);
+    i32x4 rs_out = rsrc(reinterpret_cast<unsigned char*>(p.out) + (size_t)T.b * obytes, obytes);
+    i32x4 rs_out_prev = rsrc(p.out, 0u);
     req_i(rs_in, voff, 0, 0, 0);
     req_i(rs_in, voff, 1, 0, 1);
     req_w(0, 0, 0);
@@ -294,8 +263,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2), amdg
             decode_slots(Tn, voff_n);
             pix_geom(Tn, ttid, pbase_, vo_n);
             tile_pitch(Tn, lw16_, perkb16_);
-            rs_in_n = w16_rsrc(reinterpret_cast<const unsigned char*>(p.in) + (size_t)Tn.b * ibytes, ibytes);
-            rs_out_n = w16_rsrc(reinterpret_cast<unsigned char*>(p.out) + (size_t)Tn.b * obytes, obytes);
+            rs_in_n = rsrc(reinterpret_cast<const unsigned char*>(p.in) + (size_t)Tn.b * ibytes, ibytes);
+            rs_out_n = rsrc(reinterpret_cast<unsigned char*>(p.out) + (size_t)Tn.b * obytes, obytes);
           }
         }
         // the NEXT tile's operand addresses for the compute wavefronts: written in period 1 (they read the previous message at their
@@ -336,7 +305,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2), amdg
   // COMPUTE
   // =======================================================================================================================
   __builtin_amdgcn_s_setprio(3);
-  const int lane = w16_lane(), c16 = lane & 15, g = lane >> 4;
+  const int lane = lane_id(), c16 = lane & 15, g = lane >> 4;
   const unsigned pa_lane = (unsigned)(W16_W0 + (g >> 1) * 4096 + (g & 1) * 2048 + c16 * 16);
   const unsigned stg = (unsigned)(W16_STG + tw * 8192 + (g >> 1) * 1024 + c16 * 16 + (g & 1) * 8);
   const unsigned eb = (unsigned)(W16_EB + g * 16);
@@ -386,8 +355,7 @@ int launch_conv_bf16_ws16(const ConvWsParams& p, hipStream_t stream) {
     yogo_set_error("conv_bf16_ws16: plain epilogue and whole chunk-pair pairs only");
     return YOGO_ERR_ARG;
   }
-  int grid = min(p.ntiles, n_cu);
-  if (grid >= 8) grid &= ~7;
+  const int grid = persistent_grid(p.ntiles, n_cu);
   const void* kernel = p.bias == nullptr ? reinterpret_cast<const void*>(&conv_bf16_ws16_kernel<false>) : reinterpret_cast<const void*>(&conv_bf16_ws16_kernel<true>);
   if (int e = yogo_func_dynamic_lds(kernel, W16_LDS_BYTES, "conv_bf16_ws16")) return e;
   if (p.bias != nullptr) hipLaunchKernelGGL(conv_bf16_ws16_kernel<true>, dim3(grid), dim3(512), W16_LDS_BYTES, stream, p);

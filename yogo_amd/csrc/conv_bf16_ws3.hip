@@ -10,38 +10,18 @@
 // stride costs is LDS: an output pixel's taps touch a 3x3 input window at stride 2, so a tile's input footprint is ~4x its
 // output -- 128-pixel tiles (27 KB per 16-channel chunk, ring of three) where the stride-1 kernel has 256.  The staged rows hold
 // their even and odd columns de-interleaved, so a tap's 32 consecutive output pixels read 32 consecutive units and every tap offset is
-// an immediate of the ds_read.  Operands are requested two K steps ahead (conv_bf16_ws2.hip: an LDS read takes 200+ cycles beside
-// the LDS-DMA stream, a step's 4 MFMAs 128).
+// an immediate of the ds_read.  Operands are requested two K steps ahead (an LDS read takes 200+ cycles beside the LDS-DMA stream, a step's
+// 4 MFMAs 128).
 #include "conv_bf16_ws3.h"
-#include <type_traits>
-#include <utility>
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "bf16_dev.h"
 
 namespace {
 
-__device__ __forceinline__ int w3_udivm(int n, unsigned m) { return (int)__umulhi((unsigned)n, m); }   // n / d, m = ceil(2^32 / d), d > 1
-__device__ __forceinline__ int w3_udivm1(int n, int d, unsigned m) { return d == 1 ? n : (int)__umulhi((unsigned)n, m); }
-__device__ __forceinline__ int w3_lane() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
-__device__ __forceinline__ i32x4 w3_rsrc(const void* ptr, unsigned bytes) {
-  const unsigned long long a = reinterpret_cast<unsigned long long>(ptr);
-  return i32x4{(int)(unsigned)a, (int)((unsigned)(a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-__device__ __forceinline__ unsigned w3_u(unsigned x) { return (unsigned)__builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ i32x4 w3_u4(i32x4 r) {
-  return i32x4{__builtin_amdgcn_readfirstlane(r.x), __builtin_amdgcn_readfirstlane(r.y), __builtin_amdgcn_readfirstlane(r.z), __builtin_amdgcn_readfirstlane(r.w)};
-}
 // nine LDS-DMA pieces (64 lanes x 16 bytes each) of one descriptor with one per-lane offset: LDS + 4 KB each, scalar offset + step each
 // (this wavefront's quarter of the nine taps' weight slices)
 __device__ __forceinline__ void w3_dma9(i32x4 rs, unsigned lds, int voff, unsigned soff, unsigned step) {
   unsigned so;
-  rs = w3_u4(rs); lds = w3_u(lds); soff = w3_u(soff); step = w3_u(step);
+  rs = uniform4(rs); lds = uniform(lds); soff = uniform(soff); step = uniform(step);
 #define W3_P9 "s_add_u32 m0, m0, 4096\n\ts_add_u32 %0, %0, %5\n\tbuffer_load_dwordx4 %1, %2, %0 offen lds\n\t"
   asm volatile("s_mov_b32 m0, %3\n\ts_mov_b32 %0, %4\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %2, %0 offen lds\n\t" W3_P9 W3_P9 W3_P9 W3_P9 W3_P9 W3_P9 W3_P9 W3_P9
                : "=&s"(so)
@@ -52,7 +32,7 @@ __device__ __forceinline__ void w3_dma9(i32x4 rs, unsigned lds, int voff, unsign
 // N (6 or 7) pieces of one descriptor with one scalar offset and their own per-lane offsets: LDS + 4 KB each (the input slots of a chunk)
 template <int N>
 __device__ __forceinline__ void w3_dman(i32x4 rs, unsigned lds, const int (&v)[W3_NI], unsigned soff) {
-  rs = w3_u4(rs); lds = w3_u(lds); soff = w3_u(soff);
+  rs = uniform4(rs); lds = uniform(lds); soff = uniform(soff);
 #define W3_PI(K) "s_add_u32 m0, m0, 4096\n\ts_nop 0\n\tbuffer_load_dwordx4 %" #K ", %7, %9 offen lds\n\t"
   if constexpr (N == 7)
     asm volatile("s_mov_b32 m0, %8\n\ts_nop 4\n\tbuffer_load_dwordx4 %0, %7, %9 offen lds\n\t" W3_PI(1) W3_PI(2) W3_PI(3) W3_PI(4) W3_PI(5) W3_PI(6)
@@ -61,16 +41,6 @@ __device__ __forceinline__ void w3_dman(i32x4 rs, unsigned lds, const int (&v)[W
     asm volatile("s_mov_b32 m0, %8\n\ts_nop 4\n\tbuffer_load_dwordx4 %0, %7, %9 offen lds\n\t" W3_PI(1) W3_PI(2) W3_PI(3) W3_PI(4) W3_PI(5)
                  ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "s"(rs), "s"(lds), "s"(soff) : "memory", "scc");
 #undef W3_PI
-}
-__device__ __forceinline__ void w3_dma_dword(i32x4 rs, unsigned lds, int voff, unsigned soff) {
-  rs = w3_u4(rs); lds = w3_u(lds); soff = w3_u(soff);
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 4\n\tbuffer_load_dword %0, %2, %3 offen lds" ::"v"(voff), "s"(lds), "s"(rs), "s"(soff) : "memory");
-}
-__device__ __forceinline__ void w3_store16(u32x4 data, int voff, i32x4 rs, unsigned soff) {
-  rs = w3_u4(rs); soff = w3_u(soff);
-  // (s_nop in front: the descriptor may come from v_readfirstlane; behind: a 16-byte store's data registers must not be overwritten by
-  //  the next vector instruction -- hipcc does not look inside asm statements)
-  asm volatile("s_nop 4\n\tbuffer_store_dwordx4 %0, %1, %2, %3 offen\n\ts_nop 1" ::"v"(data), "v"(voff), "s"(rs), "s"(soff) : "memory");
 }
 template <int N>
 __device__ __forceinline__ void w3_vmwait() {
@@ -81,7 +51,7 @@ __device__ __forceinline__ void w3_barrier() { asm volatile("s_barrier" ::: "mem
 // ---- the asm statements of a compute wavefront's K steps.  The four 32x32 accumulator tiles (row block mb, pixel group n) -> tile 2 mb + n
 // are a[0:63], OWNED BY THE ASM STATEMENTS (named literally, listed as clobbers; build.sh audits that no compiler-generated instruction
 // touches an AGPR: conv_bf16_ws.hip)
-#define W3_ACC_CLOBBER "a0","a1","a2","a3","a4","a5","a6","a7","a8","a9","a10","a11","a12","a13","a14","a15","a16","a17","a18","a19","a20","a21","a22","a23","a24","a25","a26","a27","a28","a29","a30","a31","a32","a33","a34","a35","a36","a37","a38","a39","a40","a41","a42","a43","a44","a45","a46","a47","a48","a49","a50","a51","a52","a53","a54","a55","a56","a57","a58","a59","a60","a61","a62","a63"
+#define W3_ACC_CLOBBER ACC_A0_63
 #ifndef W3_ABL
 #define W3_ABL 0   // (compile-time ablations for timing runs, results wrong: bit 0 = no MFMAs, 1 = no operand reads, 2 = no weight DMA, 3 = no epilogue)
 #endif
@@ -148,25 +118,10 @@ __device__ __forceinline__ void w3_k_first(u32x4& an0, u32x4& an1, u32x4& bn0, u
                : [pa] "v"(pa), [pb0] "v"(pb0), [pb1] "v"(pb1), [z0] "n"(0), [z512] "n"(512), [z4096] "n"(4096), [z4608] "n"(4608), [bo0] "n"(BIMM0), [bo1] "n"(BIMM1)
                : "memory");
 }
-// eight consecutive accumulator registers -> VGPRs in ONE statement (it clobbers every accumulator register: conv_bf16_ws.hip, ws_acc_read8)
-template <int R>
-__device__ __forceinline__ void w3_acc_read8(float (&r)[8]) {
-  asm volatile(
-      "v_accvgpr_read_b32 %0, a[%8]\n\tv_accvgpr_read_b32 %1, a[%8+1]\n\tv_accvgpr_read_b32 %2, a[%8+2]\n\tv_accvgpr_read_b32 %3, a[%8+3]\n\t"
-      "v_accvgpr_read_b32 %4, a[%8+4]\n\tv_accvgpr_read_b32 %5, a[%8+5]\n\tv_accvgpr_read_b32 %6, a[%8+6]\n\tv_accvgpr_read_b32 %7, a[%8+7]"
-      : "=v"(r[0]), "=v"(r[1]), "=v"(r[2]), "=v"(r[3]), "=v"(r[4]), "=v"(r[5]), "=v"(r[6]), "=v"(r[7])
-      : "n"(R)
-      : W3_ACC_CLOBBER);
-}
+DEFINE_ACC_READ8(W3_ACC_CLOBBER)   // (bf16_dev.h)
 // byte offset of tap t's pixel quads inside the staged chunk: row 2 (i - i_lo) + ky, column plane (kx = 1: even columns, index j; kx = 0: odd
 // columns, index j; kx = 2: odd columns, index j + 1)
 __device__ constexpr int w3_bimm(int t) { return ((t / 3) * W3_LW + ((t % 3) == 1 ? 0 : W3_PL + ((t % 3) == 2 ? 1 : 0))) * 16; }
-
-template <class F, int... I>
-__device__ __forceinline__ void w3_static_for(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-
 #ifdef YOGO_DIAG
 #define W3_DBG(BIT) (p.dbg & (BIT))
 #define W3_STAMP() __builtin_amdgcn_s_memtime()
@@ -181,7 +136,6 @@ __device__ __forceinline__ void w3_static_for(F&& f, std::integer_sequence<int, 
 template <int MODE>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_bf16_ws3_kernel(const ConvWs3Params p) {
   extern __shared__ __attribute__((aligned(16))) u32x4 smem4[];
-  constexpr unsigned OOB = 0x80000000u;
   float* const ldsf = reinterpret_cast<float*>(smem4);
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -195,17 +149,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
   // ---- tile walk (as conv_bf16_ws_kernel): virtual block lin = slot + k * G, an XCD's workgroups share a contiguous run of tiles
   const unsigned NV = (unsigned)p.ntiles, G = gridDim.x, slot = blockIdx.x;
-  const unsigned xq = NV >> 3, xr = NV & 7;
   struct TileS { int b, j0, bw, p0, p1, lastband; };
   auto find_tile = [&](unsigned& k, TileS& t) __attribute__((always_inline)) -> bool {   // (uniform) next non-empty tile of this workgroup from ordinal k on
     for (;; ++k) {
       const unsigned lin = slot + k * G;
       if (lin >= NV) return false;
-      const unsigned xcd = lin & 7;
-      const int widx = (int)((xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (lin >> 3));
-      const int b = w3_udivm1(widx, p.gx, p.m_gx);
+      const int widx = (int)xcd_remap(lin, NV);
+      const int b = udivm1(widx, p.gx, p.m_gx);
       const int bx = widx - b * p.gx;
-      const int cb = w3_udivm1(bx, p.tiles_per_band, p.m_tpb);
+      const int cb = udivm1(bx, p.tiles_per_band, p.m_tpb);
       const int tb = bx - cb * p.tiles_per_band;
       const int j0 = cb * p.TW;
       const int bw = min(p.TW, OW - j0);
@@ -235,24 +187,24 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // LOADERS: per period -- the weight slices of the next chunk (9 pieces per wavefront; needed at this period's barrier), the input
     // tile of the chunk after it (7 pieces, 6 for wavefront 3; it may stay in flight), wait, barrier.  The stream crosses tile seams.
     // =====================================================================================================================
-    const int lane = w3_lane();
+    const int lane = lane_id();
     const int ttid = tw * 64 + lane;
     const int rowb = IW * 16, kcb = IH * IW * 16;
     const unsigned ibytes = (unsigned)p.Kb * kcb, wbytes = 9u * p.Kb * 2048u;
     const unsigned so_i = 2u * kcb;                  // bytes between the 16-channel chunks of an image
     const unsigned wstep = (unsigned)p.Kb * 2048u;   // bytes between the taps of the packed weights
-    const i32x4 rs_w = w3_rsrc(p.wp, wbytes);
+    const i32x4 rs_w = rsrc(p.wp, wbytes);
     const int lane16 = W3_DBG(4) ? (int)OOB : lane * 16;
     const bool has_scale = p.chan_scale != nullptr;
-    const i32x4 rs_sc = w3_rsrc(p.chan_scale, has_scale ? (unsigned)p.B * 512u : 0u);
+    const i32x4 rs_sc = rsrc(p.chan_scale, has_scale ? (unsigned)p.B * 512u : 0u);
     auto issue_scale = [&](int b, int par) __attribute__((always_inline)) {   // [128] channel scale of image b -> es[par] (loaders 0 and 1, 64 floats each)
-      if (has_scale && tw < 2) w3_dma_dword(rs_sc, (unsigned)(W3_ES + par * 512 + tw * 256), lane * 4, (unsigned)((b * 128 + tw * 64) * 4));
+      if (has_scale && tw < 2) dma_dword_uniform(rs_sc, (unsigned)(W3_ES + par * 512 + tw * 256), lane * 4, (unsigned)((b * 128 + tw * 64) * 4));
     };
     // DMA source offsets of this lane's input slots: element e = ttid + i * 256 of the staged chunk [2 channel blocks][9 rows][even | odd columns]
     auto decode_slots = [&](const TileS& t, int (&voff)[W3_NI]) __attribute__((always_inline)) {
       const unsigned m_bw = t.lastband ? p.m_bwl : p.m_bw;
       const int bw = t.bw;
-      const int i_lo = w3_udivm1(t.p0, bw, m_bw), i_hi = w3_udivm1(t.p1 - 1, bw, m_bw);
+      const int i_lo = udivm1(t.p0, bw, m_bw), i_hi = udivm1(t.p1 - 1, bw, m_bw);
       const int rows_in = 2 * (i_hi - i_lo) + 3;
       const int iy0 = 2 * i_lo - 1;
 #pragma unroll
@@ -278,7 +230,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       if (tw == 3) w3_dman<6>(rs, dst, voff, (unsigned)cn * so_i);   // (wavefront 3's seventh piece would lie behind the buffer)
       else w3_dman<7>(rs, dst, voff, (unsigned)cn * so_i);
     };
-    auto rs_in_of = [&](int b) __attribute__((always_inline)) { return w3_rsrc(reinterpret_cast<const unsigned char*>(p.in) + (size_t)b * ibytes, ibytes); };
+    auto rs_in_of = [&](int b) __attribute__((always_inline)) { return rsrc(reinterpret_cast<const unsigned char*>(p.in) + (size_t)b * ibytes, ibytes); };
     int voff[W3_NI], voff_n[W3_NI];
     decode_slots(T, voff);
 #pragma unroll
@@ -345,7 +297,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // =======================================================================================================================
   // COMPUTE
   // =======================================================================================================================
-  const int lane = w3_lane(), l31 = lane & 31, half = lane >> 5;
+  const int lane = lane_id(), l31 = lane & 31, half = lane >> 5;
   const unsigned a_b0 = (unsigned)(half * 128 + mh * 64 + l31) * 16u;   // weight unit [channel block half][channel] of row block mb = 0
   const unsigned obytes = 16u * plane16;
   unsigned pbr[2];
@@ -353,13 +305,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   auto decode_pix = [&](const TileS& t) __attribute__((always_inline)) {
     const unsigned m_bw = t.lastband ? p.m_bwl : p.m_bw;
     const int bw = t.bw;
-    const int i_lo = w3_udivm1(t.p0, bw, m_bw);
+    const int i_lo = udivm1(t.p0, bw, m_bw);
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
       const int pp = t.p0 + (nh * 2 + n) * 32 + l31;
       const bool pv = pp < t.p1;
       const int pc = pv ? pp : (t.p1 - 1);
-      const int i = w3_udivm1(pc, bw, m_bw), j = pc - i * bw;
+      const int i = udivm1(pc, bw, m_bw), j = pc - i * bw;
       pbr[n] = (unsigned)(2 * (i - i_lo) * W3_LW + j + half * W3_KBU) * 16u;
       vo[n] = (pv && !W3_DBG(1)) ? (i * OW + t.j0 + j) * 16 + half * plane16 : (int)OOB;
     }
@@ -373,7 +325,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   auto epilogue = [&](i32x4 rs_o) __attribute__((always_inline)) {
     if constexpr ((W3_ABL & 8) != 0) return;
     [[maybe_unused]] unsigned sg[2] = {0u, 0u};   // this lane's sign bytes of the tile: [pixel group], byte mb * 2 + gp
-    w3_static_for([&](auto q_tag) __attribute__((always_inline)) {
+    static_for([&](auto q_tag) __attribute__((always_inline)) {
       constexpr int Q = decltype(q_tag)::value, MB = Q >> 1, GP = Q & 1;
       const int cl = mh * 64 + MB * 32 + 16 * GP + 4 * half;   // channel of group A; group B = cl + 8
       const float* eb = ldsf + W3_EB / 4 + cl;
@@ -388,10 +340,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
       for (int i = 0; i < 8; ++i) bs[i] = SCALED ? ba[i] * sa[i] : ba[i];
       const unsigned so = (unsigned)(mh * 8 + MB * 4 + GP * 2) * (unsigned)plane16;   // channel block the lower half-wave stores
-      w3_static_for([&](auto n_tag) __attribute__((always_inline)) {
+      static_for([&](auto n_tag) __attribute__((always_inline)) {
         constexpr int n = decltype(n_tag)::value;
         float v[8], r[8];
-        w3_acc_read8<16 * (2 * MB + n) + 8 * GP>(r);
+        acc_read8<16 * (2 * MB + n) + 8 * GP>(r);
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[i] = SCALED ? fmaf(r[i], sa[i], bs[i]) : r[i] + bs[i];   // (fma(acc, 1, bias) = acc + bias: the same bits)
         if constexpr (leaky) {   // max(v, 0.01 v) as bare v_max_f32 (conv_bf16_epi_groups.inc's lean order)
@@ -401,36 +353,21 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
           for (int i = 0; i < 8; ++i) asm("v_max_f32 %0, %0, %1" : "+v"(v[i]) : "v"(sv[i]));
         }
-        if constexpr (write_signs) {   // byte = sum of (v[i] > 0) << i: compare into vcc, add-with-carry shifts it in (values 7 down to 0; conv_bf16_ws.hip)
-          unsigned mA = 0;
-#define W3_SGN(I) "v_cmp_lt_f32_e32 vcc, 0, %" #I "\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-          asm(W3_SGN(8) W3_SGN(7) W3_SGN(6) W3_SGN(5) W3_SGN(4) W3_SGN(3) W3_SGN(2) "v_cmp_lt_f32_e32 vcc, 0, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc"
-              : "+v"(mA)
-              : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7])
-              : "vcc");
-#undef W3_SGN
-          sg[n] |= mA << (8 * Q);
-        }
+        if constexpr (write_signs) sg[n] |= sign_byte(v) << (8 * Q);
         if (W3_DBG(2)) {
 #pragma unroll
           for (int i = 0; i < 8; ++i) v[i] = r[i];
         }
-        bf16x8 o;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o[i] = (__bf16)v[i];
-        const u32x4 w = __builtin_bit_cast(u32x4, o);   // (x, y) = this lane's 4 channels of block cb, (z, w) = of block cb + 1
-        const auto r0 = __builtin_amdgcn_permlane32_swap(w.x, w.z, false, false);
-        const auto r1 = __builtin_amdgcn_permlane32_swap(w.y, w.w, false, false);
-        const u32x4 st = {r0[0], r1[0], r0[1], r1[1]};
-        w3_store16(st, vo[n], rs_o, so);
+        const u32x4 st = pack_unit_swap(v);
+        store16_uniform(st, vo[n], rs_o, so);
       }, std::make_integer_sequence<int, 2>{});
     }, std::make_integer_sequence<int, 4>{});
     if constexpr (write_signs) {   // this wavefront's 4 sign bytes of a pixel (its 64 channels' share of the half-wave's 8) go out together
-      const i32x4 rs_s = w3_rsrc(p.signs + (size_t)T.b * plane * 16, (unsigned)plane * 16u);
+      const i32x4 rs_s = rsrc(p.signs + (size_t)T.b * plane * 16, (unsigned)plane * 16u);
 #pragma unroll
       for (int n = 0; n < 2; ++n) {
         const int vs = vo[n] < 0 ? (int)OOB : (vo[n] >> 1) + mh * 4;   // ((half * plane + pixel) * 8 bytes: ConvBf16Params::signs)
-        asm volatile("s_nop 4\n\tbuffer_store_dword %0, %1, %2, 0 offen\n\ts_nop 1" ::"v"(sg[n]), "v"(vs), "s"(w3_u4(rs_s)) : "memory");
+        asm volatile("s_nop 4\n\tbuffer_store_dword %0, %1, %2, 0 offen\n\ts_nop 1" ::"v"(sg[n]), "v"(vs), "s"(uniform4(rs_s)) : "memory");
       }
     }
   };
@@ -438,7 +375,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   auto period = [&](auto first_tag, auto last_tag, unsigned pa, unsigned pan, unsigned ib, unsigned ibn) __attribute__((always_inline)) {
     constexpr bool FIRST = decltype(first_tag)::value, LASTP = decltype(last_tag)::value;
     const unsigned pb0 = pbr[0] + ib, pb1 = pbr[1] + ib;
-    w3_static_for([&](auto s_tag) __attribute__((always_inline)) {
+    static_for([&](auto s_tag) __attribute__((always_inline)) {
       constexpr int S = decltype(s_tag)::value;
       u32x4(&Ac)[2] = A[S % 3];
       u32x4(&Bc)[2] = B[S % 3];
@@ -463,7 +400,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   unsigned ibo = W3_I0;   // input buffer of the chunk being computed (ring of three)
   [[maybe_unused]] unsigned long long t_k = 0, t_e = 0;
   for (;;) {
-    const i32x4 rs_o = w3_rsrc(reinterpret_cast<unsigned char*>(p.out) + (size_t)T.b * obytes, obytes);
+    const i32x4 rs_o = rsrc(reinterpret_cast<unsigned char*>(p.out) + (size_t)T.b * obytes, obytes);
     [[maybe_unused]] const unsigned long long s0 = W3_STAMP();
     w3_k_first<w3_bimm(0), w3_bimm(1)>(A[0][0], A[0][1], B[0][0], B[0][1], A[1][0], A[1][1], B[1][0], B[1][1], (unsigned)(wpar * W3_WB) + a_b0, pbr[0] + ibo, pbr[1] + ibo);
     for (int c = 0; c < nck; ++c) {
@@ -543,8 +480,7 @@ int launch_conv_bf16_ws3(const ConvWs3Params& p, hipStream_t stream) {
   int n_cu;
   if (int e = yogo_device_cus("conv_bf16_ws3", &n_cu)) return e;
   if (p.ntiles <= 0) return YOGO_OK;
-  int grid = min(p.ntiles, n_cu);
-  if (grid >= 8) grid &= ~7;
+  const int grid = persistent_grid(p.ntiles, n_cu);
   const int mode = (p.act == ACT_LEAKY ? 1 : 0) | (p.chan_scale != nullptr ? 2 : 0) | (p.signs != nullptr ? 4 : 0);   // (a sign map goes with LeakyReLU: the dispatch checks)
 #define W3_LAUNCH(M) case M:                                                                                                      \
     if (int e = yogo_func_dynamic_lds(reinterpret_cast<const void*>(&conv_bf16_ws3_kernel<M>), W3_LDS_BYTES, "conv_bf16_ws3")) return e; \

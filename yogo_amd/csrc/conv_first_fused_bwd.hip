@@ -14,15 +14,7 @@
 // MFMA's fp32 accumulation; LeakyReLU' multiplies the sum of the negative-side products by 0.01 once instead of every element.  The unfused
 // pair rounds 0.01 dy per element and sums in another order, so the two agree to fp32 rounding of sums over the whole batch, not bit for
 // bit (tests/test_gpu_first_fused_bwd.py: both against a CPU fp64 reference).
-#include "common.h"
-#include <type_traits>
-#include <utility>
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "bf16_dev.h"
 
 struct DgFirstParams {
   const u32x4* g;                // bf16 NCHW8c [B][4][H][W] units: gradient w.r.t. layer 1's conv output
@@ -44,29 +36,22 @@ struct DgFirstParams {
 
 namespace {
 constexpr int DF_NJ = 9, DF_PER = 2 * DF_NJ + 2, DF_COUT = 16;   // the partial rows of conv_first_bn_wgrad_*: [Cout][A1 9 | A2 9 | S1 | S2] + P[9] + G[9][9]
-__device__ __forceinline__ int df_udivm1(int n, int d, unsigned m) { return d == 1 ? n : (int)__umulhi((unsigned)n, m); }
-__device__ __forceinline__ unsigned df_u(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ i32x4 df_rsrc(const void* ptr, unsigned bytes) {
-  const unsigned long long a = reinterpret_cast<unsigned long long>(ptr);
-  return i32x4{(int)df_u((unsigned)a), (int)df_u((unsigned)(a >> 32) & 0xFFFFu), (int)df_u(bytes), 0x00020000};
-}
 // LDS-DMA pieces (conv_bf16_staged.hip): 64 lanes x 16 bytes -> LDS [lds_addr, + 1024); 64 lanes x 4 bytes -> [lds_addr, + 256)
 __device__ __forceinline__ void df_dma16(i32x4 rs, unsigned lds_addr, int voff) {
   unsigned keep;
-  lds_addr = df_u(lds_addr);
+  lds_addr = uniform(lds_addr);
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(voff), "s"(lds_addr), "s"(rs) : "memory");
 }
 __device__ __forceinline__ void df_dma4(i32x4 rs, unsigned lds_addr, int voff) {
   unsigned keep;
-  lds_addr = df_u(lds_addr);
+  lds_addr = uniform(lds_addr);
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 4\n\tbuffer_load_dword %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(voff), "s"(lds_addr), "s"(rs) : "memory");
 }
 __device__ __forceinline__ void df_wait_dma() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 // eight pixels of this lane's channel: two transposed reads of four pixels each, `second` bytes apart (wgrad_bf16.hip: lds_tr8)
 __device__ __forceinline__ bf16x8 df_tr8(const unsigned char* a, int second) {
-  typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
   typedef bf16x4 __attribute__((address_space(3))) * lds_v4;
   const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4)(a));
   const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4)(a + second));
@@ -95,12 +80,6 @@ __device__ __forceinline__ bf16x8 df_tr8(const unsigned char* a, int second) {
 #ifndef DF_NPF_WG
 #define DF_NPF_WG 3   // ... with the weight gradient's 80 accumulator registers beside them
 #endif
-namespace {
-template <class F, int... I>
-__device__ __forceinline__ void df_static_for(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-}  // namespace
 //
 // WG: layer 1's WEIGHT gradient in the same sweep -- it reads the same gradient tile (1.63 GB that wgrad_bf16_kernel would read again) and
 // layer 0's output x (the tile's own pixels, no halo).  dW[tap][co][ci] = sum over pixels p of g[co][p - tap + 1] x[ci][p], K = the 32 pixels of a
@@ -110,7 +89,6 @@ __device__ __forceinline__ void df_static_for(F&& f, std::integer_sequence<int, 
 template <int R, int NWV, bool WG>
 __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(DF_WAVES_PER_EU))) void conv_bf16_dgrad_first_bwd_kernel(const DgFirstParams p) {
   extern __shared__ __attribute__((aligned(16))) u32x4 lds_u[];   // (the dynamic block starts at LDS address 0: LDS-DMA takes addresses)
-  constexpr int OOB = (int)0x80000000u;
   constexpr int KB = 4, NR = R + 2, ROWU = 34, TU = KB * NR * ROWU, NDMA = (TU + 63) / 64;
   constexpr int IR = 2 * R + 1, IROWB = 72, IDW = IROWB / 4, IU = IR * IDW, NIDMA = (IU + 63) / 64;   // staged image: IR rows of 18 dwords = columns 2 ox0 - 4 .. 2 ox0 + 67
   constexpr int SU = R * 16, NSDMA = (SU + 63) / 64;   // staged sign words: R rows of 16 dwords (32 pixels x 2 bytes)
@@ -151,7 +129,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(DF_WAV
     const int u = i * 64 + lane;
     const int kb = u / (NR * ROWU), rem = u - kb * (NR * ROWU);
     const int r = rem / ROWU, cc = rem - r * ROWU;
-    rel[i] = u < TU ? kb * kcb + (r * W + cc) * 16 : OOB;
+    rel[i] = u < TU ? kb * kcb + (r * W + cc) * 16 : (int)OOB;
     rc[i] = u < TU ? (unsigned)(r << 16 | cc) : 0xFFFFFFFFu;
   }
   unsigned irc[NIDMA];
@@ -187,48 +165,48 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(DF_WAV
   const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslot = gridDim.x >> 3;
   const int s8 = (p.nsegs + 7) >> 3, s_end = min(p.nsegs, (xcd + 1) * s8);
   for (int sgm = xcd * s8 + slot * NWV + wave; sgm < s_end; sgm += nslot * NWV) {
-    const int b = df_udivm1(sgm, p.segs_per_img, p.m_spi);
+    const int b = udivm1(sgm, p.segs_per_img, p.m_spi);
     const int t = sgm - b * p.segs_per_img;
-    const int sy = df_udivm1(t, p.tiles_per_row, p.m_tpr), ox0 = (t - sy * p.tiles_per_row) * 32;
+    const int sy = udivm1(t, p.tiles_per_row, p.m_tpr), ox0 = (t - sy * p.tiles_per_row) * 32;
     const int ty_end = min(p.tile_rows, (sy + 1) * p.seg);
    for (int ty = sy * p.seg; ty < ty_end; ++ty) {
     const int oy0 = ty * R;
     // ---- stage the gradient tile (rows oy0 - 1 .. oy0 + R, columns ox0 - 1 .. ox0 + 32; zeros beyond the image), the image window and the sign words
     {
-      const i32x4 rs_g = df_rsrc(p.g + (size_t)b * KB * H * W, (unsigned)(KB * kcb));
+      const i32x4 rs_g = uniform4(rsrc(p.g + (size_t)b * KB * H * W, (unsigned)(KB * kcb)));
       const int iy0 = oy0 - 1, ix0 = ox0 - 1;
       const int base = (iy0 * W + ix0) * 16;
       if (iy0 >= 0 && iy0 + NR <= H && ix0 >= 0 && ix0 + ROWU <= W) {   // (uniform) an interior tile: no border tests
 #pragma unroll
-        for (int i = 0; i < NDMA; ++i) df_dma16(rs_g, my_addr + (unsigned)i * 1024u, (i + 1) * 64 <= TU ? rel[i] + base : (rel[i] == OOB ? OOB : rel[i] + base));
+        for (int i = 0; i < NDMA; ++i) df_dma16(rs_g, my_addr + (unsigned)i * 1024u, (i + 1) * 64 <= TU ? rel[i] + base : (rel[i] == (int)OOB ? (int)OOB : rel[i] + base));
       } else {
 #pragma unroll
         for (int i = 0; i < NDMA; ++i) {
           const int r = (int)(rc[i] >> 16), c = (int)(rc[i] & 0xFFFFu);
           const bool ok = ((unsigned)(iy0 + r) < (unsigned)H) && ((unsigned)(ix0 + c) < (unsigned)W);   // (all ones: r = 65535 fails the row test)
-          df_dma16(rs_g, my_addr + (unsigned)i * 1024u, ok ? rel[i] + base : OOB);
+          df_dma16(rs_g, my_addr + (unsigned)i * 1024u, ok ? rel[i] + base : (int)OOB);
         }
       }
-      const i32x4 rs_i = df_rsrc(p.img + (size_t)b * IH0 * IW0, (unsigned)(IH0 * IW0));
+      const i32x4 rs_i = uniform4(rsrc(p.img + (size_t)b * IH0 * IW0, (unsigned)(IH0 * IW0)));
       const int jy0 = 2 * oy0 - 1, jx0 = 2 * ox0 - 4;
 #pragma unroll
       for (int i = 0; i < NIDMA; ++i) {
         const int r = (int)(irc[i] >> 16), d = (int)(irc[i] & 0xFFFFu);
         const int iy = jy0 + r, ix = jx0 + 4 * d;   // (a dword is inside the row or outside it as a whole: 2 W is a multiple of 4)
         const bool ok = ((unsigned)iy < (unsigned)IH0) && ((unsigned)ix < (unsigned)IW0);
-        df_dma4(rs_i, my_img_addr + (unsigned)i * 256u, ok ? iy * IW0 + ix : OOB);
+        df_dma4(rs_i, my_img_addr + (unsigned)i * 256u, ok ? iy * IW0 + ix : (int)OOB);
       }
       if (leaky) {
-        const i32x4 rs_s = df_rsrc(p.signs + (size_t)b * H * W, (unsigned)(H * W * 2));
+        const i32x4 rs_s = uniform4(rsrc(p.signs + (size_t)b * H * W, (unsigned)(H * W * 2)));
 #pragma unroll
         for (int i = 0; i < NSDMA; ++i) {
           const int e = i * 64 + lane, r = e >> 4, d = e & 15;   // dword d of tile row r: pixels ox0 + 2 d, + 1 (W is even: inside the row or outside as a whole)
           const bool ok = e < SU && oy0 + r < H && ox0 + 2 * d < W;
-          df_dma4(rs_s, my_sg_addr + (unsigned)i * 256u, ok ? ((oy0 + r) * W + ox0 + 2 * d) * 2 : OOB);
+          df_dma4(rs_s, my_sg_addr + (unsigned)i * 256u, ok ? ((oy0 + r) * W + ox0 + 2 * d) * 2 : (int)OOB);
         }
       }
       if constexpr (WG) {   // piece i = rows 2 i, 2 i + 1 of the flattened [channel block][row]: lanes 0-31 / 32-63, column = lane & 31
-        const i32x4 rs_x = df_rsrc(p.x + (size_t)b * 2 * H * W, (unsigned)(2 * kcb));
+        const i32x4 rs_x = uniform4(rsrc(p.x + (size_t)b * 2 * H * W, (unsigned)(2 * kcb)));
         const int hi = lane >> 5, col = lane & 31;
         const int xo = ((oy0 + hi) * W + ox0 + col) * 16;
         const bool cok = ox0 + col < W;
@@ -236,7 +214,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(DF_WAV
         for (int i = 0; i < NXDMA; ++i) {
           constexpr int dummy = 0; (void)dummy;
           const int kb = (2 * i) / R, row0 = (2 * i) % R;
-          df_dma16(rs_x, my_x_addr + (unsigned)i * 1024u, (cok && oy0 + row0 + hi < H) ? xo + kb * kcb + row0 * W * 16 : OOB);
+          df_dma16(rs_x, my_x_addr + (unsigned)i * 1024u, (cok && oy0 + row0 + hi < H) ? xo + kb * kcb + row0 * W * 16 : (int)OOB);
         }
       }
     }
@@ -282,7 +260,6 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(DF_WAV
       u32x4 xop, gpos, gneg;
       auto p3 = [&](auto k_tag) {
         constexpr int K = decltype(k_tag)::value;
-        typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
         if constexpr (K == 0) {
 #pragma unroll
           for (int pb = 0; pb < 2; ++pb) {
@@ -322,9 +299,9 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(DF_WAV
           d2n = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, xop), __builtin_bit_cast(bf16x8, gneg), d2n, 0, 0, 0);
         }
       };
-      df_static_for([&](auto s_tag) { load(s_tag); }, std::make_integer_sequence<int, NPF>{});
+      static_for([&](auto s_tag) { load(s_tag); }, std::make_integer_sequence<int, NPF>{});
       __builtin_amdgcn_sched_barrier(0);
-      df_static_for(
+      static_for(
           [&](auto s_tag) {
             constexpr int S = decltype(s_tag)::value;
             use(s_tag);

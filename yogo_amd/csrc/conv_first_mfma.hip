@@ -14,21 +14,17 @@
 // activations: pass A forms the batch statistics without writing anything, pass B recomputes the convolution and writes
 // z (saved for backward) and y = act(BN(z)) (the next layer's input) -- 0.1 + 0.1 GB read and 1.6 GB written per 128 images
 // where conv + separate BatchNorm apply read 0.9 GB and wrote 1.6 GB.
-#include "common.h"
+#include "bf16_dev.h"
 #ifndef CFM_ST_AUX
 #define CFM_ST_AUX 2   // non-temporal y / z stores of the pair kernel: 0.243 -> 0.211 ms in the same-box A/B (gpurun_out/r5_nt_ab5.log; A/B variant builds: 0 = cached)
 #endif
-
-typedef float cfm_f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 cfm_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int cfm_u32x4 __attribute__((ext_vector_type(4)));
 
 struct ConvFirstMfmaParams {
   const unsigned char* in;  // [B][IH][IW] uint8
   const float* w;           // [Cout][3][3] fp32 (rounded to bf16 here)
   const float* bias;        // optional [Cout]
-  cfm_u32x4* z;             // optional: conv output, bf16 NCHW8c [B][2][OH*OW] units
-  cfm_u32x4* y;             // optional: act(BatchNorm(z)), same layout
+  u32x4* z;                 // optional: conv output, bf16 NCHW8c [B][2][OH*OW] units
+  u32x4* y;                 // optional: act(BatchNorm(z)), same layout
   unsigned char* signs;     // optional (with y): [B][OH*OW][2] bytes, bit = (BatchNorm output > 0) -- see yogo_conv_first_mfma_signs
   const float* mean;        // for y: [Cout] each
   const float* invstd;
@@ -70,10 +66,9 @@ __global__ __launch_bounds__(256) void conv_first_mfma_kernel(const ConvFirstMfm
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, half = lane >> 5;
   const int wave_g = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(tid >> 6), nwaves = gridDim.x * 4;  // (scalar: descriptors stay in SGPRs)
   const int npix = p.OH * p.OW;
-  constexpr unsigned OOB = 0x80000000u;
 
   // A operand: row m = l31 (output channel), K slots 8 * half + j = (ky = slot / 4, kx = slot % 4); kx = 3 and ky = 3 are padding
-  cfm_bf16x8 wa;
+  bf16x8 wa;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int slot = 8 * half + j, ky = slot >> 2, kx = slot & 3;
@@ -111,7 +106,7 @@ __global__ __launch_bounds__(256) void conv_first_mfma_kernel(const ConvFirstMfm
     /* image rows of this lane's K slots: half 0 -> ky = 0, 1; half 1 -> ky = 2 (and the padding row) */              \
     const int r0_ = 2 * oy_ - 1 + 2 * half;                                                                            \
     const auto rs_ = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + (size_t)min(nb, p.B - 1) * p.IH * p.IW), (short)0, \
-                                                       p.IH * p.IW, 0x00020000);                                       \
+                                                       p.IH * p.IW, RSRC_WORD3);                                       \
     const int o0_ = r0_ * p.IW + 2 * ox_ - 2; /* bytes (2ox - 2 .. 2ox + 1) of the row: two aligned 16-bit loads */    \
     const bool ok0_ = valid_ && r0_ >= 0, ok1_ = valid_ && half == 0; /* rows <= IH - 1: even sizes only */            \
     n_lo0 = (unsigned)__builtin_amdgcn_raw_buffer_load_b16(rs_, (ok0_ && ox_ > 0) ? o0_ : (int)OOB, 0, 0);             \
@@ -133,11 +128,11 @@ __global__ __launch_bounds__(256) void conv_first_mfma_kernel(const ConvFirstMfm
     unsigned bx, by, bz, bw_;
     cfm_bytes_to_bf16((lo0 & 0xFFFFu) | (hi0 << 16), bx, by);
     cfm_bytes_to_bf16((lo1 & 0xFFFFu) | (hi1 << 16), bz, bw_);
-    const cfm_u32x4 bw = {bx, by, bz, bw_};
-    cfm_f32x16 acc;
+    const u32x4 bw = {bx, by, bz, bw_};
+    f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa, __builtin_bit_cast(cfm_bf16x8, bw), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa, __builtin_bit_cast(bf16x8, bw), acc, 0, 0, 0);
 
     float v[8];
 #pragma unroll
@@ -165,17 +160,17 @@ __global__ __launch_bounds__(256) void conv_first_mfma_kernel(const ConvFirstMfm
       }
     }
     if (p.z != nullptr || p.y != nullptr) {
-      cfm_bf16x8 o;
+      bf16x8 o;
 #pragma unroll
       for (int i = 0; i < 8; ++i) o[i] = (__bf16)v[i];
       // lanes 0-31 end up with channel block 0 (channels 0-7) of their pixel, lanes 32-63 with block 1: one 16-byte unit each
       const int vo = valid ? (half * npix + pix) * 16 : (int)OOB;
       if (p.z != nullptr) {
-        const cfm_u32x4 w4 = __builtin_bit_cast(cfm_u32x4, o);
+        const u32x4 w4 = __builtin_bit_cast(u32x4, o);
         const auto r0s = __builtin_amdgcn_permlane32_swap(w4.x, w4.z, false, false);
         const auto r1s = __builtin_amdgcn_permlane32_swap(w4.y, w4.w, false, false);
-        const cfm_u32x4 st = {r0s[0], r1s[0], r0s[1], r1s[1]};
-        const auto rs_z = __builtin_amdgcn_make_buffer_rsrc((void*)(p.z + (size_t)b * 2 * npix), (short)0, 2 * npix * 16, 0x00020000);
+        const u32x4 st = {r0s[0], r1s[0], r0s[1], r1s[1]};
+        const auto rs_z = __builtin_amdgcn_make_buffer_rsrc((void*)(p.z + (size_t)b * 2 * npix), (short)0, 2 * npix * 16, RSRC_WORD3);
         __builtin_amdgcn_raw_buffer_store_b128(st, rs_z, vo, 0, 0);
       }
       if (p.y != nullptr) {  // BatchNorm + activation of the ROUNDED z, as yogo_bn_apply_act_bf16 computes it from the stored tensor
@@ -183,14 +178,8 @@ __global__ __launch_bounds__(256) void conv_first_mfma_kernel(const ConvFirstMfm
 #pragma unroll
         for (int i = 0; i < 8; ++i) r[i] = fmaf((float)o[i], sc[i], sh[i]);
         if (p.signs != nullptr) {  // what the backward pass needs of the pre-activation: one byte per lane (its 8 channels of the pixel)
-          unsigned m = 0;   // bit i = (r[i] > 0): compare into vcc, add-with-carry shifts it in (values 7 down to 0) -- 2 instructions per value
-#define CFM_SGN(I) "v_cmp_lt_f32_e32 vcc, 0, %" #I "\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-          asm(CFM_SGN(8) CFM_SGN(7) CFM_SGN(6) CFM_SGN(5) CFM_SGN(4) CFM_SGN(3) CFM_SGN(2) "v_cmp_lt_f32_e32 vcc, 0, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc"
-              : "+v"(m)
-              : "v"(r[0]), "v"(r[1]), "v"(r[2]), "v"(r[3]), "v"(r[4]), "v"(r[5]), "v"(r[6]), "v"(r[7])
-              : "vcc");
-#undef CFM_SGN
-          const auto rs_s = __builtin_amdgcn_make_buffer_rsrc((void*)(p.signs + (size_t)b * 2 * npix), (short)0, 2 * npix, 0x00020000);
+          const unsigned m = sign_byte(r);
+          const auto rs_s = __builtin_amdgcn_make_buffer_rsrc((void*)(p.signs + (size_t)b * 2 * npix), (short)0, 2 * npix, RSRC_WORD3);
           __builtin_amdgcn_raw_buffer_store_b8((unsigned char)m, rs_s, valid ? 2 * pix + half : (int)OOB, 0, 0);
         }
         if (p.act == ACT_LEAKY) {  // (uniform branches around whole blocks)
@@ -200,14 +189,8 @@ __global__ __launch_bounds__(256) void conv_first_mfma_kernel(const ConvFirstMfm
 #pragma unroll
           for (int i = 0; i < 8; ++i) r[i] = act_fwd(r[i], ACT_SILU);
         }
-        cfm_bf16x8 yo;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) yo[i] = (__bf16)r[i];
-        const cfm_u32x4 w4 = __builtin_bit_cast(cfm_u32x4, yo);
-        const auto r0s = __builtin_amdgcn_permlane32_swap(w4.x, w4.z, false, false);
-        const auto r1s = __builtin_amdgcn_permlane32_swap(w4.y, w4.w, false, false);
-        const cfm_u32x4 st = {r0s[0], r1s[0], r0s[1], r1s[1]};
-        const auto rs_y = __builtin_amdgcn_make_buffer_rsrc((void*)(p.y + (size_t)b * 2 * npix), (short)0, 2 * npix * 16, 0x00020000);
+        const u32x4 st = pack_unit_swap(r);
+        const auto rs_y = __builtin_amdgcn_make_buffer_rsrc((void*)(p.y + (size_t)b * 2 * npix), (short)0, 2 * npix * 16, RSRC_WORD3);
         __builtin_amdgcn_raw_buffer_store_b128(st, rs_y, vo, 0, 0);
       }
     }
@@ -241,8 +224,7 @@ __global__ __launch_bounds__(256) void conv_first_mfma2_kernel(const ConvFirstMf
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, half = lane >> 5;
   const int wave_g = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(tid >> 6), nwaves = gridDim.x * 4;
   const int npix = p.OH * p.OW;
-  constexpr unsigned OOB = 0x80000000u;
-  cfm_bf16x8 wa;
+  bf16x8 wa;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int slot = 8 * half + j, ky = slot >> 2, kx = slot & 3;
@@ -273,7 +255,7 @@ __global__ __launch_bounds__(256) void conv_first_mfma2_kernel(const ConvFirstMf
     const int oy_ = (int)__umulhi((unsigned)pc_, p.m_ow), ox_ = pc_ - oy_ * p.OW;                                      \
     const int r0_ = 2 * oy_ - 1 + 2 * half;                                                                            \
     const auto rs_ = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + (size_t)min(nb, p.B - 1) * p.IH * p.IW), (short)0, \
-                                                       p.IH * p.IW, 0x00020000);                                       \
+                                                       p.IH * p.IW, RSRC_WORD3);                                       \
     const int o0_ = r0_ * p.IW + 2 * ox_; /* columns 4m .. 4m + 3 of the row; 4m - 4 .. 4m - 1 for the left neighbour */ \
     const bool ok0_ = valid_ && r0_ >= 0, ok1_ = valid_ && half == 0;                                                  \
     n_a0 = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rs_, (ok0_ && ox_ > 0) ? o0_ - 4 : (int)OOB, 0, 0);          \
@@ -293,8 +275,8 @@ __global__ __launch_bounds__(256) void conv_first_mfma2_kernel(const ConvFirstMf
     }
     CFM2_FETCH()
     unsigned sgn2 = 0;   // this lane's sign bytes of the pair: pixel 2m in bits 0..7, pixel 2m + 1 in bits 16..23
-    cfm_u32x4 sty[2];    // [e]: y of pixel 2m + e: lanes 0-31 channel block 0, lanes 32-63 block 1 (after the half-wave exchange)
-    cfm_u32x4 stz[2];    // ... and z (the inference forward stores z = act(conv + bias) only)
+    u32x4 sty[2];    // [e]: y of pixel 2m + e: lanes 0-31 channel block 0, lanes 32-63 block 1 (after the half-wave exchange)
+    u32x4 stz[2];    // ... and z (the inference forward stores z = act(conv + bias) only)
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
       // bytes 1, 2, 3 of a word = kernel columns 0, 1, 2: pixel 2m reads (4m - 1, 4m, 4m + 1), pixel 2m + 1 (4m + 1, 4m + 2, 4m + 3)
@@ -303,11 +285,11 @@ __global__ __launch_bounds__(256) void conv_first_mfma2_kernel(const ConvFirstMf
       unsigned bx, by, bz, bw_;
       cfm_bytes_to_bf16(w0, bx, by);
       cfm_bytes_to_bf16(w1, bz, bw_);
-      const cfm_u32x4 bw = {bx, by, bz, bw_};
-      cfm_f32x16 acc;
+      const u32x4 bw = {bx, by, bz, bw_};
+      f32x16 acc;
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa, __builtin_bit_cast(cfm_bf16x8, bw), acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa, __builtin_bit_cast(bf16x8, bw), acc, 0, 0, 0);
       float v[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) v[i] = acc[i];
@@ -324,27 +306,21 @@ __global__ __launch_bounds__(256) void conv_first_mfma2_kernel(const ConvFirstMf
           for (int i = 0; i < 8; ++i) v[i] = act_fwd(v[i], ACT_SILU);
         }
       }
-      cfm_bf16x8 o;
+      bf16x8 o;
 #pragma unroll
       for (int i = 0; i < 8; ++i) o[i] = (__bf16)v[i];
       if (p.z != nullptr) {
-        const cfm_u32x4 w4 = __builtin_bit_cast(cfm_u32x4, o);
+        const u32x4 w4 = __builtin_bit_cast(u32x4, o);
         const auto r0s = __builtin_amdgcn_permlane32_swap(w4.x, w4.z, false, false);
         const auto r1s = __builtin_amdgcn_permlane32_swap(w4.y, w4.w, false, false);
-        stz[e] = cfm_u32x4{r0s[0], r1s[0], r0s[1], r1s[1]};
+        stz[e] = u32x4{r0s[0], r1s[0], r0s[1], r1s[1]};
       }
       if (p.y == nullptr) continue;   // (uniform)
       float r[8];   // BatchNorm + activation of the ROUNDED z, as yogo_bn_apply_act_bf16 computes it from the stored tensor
 #pragma unroll
       for (int i = 0; i < 8; ++i) r[i] = fmaf((float)o[i], sc[i], sh[i]);
       if (p.signs != nullptr) {
-        unsigned m = 0;
-#define CFM_SGN(I) "v_cmp_lt_f32_e32 vcc, 0, %" #I "\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-        asm(CFM_SGN(8) CFM_SGN(7) CFM_SGN(6) CFM_SGN(5) CFM_SGN(4) CFM_SGN(3) CFM_SGN(2) "v_cmp_lt_f32_e32 vcc, 0, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc"
-            : "+v"(m)
-            : "v"(r[0]), "v"(r[1]), "v"(r[2]), "v"(r[3]), "v"(r[4]), "v"(r[5]), "v"(r[6]), "v"(r[7])
-            : "vcc");
-#undef CFM_SGN
+        const unsigned m = sign_byte(r);
         sgn2 |= m << (16 * e);
       }
       if (p.act == ACT_LEAKY) {  // (uniform branches around whole blocks)
@@ -354,21 +330,15 @@ __global__ __launch_bounds__(256) void conv_first_mfma2_kernel(const ConvFirstMf
 #pragma unroll
         for (int i = 0; i < 8; ++i) r[i] = act_fwd(r[i], ACT_SILU);
       }
-      cfm_bf16x8 yo;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) yo[i] = (__bf16)r[i];
-      const cfm_u32x4 w4 = __builtin_bit_cast(cfm_u32x4, yo);
-      const auto r0s = __builtin_amdgcn_permlane32_swap(w4.x, w4.z, false, false);
-      const auto r1s = __builtin_amdgcn_permlane32_swap(w4.y, w4.w, false, false);
-      sty[e] = cfm_u32x4{r0s[0], r1s[0], r0s[1], r1s[1]};
+      sty[e] = pack_unit_swap(r);
     }
     if (p.z != nullptr) {   // (uniform) the pair's z units as two contiguous kilobytes, non-temporal: the same exchange as for y below
       const auto x0 = __builtin_amdgcn_permlane32_swap(stz[0].x, stz[1].x, false, false);
       const auto x1 = __builtin_amdgcn_permlane32_swap(stz[0].y, stz[1].y, false, false);
       const auto x2 = __builtin_amdgcn_permlane32_swap(stz[0].z, stz[1].z, false, false);
       const auto x3 = __builtin_amdgcn_permlane32_swap(stz[0].w, stz[1].w, false, false);
-      const cfm_u32x4 se0 = {x0[0], x1[0], x2[0], x3[0]}, se1 = {x0[1], x1[1], x2[1], x3[1]};
-      const auto rs_z = __builtin_amdgcn_make_buffer_rsrc((void*)(p.z + (size_t)b * 2 * npix), (short)0, 2 * npix * 16, 0x00020000);
+      const u32x4 se0 = {x0[0], x1[0], x2[0], x3[0]}, se1 = {x0[1], x1[1], x2[1], x3[1]};
+      const auto rs_z = __builtin_amdgcn_make_buffer_rsrc((void*)(p.z + (size_t)b * 2 * npix), (short)0, 2 * npix * 16, RSRC_WORD3);
       const int vdz = valid ? (pix + half) * 16 : (int)OOB;
       __builtin_amdgcn_raw_buffer_store_b128(se0, rs_z, vdz, 0, CFM_ST_AUX);
       __builtin_amdgcn_raw_buffer_store_b128(se1, rs_z, valid ? vdz + npix * 16 : (int)OOB, 0, CFM_ST_AUX);
@@ -377,7 +347,7 @@ __global__ __launch_bounds__(256) void conv_first_mfma2_kernel(const ConvFirstMf
 #define CFM_DENSE 1   // (A/B variant builds: 0 = one half-filled store per pixel parity)
 #endif
     if (p.y != nullptr && !CFM_DENSE) {
-      const auto rs_y = __builtin_amdgcn_make_buffer_rsrc((void*)(p.y + (size_t)b * 2 * npix), (short)0, 2 * npix * 16, 0x00020000);
+      const auto rs_y = __builtin_amdgcn_make_buffer_rsrc((void*)(p.y + (size_t)b * 2 * npix), (short)0, 2 * npix * 16, RSRC_WORD3);
 #pragma unroll
       for (int e = 0; e < 2; ++e) __builtin_amdgcn_raw_buffer_store_b128(sty[e], rs_y, valid ? (half * npix + pix + e) * 16 : (int)OOB, 0, 0);
     } else
@@ -390,8 +360,8 @@ __global__ __launch_bounds__(256) void conv_first_mfma2_kernel(const ConvFirstMf
       const auto x1 = __builtin_amdgcn_permlane32_swap(sty[0].y, sty[1].y, false, false);
       const auto x2 = __builtin_amdgcn_permlane32_swap(sty[0].z, sty[1].z, false, false);
       const auto x3 = __builtin_amdgcn_permlane32_swap(sty[0].w, sty[1].w, false, false);
-      const cfm_u32x4 se0 = {x0[0], x1[0], x2[0], x3[0]}, se1 = {x0[1], x1[1], x2[1], x3[1]};
-      const auto rs_y = __builtin_amdgcn_make_buffer_rsrc((void*)(p.y + (size_t)b * 2 * npix), (short)0, 2 * npix * 16, 0x00020000);
+      const u32x4 se0 = {x0[0], x1[0], x2[0], x3[0]}, se1 = {x0[1], x1[1], x2[1], x3[1]};
+      const auto rs_y = __builtin_amdgcn_make_buffer_rsrc((void*)(p.y + (size_t)b * 2 * npix), (short)0, 2 * npix * 16, RSRC_WORD3);
       const int vd = valid ? (pix + half) * 16 : (int)OOB;   // (npix is even: a pair is valid or not as a whole)
       __builtin_amdgcn_raw_buffer_store_b128(se0, rs_y, vd, 0, CFM_ST_AUX);
       __builtin_amdgcn_raw_buffer_store_b128(se1, rs_y, valid ? vd + npix * 16 : (int)OOB, 0, CFM_ST_AUX);   // (vector offset: conv_bf16_epi_groups.inc on scalar store offsets)
@@ -401,7 +371,7 @@ __global__ __launch_bounds__(256) void conv_first_mfma2_kernel(const ConvFirstMf
       // four bytes as one dword
       const unsigned other = (unsigned)__builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, (int)sgn2);
       const unsigned word = (sgn2 & 0xFFu) | ((other & 0xFFu) << 8) | ((sgn2 & 0xFF0000u)) | ((other & 0xFF0000u) << 8);
-      const auto rs_s = __builtin_amdgcn_make_buffer_rsrc((void*)(p.signs + (size_t)b * 2 * npix), (short)0, 2 * npix, 0x00020000);
+      const auto rs_s = __builtin_amdgcn_make_buffer_rsrc((void*)(p.signs + (size_t)b * 2 * npix), (short)0, 2 * npix, RSRC_WORD3);
       __builtin_amdgcn_raw_buffer_store_b32(word, rs_s, (valid && half == 0) ? 2 * pix : (int)OOB, 0, 0);
     }
   }
@@ -648,7 +618,7 @@ static int conv_first_mfma_impl(const void* in, const float* w, const float* bia
   if (B == 0) return YOGO_OK;
   ConvFirstMfmaParams p{};
   p.in = reinterpret_cast<const unsigned char*>(in); p.w = w; p.bias = bias;
-  p.z = reinterpret_cast<cfm_u32x4*>(z); p.y = reinterpret_cast<cfm_u32x4*>(y); p.signs = reinterpret_cast<unsigned char*>(signs);
+  p.z = reinterpret_cast<u32x4*>(z); p.y = reinterpret_cast<u32x4*>(y); p.signs = reinterpret_cast<unsigned char*>(signs);
   p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.beta = beta; p.stats_part = stats_part;
   p.B = B; p.Cout = Cout; p.IH = IH; p.IW = IW; p.OH = IH / 2; p.OW = IW / 2; p.act = act;
   p.gpi = cdiv(p.OH * p.OW, 32); p.total = B * p.gpi;

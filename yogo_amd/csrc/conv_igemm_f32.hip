@@ -15,10 +15,9 @@
 //
 // fp32 MFMA is an exact k-ordered fmaf chain (MI355X guide), so results differ from the CPU reference only
 // by summation order.
-#include "common.h"
+#include "bf16_dev.h"
 #include <cstdlib>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define MAX_TAPS 9
 #define IGEMM_LDS_BUDGET (80 * 1024)
@@ -68,8 +67,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f32_kernel(const IgemmParam
   // contiguous run of (image, tile) work so that vertically adjacent tiles -- which share halo rows -- hit the same L2.
   const unsigned nwg = gridDim.x * gridDim.y * gridDim.z;
   const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-  const unsigned xq = nwg >> 3, xr = nwg & 7, xcd = lin & 7;
-  const unsigned widx = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (lin >> 3);
+  const unsigned widx = xcd_remap(lin, nwg);
   const int bx = widx % gridDim.x;
   const int by = (widx / gridDim.x) % gridDim.y;
   const int b = widx / (gridDim.x * gridDim.y);

@@ -15,14 +15,7 @@
 // are decoded once, per unit only the unit's origin is added and the image / chunk borders are turned into out-of-range
 // offsets (which the buffer unit writes as zeros).  One barrier per unit, up to two units in flight ahead of the MFMAs.  Split-K slabs + the fixed-order reduction of
 // wgrad_f32.hip (clamp, OIHW, bias) finish the gradient.
-#include "common.h"
-#include <type_traits>
-#include <utility>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+#include "bf16_dev.h"
 
 #define WGB_LDS_MAX (160 * 1024)
 #ifndef WGB_BLK4
@@ -79,24 +72,16 @@ extern "C" int yogo_diag_wgrad_bf16_stamps(void* buf, size_t bytes) { g_wb_stamp
 #define WB_STAMP(ACC)
 #endif
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
 // One LDS-DMA piece: 64 lanes x 16 bytes from (descriptor, per-lane byte offset) to LDS bytes [lds_addr, lds_addr + 1024).
 // Issued from inline asm on purpose: hipcc (ROCm 7.2) makes every later LDS read wait for ALL of its own LDS-DMA loads
 // (vmcnt(0)), which would serialise the ring; these loads are invisible to it and are retired by wait_dma() below.
-__device__ __forceinline__ void dma16(i32x4 rsrc, unsigned lds_addr, int voff) {
+__device__ __forceinline__ void dma16(i32x4 rs, unsigned lds_addr, int voff) {
   unsigned keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
                : "=&s"(keep)
-               : "v"(voff), "s"(lds_addr), "s"(rsrc)
+               : "v"(voff), "s"(lds_addr), "s"(rs)
                : "memory");
 }
-// descriptor of `bytes` bytes at `ptr` (raw buffer, no swizzle)
-__device__ __forceinline__ i32x4 make_rsrc(const void* ptr, int bytes) {
-  const unsigned long long a = reinterpret_cast<unsigned long long>(ptr);
-  return i32x4{(int)(unsigned)a, (int)((unsigned)(a >> 32) & 0xFFFFu), bytes, 0x00020000};
-}
-
 // counted wait for this wavefront's LDS-DMA: at most n of its newest loads may still be in flight
 __device__ __forceinline__ void wait_dma(int n) {
   switch (n) {
@@ -112,12 +97,6 @@ __device__ __forceinline__ bf16x8 lds_tr8(const unsigned char* base, int off0, i
   const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4)(base + off0));
   const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4)(base + off1));
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
-// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a compile-time unrolled loop whose index can feed constexpr
-template <class F, int... I>
-__device__ __forceinline__ void wb_static_for(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
 }
 
 // MPW: co-blocks per wavefront (the wavefront grid is MBW x NBW x KS x kernel rows; a workgroup covers MBW * MPW co-blocks and
@@ -140,7 +119,6 @@ __global__ __launch_bounds__(64 * MBW * NBW * KS * (T == 1 ? 1 : 3)) void wgrad_
   constexpr int TM = PACK2 ? (TT + 1) / 2 : TT;  // MFMAs (B operands, accumulator tiles) per k-step and (co, ci) block pair
   constexpr int NT = 64 * MBW * NBW * KS * TG;
   constexpr int XR = (T == 1) ? R : (R - 1) * S + 3;
-  constexpr unsigned OOB = 0x80000000u;
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, half = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int tg = wave % TG;
@@ -223,8 +201,8 @@ __global__ __launch_bounds__(64 * MBW * NBW * KS * (T == 1 ? 1 : 3)) void wgrad_
       iu_cw = 0;                                                                                                      \
       if (++iu_rg == p.nrowg) { iu_rg = 0; ++iu_b; }                                                                  \
     }                                                                                                                 \
-    const i32x4 rs_g = make_rsrc(p.g + (size_t)b_ * p.Mbk * gplane, p.Mbk * gplane * 16);                             \
-    const i32x4 rs_x = make_rsrc(p.x + (size_t)b_ * p.Nb * xplane, p.Nb * xplane * 16);                               \
+    const i32x4 rs_g = rsrc(p.g + (size_t)b_ * p.Mbk * gplane, p.Mbk * gplane * 16);                                  \
+    const i32x4 rs_x = rsrc(p.x + (size_t)b_ * p.Nb * xplane, p.Nb * xplane * 16);                                    \
     const unsigned lb_ = (unsigned)(((BUF) * p.bufu + wave * 64) * 16);  /* the dynamic LDS block starts at LDS address 0 */ \
     const int gorg_ = (oy0_ * p.OW + ox0_) * 16, rmax_ = p.OH - oy0_;                                                 \
     const int iy0_ = oy0_ * S - p.pad, ix0_ = ox0_ * S - p.pad;                                                       \
@@ -385,7 +363,7 @@ __global__ __launch_bounds__(64 * MBW * NBW * KS * (T == 1 ? 1 : 3)) void wgrad_
           }
           __builtin_amdgcn_sched_barrier(0);
         };
-        wb_static_for(step, std::make_integer_sequence<int, NSB>{});
+        static_for(step, std::make_integer_sequence<int, NSB>{});
         if (wide) step(std::integral_constant<int, NSB>{});
       } else if (issue_) {
         WB_ISSUE_SLOTS   // (diagnostic: no operand reads -- the DMA still goes out; PREP above has advanced the iterators)
@@ -444,7 +422,7 @@ __global__ __launch_bounds__(64 * MBW * NBW * KS * (T == 1 ? 1 : 3)) void wgrad_
         }
         __builtin_amdgcn_sched_barrier(0);
       };
-      wb_static_for(step, std::make_integer_sequence<int, NS>{});
+      static_for(step, std::make_integer_sequence<int, NS>{});
       }
     } else if constexpr (LEAN2) {
       constexpr int RJ = (R / KS) > 0 ? R / KS : 1, NS2 = RJ * KR, XPB = PACK2 ? 32 : 64;  // (RJ >= 1 wherever LEAN2_OK holds)
@@ -479,7 +457,7 @@ __global__ __launch_bounds__(64 * MBW * NBW * KS * (T == 1 ? 1 : 3)) void wgrad_
           WB_BIAS(av[set])
           __builtin_amdgcn_sched_barrier(0);
         };
-        wb_static_for(step, std::make_integer_sequence<int, NS2>{});
+        static_for(step, std::make_integer_sequence<int, NS2>{});
       } else if (issue_) {
         WB_ISSUE_SLOTS   // (diagnostic: no operand reads -- the DMA still has to go out; the iterators were advanced by PREP above)
       }
