@@ -723,6 +723,91 @@ def bf16_block_forward(i: int, x_in: torch.Tensor, sd: Dict[str, torch.Tensor], 
     return S
 
 
+# ---------------------------------------------------------------------------
+# bf16-STORAGE emulation of the INFERENCE forward (yogo_amd/engine.py: InferEngineBF16; the reference runs `yogo infer` under bf16
+# autocast, yogo/infer.py:313-317).  Its arithmetic is not training's: eval-mode BatchNorm is FOLDED on the host into a per-channel
+# weight scale and a bias, and the convolutions run launches no training step runs.  As above, a plain fp32 forward bounds it only
+# loosely (3e-2 of the output range after eight layers); this restates the folded network and rounds where the product rounds, so
+# every layer can be held to one bf16 ulp given its actual input (tests/_util.py: teacher_forced_infer_check).  Rounding points:
+#   * scale = gamma / sqrt(running_var + eps), bias' = beta + (bias_or_0 - running_mean) * scale, fp32, in that order of operations
+#     (engine.py: InferEngineBF16._prepare)
+#   * layers >= 1: weights bf16(w * scale) -- one fp32 product, one rounding (conv_bf16.hip: conv_bf16_pack_kernel, `w[...] * sc`
+#     then `(__bf16)v`); fp32 accumulation; y = bf16(act(conv + bias')) (the lean / merged epilogues of conv_bf16.hip: conv_bf16_kernel,
+#     conv_bf16_ws.hip, conv_bf16_ws3.hip, conv_bf16_staged.hip)
+#   * layer 0 on the matrix cores: the folded fp32 weights w * scale are rounded to bf16 by the kernel (conv_first_mfma.hip:
+#     conv_first_mfma2_kernel `wa`); 8-bit pixels are exact in bf16, every product and the sum of nine are exact in fp32;
+#     z = bf16(act(sum + bias')) (its `p.y == nullptr` branch)
+#   * layer 0 on the direct kernel (odd sizes, rgb or float input): the folded fp32 weights UNROUNDED in an fp32 fma chain, then
+#     bf16(act(acc + bias')) (conv_bf16.hip: conv_first_bf16_kernel)
+#   * last layer: fp32 output, no rounding (conv_bf16_head.hip: conv_bf16_1x1_f32_kernel; conv_bf16_kernel with F32 = true)
+#   * a block without BatchNorm: as in training's emulation (bf16(w), bias unchanged), without dropout mask and without sign map
+# ---------------------------------------------------------------------------
+def l0_infer_on_matrix_cores(spec: list, x: torch.Tensor) -> bool:
+    """the shapes InferEngineBF16.forward hands to yogo_conv_first_mfma (conv_first_mfma.hip: yogo_conv_first_mfma_supported)"""
+    co, k, s, hb, hbn, act, dp = spec[0]
+    H, W = x.shape[-2:]
+    return bool(x.dtype == torch.uint8 and x.shape[1] == 1 and 1 <= co <= 16 and s == 2 and k == 3 and H % 2 == 0 and W % 2 == 0
+                and H >= 4 and W >= 4 and (H // 2) * (W // 2) > 1)
+
+
+def bf16_infer_fold(i: int, sd: Dict[str, torch.Tensor], spec: list, dtype: torch.dtype = torch.float32):
+    """engine.py: InferEngineBF16._prepare -- (scale, bias') of block i, either None where the block has none"""
+    co, k, s, hb, hbn, act, dp = spec[i]
+    pre = conv_prefix(spec, i)
+    bias = sd[pre + "bias"].to(dtype) if hb else None
+    scale = None
+    if hbn:
+        b = f"model.{i}.1."
+        gamma, beta = sd[b + "weight"].to(dtype), sd[b + "bias"].to(dtype)
+        scale = gamma / torch.sqrt(sd[b + "running_var"].to(dtype) + BN_EPS)   # _prepare: gamma / torch.sqrt(running_var + eps)
+        base = bias if bias is not None else torch.zeros_like(scale)
+        bias = beta + (base - sd[b + "running_mean"].to(dtype)) * scale        # _prepare: beta + (base - running_mean) * scale
+    return scale, bias
+
+
+def bf16_infer_block_forward(i: int, x_in: torch.Tensor, sd: Dict[str, torch.Tensor], spec: list, l0_mfma: bool,
+                             fold_given: Optional[Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]] = None,
+                             exact: bool = False, conv64: bool = False) -> Dict[str, torch.Tensor]:
+    """block i of the bf16 inference forward from the (bf16-valued, fp32-typed) input ``x_in`` (layer 0: the image as floats):
+    a dict with ``y`` (bf16-valued fp32; the last layer: plain fp32), ``scale``, ``bias``, ``wq`` (the weights as multiplied).
+    ``fold_given`` = (scale, bias') substitutes the engine's own folded tensors (teacher-forced: they are checked on their own).
+    ``exact``: the same folded form in float64 with NO rounding anywhere (the folding algebra against the unfolded BatchNorm).
+    ``conv64``: the same operands and rounding points with the convolution accumulated in float64 -- what a correct kernel with any
+    fp32 summation order must agree with to one bf16 ulp."""
+    n = len(spec)
+    co, k, s, hb, hbn, act, dp = spec[i]
+    f = torch.float64 if exact else torch.float32
+    rb = (lambda t: t) if exact else _rb
+    scale, bias = bf16_infer_fold(i, sd, spec, f) if fold_given is None else fold_given
+    w = sd[conv_prefix(spec, i) + "weight"].to(f)
+    wf = w * scale[:, None, None, None] if scale is not None else w   # ONE fp32 product (layer 0: engine.py `w * scale[:, None, None, None]`)
+    wq = wf if (i == 0 and not l0_mfma) else rb(wf)                   # conv_first_bf16_kernel multiplies the fp32 weights; all others bf16
+    cd = torch.float64 if (exact or conv64) else torch.float32
+    a = F.conv2d(x_in.to(cd), wq.to(cd), None, stride=s, padding=1 if k == 3 else 0)
+    if bias is not None:
+        a = a + bias.to(cd)[None, :, None, None]                      # the epilogues add the bias to the finished fp32 sum
+    a = a.to(f)
+    v = _act(a, act)
+    y = v if i == n - 1 else rb(v)                                    # the last layer stores fp32
+    return {"x": x_in, "wq": wq, "scale": scale, "bias": bias, "y": y}
+
+
+def bf16_infer_forward(x: torch.Tensor, sd: Dict[str, torch.Tensor], spec: list, l0_mfma: Optional[bool] = None,
+                       taps: Optional[Dict[int, torch.Tensor]] = None, exact: bool = False, conv64: bool = False) -> torch.Tensor:
+    """the raw head output [B, 5 + C, Sy, Sx] of InferEngineBF16.forward on a uint8 or float image batch; ``taps[i]`` receives the
+    output of block i"""
+    if x.ndim == 3:
+        x = x[None]
+    if l0_mfma is None:
+        l0_mfma = l0_infer_on_matrix_cores(spec, x)
+    cur = x.to(torch.float64 if exact else torch.float32)
+    for i in range(len(spec)):
+        cur = bf16_infer_block_forward(i, cur, sd, spec, l0_mfma, exact=exact, conv64=conv64)["y"]
+        if taps is not None:
+            taps[i] = cur
+    return cur
+
+
 def bf16_head_gradient(raw: torch.Tensor, sd: Dict[str, torch.Tensor], label: torch.Tensor, anchor_w: float, anchor_h: float,
                        no_obj_weight: float = 0.5, iou_weight: float = 5.0, classify_weight: float = 1.0,
                        label_smoothing: float = 0.01):

@@ -156,7 +156,8 @@ def test_predict_outputs_match_oracle(in_repo_root, tmp_path, half, capsys):
                    obj_thresh=0.4, iou_thresh=0.5, half=half, return_full_predictions=True, class_names=CLASSES)
     files = sorted(imgdir.glob("*.png"))
     assert full.shape == (3, 9, 8, 12)
-    # the forward itself: fp32 == the oracle to fp32 tolerance; bf16 within bf16's (3e-2 of the output range, as test_gpu_parity)
+    # the forward itself: fp32 == the oracle to fp32 tolerance; bf16 within bf16's (3e-2 of the output range, as test_gpu_parity; the
+    # layer-by-layer one-ulp check of the bf16 forward is tests/test_gpu_infer_teacher_forced.py)
     sd = {k: v.cpu() for k, v in net.state_dict().items()}
     x = torch.stack([read_image(f) for f in files])
     ref = O.yogo_forward(x, sd, O.arch("base_model", 4), 0.0425, 0.0555, inference=True)

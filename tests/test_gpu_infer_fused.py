@@ -192,7 +192,8 @@ def test_configs4_batch_256_inference_plan_and_results():
         ref = O.format_preds(dec[b].cpu(), obj_thresh=0.5, iou_thresh=0.5)
         assert ref.shape[0] == n[b]
         assert torch.equal(ref.view(torch.int32), rows[b, :n[b]].cpu().view(torch.int32))
-    # (iv) the forward itself against the fp32 oracle (the bound of test_gpu_bf16.py's inference tests: 3e-2 of the output range)
+    # (iv) the forward itself against the fp32 oracle (the bound of test_gpu_bf16.py's inference tests: 3e-2 of the output range; the tight
+    # per-layer check of this forward against the folded bf16 oracle is tests/test_gpu_infer_teacher_forced.py)
     want_out = O.yogo_forward(x2, sd, O.arch("base_model", 7), 0.0425, 0.0555, inference=True)
     err = (dec[0:2].cpu() - want_out).abs().max().item()
     assert err <= 3e-2 * float(want_out.abs().max()), err

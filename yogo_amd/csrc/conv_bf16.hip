@@ -1290,6 +1290,7 @@ extern "C" int yogo_conv_bf16_pack(const float* w_oihw, const float* scale, void
   hipLaunchKernelGGL(conv_bf16_pack_kernel, dim3(min(1024, cdiv(total, 256))), dim3(256), 0, stream, w_oihw, scale,
                      reinterpret_cast<u32x4*>(packed), Cin, Cout, ks, Kb, Mpad, mode);
   YOGO_CHECK_LAUNCH("conv_bf16_pack");
+  if (yogo_launch_log_enabled()) yogo_launch_log("conv_bf16_pack_kernel | Cin=%d Cout=%d ks=%d mode=%d scale=%d", Cin, Cout, ks, mode, scale != nullptr);
   return YOGO_OK;
 }
 
@@ -1791,5 +1792,8 @@ extern "C" int yogo_conv_first_fwd_bf16(const void* in, int in_dtype, const floa
   else if (Cin == 1) hipLaunchKernelGGL((conv_first_bf16_kernel<float, 1>), grid, dim3(256), 0, stream, p);
   else hipLaunchKernelGGL((conv_first_bf16_kernel<float, 3>), grid, dim3(256), 0, stream, p);
   YOGO_CHECK_LAUNCH("conv_first_fwd_bf16");
+  if (yogo_launch_log_enabled())
+    yogo_launch_log("conv_first_bf16_kernel<%s, %d> | B=%d Cout=%d in=%dx%d out=%dx%d stride=%d act=%d bias=%d", in_dtype == 0 ? "uint8_t" : "float", Cin, B, Cout, IH, IW,
+                    p.OH, p.OW, stride, act, bias != nullptr);
   return YOGO_OK;
 }

@@ -625,11 +625,15 @@ static int conv_first_mfma_impl(const void* in, const float* w, const float* bia
   p.m_ow = cfm_magic(p.OW);
   YOGO_CHECK_ARG((long long)p.total * 32 < (1ll << 31) && (long long)p.OH * p.OW * p.OW < (1ll << 32), "conv_first_mfma: batch / image too large");
   // the sweeps that write tensors (training: y [+ z] [+ sign map]; inference: z = act(conv + bias)) at an even output width: two pixels per lane
-  if (g_cfm_pairs && (y != nullptr || z != nullptr) && stats_part == nullptr && p.OW % 2 == 0 && p.OW >= 4)
+  const bool pairs = g_cfm_pairs && (y != nullptr || z != nullptr) && stats_part == nullptr && p.OW % 2 == 0 && p.OW >= 4;
+  if (pairs)
     hipLaunchKernelGGL(conv_first_mfma2_kernel, dim3(cfm_grid(B * cdiv(p.OH * p.OW, 64))), dim3(256), 0, stream, p);
   else
     hipLaunchKernelGGL(conv_first_mfma_kernel, dim3(cfm_grid(p.total)), dim3(256), 0, stream, p);
   YOGO_CHECK_LAUNCH("conv_first_mfma");
+  if (yogo_launch_log_enabled())
+    yogo_launch_log("%s | B=%d Cout=%d in=%dx%d act=%d bias=%d z=%d y=%d signs=%d stats=%d", pairs ? "conv_first_mfma2_kernel" : "conv_first_mfma_kernel", B, Cout,
+                    IH, IW, act, bias != nullptr, z != nullptr, y != nullptr, signs != nullptr, stats_part != nullptr);
   return YOGO_OK;
 }
 

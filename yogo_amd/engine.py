@@ -962,6 +962,11 @@ class InferEngineBF16:
         self.engine = engine
         self._key = None
         self._prep: List[Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]] = []
+        self._fold: List[Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]] = []   # per layer: the folded (scale, bias) _prep was made of
+        # tests: when a dict, forward() stores a clone of every layer's output under ("y", i) and the folded ("scale", i) / ("bias", i)
+        # of _prepare (None where a layer has none; under the fused head + decode the last "y" is the decoded tensor) -- the teacher-forced check of
+        # tests/_util.py.  It records the plan, it does not change it
+        self.trace: Optional[dict] = None
 
     def _state_key(self):
         k = [self.engine.generation]
@@ -985,7 +990,7 @@ class InferEngineBF16:
         if key == self._key:
             return
         st = _hip.stream_ptr()
-        prep = []
+        prep, fold = [], []
         for i, L in enumerate(self.engine.layers):
             w = _f32(L.conv.weight.detach())
             bias = L.conv.bias.detach().float() if L.conv.bias is not None else None
@@ -997,6 +1002,7 @@ class InferEngineBF16:
                 scale = gamma / torch.sqrt(bn.running_var.float() + bn.eps)
                 base = bias if bias is not None else torch.zeros_like(scale)
                 bias = beta + (base - bn.running_mean.float()) * scale
+            fold.append((scale, bias))
             if i == 0:
                 wf = w * scale[:, None, None, None] if scale is not None else w
                 prep.append((wf.contiguous(), bias.contiguous() if bias is not None else None))
@@ -1005,7 +1011,7 @@ class InferEngineBF16:
                 packed = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
                 _hip.call("yogo_conv_bf16_pack", w, scale.contiguous() if scale is not None else None, packed, L.cin, L.cout, L.k, 0, st)
                 prep.append((packed, bias.contiguous() if bias is not None else None))
-        self._prep = prep
+        self._prep, self._fold = prep, fold
         self._key = key
 
     @torch.no_grad()
@@ -1023,6 +1029,11 @@ class InferEngineBF16:
         cur = x.contiguous() if x.dtype == torch.uint8 else _f32(x)
         H, W = int(cur.shape[2]), int(cur.shape[3])
         n = len(self.engine.layers)
+        tc = self.trace
+        if tc is not None:
+            for i, (sc, bs) in enumerate(self._fold):
+                tc[("scale", i)] = None if sc is None else sc.clone()
+                tc[("bias", i)] = None if bs is None else bs.clone()
         for i, L in enumerate(self.engine.layers):
             OH, OW = L.out_hw(H, W)
             if OH <= 0 or OW <= 0:
@@ -1055,6 +1066,8 @@ class InferEngineBF16:
                 mb = _hip.lib().yogo_bf16_channel_blocks(L.cout)
                 out = torch.empty(B, mb, OH, OW, 8, dtype=torch.bfloat16, device=dev)
                 _hip.call("yogo_conv2d_fwd_bf16", cur, wq, bias, out, None, None, None, B, L.cin, L.cout, H, W, L.k, L.s, L.act, st)
+            if tc is not None:
+                tc[("y", i)] = out.clone()
             cur, H, W = out, OH, OW
         return cur
 
