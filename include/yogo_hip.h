@@ -524,6 +524,23 @@ int yogo_png_unpack(unsigned char* scan, long long scan_bytes, const long long* 
 int yogo_png_unpack_planes(unsigned char* scan, long long scan_bytes, const long long* table, int B, int H, int W, int C_out,
                            unsigned char* out, int* status, yogo_stream_t stream);
 
+/* ---- other-size files into the device image cache (yogo_amd/png_prefill.py, `yogo train ... --device-image-resize`) ------------
+ * Separable antialiased bilinear (triangle filter) resampling of planar uint8 images: torch._upsample_bilinear2d_aa with
+ * align_corners = False, then round-half-even and a clamp to 0 .. 255 -- what yogo_amd.yogo_dataset.resize_image computes.
+ * src: [n][C][Hs][Ws] uint8 device; dst: [N][C][Hd][Wd] uint8 device (any alignment: a view into the cache); image k goes to
+ * dst[dst_index[k]].  The taps are made on the host (yogo_amd/resize.py: aa_taps), per axis start[n_out] int32 and
+ * weights[n_out][K] fp32 zero-padded to K, and travel packed in one 8-byte aligned buffer
+ *   int64 dst_index[n] | int32 start_y[Hd] | int32 start_x[Wd] | float wy[Hd][Ky] | float wx[Wd][Kx]
+ * of which tables_host is the copy in host memory and tables_dev the same bytes in device memory.  The host copy is checked before
+ * anything is launched (YOGO_ERR_ARG, nothing written): dst_index distinct and inside [0, N); per axis the starts ascending and
+ * inside the source, every weight in [0, 1], none on an index past the source, each output's weights summing to 1; K <= 18 and a
+ * down-scale of at most 8 per axis (any up-scale); the tables' spans within what a tile stages.  So every source index the kernel
+ * forms lies in [0, n_in) and it needs no status.  Arithmetic: the horizontal pass into an fp32 intermediate, then the vertical
+ * one; each sum from 0 in ascending tap order with fmaf; rintf, then the clamp.  One workgroup per (image, plane, TH x 64 output
+ * tile), the source rows staged in LDS, TH sized from the tables so that several workgroups share a CU.  n, C <= 65535. */
+int yogo_resize_aa_u8(const unsigned char* src, int n, int C, int Hs, int Ws, unsigned char* dst, int N, int Hd, int Wd,
+                      const void* tables_host, const void* tables_dev, int Ky, int Kx, yogo_stream_t stream);
+
 /* ---- optimiser: torch.optim.AdamW over one flat buffer, yogo/train.py:213-217,324 ---------------------------------------- */
 int yogo_adamw_step(float* p, const float* g, float* m, float* v, long long n, int step, double lr, double beta1,
                     double beta2, double eps, double weight_decay, double grad_scale, yogo_stream_t stream);

@@ -1,7 +1,7 @@
 """What the routes that decode stored bytes on the device share -- zarr stacks (yogo_amd/zarr_feed.py), PNG directories for inference
 (yogo_amd/png_feed.py), the PNG prefill of the device image cache (yogo_amd/png_prefill.py): the launch wrappers of
-``yogo_blosc_lz4_decode``, ``yogo_inflate_zlib``, ``yogo_png_unpack`` and ``yogo_png_unpack_planes`` with their tensor checks,
-``gather`` (a pool's futures), ``raise_first_bad`` (a status vector -> RuntimeError), ``png_stream_into`` (one PNG file -> one zlib
+``yogo_blosc_lz4_decode``, ``yogo_inflate_zlib``, ``yogo_png_unpack``, ``yogo_png_unpack_planes`` and ``yogo_resize_aa_u8`` (the
+prefill's resize of other-size files) with their tensor checks, ``gather`` (a pool's futures), ``raise_first_bad`` (a status vector -> RuntimeError), ``png_stream_into`` (one PNG file -> one zlib
 stream in its room of a pinned slot) and ``PrefetchFeed`` (the iterator that loads batch n + 1 while the caller works on batch n)."""
 from __future__ import annotations
 
@@ -121,6 +121,43 @@ def png_unpack_planes(scan: torch.Tensor, table: torch.Tensor, image_hw: Tuple[i
     with torch.cuda.device(out.device):
         _hip.call("yogo_png_unpack_planes", scan, scan.numel(), table, B, H, W, C, out, status, _hip.stream_ptr())
     return out
+
+
+def resize_aa(src: torch.Tensor, dst: torch.Tensor, dst_index, taps_y: Tuple[np.ndarray, np.ndarray],
+              taps_x: Tuple[np.ndarray, np.ndarray]) -> torch.Tensor:
+    """One ``yogo_resize_aa_u8`` launch on the current stream: dst[dst_index[k]] = src[k] resampled as ``resize_image`` does it.
+    src: contiguous uint8 [n, C, Hs, Ws] device; dst: contiguous uint8 [N, C, Hd, Wd] on the same device; dst_index: n distinct
+    slots of dst (a sequence or an int64 tensor, on the host); taps_y / taps_x: ``yogo_amd.resize.aa_taps(Hs, Hd)`` / ``(Ws, Wd)``,
+    (start int32 [n_out], weights float32 [n_out, K]).  The entry point checks the tables and the slots before it launches."""
+    for t, what in ((src, "the source images"), (dst, "the resized images")):
+        _hip.require_cuda(t, what)
+    for t, name in ((src, "src"), (dst, "dst")):
+        if t.dtype != torch.uint8 or t.ndim != 4 or not t.is_contiguous() or t.numel() == 0:
+            raise ValueError(f"resize_aa: {name} must be a non-empty contiguous uint8 [n, C, H, W] tensor, got {tuple(t.shape)} {t.dtype}")
+    if src.shape[1] != dst.shape[1]:
+        raise ValueError(f"resize_aa: src has {src.shape[1]} planes, dst {dst.shape[1]}")
+    require_same_device("resize_aa", src, dst)
+    n, C, Hs, Ws = (int(v) for v in src.shape)
+    N, _, Hd, Wd = (int(v) for v in dst.shape)
+    index = np.ascontiguousarray(torch.as_tensor(dst_index, dtype=torch.int64).reshape(-1).cpu().numpy())
+    if index.size != n:
+        raise ValueError(f"resize_aa: {index.size} destination slots for {n} images")
+    parts = [index]
+    for (start, weights), n_out, axis in ((taps_y, Hd, "y"), (taps_x, Wd, "x")):
+        start, weights = np.asarray(start), np.asarray(weights)
+        if start.dtype != np.int32 or start.shape != (n_out,) or weights.dtype != np.float32 or weights.ndim != 2 or weights.shape[0] != n_out \
+                or weights.shape[1] < 1:
+            raise ValueError(f"resize_aa: the {axis} taps must be (int32 [{n_out}], float32 [{n_out}, K]), got {start.dtype} {start.shape}, "
+                             f"{weights.dtype} {weights.shape}")
+    (sy, wy), (sx, wx) = taps_y, taps_x
+    parts += [np.ascontiguousarray(sy), np.ascontiguousarray(sx), np.ascontiguousarray(wy), np.ascontiguousarray(wx)]
+    packed = np.concatenate([p.reshape(-1).view(np.uint8) for p in parts])
+    host = np.zeros(-(-packed.size // 8), dtype=np.int64)   # (8-byte aligned, as the entry point asks)
+    host.view(np.uint8)[:packed.size] = packed
+    with torch.cuda.device(dst.device):
+        _hip.call("yogo_resize_aa_u8", src, n, C, Hs, Ws, dst, N, Hd, Wd, host.ctypes.data, torch.from_numpy(host).to(dst.device),
+                  int(np.asarray(wy).shape[1]), int(np.asarray(wx).shape[1]), _hip.stream_ptr())
+    return dst
 
 
 def gather(futures: Sequence[Future]) -> list:

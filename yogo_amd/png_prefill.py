@@ -23,6 +23,15 @@ not on the host route, where it stays with the workers.  Files both accept give 
 The scratch -- two pinned slots, the stored streams and the scanlines on the device -- lives only while ``fill`` runs and is NOT
 part of the cache budget: per chunk the files' bytes twice pinned, once on the device, and ``H * (1 + bpp * W)`` bytes of scanlines
 per image (``stats["scratch_device_bytes"]``, ``stats["scratch_pinned_bytes"]``).  torch's global RNG is not touched.
+
+``device_resize=True`` (``--device-image-resize``) keeps a device-decodable file of ANOTHER size on the device as well, as long as
+each axis scales down by at most ``resize.MAX_DOWNSCALE`` (up by anything): the files of a chunk are grouped by their size, a group is
+inflated with the rest, unpacked by a ``yogo_png_unpack_planes`` launch of its own into a staging tensor ``[n, C, Hs, Ws]`` -- the
+colour conversion comes before the resize, as in ``read_image`` then ``resize_image`` -- and ONE ``yogo_resize_aa_u8`` launch
+(csrc/resize_aa.hip, the taps of yogo_amd/resize.py) writes it into the group's slots.  The staging is scratch like the rest.  The
+pixels are those of the definition ``resize_image`` implements, computed in fp32 from fp64 taps; torch's CPU kernel rounds its own
+way, so a few pixels per image whose exact value lies within about 1e-3 of a rounding edge may differ by one grey level from the
+host route's.  Off (the default), nothing changes.
 """
 from __future__ import annotations
 
@@ -34,7 +43,8 @@ import numpy as np
 import torch
 
 from yogo_amd import _hip, png
-from yogo_amd.device_decode import ALIGN, MAX_THREADS, inflate_streams, png_stream_into, png_unpack_planes
+from yogo_amd.device_decode import ALIGN, MAX_THREADS, inflate_streams, png_stream_into, png_unpack_planes, resize_aa
+from yogo_amd.resize import aa_taps, device_serves
 
 # images per decode chunk, from tools/bench_prefill.py's sweep (profiles/prefill_decode.log: 772 x 1032 frames, three runs per size):
 # every run at 1 024 beat every run at 256 on the noise frames; against 2 048 and 4 096 the prefill times lie inside their scatter
@@ -64,12 +74,13 @@ def slot_layout(sizes: Sequence[int]) -> Tuple[np.ndarray, int]:
 
 class _Sample:
     """what one sample of a chunk turned out to be: a zlib stream for the device (``stored`` bytes at the start of its room, the
-    DEFLATE range and Adler-32 inside them, ``bpp`` bytes per pixel) or a sample for the host decoder (``host``: ``pixels`` is what
-    ``image_uint8`` gave, None when the file is unreadable).  ``rows``: the label rows, or the exception their parsing raised."""
-    __slots__ = ("host", "stored", "deflate", "adler", "bpp", "pixels", "rows")
+    DEFLATE range and Adler-32 inside them, ``bpp`` bytes per pixel, ``hw`` the file's size when it is not the cache's and the device
+    resizes it, else None) or a sample for the host decoder (``host``: ``pixels`` is what ``image_uint8`` gave, None when the file is
+    unreadable).  ``rows``: the label rows, or the exception their parsing raised."""
+    __slots__ = ("host", "stored", "deflate", "adler", "bpp", "hw", "pixels", "rows")
 
     def __init__(self):
-        self.host, self.stored, self.deflate, self.adler, self.bpp, self.pixels, self.rows = False, 0, (0, 0), 0, 1, None, None
+        self.host, self.stored, self.deflate, self.adler, self.bpp, self.hw, self.pixels, self.rows = False, 0, (0, 0), 0, 1, None, None, None
 
 
 def _label_rows(ds, j: int):
@@ -87,9 +98,10 @@ def _host_sample(s: _Sample, ds, j: int) -> _Sample:
     return s
 
 
-def _read(ds, j: int, room: np.ndarray, image_hw: Tuple[int, int]) -> _Sample:
+def _read(ds, j: int, room: np.ndarray, image_hw: Tuple[int, int], device_resize: bool = False) -> _Sample:
     """(pool thread) one sample: its file's zlib stream into ``room`` (its bytes of the pinned slot) and its label rows, or its
-    pixels from the host decoder"""
+    pixels from the host decoder.  device_resize: a file of another size than ``image_hw`` stays on the device when the resize
+    kernel serves both of its scales"""
     s = _Sample()
     try:
         with open(str(ds._image_paths[j]), "rb") as f:
@@ -97,8 +109,12 @@ def _read(ds, j: int, room: np.ndarray, image_hw: Tuple[int, int]) -> _Sample:
         info = png.parse_png(data)
     except (OSError, ValueError):   # unreadable, another format under its name (png.NotPng), a PNG that does not parse
         return _host_sample(s, ds, j)
-    if not info.prefill_decodable or (info.height, info.width) != tuple(image_hw) or info.idat_bytes > len(room):
+    if not info.prefill_decodable or info.idat_bytes > len(room):
         return _host_sample(s, ds, j)   # (longer than its room: the file grew after its size was taken)
+    if (info.height, info.width) != tuple(image_hw):
+        if not (device_resize and device_serves(info.height, image_hw[0]) and device_serves(info.width, image_hw[1])):
+            return _host_sample(s, ds, j)
+        s.hw = (int(info.height), int(info.width))
     try:
         s.stored, off, ln, s.adler = png_stream_into(data, info, room)
     except ValueError:
@@ -106,6 +122,10 @@ def _read(ds, j: int, room: np.ndarray, image_hw: Tuple[int, int]) -> _Sample:
     s.deflate, s.bpp = (off, ln), info.bytes_per_pixel
     s.rows = _label_rows(ds, j)
     return s
+
+
+def _kind(s: _Sample) -> int:
+    return KIND_RGB if s.bpp == 3 else KIND_GREY
 
 
 def _file_size(path: str) -> int:
@@ -116,12 +136,13 @@ def _file_size(path: str) -> int:
 
 
 def fill(images: torch.Tensor, samples: Sequence[Tuple[object, int]], decode_batch: int = DEFAULT_DECODE_BATCH,
-         stats: Optional[Dict] = None) -> List[Optional[torch.Tensor]]:
+         stats: Optional[Dict] = None, device_resize: bool = False) -> List[Optional[torch.Tensor]]:
     """images[i] = the uint8 image of samples[i] = (ObjectDetectionDataset, index in it), what ``ds.image_uint8(index)`` gives, for
     every sample that can be read.  images: contiguous uint8 [N, C, H, W] on an MI355X device (a view of the cache), C 1 or 3.
     -> per sample its fp32 [n, 5] label rows, or None for a sample nothing could decode (its image is left as it was).  Returns after
     the device has finished.  stats (optional dict) receives ``scratch_device_bytes``, ``scratch_pinned_bytes``, ``host_decoded`` and
-    per chunk the device-event times ``inflate_ms`` / ``unpack_ms``."""
+    per chunk the device-event times ``inflate_ms`` / ``unpack_ms``.  device_resize: files of another size are resized on the device
+    (see the module's text); stats then also counts them (``device_resized``) and times every resize launch (``resize_ms``)."""
     _hip.require_cuda(images, "the image cache")
     if images.dtype != torch.uint8 or images.ndim != 4 or images.shape[1] not in (1, 3) or not images.is_contiguous():
         raise ValueError(f"fill: images must be a contiguous uint8 [N, 1 or 3, H, W] tensor, got {tuple(images.shape)} {images.dtype}")
@@ -132,7 +153,7 @@ def fill(images: torch.Tensor, samples: Sequence[Tuple[object, int]], decode_bat
     dev = images.device
     out: List[Optional[torch.Tensor]] = [None] * N
     if stats is not None:
-        stats.update(scratch_device_bytes=0, scratch_pinned_bytes=0, host_decoded=0, inflate_ms=[], unpack_ms=[])
+        stats.update(scratch_device_bytes=0, scratch_pinned_bytes=0, host_decoded=0, inflate_ms=[], unpack_ms=[], device_resized=0, resize_ms=[])
     if N == 0:
         return out
     chunks = [(lo, min(lo + decode_batch, N)) for lo in range(0, N, decode_batch)]
@@ -150,18 +171,20 @@ def fill(images: torch.Tensor, samples: Sequence[Tuple[object, int]], decode_bat
         def stage(n: int) -> List[_Sample]:
             (lo, hi), (offsets, _) = chunks[n], layouts[n]
             host = pinned[n % 2].numpy()
-            futures = [pool.submit(_read, *samples[i], host[int(offsets[i - lo]):int(offsets[i - lo]) + sizes[i]], (H, W)) for i in range(lo, hi)]
+            futures = [pool.submit(_read, *samples[i], host[int(offsets[i - lo]):int(offsets[i - lo]) + sizes[i]], (H, W), device_resize) for i in range(lo, hi)]
             return [f.result() for f in futures]
 
         with torch.cuda.device(dev), torch.cuda.stream(side):
             sdev = torch.empty(slot_bytes, dtype=torch.uint8, device=dev)
             scan: Optional[torch.Tensor] = None
+            staged = 0   # the most bytes a chunk's other-size files took, unpacked, while they waited for their resize
             pending = stager.submit(stage, 0)
             for n, (lo, hi) in enumerate(chunks):
                 chunk = pending.result()
                 if n + 1 < len(chunks):
                     pending = stager.submit(stage, n + 1)
-                scan = _decode(chunk, samples[lo:hi], layouts[n], pinned[n % 2], sdev, scan, images[lo:hi], stats)
+                scan, staging = _decode(chunk, samples[lo:hi], layouts[n], pinned[n % 2], sdev, scan, images[lo:hi], stats)
+                staged = max(staged, staging)
                 for i, s in enumerate(chunk):
                     if s.host and s.pixels is None:
                         continue
@@ -170,7 +193,7 @@ def fill(images: torch.Tensor, samples: Sequence[Tuple[object, int]], decode_bat
                     out[lo + i] = s.rows
             side.synchronize()
         if stats is not None:
-            stats["scratch_device_bytes"] = slot_bytes + (scan.numel() if scan is not None else 0)
+            stats["scratch_device_bytes"] = slot_bytes + (scan.numel() if scan is not None else 0) + staged
             stats["scratch_pinned_bytes"] = slot_bytes * len(pinned)
     finally:
         stager.shutdown(wait=True)
@@ -179,13 +202,14 @@ def fill(images: torch.Tensor, samples: Sequence[Tuple[object, int]], decode_bat
 
 
 def _decode(chunk: List[_Sample], samples, layout, pinned: torch.Tensor, sdev: torch.Tensor, scan: Optional[torch.Tensor],
-            out: torch.Tensor, stats: Optional[Dict]) -> torch.Tensor:
-    """one chunk on the current (side) stream: upload, inflate, unpack into ``out``, the statuses back; then whatever the device
-    refused through the host decoder.  -> the scanline buffer (grown when this chunk needed more)"""
+            out: torch.Tensor, stats: Optional[Dict]) -> Tuple[torch.Tensor, int]:
+    """one chunk on the current (side) stream: upload, inflate, unpack into ``out`` (the files of another size: into a staging tensor
+    per size, resized from there into ``out``), the statuses back; then whatever the device refused through the host decoder.
+    -> the scanline buffer (grown when this chunk needed more), the staging bytes this chunk took"""
     offsets, _ = layout
     B, C, H, W = (int(v) for v in out.shape)
     dev = out.device
-    need = [C * H * W if s.host else H * (1 + s.bpp * W) for s in chunk]
+    need = [C * H * W if s.host else (s.hw or (H, W))[0] * (1 + s.bpp * (s.hw or (H, W))[1]) for s in chunk]
     at = np.zeros(B + 1, dtype=np.int64)
     at[1:] = np.cumsum([-(-v // SCAN_ALIGN) * SCAN_ALIGN for v in need])
     if scan is None or scan.numel() < int(at[B]):
@@ -194,7 +218,7 @@ def _decode(chunk: List[_Sample], samples, layout, pinned: torch.Tensor, sdev: t
     device_rows = [i for i, s in enumerate(chunk) if not s.host]
     kept = [i for i, s in enumerate(chunk) if not (s.host and s.pixels is None)]
     if not kept:
-        return scan
+        return scan, 0
     timed = stats is not None
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timed else None
     inflate_status = None
@@ -215,8 +239,9 @@ def _decode(chunk: List[_Sample], samples, layout, pinned: torch.Tensor, sdev: t
             if tuple(s.pixels.shape) != (C, H, W):
                 raise ValueError(f"fill: {samples[i][0]._image_paths[samples[i][1]]} decodes to {tuple(s.pixels.shape)}, the cache holds {(C, H, W)}")
             scan[int(at[i]):int(at[i]) + need[i]].copy_(s.pixels.contiguous().reshape(-1))
-    # a sample nothing could decode keeps its place in the launch as an entry the kernel refuses before it reads anything
-    table = np.asarray([(int(at[i]), -1 if (s.host and s.pixels is None) else KIND_PLANAR if s.host else KIND_RGB if s.bpp == 3 else KIND_GREY)
+    # a sample nothing could decode keeps its place in the launch as an entry the kernel refuses before it reads anything, and so
+    # does a file of another size: its group's own launches follow
+    table = np.asarray([(int(at[i]), -1 if (s.host and s.pixels is None) or (not s.host and s.hw) else KIND_PLANAR if s.host else _kind(s))
                         for i, s in enumerate(chunk)], dtype=np.int64).reshape(-1, 2)
     status = torch.empty(B, dtype=torch.int32, device=dev)
     table_dev = torch.from_numpy(table).to(dev)
@@ -225,7 +250,30 @@ def _decode(chunk: List[_Sample], samples, layout, pinned: torch.Tensor, sdev: t
     png_unpack_planes(scan, table_dev, (H, W), out, status)
     if timed:
         ev[3].record()
+    groups: Dict[Tuple[int, int], List[int]] = {}
+    for i in device_rows:
+        if chunk[i].hw:
+            groups.setdefault(chunk[i].hw, []).append(i)
+    resized, staging = [], 0
+    for (Hs, Ws), members in groups.items():
+        stage = torch.empty((len(members), C, Hs, Ws), dtype=torch.uint8, device=dev)
+        staging += stage.numel()
+        gstatus = torch.empty(len(members), dtype=torch.int32, device=dev)
+        gtable = np.asarray([(int(at[i]), _kind(chunk[i])) for i in members], dtype=np.int64).reshape(-1, 2)
+        png_unpack_planes(scan, torch.from_numpy(gtable).to(dev), (Hs, Ws), stage, gstatus)
+        gev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timed else None
+        if timed:
+            gev[0].record()
+        # (a file the unpack refused is resized as well, from whatever its staging holds, and overwritten by the host's below)
+        resize_aa(stage, out, members, aa_taps(Hs, H), aa_taps(Ws, W))
+        if timed:
+            gev[1].record()
+        resized.append((members, gstatus, gev))
     bad = status.cpu().numpy().copy()   # waits for the launches
+    for members, gstatus, gev in resized:
+        bad[members] = gstatus.cpu().numpy()
+        if timed:
+            stats["resize_ms"].append(gev[0].elapsed_time(gev[1]))
     if inflate_status is not None:
         bad[np.asarray(device_rows)[inflate_status.cpu().numpy() != 0]] = 1
     if timed:
@@ -233,6 +281,7 @@ def _decode(chunk: List[_Sample], samples, layout, pinned: torch.Tensor, sdev: t
             stats["inflate_ms"].append(ev[0].elapsed_time(ev[1]))
         stats["unpack_ms"].append(ev[2].elapsed_time(ev[3]))
         stats["host_decoded"] += sum(1 for s in chunk if s.host)
+        stats["device_resized"] += sum(1 for i in device_rows if chunk[i].hw and not bad[i])
     # what the device refused: the host decoder's turn (the kernel may have written part of the image: it is overwritten or,
     # where the host cannot read the file either, not resident)
     for i in device_rows:
@@ -249,4 +298,4 @@ def _decode(chunk: List[_Sample], samples, layout, pinned: torch.Tensor, sdev: t
         png_unpack_planes(px, one, (H, W), out[i:i + 1], st)
         if int(st.cpu()[0]) != 0:
             raise RuntimeError(f"yogo_amd: the host-decoded image of {samples[i][0]._image_paths[samples[i][1]]} was refused by the unpack kernel")
-    return scan
+    return scan, staging

@@ -188,7 +188,8 @@ class Trainer:
                                      normalize_images=self.config["normalize_images"],
                                      split_fraction_override=self.config["dataset_split_override"], device=self._torch_device(),
                                      device_image_cache_gib=self.config.get("device_image_cache_gib"),
-                                     device_image_decode=bool(self.config.get("device_image_decode", False)))
+                                     device_image_decode=bool(self.config.get("device_image_decode", False)),
+                                     device_image_resize=bool(self.config.get("device_image_resize", False)))
         self.train_dataloader = loaders["train"]
         self.validate_dataloader = loaders.get("val", [])
         self.test_dataloader = loaders.get("test", [])
@@ -412,6 +413,7 @@ def build_config(args) -> dict:
         "dataset_split_override": args.dataset_split_override,
         "device_image_cache_gib": args.device_image_cache,
         "device_image_decode": args.device_image_decode,
+        "device_image_resize": args.device_image_resize,
         "device_metrics": args.device_metrics,
         "dataset_descriptor_file": args.dataset_descriptor_file,
         "slurm-job-id": os.getenv("SLURM_JOB_ID", default=None),

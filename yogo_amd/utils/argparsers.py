@@ -95,6 +95,12 @@ def _decode_needs_cache(ns):
     return None
 
 
+def _resize_needs_decode(ns):
+    if ns.device_image_resize and not ns.device_image_decode:
+        return "--device-image-resize resizes what the device decoded: it needs --device-image-decode"
+    return None
+
+
 def global_parser():
     parser = argparse.ArgumentParser(description="what can yogo do for you today?", allow_abbrev=False)
     sub = parser.add_subparsers(help="here is what you can do", dest="task", parser_class=CheckedParser)
@@ -141,6 +147,10 @@ def train_parser(parser=None):
                              "and RGB) instead of a pool of PIL workers; other files are decoded on the host; same batches.  Its scratch "
                              "memory (pinned staging, stored streams, scanlines) is freed after the prefill and is not counted in the "
                              "GIB budget (default: False)")
+    parser.add_argument("--device-image-resize", default=False, action=boolean_action,
+                        help="with --device-image-decode: also resize on the GPU the 8-bit greyscale and RGB PNG files whose size is not "
+                             "--image-hw (down to 1/8 per axis, or up) instead of handing them to the host; a few pixels of such an image "
+                             "may differ by one grey level from the host's resize (default: False)")
     parser.add_argument("--device-metrics", default=False, action=boolean_action,
                         help="match predictions to labels and accumulate the test metrics on the GPU instead of per image on the host; "
                              "same results (default: False)")
@@ -151,6 +161,7 @@ def train_parser(parser=None):
     parser.add_argument("--wandb-entity", type=str, default=os.getenv("wandb_entity"), help="wandb entity - defaults to the environment variable wandb_entity")
     parser.add_argument("--wandb-project", type=str, default=os.getenv("wandb_project"), help="wandb project name - defaults to the environment variable wandb_project")
     parser.checks.append(_decode_needs_cache)
+    parser.checks.append(_resize_needs_decode)
     return parser
 
 
