@@ -524,6 +524,31 @@ int yogo_png_unpack(unsigned char* scan, long long scan_bytes, const long long* 
 int yogo_png_unpack_planes(unsigned char* scan, long long scan_bytes, const long long* table, int B, int H, int W, int C_out,
                            unsigned char* out, int* status, yogo_stream_t stream);
 
+/* ---- PNG files of every colour type, bit depth and interlace method (`--device-image-decode-all`, on both routes above) --------
+ * yogo_png_unpack and yogo_png_unpack_planes in one, for whatever a PNG file may hold; the images of a launch may each be of another
+ * format.  Same scan buffer; table: [B][3] int64 device, one row { off, fmt, pal } per image.  off: where it lies in scan.
+ * fmt = colour type | bit depth << 8 | interlace << 16, IHDR's fields, for the pairs the PNG specification allows (0 at 1 2 4 8 16,
+ * 2 at 8 16, 3 at 1 2 4 8, 4 and 6 at 8 16; interlace 0 or 1): the scanlines as the file's zlib stream inflates to, rows of one
+ * filter-type byte and ceil(w * channels * depth / 8) bytes -- for Adam7 the seven reduced images one after the other, a pass
+ * without pixels without scanlines.  fmt = 1: C_out x H x W planar pixels as they are (an image the host decoded; kind 1 of
+ * yogo_png_unpack_planes).  pal: for colour type 3 where the image's palette lies in scan, 256 x 3 bytes R G B (a shorter PLTE
+ * padded with zeros by the host), else ignored.  Filter types 0 .. 4 act on bytes, the byte to the left max(1, channels * depth / 8)
+ * bytes back (1, 2, 3, 4, 6 or 8); a depth below 8 is unfiltered byte by byte and a byte then expanded into 8 / depth pixels, most
+ * significant bits first, the padding bits of a row's last byte dropped.  Samples become 8-bit planes as
+ * yogo_amd.yogo_dataset.read_image(path, rgb) (PIL) has them -- yogo_amd.png.decode_any is the restatement on the host: grey 1 / 2 /
+ * 4 v * 255 / (2^depth - 1); grey 8 as it is; grey 16 min(v, 255) (a clip, not a shift); grey+alpha, RGB and RGBA the high byte of
+ * each sample, alpha dropped; palette PLTE[index]; one plane from colour L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16; three
+ * planes from grey the plane three times.  out: [B][C_out][OH][OW], C_out 1 or 3, uint8 (any alignment: a view into the cache) or
+ * fp32 x / 255 bit-identical to torch's CPU uint8_tensor / 255: out[b][c][oy][ox] = image_b[c][top + oy][left + ox],
+ * 1 <= OH <= H - top, 1 <= OW <= W - left; with top = left = 0, OH = H, OW = W and uint8 the layout is yogo_png_unpack_planes's.
+ * scan is WRITTEN as by yogo_png_unpack (the last row of every band of 64 rows, of every pass).  status: [B] int32 device, per
+ * image 0, 1 (a filter-type byte above 4, in any pass: its rows from that band on are not written) or 2 (a fmt outside the list, or
+ * the image or its palette does not lie inside scan: nothing of it is read).  No byte outside scan and the image's own output is
+ * read or written, whatever the bytes say.  One wavefront per image: csrc/png_unfilter.h's loop once per pass, so for 8-bit grey
+ * and 8-bit RGB the output is that of the two entries above, bit for bit.  B <= 65535, H, W <= 65535. */
+int yogo_png_unpack_any(unsigned char* scan, long long scan_bytes, const long long* table, int B, int H, int W, int top, int left,
+                        int OH, int OW, int C_out, void* out, int out_fp32, int* status, yogo_stream_t stream);
+
 /* ---- other-size files into the device image cache (yogo_amd/png_prefill.py, `yogo train ... --device-image-resize`) ------------
  * Separable antialiased bilinear (triangle filter) resampling of planar uint8 images: torch._upsample_bilinear2d_aa with
  * align_corners = False, then round-half-even and a clamp to 0 .. 255 -- what yogo_amd.yogo_dataset.resize_image computes.

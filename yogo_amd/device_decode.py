@@ -1,6 +1,6 @@
 """What the routes that decode stored bytes on the device share -- zarr stacks (yogo_amd/zarr_feed.py), PNG directories for inference
 (yogo_amd/png_feed.py), the PNG prefill of the device image cache (yogo_amd/png_prefill.py): the launch wrappers of
-``yogo_blosc_lz4_decode``, ``yogo_inflate_zlib``, ``yogo_png_unpack``, ``yogo_png_unpack_planes`` and ``yogo_resize_aa_u8`` (the
+``yogo_blosc_lz4_decode``, ``yogo_inflate_zlib``, ``yogo_png_unpack``, ``yogo_png_unpack_planes``, ``yogo_png_unpack_any`` and ``yogo_resize_aa_u8`` (the
 prefill's resize of other-size files) with their tensor checks, ``gather`` (a pool's futures), ``raise_first_bad`` (a status vector -> RuntimeError), ``png_stream_into`` (one PNG file -> one zlib
 stream in its room of a pinned slot) and ``PrefetchFeed`` (the iterator that loads batch n + 1 while the caller works on batch n)."""
 from __future__ import annotations
@@ -120,6 +120,31 @@ def png_unpack_planes(scan: torch.Tensor, table: torch.Tensor, image_hw: Tuple[i
         return out
     with torch.cuda.device(out.device):
         _hip.call("yogo_png_unpack_planes", scan, scan.numel(), table, B, H, W, C, out, status, _hip.stream_ptr())
+    return out
+
+
+def png_unpack_any(scan: torch.Tensor, table: torch.Tensor, image_hw: Tuple[int, int], out: torch.Tensor, status: torch.Tensor,
+                   top: int = 0, left: int = 0) -> torch.Tensor:
+    """One ``yogo_png_unpack_any`` launch on the current stream: PNG scanlines of every colour type, bit depth and interlace method.
+    scan: 1-D uint8 device tensor of inflated scanlines and palettes (written: the kernel unfilters one row of every 64 in place);
+    table: int64 [B, 3] device, rows (offset, ``PngInfo.format_code`` or ``png.FMT_PLANAR``, offset of the 768-byte palette);
+    out: contiguous [B, 1 or 3, OH, OW] uint8 or float32, the crop at (top, left) of the H x W images; status: int32 [B].  The
+    kernel holds every image and palette to ``scan`` itself."""
+    for t, what in ((scan, "the scanlines"), (table, "the image table"), (out, "the unpack output"), (status, "the status")):
+        _hip.require_cuda(t, what)
+    H, W = (int(v) for v in image_hw)
+    require_bytes("png_unpack_any", "scan", scan)
+    if out.dtype not in (torch.uint8, torch.float32) or out.ndim != 4 or out.shape[1] not in (1, 3) or not out.is_contiguous():
+        raise ValueError(f"png_unpack_any: out must be a contiguous [B, 1 or 3, OH, OW] uint8 or float32 tensor, got {tuple(out.shape)} {out.dtype}")
+    B, C, OH, OW = (int(v) for v in out.shape)
+    require_table("png_unpack_any", table, 3, B)
+    require_status("png_unpack_any", status, B)
+    require_same_device("png_unpack_any", scan, table, out, status)
+    if B == 0:
+        return out
+    with torch.cuda.device(out.device):
+        _hip.call("yogo_png_unpack_any", scan, scan.numel(), table, B, H, W, int(top), int(left), OH, OW, C, out,
+                  1 if out.dtype == torch.float32 else 0, status, _hip.stream_ptr())
     return out
 
 

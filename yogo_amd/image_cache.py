@@ -18,7 +18,8 @@ stays with the workers, which retry it every epoch as before.
 device inflates and unfilters them in chunks of ``decode_batch`` images straight into their slots (yogo_amd/png_prefill.py), and
 whatever the device does not take goes through ``image_uint8`` as above.  Its scratch (pinned slots, stored streams, scanlines) is
 dropped when the prefill returns and is not part of the budget.  Everything after the fill is the same code on both routes.
-``device_resize=True`` (``--device-image-resize``) lets that route also resize, on the device, the files whose size is not the
+``device_decode_all=True`` (``--device-image-decode-all``) has that route take every PNG colour type, bit depth and Adam7 instead of
+8-bit greyscale and RGB alone (yogo_amd/png_prefill.py: decode_all).  ``device_resize=True`` (``--device-image-resize``) lets that route also resize, on the device, the files whose size is not the
 cache's (csrc/resize_aa.hip); a few of their pixels may then differ by one grey level from ``resize_image``'s (png_prefill.py).
 
 The one deliberate difference to the uncached path: a resident image is a snapshot taken at prefill, so a file changed or
@@ -43,6 +44,7 @@ GIB = 2 ** 30
 FLAG = "--device-image-cache"
 DECODE_FLAG = "--device-image-decode"
 RESIZE_FLAG = "--device-image-resize"
+DECODE_ALL_FLAG = "--device-image-decode-all"
 
 
 def check_budget_gib(gib: float) -> float:
@@ -200,9 +202,11 @@ class ImageCache:
 
     def __init__(self, split: Dataset, S: int, image_shape: Tuple[int, int, int], normalize_images: bool, device=None,
                  num_workers: int = 0, batch_size: int = 64, name: str = "train", log: bool = False, device_decode: bool = False,
-                 decode_batch: int = DEFAULT_DECODE_BATCH, device_resize: bool = False):
+                 decode_batch: int = DEFAULT_DECODE_BATCH, device_resize: bool = False, device_decode_all: bool = False):
         if device_resize and not device_decode:
             raise ValueError(f"{RESIZE_FLAG} resizes what the device decoded: it needs {DECODE_FLAG}")
+        if device_decode_all and not device_decode:
+            raise ValueError(f"{DECODE_ALL_FLAG} widens what {DECODE_FLAG} takes: it needs {DECODE_FLAG}")
         if not torch.cuda.is_available():
             raise RuntimeError(f"yogo_amd: {FLAG} keeps images on an MI355X device; there is no CPU fallback")
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -218,7 +222,7 @@ class ImageCache:
         self.normalize_images, self.device = bool(normalize_images), dev
         self.num_workers, self.batch_size, self.name, self.log = int(num_workers), max(1, int(batch_size)), name, log
         self.device_decode, self.decode_batch = bool(device_decode), png_prefill.check_decode_batch(decode_batch)
-        self.device_resize = bool(device_resize)
+        self.device_resize, self.device_decode_all = bool(device_resize), bool(device_decode_all)
         self.decode_stats: dict = {}   # what png_prefill.fill reports of a device prefill (chunk times, scratch bytes); empty otherwise
         self.nbytes = self.S * C * H * W
         try:
@@ -283,4 +287,4 @@ class ImageCache:
     def _fill_on_device(self) -> List[Optional[torch.Tensor]]:
         """the device route (yogo_amd/png_prefill.py): the same result, the PNG files inflated and unfiltered on the device"""
         return png_prefill.fill(self.images, [resolve_sample(self.split, i) for i in range(self.S)], self.decode_batch, self.decode_stats,
-                                device_resize=self.device_resize)
+                                device_resize=self.device_resize, **({"decode_all": True} if self.device_decode_all else {}))

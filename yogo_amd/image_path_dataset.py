@@ -4,6 +4,7 @@ is not needed); `predict` does not index a ZarrDataset per image but hands it to
 from __future__ import annotations
 
 import math
+from functools import partial
 from pathlib import Path
 from typing import Callable, List, Optional, Tuple, Union
 
@@ -112,11 +113,13 @@ def collate_fn(batch: List[Tuple[torch.Tensor, str]]) -> Tuple[torch.Tensor, Tup
 
 
 def get_dataset(path_to_images: Optional[Path] = None, path_to_zarr: Optional[Path] = None,
-                image_transforms: Optional[List[Callable]] = None, normalize_images: bool = False) -> ImageAndIdDataset:
+                image_transforms: Optional[List[Callable]] = None, normalize_images: bool = False, rgb: bool = False) -> ImageAndIdDataset:
+    """rgb: the files of ``path_to_images`` are read as 3 planes (an RGB model); a zarr stack holds single planes"""
     if path_to_images is not None and path_to_zarr is not None:
         raise ValueError("can only take one of 'path_to_images' or 'path_to_zarr', but got both")
     if path_to_images is not None:
-        return ImagePathDataset(path_to_images, image_transforms=image_transforms, normalize_images=normalize_images)
+        return ImagePathDataset(path_to_images, image_transforms=image_transforms, normalize_images=normalize_images,
+                                **({"loader": partial(read_image, rgb=True)} if rgb else {}))
     if path_to_zarr is not None:
         return ZarrDataset(path_to_zarr, image_transforms=image_transforms, normalize_images=normalize_images)
     raise ValueError("one of 'path_to_images' or 'path_to_zarr' must not be None")

@@ -73,6 +73,7 @@ def predict(
     return_full_predictions: bool = False,
     device_outputs: bool = False,
     device_image_decode: bool = False,
+    device_image_decode_all: bool = False,
 ) -> Optional[torch.Tensor]:
     if save_preds and draw_boxes:
         raise ValueError("cannot save predictions in YOGO format and draw_boxes at the same time")
@@ -85,6 +86,8 @@ def predict(
     elif output_img_ftype not in [".png", ".tif", ".tiff"]:
         raise ValueError(f"only .png, .tif, and .tiff are supported for output img filetype; got {output_img_ftype}")
 
+    if device_image_decode_all and not device_image_decode:
+        raise ValueError("device_image_decode_all widens what device_image_decode takes: it needs device_image_decode")
     if device_image_decode and path_to_zarr is not None:
         raise ValueError("device_image_decode decodes the PNG files of path_to_images; a zarr stack has its own device route")
     device = torch.device(device or choose_device())
@@ -102,14 +105,15 @@ def predict(
         model.resize_model(crop_px)
         img_h = crop_px
     assert model.img_size.numel() == 2, f"YOGO model must be 2D, is {model.img_size}"
-    if device_image_decode and bool(model.is_rgb):
-        raise ValueError("device_image_decode reads 8-bit greyscale images; this model takes RGB input")
+    if device_image_decode and bool(model.is_rgb) and not device_image_decode_all:
+        raise ValueError("device_image_decode reads 8-bit greyscale images; this model takes RGB input (device_image_decode_all converts "
+                         "every PNG colour type to RGB planes on the device)")
     num_classes = int(model.num_classes)
     if class_names is not None and len(class_names) != num_classes:
         raise ValueError(f"expected {num_classes} class names, got {len(class_names)}")
 
     image_dataset = get_dataset(path_to_images=path_to_images, path_to_zarr=path_to_zarr, image_transforms=transforms,
-                                normalize_images=bool(model.normalize_images))
+                                normalize_images=bool(model.normalize_images), rgb=bool(model.is_rgb))
     if isinstance(image_dataset, ZarrDataset):
         # no workers and none of the reference's slow-path warning (infer.py:257-265): chunks are read on threads and unpacked
         # on the device, crop and / 255 included (yogo_amd/zarr_feed.py); the batches arrive on the device
@@ -124,7 +128,8 @@ def predict(
 
         with torch.cuda.device(device):
             loader = PngDeviceFeed(image_dataset, batch_size, device, crop=(img_h, img_w) if vertical_crop_height else None,
-                                   normalize=bool(model.normalize_images))
+                                   normalize=bool(model.normalize_images), all_types=bool(device_image_decode_all),
+                                   rgb=bool(model.is_rgb))
     else:
         num_workers = choose_dataloader_num_workers(len(image_dataset), requested_num_workers=requested_num_workers)
         loader = DataLoader(image_dataset, batch_size=batch_size, shuffle=False, drop_last=False, pin_memory=True, collate_fn=collate_fn,
@@ -254,5 +259,5 @@ def do_infer(args) -> None:
         obj_thresh=args.obj_thresh, iou_thresh=args.iou_thresh, batch_size=args.batch_size, device=args.device, use_tqdm=args.use_tqdm,
         vertical_crop_height=args.crop_height, count_predictions=args.count, output_img_ftype=args.output_img_filetype,
         min_class_confidence_threshold=args.min_class_confidence_threshold, half=args.half, device_outputs=args.device_outputs,
-        device_image_decode=args.device_image_decode,
+        device_image_decode=args.device_image_decode, device_image_decode_all=args.device_image_decode_all,
     )

@@ -12,6 +12,13 @@ What the device does not take -- anything but 8-bit greyscale without interlace 
 a file larger than the room a slot has per image -- is decoded by ``read_image`` on the host and enters the unpack launch as a raw
 image.  A file nothing can decode, or whose size differs from the first file's of its batch, raises RuntimeError naming it and
 costs exactly its batch, the class ``predict`` warns on and goes on.
+
+``all_types=True`` (``--device-image-decode-all``) sends every parsable PNG to the device instead: all colour types and bit depths,
+tRNS or not, Adam7 (``PngInfo.any_decodable``), unpacked by ``yogo_png_unpack_any`` (csrc/png_unpack_any.hip, the same loop) into
+1 plane or, for an RGB model (``rgb=True``), 3, converted as ``read_image(path, rgb)`` converts them.  The images of a batch may
+each be of another format: every image has its own inflated size in the scanline buffer, the palettes of the batch's palette
+files lie behind the last image; the pinned slot gives every file room for its own size.  Still one inflate and one unpack launch per batch; the host keeps another format under a .png
+name, a stream larger than its room and a palette file without a usable PLTE chunk.
 """
 from __future__ import annotations
 
@@ -24,28 +31,43 @@ import torch
 
 from yogo_amd import inflate, png
 from yogo_amd.device_decode import ALIGN, MAX_THREADS, PrefetchFeed, center_crop_origin, gather, inflate_streams, png_stream_into, \
-    png_unpack, raise_first_bad
+    png_unpack, png_unpack_any, raise_first_bad
+from yogo_amd.png_prefill import slot_layout
 from yogo_amd.yogo_dataset import read_image
 
 UNPACK_STATUS = {1: "a filter-type byte above 4", 2: "the image lies outside the scanline buffer"}
+SCAN_ALIGN = 16   # yogo_inflate_zlib asks for 16-byte aligned destinations
+
+
+def _file_size(path: str) -> int:
+    try:
+        return os.stat(path).st_size
+    except OSError:
+        return 0
 
 
 class _Image:
     """what one file of a batch turned out to be: a zlib stream for the device (``stored`` bytes at its place in the slot, the
     DEFLATE range and Adler-32 inside them; ``stream``: the bytes themselves while the slots are not sized yet) or pixels decoded
-    on the host (``pixels``)"""
-    __slots__ = ("hw", "stored", "deflate", "adler", "pixels", "stream")
+    on the host (``pixels``).  With all_types: ``need`` bytes the stream inflates to, the format ``code`` of yogo_png_unpack_any's
+    table, the ``palette`` (768 bytes) of a palette file"""
+    __slots__ = ("hw", "stored", "deflate", "adler", "pixels", "stream", "need", "code", "palette")
 
-    def __init__(self, hw, stored=0, deflate=(0, 0), adler=0, pixels=None, stream=None):
+    def __init__(self, hw, stored=0, deflate=(0, 0), adler=0, pixels=None, stream=None, need=0, code=png.FMT_PLANAR, palette=None):
         self.hw, self.stored, self.deflate, self.adler, self.pixels, self.stream = hw, stored, deflate, adler, pixels, stream
+        self.need, self.code, self.palette = need, code, palette
 
 
 class PngDeviceFeed(PrefetchFeed):
     """Iterator over ``(device batch [B, 1, OH, OW], tuple of paths)`` in the dataset's order; the last batch may be partial; a batch
     that raises RuntimeError costs that batch alone (device_decode.PrefetchFeed).  ``crop``: (OH, OW) of a centre crop done in the
-    kernel; ``normalize``: fp32 ``/ 255`` in the kernel, else uint8."""
+    kernel; ``normalize``: fp32 ``/ 255`` in the kernel, else uint8.  ``all_types``: every PNG colour type, bit depth and Adam7 goes
+    to the device (see the module's text); ``rgb`` (with all_types only): batches of 3 planes, ``[B, 3, OH, OW]``."""
 
-    def __init__(self, dataset, batch_size: int, device, crop: Optional[Tuple[int, int]] = None, normalize: bool = False):
+    all_types = rgb = False   # (the defaults, also of an object made without __init__)
+
+    def __init__(self, dataset, batch_size: int, device, crop: Optional[Tuple[int, int]] = None, normalize: bool = False,
+                 all_types: bool = False, rgb: bool = False):
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError(f"yogo_amd: the PNG feed decodes on an MI355X device (got {dev}); there is no CPU fallback")
@@ -53,7 +75,10 @@ class PngDeviceFeed(PrefetchFeed):
             dev = torch.device("cuda", torch.cuda.current_device())
         if batch_size < 1 or batch_size > 65535:
             raise ValueError(f"batch size {batch_size} outside [1, 65535]")
+        if rgb and not all_types:
+            raise ValueError("PngDeviceFeed: batches of 3 planes (rgb) need all_types: yogo_png_unpack writes one plane of 8-bit greyscale")
         self.dataset, self.batch_size, self.device, self.normalize = dataset, int(batch_size), dev, bool(normalize)
+        self.all_types, self.rgb = bool(all_types), bool(rgb)
         self.crop = None if crop is None else (int(crop[0]), int(crop[1]))
         self.paths = [str(p) for p in dataset.image_paths]
         n = len(self.paths)
@@ -70,13 +95,12 @@ class PngDeviceFeed(PrefetchFeed):
         super().close()
         self._pool.shutdown(wait=True)
 
-    @staticmethod
-    def _host_image(path: str) -> _Image:
+    def _host_image(self, path: str) -> _Image:
         try:
-            t = read_image(path)
+            t = read_image(path, rgb=self.rgb)
         except Exception as e:
             raise RuntimeError(f"{path} could not be decoded ({type(e).__name__}: {e})") from e
-        return _Image((int(t.shape[1]), int(t.shape[2])), pixels=t[0].contiguous().numpy())
+        return _Image((int(t.shape[1]), int(t.shape[2])), pixels=(t if self.rgb else t[0]).contiguous().numpy())
 
     def _read(self, path: str, room: Optional[np.ndarray]) -> _Image:
         """(pool thread) one file: its zlib stream into ``room`` (this image's bytes of the slot's pinned buffer; None while the
@@ -92,7 +116,7 @@ class PngDeviceFeed(PrefetchFeed):
             return self._host_image(path)   # another format under a .png name: PIL's to read if it can
         except ValueError as e:
             raise RuntimeError(f"{path} could not be decoded ({e})") from e
-        if not info.device_decodable or (room is not None and info.idat_bytes > len(room)):
+        if not (info.any_decodable if self.all_types else info.device_decodable) or (room is not None and info.idat_bytes > len(room)):
             return self._host_image(path)
         stream = None
         try:
@@ -103,7 +127,10 @@ class PngDeviceFeed(PrefetchFeed):
                 stored, off, ln, adler = png_stream_into(data, info, room)
         except ValueError as e:
             raise RuntimeError(f"{path} could not be decoded ({e})") from e
-        return _Image((info.height, info.width), stored, (off, ln), adler, stream=stream)
+        if not self.all_types:
+            return _Image((info.height, info.width), stored, (off, ln), adler, stream=stream)
+        return _Image((info.height, info.width), stored, (off, ln), adler, stream=stream, need=info.inflated_bytes, code=info.format_code,
+                      palette=png.palette_table(data, info) if info.color_type == 3 else None)
 
     def _size_slots(self, streams: List[int], B: int) -> None:
         """the room per image from the longest stream of the first batch, with a quarter and 4 KiB to spare"""
@@ -118,7 +145,19 @@ class PngDeviceFeed(PrefetchFeed):
         lo, hi = self.batches[n]
         paths = self.paths[lo:hi]
         B = len(paths)
-        if self.room == 0:
+        if self.all_types:
+            # the formats of a directory differ in size by more than an order of magnitude: every file has room for its own bytes
+            # (an IDAT payload is shorter than its file), the slots grow with the largest batch
+            sizes = list(self._pool.map(_file_size, paths))
+            src_at, slot_bytes = slot_layout(sizes)
+            if self._pinned[slot] is None or self._pinned[slot].numel() < slot_bytes:
+                self._pinned[slot] = self._sdev[slot] = None   # (the smaller buffers go back first)
+                grown = -(-max(1, slot_bytes) * self.batch_size // B)
+                self._pinned[slot] = torch.empty(grown, dtype=torch.uint8).pin_memory()
+                self._sdev[slot] = torch.empty(grown, dtype=torch.uint8, device=self.device)
+            host = self._pinned[slot].numpy()
+            images = gather([self._pool.submit(self._read, p, host[int(src_at[i]):int(src_at[i]) + sizes[i]]) for i, p in enumerate(paths)])
+        elif self.room == 0:
             # the first batch sizes the slots: its streams come back as bytes and are copied in here
             images = gather([self._pool.submit(self._read, p, None) for p in paths])
             self._size_slots([im.stored for im in images], self.batch_size)
@@ -130,6 +169,8 @@ class PngDeviceFeed(PrefetchFeed):
         else:
             host = self._pinned[slot].numpy()
             images = gather([self._pool.submit(self._read, p, host[i * self.room:(i + 1) * self.room]) for i, p in enumerate(paths)])
+        if not self.all_types:
+            src_at = np.arange(B, dtype=np.int64) * self.room
         H, W = images[0].hw
         for p, im in zip(paths, images):
             if im.hw != (H, W):
@@ -139,28 +180,49 @@ class PngDeviceFeed(PrefetchFeed):
             top, left = center_crop_origin(H, W, OH, OW)
         except ValueError as e:
             raise RuntimeError(f"{paths[0]}: {e}") from e
-        stride = -(-(H * (1 + W)) // 16) * 16
-        if self._scan[slot] is None or self._scan[slot].numel() < B * stride:
-            self._scan[slot] = torch.empty(self.batch_size * stride, dtype=torch.uint8, device=self.device)
+        C = 3 if self.rgb else 1
+        if self.all_types:
+            # every image at its own inflated size; behind the last one the palettes of the batch, 768 bytes each
+            need = [C * H * W if im.pixels is not None else im.need for im in images]
+            at = np.zeros(B + 1, dtype=np.int64)
+            at[1:] = np.cumsum([-(-v // SCAN_ALIGN) * SCAN_ALIGN for v in need])
+            with_palette = [i for i, im in enumerate(images) if im.palette is not None]
+            palette_at = {i: int(at[B]) + k * png.PALETTE_BYTES for k, i in enumerate(with_palette)}
+            total = int(at[B]) + len(with_palette) * png.PALETTE_BYTES
+            if self._scan[slot] is None or self._scan[slot].numel() < total:
+                self._scan[slot] = None   # (the smaller buffer goes back to the allocator first)
+                self._scan[slot] = torch.empty(-(-total * self.batch_size // B), dtype=torch.uint8, device=self.device)
+            table = np.asarray([(int(at[i]), im.code, palette_at.get(i, 0)) for i, im in enumerate(images)], dtype=np.int64).reshape(-1, 3)
+        else:
+            stride = -(-(H * (1 + W)) // 16) * 16
+            need, at = [H * W if im.pixels is not None else H * (1 + W) for im in images], np.arange(B + 1, dtype=np.int64) * stride
+            if self._scan[slot] is None or self._scan[slot].numel() < B * stride:
+                self._scan[slot] = torch.empty(self.batch_size * stride, dtype=torch.uint8, device=self.device)
+            table = np.asarray([(i * stride, 0 if im.pixels is None else 1) for i, im in enumerate(images)], dtype=np.int64)
         scan = self._scan[slot]
         device_rows = [i for i, im in enumerate(images) if im.pixels is None]
         self.host_decoded += B - len(device_rows)
-        rows = np.asarray([(i * self.room + images[i].deflate[0], images[i].deflate[1], i * stride, H * (1 + W), images[i].adler)
+        rows = np.asarray([(int(src_at[i]) + images[i].deflate[0], images[i].deflate[1], int(at[i]), need[i], images[i].adler)
                            for i in device_rows], dtype=np.int64).reshape(-1, 5)
-        table = np.asarray([(i * stride, 0 if im.pixels is None else 1) for i, im in enumerate(images)], dtype=np.int64)
         with torch.cuda.device(self.device), torch.cuda.stream(self._side):
             inflate_status = None
             if device_rows:
-                used = device_rows[-1] * self.room + images[device_rows[-1]].stored
+                used = int(src_at[device_rows[-1]]) + images[device_rows[-1]].stored
                 self._sdev[slot][:used].copy_(self._pinned[slot][:used], non_blocking=True)
                 inflate_status = torch.empty(len(device_rows), dtype=torch.int32, device=self.device)
                 inflate_streams(self._sdev[slot], torch.from_numpy(rows).to(self.device), scan, inflate_status)
             for i, im in enumerate(images):
                 if im.pixels is not None:   # (rare: a pageable copy per image)
-                    scan[i * stride:i * stride + H * W].copy_(torch.from_numpy(im.pixels).reshape(-1))
-            out = torch.empty((B, 1, OH, OW), dtype=torch.float32 if self.normalize else torch.uint8, device=self.device)
+                    scan[int(at[i]):int(at[i]) + need[i]].copy_(torch.from_numpy(im.pixels).reshape(-1))
+            out = torch.empty((B, C, OH, OW), dtype=torch.float32 if self.normalize else torch.uint8, device=self.device)
             status = torch.empty(B, dtype=torch.int32, device=self.device)
-            png_unpack(scan, torch.from_numpy(table).to(self.device), (H, W), out, status, top, left)
+            if self.all_types:
+                if with_palette:   # one copy for the palettes of the batch
+                    palettes = torch.from_numpy(np.concatenate([images[i].palette for i in with_palette]))
+                    scan[int(at[B]):total].copy_(palettes)
+                png_unpack_any(scan, torch.from_numpy(table).to(self.device), (H, W), out, status, top, left)
+            else:
+                png_unpack(scan, torch.from_numpy(table).to(self.device), (H, W), out, status, top, left)
             ev = torch.cuda.Event()
             ev.record(self._side)
             bad_inflate = inflate_status.cpu() if inflate_status is not None else None   # waits for the launches

@@ -32,6 +32,13 @@ colour conversion comes before the resize, as in ``read_image`` then ``resize_im
 pixels are those of the definition ``resize_image`` implements, computed in fp32 from fp64 taps; torch's CPU kernel rounds its own
 way, so a few pixels per image whose exact value lies within about 1e-3 of a rounding edge may differ by one grey level from the
 host route's.  Off (the default), nothing changes.
+
+``decode_all=True`` (``--device-image-decode-all``) widens what the device takes to every PNG colour type and bit depth, tRNS or
+not, Adam7-interlaced or not (``PngInfo.any_decodable``): the chunk's launch -- and with ``device_resize`` every group's -- is then
+``yogo_png_unpack_any`` (csrc/png_unpack_any.hip, the same loop), whose table names each image's format, so one launch still takes
+a chunk of mixed files; every image has its own inflated size in the scanline buffer and the palettes of the chunk's palette files
+lie behind the last image.  The conversions are ``read_image``'s, bit for bit.  The host keeps what is no PNG, what does not parse,
+a palette file without a usable PLTE chunk, and whatever the inflate or unpack launch refuses.  Off (the default), nothing changes.
 """
 from __future__ import annotations
 
@@ -43,7 +50,7 @@ import numpy as np
 import torch
 
 from yogo_amd import _hip, png
-from yogo_amd.device_decode import ALIGN, MAX_THREADS, inflate_streams, png_stream_into, png_unpack_planes, resize_aa
+from yogo_amd.device_decode import ALIGN, MAX_THREADS, inflate_streams, png_stream_into, png_unpack_any, png_unpack_planes, resize_aa
 from yogo_amd.resize import aa_taps, device_serves
 
 # images per decode chunk, from tools/bench_prefill.py's sweep (profiles/prefill_decode.log: 772 x 1032 frames, three runs per size):
@@ -76,11 +83,13 @@ class _Sample:
     """what one sample of a chunk turned out to be: a zlib stream for the device (``stored`` bytes at the start of its room, the
     DEFLATE range and Adler-32 inside them, ``bpp`` bytes per pixel, ``hw`` the file's size when it is not the cache's and the device
     resizes it, else None) or a sample for the host decoder (``host``: ``pixels`` is what ``image_uint8`` gave, None when the file is
-    unreadable).  ``rows``: the label rows, or the exception their parsing raised."""
-    __slots__ = ("host", "stored", "deflate", "adler", "bpp", "hw", "pixels", "rows")
+    unreadable).  ``rows``: the label rows, or the exception their parsing raised.  With decode_all: ``need`` bytes the stream
+    inflates to, the format ``code`` of yogo_png_unpack_any's table, the ``palette`` (768 bytes) of a palette file."""
+    __slots__ = ("host", "stored", "deflate", "adler", "bpp", "hw", "pixels", "rows", "need", "code", "palette")
 
     def __init__(self):
         self.host, self.stored, self.deflate, self.adler, self.bpp, self.hw, self.pixels, self.rows = False, 0, (0, 0), 0, 1, None, None, None
+        self.need, self.code, self.palette = 0, None, None
 
 
 def _label_rows(ds, j: int):
@@ -98,10 +107,10 @@ def _host_sample(s: _Sample, ds, j: int) -> _Sample:
     return s
 
 
-def _read(ds, j: int, room: np.ndarray, image_hw: Tuple[int, int], device_resize: bool = False) -> _Sample:
+def _read(ds, j: int, room: np.ndarray, image_hw: Tuple[int, int], device_resize: bool = False, decode_all: bool = False) -> _Sample:
     """(pool thread) one sample: its file's zlib stream into ``room`` (its bytes of the pinned slot) and its label rows, or its
     pixels from the host decoder.  device_resize: a file of another size than ``image_hw`` stays on the device when the resize
-    kernel serves both of its scales"""
+    kernel serves both of its scales; decode_all: every PNG format the device knows stays there"""
     s = _Sample()
     try:
         with open(str(ds._image_paths[j]), "rb") as f:
@@ -109,7 +118,7 @@ def _read(ds, j: int, room: np.ndarray, image_hw: Tuple[int, int], device_resize
         info = png.parse_png(data)
     except (OSError, ValueError):   # unreadable, another format under its name (png.NotPng), a PNG that does not parse
         return _host_sample(s, ds, j)
-    if not info.prefill_decodable or info.idat_bytes > len(room):
+    if not (info.any_decodable if decode_all else info.prefill_decodable) or info.idat_bytes > len(room):
         return _host_sample(s, ds, j)   # (longer than its room: the file grew after its size was taken)
     if (info.height, info.width) != tuple(image_hw):
         if not (device_resize and device_serves(info.height, image_hw[0]) and device_serves(info.width, image_hw[1])):
@@ -120,6 +129,9 @@ def _read(ds, j: int, room: np.ndarray, image_hw: Tuple[int, int], device_resize
     except ValueError:
         return _host_sample(s, ds, j)
     s.deflate, s.bpp = (off, ln), info.bytes_per_pixel
+    if decode_all:
+        s.need, s.code = info.inflated_bytes, info.format_code
+        s.palette = png.palette_table(data, info) if info.color_type == 3 else None
     s.rows = _label_rows(ds, j)
     return s
 
@@ -136,13 +148,14 @@ def _file_size(path: str) -> int:
 
 
 def fill(images: torch.Tensor, samples: Sequence[Tuple[object, int]], decode_batch: int = DEFAULT_DECODE_BATCH,
-         stats: Optional[Dict] = None, device_resize: bool = False) -> List[Optional[torch.Tensor]]:
+         stats: Optional[Dict] = None, device_resize: bool = False, decode_all: bool = False) -> List[Optional[torch.Tensor]]:
     """images[i] = the uint8 image of samples[i] = (ObjectDetectionDataset, index in it), what ``ds.image_uint8(index)`` gives, for
     every sample that can be read.  images: contiguous uint8 [N, C, H, W] on an MI355X device (a view of the cache), C 1 or 3.
     -> per sample its fp32 [n, 5] label rows, or None for a sample nothing could decode (its image is left as it was).  Returns after
     the device has finished.  stats (optional dict) receives ``scratch_device_bytes``, ``scratch_pinned_bytes``, ``host_decoded`` and
     per chunk the device-event times ``inflate_ms`` / ``unpack_ms``.  device_resize: files of another size are resized on the device
-    (see the module's text); stats then also counts them (``device_resized``) and times every resize launch (``resize_ms``)."""
+    (see the module's text); stats then also counts them (``device_resized``) and times every resize launch (``resize_ms``).
+    decode_all: every PNG colour type, bit depth and Adam7 is decoded on the device (see the module's text)."""
     _hip.require_cuda(images, "the image cache")
     if images.dtype != torch.uint8 or images.ndim != 4 or images.shape[1] not in (1, 3) or not images.is_contiguous():
         raise ValueError(f"fill: images must be a contiguous uint8 [N, 1 or 3, H, W] tensor, got {tuple(images.shape)} {images.dtype}")
@@ -171,7 +184,7 @@ def fill(images: torch.Tensor, samples: Sequence[Tuple[object, int]], decode_bat
         def stage(n: int) -> List[_Sample]:
             (lo, hi), (offsets, _) = chunks[n], layouts[n]
             host = pinned[n % 2].numpy()
-            futures = [pool.submit(_read, *samples[i], host[int(offsets[i - lo]):int(offsets[i - lo]) + sizes[i]], (H, W), device_resize) for i in range(lo, hi)]
+            futures = [pool.submit(_read, *samples[i], host[int(offsets[i - lo]):int(offsets[i - lo]) + sizes[i]], (H, W), device_resize, decode_all) for i in range(lo, hi)]
             return [f.result() for f in futures]
 
         with torch.cuda.device(dev), torch.cuda.stream(side):
@@ -183,7 +196,7 @@ def fill(images: torch.Tensor, samples: Sequence[Tuple[object, int]], decode_bat
                 chunk = pending.result()
                 if n + 1 < len(chunks):
                     pending = stager.submit(stage, n + 1)
-                scan, staging = _decode(chunk, samples[lo:hi], layouts[n], pinned[n % 2], sdev, scan, images[lo:hi], stats)
+                scan, staging = _decode(chunk, samples[lo:hi], layouts[n], pinned[n % 2], sdev, scan, images[lo:hi], stats, decode_all)
                 staged = max(staged, staging)
                 for i, s in enumerate(chunk):
                     if s.host and s.pixels is None:
@@ -202,19 +215,23 @@ def fill(images: torch.Tensor, samples: Sequence[Tuple[object, int]], decode_bat
 
 
 def _decode(chunk: List[_Sample], samples, layout, pinned: torch.Tensor, sdev: torch.Tensor, scan: Optional[torch.Tensor],
-            out: torch.Tensor, stats: Optional[Dict]) -> Tuple[torch.Tensor, int]:
+            out: torch.Tensor, stats: Optional[Dict], decode_all: bool = False) -> Tuple[torch.Tensor, int]:
     """one chunk on the current (side) stream: upload, inflate, unpack into ``out`` (the files of another size: into a staging tensor
     per size, resized from there into ``out``), the statuses back; then whatever the device refused through the host decoder.
     -> the scanline buffer (grown when this chunk needed more), the staging bytes this chunk took"""
     offsets, _ = layout
     B, C, H, W = (int(v) for v in out.shape)
     dev = out.device
-    need = [C * H * W if s.host else (s.hw or (H, W))[0] * (1 + s.bpp * (s.hw or (H, W))[1]) for s in chunk]
+    need = [C * H * W if s.host else s.need if decode_all else (s.hw or (H, W))[0] * (1 + s.bpp * (s.hw or (H, W))[1]) for s in chunk]
     at = np.zeros(B + 1, dtype=np.int64)
     at[1:] = np.cumsum([-(-v // SCAN_ALIGN) * SCAN_ALIGN for v in need])
-    if scan is None or scan.numel() < int(at[B]):
+    # (decode_all) behind the last image the palettes of the chunk's palette files, 768 bytes each
+    with_palette = [i for i, s in enumerate(chunk) if not s.host and s.palette is not None]
+    palette_at = {i: int(at[B]) + k * png.PALETTE_BYTES for k, i in enumerate(with_palette)}
+    total = int(at[B]) + len(with_palette) * png.PALETTE_BYTES
+    if scan is None or scan.numel() < total:
         scan = None   # (the smaller buffer goes back to the allocator first)
-        scan = torch.empty(int(at[B]), dtype=torch.uint8, device=dev)
+        scan = torch.empty(total, dtype=torch.uint8, device=dev)
     device_rows = [i for i, s in enumerate(chunk) if not s.host]
     kept = [i for i, s in enumerate(chunk) if not (s.host and s.pixels is None)]
     if not kept:
@@ -241,13 +258,18 @@ def _decode(chunk: List[_Sample], samples, layout, pinned: torch.Tensor, sdev: t
             scan[int(at[i]):int(at[i]) + need[i]].copy_(s.pixels.contiguous().reshape(-1))
     # a sample nothing could decode keeps its place in the launch as an entry the kernel refuses before it reads anything, and so
     # does a file of another size: its group's own launches follow
-    table = np.asarray([(int(at[i]), -1 if (s.host and s.pixels is None) or (not s.host and s.hw) else KIND_PLANAR if s.host else _kind(s))
-                        for i, s in enumerate(chunk)], dtype=np.int64).reshape(-1, 2)
+    table = np.asarray([(int(at[i]), -1 if (s.host and s.pixels is None) or (not s.host and s.hw) else KIND_PLANAR if s.host else
+                         s.code if decode_all else _kind(s), palette_at.get(i, 0)) for i, s in enumerate(chunk)], dtype=np.int64).reshape(-1, 3)
     status = torch.empty(B, dtype=torch.int32, device=dev)
-    table_dev = torch.from_numpy(table).to(dev)
+    if with_palette:   # one copy for the palettes of the chunk
+        scan[int(at[B]):total].copy_(torch.from_numpy(np.concatenate([chunk[i].palette for i in with_palette])))
+    table_dev = torch.from_numpy(np.ascontiguousarray(table if decode_all else table[:, :2])).to(dev)
     if timed:
         ev[2].record()
-    png_unpack_planes(scan, table_dev, (H, W), out, status)
+    if decode_all:
+        png_unpack_any(scan, table_dev, (H, W), out, status)
+    else:
+        png_unpack_planes(scan, table_dev, (H, W), out, status)
     if timed:
         ev[3].record()
     groups: Dict[Tuple[int, int], List[int]] = {}
@@ -259,8 +281,12 @@ def _decode(chunk: List[_Sample], samples, layout, pinned: torch.Tensor, sdev: t
         stage = torch.empty((len(members), C, Hs, Ws), dtype=torch.uint8, device=dev)
         staging += stage.numel()
         gstatus = torch.empty(len(members), dtype=torch.int32, device=dev)
-        gtable = np.asarray([(int(at[i]), _kind(chunk[i])) for i in members], dtype=np.int64).reshape(-1, 2)
-        png_unpack_planes(scan, torch.from_numpy(gtable).to(dev), (Hs, Ws), stage, gstatus)
+        if decode_all:
+            gtable = np.asarray([(int(at[i]), chunk[i].code, palette_at.get(i, 0)) for i in members], dtype=np.int64).reshape(-1, 3)
+            png_unpack_any(scan, torch.from_numpy(gtable).to(dev), (Hs, Ws), stage, gstatus)
+        else:
+            gtable = np.asarray([(int(at[i]), _kind(chunk[i])) for i in members], dtype=np.int64).reshape(-1, 2)
+            png_unpack_planes(scan, torch.from_numpy(gtable).to(dev), (Hs, Ws), stage, gstatus)
         gev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timed else None
         if timed:
             gev[0].record()

@@ -101,6 +101,12 @@ def _resize_needs_decode(ns):
     return None
 
 
+def _decode_all_needs_decode(ns):
+    if ns.device_image_decode_all and not ns.device_image_decode:
+        return "--device-image-decode-all widens what --device-image-decode takes: it needs --device-image-decode"
+    return None
+
+
 def global_parser():
     parser = argparse.ArgumentParser(description="what can yogo do for you today?", allow_abbrev=False)
     sub = parser.add_subparsers(help="here is what you can do", dest="task", parser_class=CheckedParser)
@@ -147,6 +153,10 @@ def train_parser(parser=None):
                              "and RGB) instead of a pool of PIL workers; other files are decoded on the host; same batches.  Its scratch "
                              "memory (pinned staging, stored streams, scanlines) is freed after the prefill and is not counted in the "
                              "GIB budget (default: False)")
+    parser.add_argument("--device-image-decode-all", default=False, action=boolean_action,
+                        help="with --device-image-decode: also decode on the GPU every other PNG colour type and bit depth (palette, 1 / 2 / "
+                             "4-bit and 16-bit, grey+alpha, RGBA, with tRNS, Adam7-interlaced) instead of handing those files to the host; "
+                             "the same pixels as the host's decoder (default: False)")
     parser.add_argument("--device-image-resize", default=False, action=boolean_action,
                         help="with --device-image-decode: also resize on the GPU the 8-bit greyscale and RGB PNG files whose size is not "
                              "--image-hw (down to 1/8 per axis, or up) instead of handing them to the host; a few pixels of such an image "
@@ -162,6 +172,7 @@ def train_parser(parser=None):
     parser.add_argument("--wandb-project", type=str, default=os.getenv("wandb_project"), help="wandb project name - defaults to the environment variable wandb_project")
     parser.checks.append(_decode_needs_cache)
     parser.checks.append(_resize_needs_decode)
+    parser.checks.append(_decode_all_needs_decode)
     return parser
 
 
@@ -197,7 +208,7 @@ def export_parser(parser=None):
 
 def infer_parser(parser=None):
     if parser is None:
-        parser = argparse.ArgumentParser(description="infer results over some dataset", allow_abbrev=False)
+        parser = CheckedParser(description="infer results over some dataset", allow_abbrev=False)
     parser.add_argument("pth_path", type=Path, help="path to .pth file defining the model")
     data_source = parser.add_mutually_exclusive_group(required=True)
     data_source.add_argument("--path-to-images", "--path-to-image", type=Path, default=None,
@@ -218,6 +229,10 @@ def infer_parser(parser=None):
     parser.add_argument("--device-image-decode", default=False, action=boolean_action,
                         help="with --path-to-images: inflate and unfilter 8-bit greyscale PNG files on the GPU instead of decoding them "
                              "in DataLoader workers; other files are decoded on the host; same outputs (default: False)")
+    parser.add_argument("--device-image-decode-all", default=False, action=boolean_action,
+                        help="with --device-image-decode: decode on the GPU every PNG colour type and bit depth (palette, 1 / 2 / 4-bit and "
+                             "16-bit, grey+alpha, RGBA, RGB, with tRNS, Adam7-interlaced), converted as the host's decoder converts them, "
+                             "and accept an RGB model; only files that are no PNG stay on the host (default: False)")
     parser.add_argument("--output-dir", type=Path, default=None,
                         help="path to directory for results, either --draw-boxes or --save-preds")
     parser.add_argument("--class-names", help="list of class names - will default to integers if not provided", nargs="*", type=str, default=None)
@@ -235,4 +250,5 @@ def infer_parser(parser=None):
     parser.add_argument("--heatmap-mask-path", type=Path, default=None,
                         help="path to heatmap mask for the run (accepted for compatibility, unused -- as in the reference)")
     parser.add_argument("--use-tqdm", default=True, action=boolean_action, help="use tqdm progress bar (default: True)")
+    parser.checks.append(_decode_all_needs_decode)
     return parser

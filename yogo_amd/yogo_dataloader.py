@@ -19,7 +19,8 @@ resident split starts no worker at all: ``DeviceLoader`` walks the sampler's ind
 device.  A partially resident one hands the workers a ``ResidentMarkers`` wrapper, and each batch is assembled from uploaded,
 resident and blob rows.  ``device_image_decode`` (``--device-image-decode``) fills the cache from PNG files decoded on the device
 (yogo_amd/png_prefill.py); the batches are the same.  ``device_image_resize`` (``--device-image-resize``) has that route resize
-files of another size than ``image_hw`` on the device too (a few pixels of those may differ by one grey level).  Without a budget nothing of this exists: the same ``DeviceLoader`` path, no allocation, no prefill.
+files of another size than ``image_hw`` on the device too (a few pixels of those may differ by one grey level);
+``device_image_decode_all`` (``--device-image-decode-all``) has it take every PNG colour type, bit depth and Adam7.  Without a budget nothing of this exists: the same ``DeviceLoader`` path, no allocation, no prefill.
 """
 from __future__ import annotations
 
@@ -34,7 +35,7 @@ from torch.utils.data.distributed import DistributedSampler
 from yogo_amd.blobgen import BlobDataset
 from yogo_amd.data import MultiArgSequential, RandomHorizontalFlipWithBBs, RandomVerticalFlipWithBBs, format_labels_batch
 from yogo_amd.dataset_definition_file import DatasetDefinition, SplitFractions
-from yogo_amd.image_cache import DECODE_FLAG, FLAG, RESIZE_FLAG, ImageCache, ResidentMarkers, budget_bytes, collate_cached, gather, resident_count
+from yogo_amd.image_cache import DECODE_ALL_FLAG, DECODE_FLAG, FLAG, RESIZE_FLAG, ImageCache, ResidentMarkers, budget_bytes, collate_cached, gather, resident_count
 from yogo_amd.yogo_dataset import ObjectDetectionDataset
 
 SPLIT_SEED = 7271978   # yogo/data/yogo_dataloader.py:176
@@ -257,15 +258,19 @@ def get_dataloader(dataset_definition: DatasetDefinition, batch_size: int, Sx: i
                    image_hw: Tuple[int, int] = (772, 1032), rgb: bool = False, normalize_images: bool = False,
                    split_fraction_override: Optional[SplitFractions] = None, device=None,
                    device_image_cache_gib: Optional[float] = None, device_image_decode: bool = False,
-                   device_image_resize: bool = False) -> Dict[str, DeviceLoader]:
+                   device_image_resize: bool = False, device_image_decode_all: bool = False) -> Dict[str, DeviceLoader]:
     """{split: DeviceLoader}.  device_image_cache_gib: keep decoded images of the train split, then of the val split with what
     is left, resident in HBM within this many GiB (yogo_amd/image_cache.py); None: no cache.  device_image_decode: fill that
     cache from PNG files inflated and unfiltered on the device (yogo_amd/png_prefill.py) instead of a pool of PIL workers.
-    device_image_resize: on that route, resize the files of another size than image_hw on the device as well."""
+    device_image_resize: on that route, resize the files of another size than image_hw on the device as well.
+    device_image_decode_all: on that route, decode every PNG colour type, bit depth and Adam7 on the device, not 8-bit greyscale
+    and RGB alone."""
     if device_image_decode and device_image_cache_gib is None:
         raise ValueError(f"{DECODE_FLAG} fills the device image cache: it needs {FLAG} GIB")
     if device_image_resize and not device_image_decode:
         raise ValueError(f"{RESIZE_FLAG} resizes what the device decoded: it needs {DECODE_FLAG}")
+    if device_image_decode_all and not device_image_decode:
+        raise ValueError(f"{DECODE_ALL_FLAG} widens what {DECODE_FLAG} takes: it needs {DECODE_FLAG}")
     budget = budget_bytes(device_image_cache_gib) if device_image_cache_gib is not None else None
     split_datasets = get_datasets(dataset_definition, Sx, Sy, rgb=rgb, image_hw=image_hw, normalize_images=normalize_images,
                                   split_fraction_override=split_fraction_override)
@@ -290,7 +295,7 @@ def get_dataloader(dataset_definition: DatasetDefinition, batch_size: int, Sx: i
         if resident.get(designation, 0) > 0:
             cache_args = dict(resident=resident[designation], image_shape=image_shape, normalize_images=normalize_images,
                               name=designation, log=rank == 0, device_decode=bool(device_image_decode),
-                              device_resize=bool(device_image_resize))
+                              device_resize=bool(device_image_resize), device_decode_all=bool(device_image_decode_all))
         d[designation] = _get_dataloader(dataset, batch_size, augs, rank, world_size, Sx, Sy, device, strict_steps=designation == "train",
                                          **cache_args)
     return d
@@ -313,7 +318,7 @@ def _num_workers(dataset_size: int, world_size: int) -> int:
 def _get_dataloader(dataset: Dataset, batch_size: int, augmentations: list, rank: int, world_size: int, Sx: int, Sy: int,
                     device=None, strict_steps: bool = False, resident: int = 0, image_shape: Optional[Tuple[int, int, int]] = None,
                     normalize_images: bool = False, name: str = "train", log: bool = False, device_decode: bool = False,
-                    device_resize: bool = False) -> DeviceLoader:
+                    device_resize: bool = False, device_decode_all: bool = False) -> DeviceLoader:
     """resident > 0: split indices 0 .. resident-1 are kept decoded on the device (image_shape = (C, H, W))"""
     blob = dataset.datasets[-1] if isinstance(dataset, ConcatDataset) and isinstance(dataset.datasets[-1], BlobDataset) else None
     # the workers iterate the split with its blob part replaced by the indices alone (same length: same sampler order)
@@ -327,7 +332,8 @@ def _get_dataloader(dataset: Dataset, batch_size: int, augmentations: list, rank
         # workers; the split's workers see the resident indices as markers
         cache = ImageCache(dataset, resident, image_shape, normalize_images, device=device, num_workers=num_workers, batch_size=batch_size,
                            name=name, log=log, **({"device_decode": True} if device_decode else {}),
-                           **({"device_resize": True} if device_resize else {}))   # (the keywords only when set:
+                           **({"device_resize": True} if device_resize else {}),
+                           **({"device_decode_all": True} if device_decode_all else {}))   # (the keywords only when set:
         #                    tests/test_image_cache_host.py puts a recording class with the earlier signature in ImageCache's place)
         host_dataset = ResidentMarkers(host_dataset, cache.resident)
         collate_fn = collate_cached
