@@ -479,6 +479,27 @@ int yogo_zarr_unpack(const unsigned char* staged, long long staged_bytes, const 
  * the stored bytes say (the same checks, in the same order: yogo_amd.blosc.lz4_block_status). */
 int yogo_blosc_lz4_decode(const unsigned char* src, long long src_bytes, const long long* table, int n, unsigned char* dst,
                           long long dst_bytes, int* status, yogo_stream_t stream);
+/* Zstandard frames decoded on the device in front of yogo_zarr_unpack: the blocks of Blosc chunks whose inner codec is zstd (one frame
+ * per block; yogo_amd/blosc.py parses the chunk headers) and the chunks of zarr's `zstd` codec (one frame per chunk); launched from
+ * yogo_amd/device_decode.py.  src, table, dst and status as yogo_blosc_lz4_decode takes them: rows { src_off, src_len, dst_off, dst_len,
+ * raw }, raw != 0 copied (src_len == dst_len), else ONE frame that decodes to exactly dst_len bytes.  work: work_bytes of device memory,
+ * 16-byte aligned, overlapping neither src nor dst, at least yogo_zstd_work_bytes(n) (128 KB per row: a block's Huffman-coded
+ * literals).  One wavefront per row; raw, RLE and compressed blocks; raw, RLE, Huffman-compressed (1 or 4 streams, direct or
+ * FSE-compressed weights) and treeless literals; predefined, RLE, FSE-compressed and repeated tables; repeat offsets; offset codes up
+ * to 31.  The window size is parsed and not enforced (a match may reach back over all the frame has produced); a content checksum must
+ * be present when flagged and is NOT verified.  status: [n] int32 device, per row 0 or the check that ended it: 1 the row does not
+ * lie inside src / dst / work, 2 the source or a block ends inside a header or a section, 3 no frame magic (a skippable frame too),
+ * 4 a reserved bit or a dictionary id in the frame header, 5 the frame content size is not dst_len, 6 block type 3 or a block above
+ * 128 KB, 7 an invalid literals section (above 128 KB, stream sizes past the section, treeless without a table), 8 Huffman weights that
+ * describe no code of at most 11 bits, 9 an invalid FSE table (accuracy log or symbol above the limit, counts that do not sum up,
+ * repeat mode without a table), 10 a backward bitstream that is empty, lacks its marker bit or is not consumed exactly, 11 an invalid
+ * sequences section (reserved mode bits, bytes after zero sequences, a literal length past the block's literals), 12 a match offset
+ * of 0 or beyond what the frame has produced, 13 the frame would pass dst_len, 14 it ends before dst_len, 15 bytes after the frame's
+ * end.  No byte outside a row's ranges is read or written, whatever the stored bytes say (the same checks, in the same order:
+ * yogo_amd.zstd.zstd_frame_status). */
+int yogo_zstd_work_bytes(int n, size_t* bytes);
+int yogo_zstd_decode(const unsigned char* src, long long src_bytes, const long long* table, int n, unsigned char* dst,
+                     long long dst_bytes, int* status, unsigned char* work, long long work_bytes, yogo_stream_t stream);
 /* The chunks of a zarr stack under the `zlib` codec, inflated on the device in front of yogo_zarr_unpack (yogo_amd/inflate.py takes
  * the zlib wrapper off on the host: split_zlib).  src: src_bytes of device memory holding stored chunks as they came off the disk;
  * table: [n][5] int64 device, one row { src_off, src_len, dst_off, dst_len, adler32 } per stream: its raw DEFLATE bytes in src

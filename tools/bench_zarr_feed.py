@@ -3,11 +3,15 @@ and `predict` from each store (optionally against a PNG directory).
 
 Input: seeded 772 x 1032 uint8 frames, written once to a scratch file and from there into each store (tests/_zarr_write.py's
 layout rules) and, with --png, into a PNG directory; everything lies in a temporary directory that is removed at the end.
---content: `incompressible` = a smooth background plus Gaussian noise of sigma 6 (as tools/bench_loader.py; LZ4 does not shrink
+The zstd legs (`blosc-zstd`: Blosc with one Zstandard frame per block; `zstd`: the zstd codec, one frame per chunk) are written by the
+system's libzstd through ctypes where it loads, else by tests/_zstd_write.py's compressor (then use --distinct 4); --reverse walks
+compressors and routes backwards, so that two runs alternate the legs in both orders.
+--content: `noise` = uniform random bytes (no codec shrinks them), `incompressible` = a smooth background plus Gaussian noise of sigma 6 (as tools/bench_loader.py; LZ4 does not shrink
 it: Blosc stores its blocks raw), `compressible` = the same with the lower third of every frame a flat field (LZ4 shrinks it to
 about two thirds).  --compressors: null, zlib (level 1), blosc (LZ4 blocks at --blocksize, framed here with the system's liblz4);
---decode: for blosc and zlib, `device` (yogo_blosc_lz4_decode / yogo_inflate_zlib) and / or `host` (ZarrDeviceFeed(device_decode=False);
-for predict, zarr_feed.DEVICE_DECODE_ZLIB = False).  Every measurement
+--decode: for blosc, zlib, blosc-zstd and zstd, `device` (yogo_blosc_lz4_decode / yogo_inflate_zlib / yogo_zstd_decode) and / or `host`
+(ZarrDeviceFeed(device_decode=False)); the feed and the predict steps set zarr_feed.DEVICE_DECODE_ZLIB and DEVICE_DECODE_ZSTD from the
+leg's route, whatever the module's defaults are.  Every measurement
 is a step in a child process of its own with its own time limit; a step that fails or runs out of time is recorded as such, and
 no further step is started.  The lines are APPENDED to --out.
 
@@ -49,6 +53,8 @@ CLASSES = ["you", "only", "glance", "once"]
 
 def _frame(k: int, content: str = "incompressible") -> np.ndarray:
     rng = np.random.default_rng(k)
+    if content == "noise":
+        return rng.integers(0, 256, size=(H, W), dtype=np.uint8)
     y, x = np.mgrid[0:H, 0:W].astype(np.float32)
     a, b, c = rng.uniform(0.5, 2.0, 3)
     smooth = 150 + 40 * np.sin(x / W * np.pi * a + c) * np.cos(y / H * np.pi * b)
@@ -87,15 +93,56 @@ def blosc_lz4_frame(raw: bytes, blocksize: int) -> bytes:
     return struct.pack("<BBBBIII", 2, 1, flags, 1, n, blocksize, pos) + struct.pack(f"<{nblocks}i", *bstarts) + bytes(body)
 
 
+ZSTD_LEVEL = 1
+_zstd_cache: dict = {}
+
+
+def zstd_writer() -> str:
+    """what writes the Zstandard frames of the zstd legs: the system's libzstd through ctypes, or tests/_zstd_write.py's compressor"""
+    from yogo_amd import zstd
+
+    return f"libzstd {zstd.libzstd().ZSTD_versionString().decode()}" if zstd.libzstd() is not None else "tests/_zstd_write.py compress()"
+
+
+def zstd_frame(raw: bytes) -> bytes:
+    from yogo_amd import zstd
+
+    if zstd.libzstd() is not None:
+        return zstd.lib_compress(raw, ZSTD_LEVEL)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _zstd_write
+
+    return _zstd_write.compress(raw)
+
+
+def blosc_zstd_frame(raw: bytes, blocksize: int) -> bytes:
+    """as blosc_lz4_frame with one Zstandard frame per block (inner format 4)"""
+    n = len(raw)
+    nblocks = -(-n // blocksize)
+    body, bstarts, pos = bytearray(), [], 16 + 4 * nblocks
+    for b in range(nblocks):
+        block = raw[b * blocksize:(b + 1) * blocksize]
+        enc = zstd_frame(block)
+        if len(enc) >= len(block):
+            enc = block
+        bstarts.append(pos)
+        body += struct.pack("<i", len(enc)) + enc
+        pos += 4 + len(enc)
+    flags = 0x01 | (4 << 5)
+    if pos > n + 16:
+        return struct.pack("<BBBBIII", 2, 1, flags | 0x02, 1, n, blocksize, n + 16) + raw
+    return struct.pack("<BBBBIII", 2, 1, flags, 1, n, blocksize, pos) + struct.pack(f"<{nblocks}i", *bstarts) + bytes(body)
+
+
 def _frames(d: str, n: int) -> np.ndarray:
     return np.memmap(os.path.join(d, "frames.u8"), dtype=np.uint8, mode="r", shape=(n, H, W))
 
 
 def _gen(args):
-    d, n, lo, hi, content = args
+    d, n, lo, hi, content, distinct = args
     m = np.memmap(os.path.join(d, "frames.u8"), dtype=np.uint8, mode="r+", shape=(n, H, W))
     for k in range(lo, hi):
-        m[k] = _frame(k, content)
+        m[k] = _frame(k % distinct if distinct else k, content)
     m.flush()
 
 
@@ -109,7 +156,9 @@ def _png(args):
 
 
 def _chunk(args):
-    d, n, t, cn, compress, blocksize = args
+    d, n, t, cn, compress, blocksize, distinct = args
+    if distinct and cn == 1 and (compress, t % distinct) in _zstd_cache:   # (--distinct: frame t is frame t % distinct)
+        return t, _zstd_cache[(compress, t % distinct)]
     m = _frames(d, n)
     block = np.zeros((H, W, cn), dtype=np.uint8)
     for j in range(cn):
@@ -118,6 +167,11 @@ def _chunk(args):
     raw = block.tobytes()
     if compress == "blosc":
         return t, blosc_lz4_frame(raw, blocksize)
+    if compress in ("blosc-zstd", "zstd"):
+        enc = blosc_zstd_frame(raw, blocksize) if compress == "blosc-zstd" else zstd_frame(raw)
+        if distinct and cn == 1:
+            _zstd_cache[(compress, t % distinct)] = enc
+        return t, enc
     return t, (zlib.compress(raw, 1) if compress == "zlib" else raw)
 
 
@@ -127,17 +181,19 @@ def _spans(n, parts):
 
 
 COMPRESSOR_DOCS = {"null": None, "zlib": {"id": "zlib", "level": 1},
-                   "blosc": {"id": "blosc", "cname": "lz4", "clevel": 5, "shuffle": 1, "blocksize": 0}}
+                   "blosc": {"id": "blosc", "cname": "lz4", "clevel": 5, "shuffle": 1, "blocksize": 0},
+                   "blosc-zstd": {"id": "blosc", "cname": "zstd", "clevel": ZSTD_LEVEL, "shuffle": 1, "blocksize": 0},
+                   "zstd": {"id": "zstd", "level": ZSTD_LEVEL}}
 
 
-def write_store(d: str, n: int, name: str, cn: int, compress: str, blocksize: int = 131072) -> str:
-    """an [H, W, n] array in (H, W, cn) chunks as a zip store of stored members; compress: null, zlib or blosc"""
+def write_store(d: str, n: int, name: str, cn: int, compress: str, blocksize: int = 131072, distinct: int = 0) -> str:
+    """an [H, W, n] array in (H, W, cn) chunks as a zip store of stored members; compress: null, zlib, blosc, blosc-zstd or zstd"""
     p = os.path.join(d, name)
     meta = {"zarr_format": 2, "shape": [H, W, n], "chunks": [H, W, cn], "dtype": "|u1", "order": "C", "fill_value": 0, "filters": None,
             "compressor": COMPRESSOR_DOCS[compress], "dimension_separator": "."}
     with zipfile.ZipFile(p, "w", zipfile.ZIP_STORED) as zf, ProcessPoolExecutor(WORKERS) as ex:
         zf.writestr(".zarray", json.dumps(meta))
-        for t, data in ex.map(_chunk, [(d, n, t, cn, compress, blocksize) for t in range(-(-n // cn))], chunksize=2):
+        for t, data in ex.map(_chunk, [(d, n, t, cn, compress, blocksize, distinct) for t in range(-(-n // cn))], chunksize=2):
             zf.writestr(f"0.0.{t}", data)
     return p
 
@@ -147,9 +203,12 @@ def write_store(d: str, n: int, name: str, cn: int, compress: str, blocksize: in
 def step_feed(store: str, n: int, device_decode: bool = True, passes: int = 2) -> dict:
     import torch
 
+    from yogo_amd import zarr_feed
     from yogo_amd.image_path_dataset import ZarrDataset
     from yogo_amd.zarr_feed import ZarrDeviceFeed
 
+    # (the codecs whose device route is off by default: the leg's label decides, not the module's default)
+    zarr_feed.DEVICE_DECODE_ZLIB = zarr_feed.DEVICE_DECODE_ZSTD = device_decode
     ds = ZarrDataset(store)
     rates, setup = [], []
     for p in range(passes + 1):
@@ -173,15 +232,17 @@ def step_feed(store: str, n: int, device_decode: bool = True, passes: int = 2) -
 
 
 def step_decode(store: str, n: int) -> dict:
-    """yogo_blosc_lz4_decode (a zlib store: yogo_inflate_zlib) alone on the rows of the first batch"""
+    """yogo_blosc_lz4_decode (a zlib store: yogo_inflate_zlib; a Blosc-zstd or zstd store: yogo_zstd_decode over the frames and
+    yogo_blosc_lz4_decode over the raw rows, as the feed launches them) alone on the rows of the first batch"""
     import torch
 
-    from yogo_amd.device_decode import decode_blocks, inflate_streams
+    from yogo_amd.device_decode import decode_blocks, inflate_streams, zstd_frames, zstd_work_bytes
     from yogo_amd.zarr_feed import ChunkStager, FrameSource, plan_batch
     from yogo_amd.zarr_store import open_zarr
 
     src = FrameSource(open_zarr(store))
     zlib_store = src.first.device_codec == "zlib"
+    zstd_store = src.first.device_codec in ("blosc-zstd", "zstd")
     launches = 5 if zlib_store else 20
     launch = inflate_streams if zlib_store else decode_blocks   # (zlib: one row per chunk, the fifth field its Adler-32)
     plan = plan_batch(src, 0, min(B, n))
@@ -197,6 +258,17 @@ def step_decode(store: str, n: int) -> dict:
     table_dev = torch.from_numpy(table).cuda()
     out = torch.empty(plan.nbytes, dtype=torch.uint8, device="cuda")
     status = torch.empty(len(table), dtype=torch.int32, device="cuda")
+    if zstd_store:
+        table = table[np.argsort(table[:, 4] != 0, kind="stable")]
+        nz = int((table[:, 4] == 0).sum())
+        table_dev = torch.from_numpy(table).cuda()
+        work = torch.empty(zstd_work_bytes(max(nz, 1)), dtype=torch.uint8, device="cuda")
+
+        def launch(stored, table_dev, out, status):   # noqa: F811
+            if nz:
+                zstd_frames(stored, table_dev[:nz], out, status[:nz], work)
+            if nz < len(table):
+                decode_blocks(stored, table_dev[nz:], out, status[nz:])
     for _ in range(1 if zlib_store else 3):
         launch(stored, table_dev, out, status)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(launches + 1)]
@@ -265,7 +337,7 @@ def step_predict_store(d: str, store: str, n: int, route: str = "device") -> dic
     from yogo_amd.infer import predict
     from yogo_amd.model import YOGO
 
-    zarr_feed.DEVICE_DECODE_ZLIB = route == "device"
+    zarr_feed.DEVICE_DECODE_ZLIB = zarr_feed.DEVICE_DECODE_ZSTD = route == "device"
 
     torch.manual_seed(3)
     net = YOGO((H, W), 0.0425, 0.0555, 4).cuda().eval()
@@ -347,6 +419,8 @@ def main() -> int:
     ap.add_argument("--compressors", default="null,zlib,blosc")
     ap.add_argument("--decode", default="device,host", help="for blosc and zlib stores: device and / or host")
     ap.add_argument("--blocksize", type=int, default=131072, help="Blosc block size (c-blosc's choice for 1-byte items at clevel 5)")
+    ap.add_argument("--distinct", type=int, default=0, help="K > 0: frame k is frame k % K (a slow writer then compresses K frames only)")
+    ap.add_argument("--reverse", action="store_true", help="walk the compressors and the routes in reverse order (the second half of an alternated run)")
     ap.add_argument("--no-predict", action="store_true")
     ap.add_argument("--unpack-kernel", action="store_true")
     ap.add_argument("--png", action="store_true")
@@ -384,18 +458,21 @@ def main() -> int:
         log("feed = ZarrDeviceFeed alone, images/s on the host clock, timed passes after a warm-up pass; predict = predict(count_predictions, "
             "half, device_outputs), host clock around the whole call (model load included); decode = the device decoder alone on the first "
             "batch, device events, median / min of 20 launches (zlib: 5)")
+        if any(c in ("blosc-zstd", "zstd") for c in a.compressors.split(",")):
+            log(f"Zstandard frames written by {zstd_writer()} at level {ZSTD_LEVEL}; Blosc-zstd: one frame per block of {a.blocksize} bytes, a block stored "
+                f"raw when its frame is no shorter; --distinct {a.distinct}" + ("; compressors and routes walked in REVERSE order" if a.reverse else ""))
         ok = True
         for content in a.content.split(","):
             np.memmap(os.path.join(d, "frames.u8"), dtype=np.uint8, mode="w+", shape=(n, H, W)).flush()
             with ProcessPoolExecutor(WORKERS) as ex:
-                list(ex.map(_gen, [(d, n, lo, hi, content) for lo, hi in _spans(n, WORKERS * 4)]))
+                list(ex.map(_gen, [(d, n, lo, hi, content, a.distinct) for lo, hi in _spans(n, WORKERS * 4)]))
             log(f"content {content}:")
-            for comp in a.compressors.split(","):
-                store = write_store(d, n, f"{content}_{comp}.zip", 1, comp, a.blocksize)
+            for comp in (a.compressors.split(",")[::-1] if a.reverse else a.compressors.split(",")):
+                store = write_store(d, n, f"{content}_{comp}.zip", 1, comp, a.blocksize, a.distinct)
                 share = os.path.getsize(store) / n / (H * W) * 100
-                routed = comp in ("blosc", "zlib")
-                for route in (a.decode.split(",") if routed else ["host"]):
-                    label = f"  {comp:<5s} {('decode on the ' + route) if routed else '':<20s}"
+                routed = comp in ("blosc", "zlib", "blosc-zstd", "zstd")
+                for route in ((a.decode.split(",")[::-1] if a.reverse else a.decode.split(",")) if routed else ["host"]):
+                    label = f"  {comp:<10s} {('decode on the ' + route) if routed else '':<20s}"
                     r = run_step(log, "feed", 300, [store, n, route])
                     if r is None:
                         ok = False
@@ -410,7 +487,7 @@ def main() -> int:
                         log(f"{label} decode   {k['median_us']:9.1f} us / {k['min_us']:9.1f} us per batch of {k['frames']} frames: {k['blocks']} blocks, "
                             f"{k['raw_blocks']} of them raw ({100 * k['raw_blocks'] / max(k['blocks'], 1):.1f} %), {k['stored_bytes'] / 1e6:.1f} MB stored -> "
                             f"{k['decoded_bytes'] / 1e6:.1f} MB decoded = {k['decoded_bytes'] / (k['median_us'] * 1e-6) / 1e9:.0f} GB/s out; every status 0: {k['all_ok']}")
-                    if not a.no_predict and (comp != "blosc" or route == "device"):
+                    if not a.no_predict and (comp not in ("blosc", "blosc-zstd") or route == "device"):
                         r = run_step(log, "predict_store", 420, [d, store, n, route])
                         if r is None:
                             ok = False

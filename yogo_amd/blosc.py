@@ -9,7 +9,7 @@ when ``csize`` equals the block's decoded size and one stream of the inner codec
 
 ``parse_chunk`` lists the blocks (what yogo_amd/zarr_feed.py hands to ``yogo_blosc_lz4_decode``), ``lz4_block_decode`` is the
 LZ4 block format with the checks and the status codes of the kernel (csrc/blosc_lz4.hip), ``decompress`` decodes a chunk on
-the host.  The LZ4 block format is pinned to liblz4 by tests/golden/lz4_blocks.npz; the framing is not pinned to c-blosc.
+the host (inner format 4, one Zstandard frame per block, with the frame decoder it is given: yogo_amd/zstd.py).  The LZ4 block format is pinned to liblz4 by tests/golden/lz4_blocks.npz; the framing is not pinned to c-blosc.
 """
 from __future__ import annotations
 
@@ -17,7 +17,7 @@ import ctypes
 import ctypes.util
 import struct
 import zlib
-from typing import List, Optional, Tuple
+from typing import Callable, List, Optional, Tuple
 
 HEADER = 16
 FLAG_SHUFFLE, FLAG_MEMCPYED, FLAG_BITSHUFFLE, FLAG_DONT_SPLIT = 0x01, 0x02, 0x04, 0x10
@@ -206,9 +206,18 @@ def device_decodable(flags: int) -> bool:
     return (flags >> 5) == 1 and not flags & FLAG_BITSHUFFLE
 
 
-def decompress(buf, expect_nbytes: int) -> bytes:
+def device_decodable_zstd(flags: int) -> bool:
+    """the blocks ``parse_chunk`` listed can go to yogo_zstd_decode: raw bytes (memcpyed) or one Zstandard frame per block, not
+    bit-shuffled"""
+    if flags & FLAG_MEMCPYED:
+        return True
+    return (flags >> 5) == 4 and not flags & FLAG_BITSHUFFLE
+
+
+def decompress(buf, expect_nbytes: int, zstd: Optional[Callable[[bytes, int], bytes]] = None) -> bytes:
     """a whole chunk on the host.  NotImplementedError naming what was found for bit-shuffle, ``typesize > 1`` and inner
-    formats other than lz4 / lz4hc and zlib; ValueError for a malformed chunk."""
+    formats other than lz4 / lz4hc and zlib; ValueError for a malformed chunk.  ``zstd``: a decoder of one Zstandard frame
+    ``(bytes, decoded size) -> bytes`` (yogo_amd.zstd.frame_decoder()); with it, inner format 4 (one frame per block) is read."""
     mv = memoryview(buf).cast("B")
     flags, entries = parse_chunk(mv, expect_nbytes)
     if flags & FLAG_MEMCPYED:
@@ -216,7 +225,7 @@ def decompress(buf, expect_nbytes: int) -> bytes:
     if flags & FLAG_BITSHUFFLE:
         raise NotImplementedError("Blosc chunk: bit-shuffle (flag 0x04) is not read")
     fmt = flags >> 5
-    if fmt not in (1, 3):
+    if fmt not in (1, 3) and not (fmt == 4 and zstd is not None):
         raise NotImplementedError(f"Blosc chunk: inner format {fmt} ({FORMATS.get(fmt, 'unknown')}) is not read (lz4, lz4hc and zlib are)")
     out = bytearray(expect_nbytes)
     for src_off, src_len, dst_off, dst_len, raw in entries:
@@ -225,6 +234,11 @@ def decompress(buf, expect_nbytes: int) -> bytes:
             out[dst_off:dst_off + dst_len] = data
         elif fmt == 1:
             out[dst_off:dst_off + dst_len] = _lz4_block(bytes(data), dst_len)
+        elif fmt == 4:
+            block = zstd(bytes(data), dst_len)
+            if len(block) != dst_len:
+                raise ValueError(f"Blosc chunk: a zstd block of {len(block)} bytes, {dst_len} expected")
+            out[dst_off:dst_off + dst_len] = block
         else:
             block = zlib.decompress(data)
             if len(block) != dst_len:

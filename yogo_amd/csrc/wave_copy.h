@@ -1,5 +1,5 @@
-// Copies done by the 64 lanes of one wavefront together: what the device decoders (blosc_lz4.hip, inflate.hip) move bytes with.
-// Neither checks a bound: the caller has held both ranges to its buffers before it calls.
+// Copies and fills done by the 64 lanes of one wavefront together: what the device decoders (blosc_lz4.hip, inflate.hip, zstd.hip) move
+// bytes with.  None checks a bound: the caller has held both ranges to its buffers before it calls.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -56,6 +56,22 @@ __device__ __forceinline__ void wave_copy_periodic(unsigned char* d, long long o
     r += step;
     if (r >= o) r -= o;
   }
+}
+
+// n bytes of value v at d by the whole wave (a run-length block, run-length literals).  Aligned 16-byte stores, bytes at both edges.
+__device__ __forceinline__ void wave_fill(unsigned char* d, unsigned char v, long long n, int lane) {
+  if (n < 4 * WAVE) {
+    for (long long i = lane; i < n; i += WAVE) d[i] = v;
+    return;
+  }
+  const long long head = (16 - (reinterpret_cast<uintptr_t>(d) & 15)) & 15;   // < n
+  const long long pieces = (n - head) >> 4;
+  if (lane < head) d[lane] = v;
+  const unsigned w = v * 0x01010101u;
+  const uint4 q = make_uint4(w, w, w, w);
+  for (long long p = lane; p < pieces; p += WAVE) *reinterpret_cast<uint4*>(d + head + 16 * p) = q;
+  const long long done = head + 16 * pieces;
+  if (done + lane < n) d[done + lane] = v;   // < 16 bytes are left
 }
 
 }  // namespace yogo_wave

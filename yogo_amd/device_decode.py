@@ -1,6 +1,6 @@
 """What the routes that decode stored bytes on the device share -- zarr stacks (yogo_amd/zarr_feed.py), PNG directories for inference
 (yogo_amd/png_feed.py), the PNG prefill of the device image cache (yogo_amd/png_prefill.py): the launch wrappers of
-``yogo_blosc_lz4_decode``, ``yogo_inflate_zlib``, ``yogo_png_unpack``, ``yogo_png_unpack_planes``, ``yogo_png_unpack_any`` and ``yogo_resize_aa_u8`` (the
+``yogo_blosc_lz4_decode``, ``yogo_zstd_decode``, ``yogo_inflate_zlib``, ``yogo_png_unpack``, ``yogo_png_unpack_planes``, ``yogo_png_unpack_any`` and ``yogo_resize_aa_u8`` (the
 prefill's resize of other-size files) with their tensor checks, ``gather`` (a pool's futures), ``raise_first_bad`` (a status vector -> RuntimeError), ``png_stream_into`` (one PNG file -> one zlib
 stream in its room of a pinned slot) and ``PrefetchFeed`` (the iterator that loads batch n + 1 while the caller works on batch n)."""
 from __future__ import annotations
@@ -77,6 +77,32 @@ def inflate_streams(stored: torch.Tensor, table: torch.Tensor, out: torch.Tensor
     """One ``yogo_inflate_zlib`` launch on the current stream; as decode_blocks, rows (src_off, src_len, dst_off, dst_len, adler32):
     the raw DEFLATE bytes of one zlib stream each (yogo_amd.inflate.split_zlib)."""
     _decode_rows("yogo_inflate_zlib", stored, table, out, status)
+
+
+def zstd_work_bytes(n: int) -> int:
+    """the workspace ``zstd_frames`` needs for a table of n rows (``yogo_zstd_work_bytes``: 128 KB per row)"""
+    return _hip.query_size("yogo_zstd_work_bytes", int(n))
+
+
+def zstd_frames(stored: torch.Tensor, table: torch.Tensor, out: torch.Tensor, status: torch.Tensor, work: torch.Tensor) -> None:
+    """One ``yogo_zstd_decode`` launch on the current stream; as decode_blocks, rows (src_off, src_len, dst_off, dst_len, raw): one
+    Zstandard frame each (a Blosc-zstd block, a chunk of the ``zstd`` codec), or raw bytes.  work: a 1-D uint8 device tensor of at
+    least ``zstd_work_bytes(n)`` bytes (a block's Huffman-coded literals, per row)."""
+    what = "zstd_decode"
+    for t, name in ((stored, "the stored chunk bytes"), (table, "the table"), (out, "the decoded chunks"), (status, "the status"),
+                    (work, "the workspace")):
+        _hip.require_cuda(t, name)
+    require_bytes(what, "stored, out and work", stored, out, work)
+    n = int(table.shape[0])
+    require_table(what, table, 5)
+    require_status(what, status, n)
+    require_same_device(what, stored, table, out, status, work)
+    if n == 0:
+        return
+    if work.numel() < zstd_work_bytes(n):
+        raise ValueError(f"{what}: a workspace of {work.numel()} bytes for {n} rows, {zstd_work_bytes(n)} needed")
+    with torch.cuda.device(out.device):
+        _hip.call("yogo_zstd_decode", stored, stored.numel(), table, n, out, out.numel(), status, work, work.numel(), _hip.stream_ptr())
 
 
 def png_unpack(scan: torch.Tensor, table: torch.Tensor, image_hw: Tuple[int, int], out: torch.Tensor, status: torch.Tensor,

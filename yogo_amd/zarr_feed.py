@@ -19,7 +19,14 @@ Stacks under zarr's ``zlib`` codec take the same route with another decoder: one
 between the zlib header and trailer, and the trailer's Adler-32 (yogo_amd/inflate.py) -- and one ``yogo_inflate_zlib`` launch
 (yogo_amd/csrc/inflate.hip).  A chunk whose wrapper is not a plain zlib one is decoded on the host and copied as a raw row by
 ``yogo_blosc_lz4_decode``.  ``DEVICE_DECODE_ZLIB`` switches the route for this codec; it is off, because the host route measured
-faster (profiles/zarr_feed.log).  The decoders' launch wrappers and the iterator's skeleton are yogo_amd/device_decode.py's.
+faster (profiles/zarr_feed.log).
+
+Stacks compressed with Zstandard go to ``yogo_zstd_decode`` (yogo_amd/csrc/zstd.hip, yogo_amd/zstd.py) the same way: Blosc with
+``cname="zstd"`` with one table row per Blosc block (one frame each; raw blocks and memcpyed chunks as raw rows), the ``zstd`` codec
+with one row per chunk (``DEVICE_DECODE_ZSTD`` switches the route for this codec; it is off, because one serial chain per chunk
+lost to the host there as it did for zlib: profiles/zstd_feed.log).  The frames go in one launch, the raw rows in
+one ``yogo_blosc_lz4_decode`` launch behind it, as a zlib stack's do.  A chunk the device cannot take -- bit-shuffle,
+``typesize > 1``, a stored size above the slot -- is decoded on the host and enters as raw rows.  The decoders' launch wrappers and the iterator's skeleton are yogo_amd/device_decode.py's.
 """
 from __future__ import annotations
 
@@ -33,14 +40,17 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from yogo_amd import _hip, blosc, inflate
+from yogo_amd import _hip, blosc, inflate, zstd
 from yogo_amd.device_decode import ALIGN, MAX_THREADS, PrefetchFeed, center_crop_origin, decode_blocks, gather, inflate_streams, \
-    raise_first_bad, require_bytes
+    raise_first_bad, require_bytes, zstd_frames, zstd_work_bytes
 from yogo_amd.zarr_store import ChunkTooLong, ZarrArray, ZarrGroup
 
 RAW_PIECE = 1 << 16  # bytes of a raw block one wavefront of the device decoder copies (longer raw entries are cut up)
 DEVICE_DECODE_ZLIB = False  # True: stacks under the zlib codec are inflated on the device.  Off: at batch 256 the device route feeds
 #                             1.0-1.5 k img/s where the host's 16 threads feed 2.5-3.4 k (profiles/zarr_feed.log); PNG files do gain
+DEVICE_DECODE_ZSTD = False  # True: stacks under the zstd codec (ONE frame, so one wavefront, per chunk) are decoded on the device.  Off: at
+#                             batch 256 the device route feeds 2.5-3.6 k img/s of smooth-plus-noise frames where the host's 16 threads
+#                             (libzstd) feed 3.6-5.4 k (profiles/zstd_feed.log); Blosc-zstd stacks, several frames per chunk, do gain
 ZLIB_RAW = -1        # fifth field of a zlib store's entry that holds host-decoded bytes (an Adler-32 is never negative)
 
 
@@ -206,9 +216,11 @@ class ChunkStager:
                             return got, [(off, ln, 0, n, adler)]
                         except ValueError:
                             pass   # not a plain zlib wrapper: the host's to decode (or to refuse)
+                    elif codec == "zstd":
+                        return got, [(0, got, 0, n, 0)]   # one frame per chunk
                     else:
                         flags, entries = blosc.parse_chunk(out[:got], n)
-                        if blosc.device_decodable(flags):
+                        if (blosc.device_decodable_zstd if codec == "blosc-zstd" else blosc.device_decodable)(flags):
                             return got, entries
                 except (ChunkTooLong, NotImplementedError):
                     pass
@@ -296,7 +308,7 @@ class ZarrDeviceFeed(PrefetchFeed):
     RuntimeError (an unreadable chunk) costs that batch alone (device_decode.PrefetchFeed).  ``crop``: (OH, OW) of a centre crop
     done in the kernel; ``normalize``: fp32 ``/ 255`` in the kernel, else uint8.
     ``num_frames``: how many frames to walk (default: ``len(dataset)``, as the reference's DataLoader does, and never more
-    than the stack holds).  ``device_decode``: a Blosc stack with LZ4 blocks (and, with DEVICE_DECODE_ZLIB set, a zlib stack) is decoded on the device
+    than the stack holds).  ``device_decode``: a Blosc stack with LZ4 or zstd blocks (and, with DEVICE_DECODE_ZLIB / DEVICE_DECODE_ZSTD set, a zlib / zstd stack) is decoded on the device
     (module docstring); False takes the host route (A/B runs); every other source takes the host route whatever it says."""
 
     def __init__(self, dataset, batch_size: int, device, crop: Optional[Tuple[int, int]] = None, normalize: bool = False,
@@ -319,7 +331,9 @@ class ZarrDeviceFeed(PrefetchFeed):
         self._host = [p.numpy() for p in self._pinned]
         self._dev = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(2)]
         self.codec = src.first.device_codec
-        self.device_decode = bool(device_decode) and self.codec is not None and (self.codec != "zlib" or DEVICE_DECODE_ZLIB)
+        self.device_decode = bool(device_decode) and self.codec is not None and (self.codec != "zlib" or DEVICE_DECODE_ZLIB) \
+            and (self.codec != "zstd" or DEVICE_DECODE_ZSTD)
+        self._zwork: Optional[torch.Tensor] = None   # yogo_zstd_decode's workspace
         if self.device_decode:
             scap = src.max_chunks(self.batch_size) * src.stored_stride
             self._spinned = [torch.empty(scap, dtype=torch.uint8).pin_memory() for _ in range(2)]
@@ -351,7 +365,9 @@ class ZarrDeviceFeed(PrefetchFeed):
 
     def _decode(self, plan: BatchPlan, table: np.ndarray, slot: int) -> Tuple[Optional[torch.Tensor], int]:
         """(side stream) stored bytes and table up, one decode launch into the slot's device buffer (a zlib stack: one inflate launch,
-        and one of raw rows where a chunk was decoded on the host) -> (the per-row status, None without a launch; its inflate rows)"""
+        and one of raw rows where a chunk was decoded on the host; a zstd stack: one launch over the frames, and one of the raw rows
+        -- raw blocks, memcpyed and host-decoded chunks --, which need no workspace) -> (the per-row status, None without a launch;
+        how many rows the first launch took)"""
         if not len(table):
             return None, 0
         n_inflate = 0
@@ -362,10 +378,20 @@ class ZarrDeviceFeed(PrefetchFeed):
             table, n_inflate = table[order], int((~raw).sum())
             table[n_inflate:, 4] = 1
             plan.row_chunk = [plan.row_chunk[i] for i in order]
+        elif self.codec in ("blosc-zstd", "zstd"):
+            raw = table[:, 4] != 0
+            order = np.argsort(raw, kind="stable")
+            table, n_inflate = table[order], int((~raw).sum())
+            plan.row_chunk = [plan.row_chunk[i] for i in order]
         table_dev = torch.from_numpy(table).to(self.device)
         status = torch.empty(len(table), dtype=torch.int32, device=self.device)
-        if n_inflate:
+        if n_inflate and self.codec == "zlib":
             inflate_streams(self._sdev[slot], table_dev[:n_inflate], self._dev[slot], status[:n_inflate])
+        elif n_inflate:
+            need = zstd_work_bytes(n_inflate)
+            if self._zwork is None or self._zwork.numel() < need:   # (grows; the launches of both slots run on the side stream, in order)
+                self._zwork = torch.empty(need, dtype=torch.uint8, device=self.device)
+            zstd_frames(self._sdev[slot], table_dev[:n_inflate], self._dev[slot], status[:n_inflate], self._zwork)
         if n_inflate < len(table):
             decode_blocks(self._sdev[slot], table_dev[n_inflate:], self._dev[slot], status[n_inflate:])
         return status, n_inflate
@@ -400,7 +426,7 @@ class ZarrDeviceFeed(PrefetchFeed):
         if bad is not None and bool(bad.any()):
             self._last = None   # what a bad chunk left in the device buffer is not handed on
             names = [f"zarr store {plan.chunks[i][0].where}: chunk {plan.keys[i]!r}" for i in plan.row_chunk]
-            raise_first_bad(bad[:n_inflate], inflate.INF_STATUS, names.__getitem__)
+            raise_first_bad(bad[:n_inflate], inflate.INF_STATUS if self.codec == "zlib" else zstd.ZSTD_STATUS, names.__getitem__)
             raise_first_bad(bad[n_inflate:], blosc.LZ4_STATUS, names[n_inflate:].__getitem__)
         return plan, toff, tk, ev
 

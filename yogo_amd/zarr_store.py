@@ -12,7 +12,8 @@ after the compressor.  What `yogo infer --path-to-zarr` needs of it (yogo/data/i
 
 ``dtype`` must be ``|u1``; ``filters`` must be null; the compressors ``null`` / ``zlib`` / ``gzip`` / ``bz2`` come from the standard
 library, any other id goes through ``numcodecs.get_codec`` when numcodecs imports; without it ``blosc`` (zarr's default) is decoded
-by yogo_amd/blosc.py when its document is complete (``cname``, ``clevel``, ``shuffle``, ``blocksize``: what numcodecs writes)
+by yogo_amd/blosc.py when its document is complete (``cname``, ``clevel``, ``shuffle``, ``blocksize``: what numcodecs writes;
+``cname`` ``zstd`` included) and ``zstd`` by yogo_amd/zstd.py (libzstd through ctypes where it loads, else a pure-Python decoder),
 and everything else raises ``NotImplementedError``.
 A chunk that cannot be read or decoded raises ``RuntimeError`` naming its key -- the class `predict`'s loop tolerates.
 """
@@ -199,9 +200,15 @@ def _decoder(compressor: Optional[dict], where: str, chunk_nbytes: int) -> Optio
         import numcodecs
     except ImportError:
         if _blosc_document(compressor):
-            from yogo_amd import blosc
+            from yogo_amd import blosc, zstd
 
-            return lambda data: blosc.decompress(data, chunk_nbytes)
+            frame = zstd.frame_decoder() if compressor.get("cname") == "zstd" else None
+            return lambda data: blosc.decompress(data, chunk_nbytes, zstd=frame)
+        if cid == "zstd":
+            from yogo_amd import zstd
+
+            frame = zstd.frame_decoder()
+            return lambda data: frame(bytes(data), chunk_nbytes)
         raise NotImplementedError(f"zarr store {where}: compressor {cid!r} needs the numcodecs package, which is not installed "
                                   "(null, zlib, gzip and bz2 are read without it)") from None
     codec = numcodecs.get_codec(dict(compressor))
@@ -276,9 +283,15 @@ class ZarrArray:
     @property
     def device_codec(self) -> Optional[str]:
         """which device decoder the feed hands the stored chunks to: "blosc" (device_decodable), "zlib" (the zlib codec: one
-        stream per chunk for yogo_inflate_zlib), or None"""
+        stream per chunk for yogo_inflate_zlib), "blosc-zstd" (Blosc with one Zstandard frame per block, not bit-shuffled) or
+        "zstd" (the zstd codec: one frame per chunk), both for yogo_zstd_decode, or None"""
         if self.device_decodable:
             return "blosc"
+        c = self.compressor
+        if _blosc_document(c) and c.get("cname") == "zstd" and c.get("shuffle") in (0, 1):
+            return "blosc-zstd"
+        if c and c.get("id") == "zstd":
+            return "zstd"
         if self.compressor and self.compressor.get("id") == "zlib":
             return "zlib"
         return None
