@@ -67,7 +67,7 @@ def test_trns_is_not_prefill_decodable():
 
 
 def test_slot_layout_packs_without_overlap_at_align():
-    from yogo_amd.png_prefill import slot_layout
+    from yogo_amd.png_batch import slot_layout
     from yogo_amd.device_decode import ALIGN
 
     rng = np.random.default_rng(2)

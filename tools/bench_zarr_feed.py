@@ -165,14 +165,10 @@ def _chunk(args):
         if t * cn + j < n:
             block[:, :, j] = m[t * cn + j]
     raw = block.tobytes()
-    if compress == "blosc":
-        return t, blosc_lz4_frame(raw, blocksize)
-    if compress in ("blosc-zstd", "zstd"):
-        enc = blosc_zstd_frame(raw, blocksize) if compress == "blosc-zstd" else zstd_frame(raw)
-        if distinct and cn == 1:
-            _zstd_cache[(compress, t % distinct)] = enc
-        return t, enc
-    return t, (zlib.compress(raw, 1) if compress == "zlib" else raw)
+    enc = ENCODERS[compress](raw, blocksize)
+    if compress in ZSTD_WRITTEN and distinct and cn == 1:
+        _zstd_cache[(compress, t % distinct)] = enc
+    return t, enc
 
 
 def _spans(n, parts):
@@ -180,6 +176,9 @@ def _spans(n, parts):
     return [(lo, min(lo + step, n)) for lo in range(0, n, step)]
 
 
+ENCODERS = {"null": lambda raw, blocksize: raw, "zlib": lambda raw, blocksize: zlib.compress(raw, 1), "blosc": blosc_lz4_frame,
+            "blosc-zstd": blosc_zstd_frame, "zstd": lambda raw, blocksize: zstd_frame(raw)}   # one chunk's bytes as the store holds them
+ZSTD_WRITTEN = ("blosc-zstd", "zstd")   # the compressors whose frames zstd_writer() writes
 COMPRESSOR_DOCS = {"null": None, "zlib": {"id": "zlib", "level": 1},
                    "blosc": {"id": "blosc", "cname": "lz4", "clevel": 5, "shuffle": 1, "blocksize": 0},
                    "blosc-zstd": {"id": "blosc", "cname": "zstd", "clevel": ZSTD_LEVEL, "shuffle": 1, "blocksize": 0},
@@ -232,19 +231,18 @@ def step_feed(store: str, n: int, device_decode: bool = True, passes: int = 2) -
 
 
 def step_decode(store: str, n: int) -> dict:
-    """yogo_blosc_lz4_decode (a zlib store: yogo_inflate_zlib; a Blosc-zstd or zstd store: yogo_zstd_decode over the frames and
-    yogo_blosc_lz4_decode over the raw rows, as the feed launches them) alone on the rows of the first batch"""
+    """the decode launches of the store's codec alone (zarr_feed.decode_rows, as the feed makes them: yogo_blosc_lz4_decode;
+    yogo_inflate_zlib or yogo_zstd_decode with yogo_blosc_lz4_decode over the raw rows behind it) on the rows of the first batch"""
     import torch
 
-    from yogo_amd.device_decode import decode_blocks, inflate_streams, zstd_frames, zstd_work_bytes
-    from yogo_amd.zarr_feed import ChunkStager, FrameSource, plan_batch
+    from yogo_amd.device_decode import zstd_work_bytes
+    from yogo_amd.zarr_feed import CODECS, ChunkStager, FrameSource, decode_rows, plan_batch
     from yogo_amd.zarr_store import open_zarr
 
     src = FrameSource(open_zarr(store))
-    zlib_store = src.first.device_codec == "zlib"
-    zstd_store = src.first.device_codec in ("blosc-zstd", "zstd")
-    launches = 5 if zlib_store else 20
-    launch = inflate_streams if zlib_store else decode_blocks   # (zlib: one row per chunk, the fifth field its Adler-32)
+    codec = CODECS[src.first.device_codec]
+    serial = not codec.copies_raw and not codec.workspace   # (one wavefront per chunk and no more: the launches are long)
+    launches = 5 if serial else 20
     plan = plan_batch(src, 0, min(B, n))
     stager = ChunkStager(src)
     buf = np.zeros(len(plan.keys) * src.stored_stride, np.uint8)
@@ -252,33 +250,22 @@ def step_decode(store: str, n: int) -> dict:
         table = stager.stage_stored(plan, buf)
     finally:
         stager.close()
-    if zlib_store:
-        table = table[table[:, 4] >= 0]   # (a chunk that went the host way is no stream for the inflater)
+    raw = plan.row_raw
     stored = torch.from_numpy(buf).cuda()
     table_dev = torch.from_numpy(table).cuda()
     out = torch.empty(plan.nbytes, dtype=torch.uint8, device="cuda")
     status = torch.empty(len(table), dtype=torch.int32, device="cuda")
-    if zstd_store:
-        table = table[np.argsort(table[:, 4] != 0, kind="stable")]
-        nz = int((table[:, 4] == 0).sum())
-        table_dev = torch.from_numpy(table).cuda()
-        work = torch.empty(zstd_work_bytes(max(nz, 1)), dtype=torch.uint8, device="cuda")
-
-        def launch(stored, table_dev, out, status):   # noqa: F811
-            if nz:
-                zstd_frames(stored, table_dev[:nz], out, status[:nz], work)
-            if nz < len(table):
-                decode_blocks(stored, table_dev[nz:], out, status[nz:])
-    for _ in range(1 if zlib_store else 3):
-        launch(stored, table_dev, out, status)
+    work = torch.empty(zstd_work_bytes(max(len(raw) - int(raw.sum()), 1)), dtype=torch.uint8, device="cuda") if codec.workspace else None
+    for _ in range(1 if serial else 3):
+        decode_rows(codec, stored, table_dev, raw, out, status, work)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(launches + 1)]
     ev[0].record()
     for i in range(launches):
-        launch(stored, table_dev, out, status)
+        decode_rows(codec, stored, table_dev, raw, out, status, work)
         ev[i + 1].record()
     torch.cuda.synchronize()
     us = sorted(ev[i].elapsed_time(ev[i + 1]) * 1e3 for i in range(launches))
-    return {"median_us": us[launches // 2], "min_us": us[0], "blocks": int(len(table)), "raw_blocks": 0 if zlib_store else int(table[:, 4].sum()),
+    return {"median_us": us[launches // 2], "min_us": us[0], "blocks": int(len(table)), "raw_blocks": int(raw.sum()),
             "stored_bytes": int(table[:, 1].sum()), "decoded_bytes": int(table[:, 3].sum()), "all_ok": not bool(status.any()),
             "frames": int(plan.hi - plan.lo)}
 
@@ -458,7 +445,7 @@ def main() -> int:
         log("feed = ZarrDeviceFeed alone, images/s on the host clock, timed passes after a warm-up pass; predict = predict(count_predictions, "
             "half, device_outputs), host clock around the whole call (model load included); decode = the device decoder alone on the first "
             "batch, device events, median / min of 20 launches (zlib: 5)")
-        if any(c in ("blosc-zstd", "zstd") for c in a.compressors.split(",")):
+        if any(c in ZSTD_WRITTEN for c in a.compressors.split(",")):
             log(f"Zstandard frames written by {zstd_writer()} at level {ZSTD_LEVEL}; Blosc-zstd: one frame per block of {a.blocksize} bytes, a block stored "
                 f"raw when its frame is no shorter; --distinct {a.distinct}" + ("; compressors and routes walked in REVERSE order" if a.reverse else ""))
         ok = True

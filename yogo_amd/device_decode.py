@@ -1,8 +1,9 @@
 """What the routes that decode stored bytes on the device share -- zarr stacks (yogo_amd/zarr_feed.py), PNG directories for inference
-(yogo_amd/png_feed.py), the PNG prefill of the device image cache (yogo_amd/png_prefill.py): the launch wrappers of
+(yogo_amd/png_feed.py) and the PNG prefill of the device image cache (yogo_amd/png_prefill.py), both on yogo_amd/png_batch.py: the launch wrappers of
 ``yogo_blosc_lz4_decode``, ``yogo_zstd_decode``, ``yogo_inflate_zlib``, ``yogo_png_unpack``, ``yogo_png_unpack_planes``, ``yogo_png_unpack_any`` and ``yogo_resize_aa_u8`` (the
 prefill's resize of other-size files) with their tensor checks, ``gather`` (a pool's futures), ``raise_first_bad`` (a status vector -> RuntimeError), ``png_stream_into`` (one PNG file -> one zlib
-stream in its room of a pinned slot) and ``PrefetchFeed`` (the iterator that loads batch n + 1 while the caller works on batch n)."""
+stream in its room of a pinned slot), ``feed_device`` (the checks of the feeds' constructors) and ``PrefetchFeed`` (the iterator that
+loads batch n + 1 while the caller works on batch n)."""
 from __future__ import annotations
 
 from concurrent.futures import Future, ThreadPoolExecutor
@@ -22,6 +23,19 @@ def center_crop_origin(H: int, W: int, OH: int, OW: int) -> Tuple[int, int]:
     if OH > H or OW > W or OH < 1 or OW < 1:
         raise ValueError(f"crop {(OH, OW)} does not fit the image {(H, W)}")
     return int(round((H - OH) / 2.0)), int(round((W - OW) / 2.0))
+
+
+def feed_device(device, batch_size: int, what: str) -> torch.device:
+    """(the feeds' constructors) ``device`` as a torch.device with its index; RuntimeError where it is no MI355X device (``what``: "the
+    zarr feed unpacks"), ValueError for a batch size a launch's grid does not take"""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"yogo_amd: {what} on an MI355X device (got {dev}); there is no CPU fallback")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if batch_size < 1 or batch_size > 65535:
+        raise ValueError(f"batch size {batch_size} outside [1, 65535]")
+    return dev
 
 
 def require_bytes(who: str, what: str, *tensors: torch.Tensor) -> None:
@@ -50,20 +64,28 @@ def require_same_device(who: str, *tensors: torch.Tensor) -> None:
         raise ValueError(f"{who}: the tensors live on different devices")
 
 
-def _decode_rows(symbol: str, stored: torch.Tensor, table: torch.Tensor, out: torch.Tensor, status: torch.Tensor) -> None:
-    """one launch of a device decoder (`symbol`): the checks the two share"""
+def _decode_rows(symbol: str, stored: torch.Tensor, table: torch.Tensor, out: torch.Tensor, status: torch.Tensor,
+                 work: Optional[torch.Tensor] = None) -> None:
+    """one launch of a device decoder (`symbol`): the checks they share.  work: the workspace of a decoder that takes one"""
     what = symbol[len("yogo_"):]
-    for t, name in ((stored, "the stored chunk bytes"), (table, "the table"), (out, "the decoded chunks"), (status, "the status")):
+    extra = () if work is None else (work,)
+    for t, name in ((stored, "the stored chunk bytes"), (table, "the table"), (out, "the decoded chunks"), (status, "the status"),
+                    (work, "the workspace"))[:4 + len(extra)]:
         _hip.require_cuda(t, name)
-    require_bytes(what, "stored and out", stored, out)
+    require_bytes(what, "stored and out" if work is None else "stored, out and work", stored, out, *extra)
     n = int(table.shape[0])
     require_table(what, table, 5)
     require_status(what, status, n)
-    require_same_device(what, stored, table, out, status)
+    require_same_device(what, stored, table, out, status, *extra)
     if n == 0:
         return
+    if work is not None and work.numel() < zstd_work_bytes(n):
+        raise ValueError(f"{what}: a workspace of {work.numel()} bytes for {n} rows, {zstd_work_bytes(n)} needed")
     with torch.cuda.device(out.device):
-        _hip.call(symbol, stored, stored.numel(), table, n, out, out.numel(), status, _hip.stream_ptr())
+        if work is None:
+            _hip.call(symbol, stored, stored.numel(), table, n, out, out.numel(), status, _hip.stream_ptr())
+        else:
+            _hip.call(symbol, stored, stored.numel(), table, n, out, out.numel(), status, work, work.numel(), _hip.stream_ptr())
 
 
 def decode_blocks(stored: torch.Tensor, table: torch.Tensor, out: torch.Tensor, status: torch.Tensor) -> None:
@@ -88,21 +110,7 @@ def zstd_frames(stored: torch.Tensor, table: torch.Tensor, out: torch.Tensor, st
     """One ``yogo_zstd_decode`` launch on the current stream; as decode_blocks, rows (src_off, src_len, dst_off, dst_len, raw): one
     Zstandard frame each (a Blosc-zstd block, a chunk of the ``zstd`` codec), or raw bytes.  work: a 1-D uint8 device tensor of at
     least ``zstd_work_bytes(n)`` bytes (a block's Huffman-coded literals, per row)."""
-    what = "zstd_decode"
-    for t, name in ((stored, "the stored chunk bytes"), (table, "the table"), (out, "the decoded chunks"), (status, "the status"),
-                    (work, "the workspace")):
-        _hip.require_cuda(t, name)
-    require_bytes(what, "stored, out and work", stored, out, work)
-    n = int(table.shape[0])
-    require_table(what, table, 5)
-    require_status(what, status, n)
-    require_same_device(what, stored, table, out, status, work)
-    if n == 0:
-        return
-    if work.numel() < zstd_work_bytes(n):
-        raise ValueError(f"{what}: a workspace of {work.numel()} bytes for {n} rows, {zstd_work_bytes(n)} needed")
-    with torch.cuda.device(out.device):
-        _hip.call("yogo_zstd_decode", stored, stored.numel(), table, n, out, out.numel(), status, work, work.numel(), _hip.stream_ptr())
+    _decode_rows("yogo_zstd_decode", stored, table, out, status, work)
 
 
 def png_unpack(scan: torch.Tensor, table: torch.Tensor, image_hw: Tuple[int, int], out: torch.Tensor, status: torch.Tensor,

@@ -3,7 +3,7 @@
 A PNG file is an 8-byte signature and a sequence of chunks -- big-endian uint32 length, 4-byte type, the data, the CRC-32 of type
 and data.  IHDR comes first (width, height, bit depth, colour type, compression, filter, interlace), the IDAT chunks' data
 concatenated are ONE zlib stream of the filtered scanlines (``height`` rows of one filter-type byte and the row's bytes), IEND is
-last.  ``parse_png`` lists what yogo_amd/png_feed.py needs: the header fields and where the IDAT payloads lie, so that they are
+last.  ``parse_png`` lists what the device routes (yogo_amd/png_batch.py, for yogo_amd/png_feed.py and yogo_amd/png_prefill.py) need: the header fields and where the IDAT payloads lie, so that they are
 copied back to back into the staging buffer and the device sees one zlib stream (csrc/inflate.hip), whose inflated rows
 csrc/png_unpack.hip unfilters (csrc/png_unfilter.h).  Only 8-bit greyscale, non-interlaced files without transparency go that way
 (``PngInfo.device_decodable``); everything else is read by ``yogo_amd.yogo_dataset.read_image`` on the host.  The prefill of the

@@ -7,6 +7,9 @@ parse the sample's label rows; then, on a side stream: the slot goes up, ONE ``y
 wavefront per stream) inflates every image's scanlines, ONE ``yogo_png_unpack_planes`` launch (csrc/png_unpack_planes.hip on csrc/png_unfilter.h) reverses
 the filters and writes the planes straight into ``images[lo:hi]``, and the per-image statuses come back.  Two pinned slots: chunk
 n + 1 is read while chunk n decodes.  The chunk is independent of the training batch, so thousands of streams share a launch.
+The record of a file, the layouts of the slot and of the scanline buffer, the inflate launch and the unpack tables are
+yogo_amd/png_batch.py's, shared with the inference feed (yogo_amd/png_feed.py); what is the prefill's own is here: which files it
+accepts, the label rows, the resize groups, and the host decoder behind everything the device does not take or refuses.
 
 A slot is sized from the files' sizes, known by ``stat`` before anything is read (an IDAT payload is shorter than its file): every
 file has room at a multiple of ``ALIGN``, whatever the sizes of the files before it.
@@ -21,8 +24,8 @@ One divergence: a file that PIL rejects but this route accepts (a defect in a ch
 not on the host route, where it stays with the workers.  Files both accept give the same bytes.
 
 The scratch -- two pinned slots, the stored streams and the scanlines on the device -- lives only while ``fill`` runs and is NOT
-part of the cache budget: per chunk the files' bytes twice pinned, once on the device, and ``H * (1 + bpp * W)`` bytes of scanlines
-per image (``stats["scratch_device_bytes"]``, ``stats["scratch_pinned_bytes"]``).  torch's global RNG is not touched.
+part of the cache budget: per chunk the files' bytes twice pinned, once on the device, and what its stream inflates to
+(``PngInfo.inflated_bytes``) of scanlines per image (``stats["scratch_device_bytes"]``, ``stats["scratch_pinned_bytes"]``).  torch's global RNG is not touched.
 
 ``device_resize=True`` (``--device-image-resize``) keeps a device-decodable file of ANOTHER size on the device as well, as long as
 each axis scales down by at most ``resize.MAX_DOWNSCALE`` (up by anything): the files of a chunk are grouped by their size, a group is
@@ -44,13 +47,16 @@ from __future__ import annotations
 
 import os
 from concurrent.futures import ThreadPoolExecutor
-from typing import Dict, List, Optional, Sequence, Tuple
+from operator import attrgetter
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from yogo_amd import _hip, png
-from yogo_amd.device_decode import ALIGN, MAX_THREADS, inflate_streams, png_stream_into, png_unpack_any, png_unpack_planes, resize_aa
+from yogo_amd.device_decode import MAX_THREADS, png_unpack_any, png_unpack_planes, resize_aa
+from yogo_amd.png_batch import KIND_PLANAR, PngStream, _file_size, batch_layout, inflate_batch, read_stream, slot_layout, unpack_table, \
+    upload_host_parts
 from yogo_amd.resize import aa_taps, device_serves
 
 # images per decode chunk, from tools/bench_prefill.py's sweep (profiles/prefill_decode.log: 772 x 1032 frames, three runs per size):
@@ -58,8 +64,6 @@ from yogo_amd.resize import aa_taps, device_serves
 # (the host threads bound it) and the scratch decides: 1.45 GiB device + 1.38 GiB pinned at 1 024, 2.90 + 2.75 GiB at 2 048
 DEFAULT_DECODE_BATCH = 1024
 MAX_DECODE_BATCH = 65535
-KIND_GREY, KIND_PLANAR, KIND_RGB = 0, 1, 2
-SCAN_ALIGN = 16   # yogo_inflate_zlib asks for 16-byte aligned destinations
 
 
 def check_decode_batch(decode_batch: int) -> int:
@@ -69,29 +73,6 @@ def check_decode_batch(decode_batch: int) -> int:
     return n
 
 
-def slot_layout(sizes: Sequence[int]) -> Tuple[np.ndarray, int]:
-    """file sizes -> (where each file's room starts in a slot, the bytes the chunk takes): room i holds ``sizes[i]`` bytes and
-    starts on a multiple of ALIGN, the rooms in order and without overlap"""
-    rooms = (np.asarray(sizes, dtype=np.int64).reshape(-1) + (ALIGN - 1)) // ALIGN * ALIGN
-    offsets = np.zeros(len(rooms), dtype=np.int64)
-    if len(rooms) > 1:
-        offsets[1:] = np.cumsum(rooms[:-1])
-    return offsets, int(rooms.sum())
-
-
-class _Sample:
-    """what one sample of a chunk turned out to be: a zlib stream for the device (``stored`` bytes at the start of its room, the
-    DEFLATE range and Adler-32 inside them, ``bpp`` bytes per pixel, ``hw`` the file's size when it is not the cache's and the device
-    resizes it, else None) or a sample for the host decoder (``host``: ``pixels`` is what ``image_uint8`` gave, None when the file is
-    unreadable).  ``rows``: the label rows, or the exception their parsing raised.  With decode_all: ``need`` bytes the stream
-    inflates to, the format ``code`` of yogo_png_unpack_any's table, the ``palette`` (768 bytes) of a palette file."""
-    __slots__ = ("host", "stored", "deflate", "adler", "bpp", "hw", "pixels", "rows", "need", "code", "palette")
-
-    def __init__(self):
-        self.host, self.stored, self.deflate, self.adler, self.bpp, self.hw, self.pixels, self.rows = False, 0, (0, 0), 0, 1, None, None, None
-        self.need, self.code, self.palette = 0, None, None
-
-
 def _label_rows(ds, j: int):
     try:
         return ds.label_rows(j).reshape(-1, 5).to(torch.float32)
@@ -99,52 +80,33 @@ def _label_rows(ds, j: int):
         return e
 
 
-def _host_sample(s: _Sample, ds, j: int) -> _Sample:
-    s.host = True
-    s.pixels = ds.image_uint8(j)
-    if s.pixels is not None and s.rows is None:
-        s.rows = _label_rows(ds, j)
+def _host_sample(ds, j: int, rows=None) -> PngStream:
+    """the sample through ``ds.image_uint8`` (``pixels`` None: nothing can decode it); ``rows``: its label rows where they are parsed"""
+    s = PngStream(host=True, pixels=ds.image_uint8(j))
+    s.rows = _label_rows(ds, j) if s.pixels is not None and rows is None else rows
     return s
 
 
-def _read(ds, j: int, room: np.ndarray, image_hw: Tuple[int, int], device_resize: bool = False, decode_all: bool = False) -> _Sample:
+def _read(ds, j: int, room: np.ndarray, image_hw: Tuple[int, int], decodable: Callable[[png.PngInfo], bool] = attrgetter("prefill_decodable"),
+          device_resize: bool = False) -> PngStream:
     """(pool thread) one sample: its file's zlib stream into ``room`` (its bytes of the pinned slot) and its label rows, or its
-    pixels from the host decoder.  device_resize: a file of another size than ``image_hw`` stays on the device when the resize
-    kernel serves both of its scales; decode_all: every PNG format the device knows stays there"""
-    s = _Sample()
+    pixels from the host decoder.  decodable: the formats the chunk's unpack kernel takes; device_resize: a file of another size than
+    ``image_hw`` stays on the device when the resize kernel serves both of its scales"""
+    def accept(info: png.PngInfo) -> bool:
+        resized = (info.height, info.width) != tuple(image_hw)
+        return decodable(info) and (not resized or (device_resize and device_serves(info.height, image_hw[0]) and device_serves(info.width, image_hw[1])))
+
+    # the host decoder's: an unreadable file, another format under its name (png.NotPng), a PNG that does not parse or has no plain
+    # zlib wrapper, one the device does not take, one longer than its room (the file grew after its size was taken)
     try:
         with open(str(ds._image_paths[j]), "rb") as f:
             data = f.read()
-        info = png.parse_png(data)
-    except (OSError, ValueError):   # unreadable, another format under its name (png.NotPng), a PNG that does not parse
-        return _host_sample(s, ds, j)
-    if not (info.any_decodable if decode_all else info.prefill_decodable) or info.idat_bytes > len(room):
-        return _host_sample(s, ds, j)   # (longer than its room: the file grew after its size was taken)
-    if (info.height, info.width) != tuple(image_hw):
-        if not (device_resize and device_serves(info.height, image_hw[0]) and device_serves(info.width, image_hw[1])):
-            return _host_sample(s, ds, j)
-        s.hw = (int(info.height), int(info.width))
-    try:
-        s.stored, off, ln, s.adler = png_stream_into(data, info, room)
-    except ValueError:
-        return _host_sample(s, ds, j)
-    s.deflate, s.bpp = (off, ln), info.bytes_per_pixel
-    if decode_all:
-        s.need, s.code = info.inflated_bytes, info.format_code
-        s.palette = png.palette_table(data, info) if info.color_type == 3 else None
+        s = read_stream(data, room, accept)
+    except (OSError, ValueError):
+        return _host_sample(ds, j)
+    s.resize = s.hw != tuple(image_hw)
     s.rows = _label_rows(ds, j)
     return s
-
-
-def _kind(s: _Sample) -> int:
-    return KIND_RGB if s.bpp == 3 else KIND_GREY
-
-
-def _file_size(path: str) -> int:
-    try:
-        return os.stat(path).st_size
-    except OSError:
-        return 0
 
 
 def fill(images: torch.Tensor, samples: Sequence[Tuple[object, int]], decode_batch: int = DEFAULT_DECODE_BATCH,
@@ -163,6 +125,7 @@ def fill(images: torch.Tensor, samples: Sequence[Tuple[object, int]], decode_bat
     if len(samples) != N:
         raise ValueError(f"fill: {len(samples)} samples for {N} images")
     decode_batch = check_decode_batch(decode_batch)
+    decodable, unpack = (attrgetter("any_decodable"), png_unpack_any) if decode_all else (attrgetter("prefill_decodable"), png_unpack_planes)
     dev = images.device
     out: List[Optional[torch.Tensor]] = [None] * N
     if stats is not None:
@@ -181,10 +144,10 @@ def fill(images: torch.Tensor, samples: Sequence[Tuple[object, int]], decode_bat
         side.wait_stream(torch.cuda.current_stream(dev))
         images.record_stream(side)
 
-        def stage(n: int) -> List[_Sample]:
+        def stage(n: int) -> List[PngStream]:
             (lo, hi), (offsets, _) = chunks[n], layouts[n]
             host = pinned[n % 2].numpy()
-            futures = [pool.submit(_read, *samples[i], host[int(offsets[i - lo]):int(offsets[i - lo]) + sizes[i]], (H, W), device_resize, decode_all) for i in range(lo, hi)]
+            futures = [pool.submit(_read, *samples[i], host[int(offsets[i - lo]):int(offsets[i - lo]) + sizes[i]], (H, W), decodable, device_resize) for i in range(lo, hi)]
             return [f.result() for f in futures]
 
         with torch.cuda.device(dev), torch.cuda.stream(side):
@@ -196,7 +159,7 @@ def fill(images: torch.Tensor, samples: Sequence[Tuple[object, int]], decode_bat
                 chunk = pending.result()
                 if n + 1 < len(chunks):
                     pending = stager.submit(stage, n + 1)
-                scan, staging = _decode(chunk, samples[lo:hi], layouts[n], pinned[n % 2], sdev, scan, images[lo:hi], stats, decode_all)
+                scan, staging = _decode(chunk, samples[lo:hi], layouts[n], pinned[n % 2], sdev, scan, images[lo:hi], stats, unpack)
                 staged = max(staged, staging)
                 for i, s in enumerate(chunk):
                     if s.host and s.pixels is None:
@@ -214,79 +177,48 @@ def fill(images: torch.Tensor, samples: Sequence[Tuple[object, int]], decode_bat
     return out
 
 
-def _decode(chunk: List[_Sample], samples, layout, pinned: torch.Tensor, sdev: torch.Tensor, scan: Optional[torch.Tensor],
-            out: torch.Tensor, stats: Optional[Dict], decode_all: bool = False) -> Tuple[torch.Tensor, int]:
-    """one chunk on the current (side) stream: upload, inflate, unpack into ``out`` (the files of another size: into a staging tensor
-    per size, resized from there into ``out``), the statuses back; then whatever the device refused through the host decoder.
-    -> the scanline buffer (grown when this chunk needed more), the staging bytes this chunk took"""
+def _decode(chunk: List[PngStream], samples, layout, pinned: torch.Tensor, sdev: torch.Tensor, scan: Optional[torch.Tensor],
+            out: torch.Tensor, stats: Optional[Dict], unpack=png_unpack_planes) -> Tuple[torch.Tensor, int]:
+    """one chunk on the current (side) stream: upload, inflate, unpack into ``out`` with the launch wrapper ``unpack`` (the files of
+    another size: into a staging tensor per size, resized from there into ``out``), the statuses back; then whatever the device
+    refused through the host decoder.  -> the scanline buffer (grown when this chunk needed more), the staging bytes this chunk took"""
     offsets, _ = layout
     B, C, H, W = (int(v) for v in out.shape)
     dev = out.device
-    need = [C * H * W if s.host else s.need if decode_all else (s.hw or (H, W))[0] * (1 + s.bpp * (s.hw or (H, W))[1]) for s in chunk]
-    at = np.zeros(B + 1, dtype=np.int64)
-    at[1:] = np.cumsum([-(-v // SCAN_ALIGN) * SCAN_ALIGN for v in need])
-    # (decode_all) behind the last image the palettes of the chunk's palette files, 768 bytes each
-    with_palette = [i for i, s in enumerate(chunk) if not s.host and s.palette is not None]
-    palette_at = {i: int(at[B]) + k * png.PALETTE_BYTES for k, i in enumerate(with_palette)}
-    total = int(at[B]) + len(with_palette) * png.PALETTE_BYTES
-    if scan is None or scan.numel() < total:
+    # every image at its own inflated size; behind the last one the palettes of the chunk's palette files, 768 bytes each
+    where = batch_layout(chunk, C * H * W)
+    if scan is None or scan.numel() < where.total:
         scan = None   # (the smaller buffer goes back to the allocator first)
-        scan = torch.empty(total, dtype=torch.uint8, device=dev)
-    device_rows = [i for i, s in enumerate(chunk) if not s.host]
-    kept = [i for i, s in enumerate(chunk) if not (s.host and s.pixels is None)]
-    if not kept:
+        scan = torch.empty(where.total, dtype=torch.uint8, device=dev)
+    if all(s.host and s.pixels is None for s in chunk):
         return scan, 0
     timed = stats is not None
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timed else None
-    inflate_status = None
-    if device_rows:
-        last = device_rows[-1]
-        used = int(offsets[last]) + chunk[last].stored
-        sdev[:used].copy_(pinned[:used], non_blocking=True)
-        rows = np.asarray([(int(offsets[i]) + chunk[i].deflate[0], chunk[i].deflate[1], int(at[i]), need[i], chunk[i].adler)
-                           for i in device_rows], dtype=np.int64).reshape(-1, 5)
-        inflate_status = torch.empty(len(device_rows), dtype=torch.int32, device=dev)
-        if timed:
-            ev[0].record()
-        inflate_streams(sdev, torch.from_numpy(rows).to(dev), scan, inflate_status)
-        if timed:
-            ev[1].record()
+    inflate_status, device_rows = inflate_batch(chunk, offsets, where, pinned, sdev, scan, ev)
     for i, s in enumerate(chunk):
-        if s.host and s.pixels is not None:   # (rare: a pageable copy per image)
-            if tuple(s.pixels.shape) != (C, H, W):
-                raise ValueError(f"fill: {samples[i][0]._image_paths[samples[i][1]]} decodes to {tuple(s.pixels.shape)}, the cache holds {(C, H, W)}")
-            scan[int(at[i]):int(at[i]) + need[i]].copy_(s.pixels.contiguous().reshape(-1))
+        if s.pixels is not None and tuple(s.pixels.shape) != (C, H, W):
+            raise ValueError(f"fill: {samples[i][0]._image_paths[samples[i][1]]} decodes to {tuple(s.pixels.shape)}, the cache holds {(C, H, W)}")
+    upload_host_parts(chunk, where, scan)
     # a sample nothing could decode keeps its place in the launch as an entry the kernel refuses before it reads anything, and so
     # does a file of another size: its group's own launches follow
-    table = np.asarray([(int(at[i]), -1 if (s.host and s.pixels is None) or (not s.host and s.hw) else KIND_PLANAR if s.host else
-                         s.code if decode_all else _kind(s), palette_at.get(i, 0)) for i, s in enumerate(chunk)], dtype=np.int64).reshape(-1, 3)
+    refused = {i for i, s in enumerate(chunk) if s.resize or (s.host and s.pixels is None)}
+    table_dev = torch.from_numpy(unpack_table(unpack, chunk, where, refused=refused)).to(dev)
     status = torch.empty(B, dtype=torch.int32, device=dev)
-    if with_palette:   # one copy for the palettes of the chunk
-        scan[int(at[B]):total].copy_(torch.from_numpy(np.concatenate([chunk[i].palette for i in with_palette])))
-    table_dev = torch.from_numpy(np.ascontiguousarray(table if decode_all else table[:, :2])).to(dev)
     if timed:
         ev[2].record()
-    if decode_all:
-        png_unpack_any(scan, table_dev, (H, W), out, status)
-    else:
-        png_unpack_planes(scan, table_dev, (H, W), out, status)
+    unpack(scan, table_dev, (H, W), out, status)
     if timed:
         ev[3].record()
     groups: Dict[Tuple[int, int], List[int]] = {}
     for i in device_rows:
-        if chunk[i].hw:
+        if chunk[i].resize:
             groups.setdefault(chunk[i].hw, []).append(i)
     resized, staging = [], 0
     for (Hs, Ws), members in groups.items():
         stage = torch.empty((len(members), C, Hs, Ws), dtype=torch.uint8, device=dev)
         staging += stage.numel()
         gstatus = torch.empty(len(members), dtype=torch.int32, device=dev)
-        if decode_all:
-            gtable = np.asarray([(int(at[i]), chunk[i].code, palette_at.get(i, 0)) for i in members], dtype=np.int64).reshape(-1, 3)
-            png_unpack_any(scan, torch.from_numpy(gtable).to(dev), (Hs, Ws), stage, gstatus)
-        else:
-            gtable = np.asarray([(int(at[i]), _kind(chunk[i])) for i in members], dtype=np.int64).reshape(-1, 2)
-            png_unpack_planes(scan, torch.from_numpy(gtable).to(dev), (Hs, Ws), stage, gstatus)
+        unpack(scan, torch.from_numpy(unpack_table(unpack, chunk, where, rows=members)).to(dev), (Hs, Ws), stage, gstatus)
         gev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timed else None
         if timed:
             gev[0].record()
@@ -307,13 +239,13 @@ def _decode(chunk: List[_Sample], samples, layout, pinned: torch.Tensor, sdev: t
             stats["inflate_ms"].append(ev[0].elapsed_time(ev[1]))
         stats["unpack_ms"].append(ev[2].elapsed_time(ev[3]))
         stats["host_decoded"] += sum(1 for s in chunk if s.host)
-        stats["device_resized"] += sum(1 for i in device_rows if chunk[i].hw and not bad[i])
+        stats["device_resized"] += sum(1 for i in device_rows if chunk[i].resize and not bad[i])
     # what the device refused: the host decoder's turn (the kernel may have written part of the image: it is overwritten or,
     # where the host cannot read the file either, not resident)
     for i in device_rows:
         if not bad[i]:
             continue
-        s = _host_sample(chunk[i], *samples[i])
+        s = chunk[i] = _host_sample(*samples[i], rows=chunk[i].rows)
         if timed:
             stats["host_decoded"] += 1
         if s.pixels is None:

@@ -26,7 +26,14 @@ Stacks compressed with Zstandard go to ``yogo_zstd_decode`` (yogo_amd/csrc/zstd.
 with one row per chunk (``DEVICE_DECODE_ZSTD`` switches the route for this codec; it is off, because one serial chain per chunk
 lost to the host there as it did for zlib: profiles/zstd_feed.log).  The frames go in one launch, the raw rows in
 one ``yogo_blosc_lz4_decode`` launch behind it, as a zlib stack's do.  A chunk the device cannot take -- bit-shuffle,
-``typesize > 1``, a stored size above the slot -- is decoded on the host and enters as raw rows.  The decoders' launch wrappers and the iterator's skeleton are yogo_amd/device_decode.py's.
+``typesize > 1``, a stored size above the slot -- is decoded on the host and enters as raw rows.  The decoders' launch wrappers
+and the iterator's skeleton are yogo_amd/device_decode.py's.
+
+What differs between the four routes is one ``DeviceCodec`` record each in ``CODECS``, keyed by ``ZarrArray.device_codec``: how a
+chunk's stored bytes become table entries (or that the chunk is the host's), the launch wrapper and its status texts, whether the
+kernel copies raw rows itself, whether it takes a workspace, and which module constant switches the route.  Whether a row is raw
+is carried beside the table (``BatchPlan.row_raw``), not in it: the fifth field is what the row's decoder reads there and nothing
+else.  ``decode_rows`` makes the launches of a table -- for the feed, and for tools/bench_zarr_feed.py.
 """
 from __future__ import annotations
 
@@ -35,14 +42,14 @@ import threading
 from collections import Counter
 from concurrent.futures import Future, ThreadPoolExecutor
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple, Union
+from typing import Callable, Dict, List, Mapping, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
 
 from yogo_amd import _hip, blosc, inflate, zstd
-from yogo_amd.device_decode import ALIGN, MAX_THREADS, PrefetchFeed, center_crop_origin, decode_blocks, gather, inflate_streams, \
-    raise_first_bad, require_bytes, zstd_frames, zstd_work_bytes
+from yogo_amd.device_decode import ALIGN, MAX_THREADS, PrefetchFeed, center_crop_origin, decode_blocks, feed_device, gather, \
+    inflate_streams, raise_first_bad, require_bytes, zstd_frames, zstd_work_bytes
 from yogo_amd.zarr_store import ChunkTooLong, ZarrArray, ZarrGroup
 
 RAW_PIECE = 1 << 16  # bytes of a raw block one wavefront of the device decoder copies (longer raw entries are cut up)
@@ -51,7 +58,56 @@ DEVICE_DECODE_ZLIB = False  # True: stacks under the zlib codec are inflated on 
 DEVICE_DECODE_ZSTD = False  # True: stacks under the zstd codec (ONE frame, so one wavefront, per chunk) are decoded on the device.  Off: at
 #                             batch 256 the device route feeds 2.5-3.6 k img/s of smooth-plus-noise frames where the host's 16 threads
 #                             (libzstd) feed 3.6-5.4 k (profiles/zstd_feed.log); Blosc-zstd stacks, several frames per chunk, do gain
-ZLIB_RAW = -1        # fifth field of a zlib store's entry that holds host-decoded bytes (an Adler-32 is never negative)
+
+# one block of a stored chunk as its codec lists it: (src_off, src_len, dst_off, dst_len, the fifth field of the row its decoder reads
+# -- a raw flag, an Adler-32 --, whether the bytes are raw: copied, not decoded), offsets relative to the chunk's stored / decoded start
+Entry = Tuple[int, int, int, int, int, bool]
+
+
+def _blosc_entries(takes: Callable[[int], bool]) -> Callable[[np.ndarray, int], Optional[List[Entry]]]:
+    def entries(stored: np.ndarray, n: int) -> Optional[List[Entry]]:
+        """one entry per Blosc block (a memcpyed chunk: one raw entry); None where the chunk's flags are not the decoder's"""
+        flags, blocks = blosc.parse_chunk(stored, n)
+        return [b + (bool(b[4]),) for b in blocks] if takes(flags) else None
+    return entries
+
+
+def _zlib_entries(stored: np.ndarray, n: int) -> Optional[List[Entry]]:
+    """one stream per chunk, the fifth field its Adler-32; None where the wrapper is no plain zlib one: the host's to decode (or to refuse)"""
+    try:
+        off, ln, adler = inflate.split_zlib(stored)
+    except ValueError:
+        return None
+    return [(off, ln, 0, n, adler, False)]
+
+
+def _zstd_entries(stored: np.ndarray, n: int) -> Optional[List[Entry]]:
+    """one frame per chunk"""
+    return [(0, len(stored), 0, n, 0, False)]
+
+
+@dataclass(frozen=True)
+class DeviceCodec:
+    """One device route of the feed; ``CODECS`` keys them by ``ZarrArray.device_codec``."""
+    entries: Callable[[np.ndarray, int], Optional[List[Entry]]]   # (a chunk's stored bytes, chunk_nbytes) -> its blocks, or None: the
+    #                                                                host decodes the chunk; ValueError for a malformed chunk
+    launch: Callable[..., None]        # the decoder's launch wrapper (yogo_amd/device_decode.py)
+    status: Mapping[int, str]          # its status texts
+    copies_raw: bool = False           # its kernel copies raw rows itself, in the same launch; else they go to decode_blocks behind it
+    workspace: bool = False            # the launch takes yogo_zstd_decode's workspace
+    default_on: bool = True            # a store under this codec is decoded on the device unless the feed is told otherwise
+    switch: Optional[str] = None       # the constant of this module that says so when a feed is built (tests and tools set it)
+
+    def on(self) -> bool:
+        return self.default_on if self.switch is None else bool(globals()[self.switch])
+
+
+CODECS: Dict[str, DeviceCodec] = {
+    "blosc": DeviceCodec(_blosc_entries(blosc.device_decodable), decode_blocks, blosc.LZ4_STATUS, copies_raw=True),
+    "zlib": DeviceCodec(_zlib_entries, inflate_streams, inflate.INF_STATUS, default_on=DEVICE_DECODE_ZLIB, switch="DEVICE_DECODE_ZLIB"),
+    "blosc-zstd": DeviceCodec(_blosc_entries(blosc.device_decodable_zstd), zstd_frames, zstd.ZSTD_STATUS, workspace=True),
+    "zstd": DeviceCodec(_zstd_entries, zstd_frames, zstd.ZSTD_STATUS, workspace=True, default_on=DEVICE_DECODE_ZSTD, switch="DEVICE_DECODE_ZSTD"),
+}
 
 
 class FrameSource:
@@ -114,9 +170,9 @@ class BatchPlan:
     tile_off: np.ndarray                  # int64 [B, gh, gw], -1 where the key is absent from the store
     tile_k: np.ndarray                    # int32 [B]
     nbytes: int                           # bytes of the staging buffer in use
-    stored: Optional[Dict[str, Tuple[int, List[Tuple[int, int, int, int, int]]]]] = None   # device decode: key -> (stored bytes,
-    #                                       its block entries relative to the chunk's stored / decoded start)
+    stored: Optional[Dict[str, Tuple[int, List[Entry]]]] = None   # device decode: key -> (stored bytes, its block entries)
     row_chunk: Optional[List[int]] = None  # device decode: per row of the decoder's table, the index of its chunk in `keys`
+    row_raw: Optional[np.ndarray] = None   # ... and whether the row is raw bytes (bool [rows])
 
 
 def plan_batch(src: FrameSource, lo: int, hi: int) -> BatchPlan:
@@ -198,46 +254,38 @@ class ChunkStager:
             futures.append(self._pool.submit(self._read, arr, coords, buf[off:off + n]))
         gather(futures)
 
-    def _read_stored(self, arr: ZarrArray, coords: Tuple[int, ...], out: np.ndarray):
+    def _read_stored(self, arr: ZarrArray, coords: Tuple[int, ...], out: np.ndarray) -> Tuple[int, List[Entry]]:
         """the stored bytes of one chunk into ``out`` (stored_stride bytes) -> (bytes in use, block entries relative to the chunk).
         What the device cannot decode is decoded here and becomes one raw entry."""
         n = self.src.chunk_nbytes
         key = arr.chunk_key(coords)
         store = self._store(arr)
         a = arr.with_store(store)
-        codec = self.src.first.device_codec   # the table's fifth field is read by the STORE's codec: a group member under
-        try:                                   # another compressor than member 0's is decoded on the host, as before
-            if codec is not None and a.device_codec == codec:
+        name = self.src.first.device_codec   # the table's rows are read by the STORE's decoder: a group member under another
+        try:                                  # compressor than member 0's is decoded on the host, as before
+            if name is not None and a.device_codec == name:
                 try:
                     got = a.read_stored_into(coords, out)
-                    if codec == "zlib":
-                        try:
-                            off, ln, adler = inflate.split_zlib(out[:got])
-                            return got, [(off, ln, 0, n, adler)]
-                        except ValueError:
-                            pass   # not a plain zlib wrapper: the host's to decode (or to refuse)
-                    elif codec == "zstd":
-                        return got, [(0, got, 0, n, 0)]   # one frame per chunk
-                    else:
-                        flags, entries = blosc.parse_chunk(out[:got], n)
-                        if (blosc.device_decodable_zstd if codec == "blosc-zstd" else blosc.device_decodable)(flags):
-                            return got, entries
+                    entries = CODECS[name].entries(out[:got], n)
+                    if entries is not None:
+                        return got, entries
                 except (ChunkTooLong, NotImplementedError):
                     pass
                 except ValueError as e:
                     raise RuntimeError(f"zarr store {arr.where}: chunk {key!r} could not be decoded ({type(e).__name__}: {e})") from e
             a.read_chunk_into(coords, out[:n])
-            return n, [(0, n, 0, n, ZLIB_RAW if codec == "zlib" else 1)]
+            return n, [(0, n, 0, n, 1, True)]
         except KeyError:
             raise RuntimeError(f"zarr store {arr.where}: chunk {key!r} disappeared from the store") from None
 
     def stage_stored(self, plan: BatchPlan, buf: np.ndarray, prev: Optional[Tuple[BatchPlan, np.ndarray]] = None) -> np.ndarray:
         """(device decode) the STORED bytes of every chunk of ``plan`` at ``i * stored_stride`` in ``buf``; fills ``plan.stored``
-        and returns the decoder's table, int64 [blocks, 5]: (src_off, src_len, dst_off, dst_len, raw) with dst_off in the layout of
-        ``plan.offsets`` (a zlib store: one row per chunk, the fifth field its Adler-32, or ZLIB_RAW for host-decoded bytes).
-        Chunks that ``prev`` holds are copied from there; errors as in ``stage``."""
+        and returns the decoder's table, int64 [rows, 5]: (src_off, src_len, dst_off, dst_len, fifth) with dst_off in the layout of
+        ``plan.offsets``; fifth: what the row's decoder reads there -- the raw flag (1 for every raw row), a zlib stream's Adler-32.
+        ``plan.row_chunk`` / ``plan.row_raw`` say per row which chunk it belongs to and whether it is raw.  The rows are in the
+        order ``decode_rows`` launches them in: under a codec whose kernel does not copy raw rows, those come last.  Chunks that
+        ``prev`` holds are copied from there; errors as in ``stage``."""
         stride = self.src.stored_stride
-        zlib_store = self.src.first.device_codec == "zlib"
         plan.stored = {}
         pending: Dict[str, Future] = {}
         for i, (key, (arr, coords)) in enumerate(zip(plan.keys, plan.chunks)):
@@ -253,15 +301,35 @@ class ChunkStager:
         plan.stored.update(zip(pending, gather(list(pending.values()))))
         rows, owner = [], []
         for i, key in enumerate(plan.keys):
-            for so, sl, do, dl, fifth in plan.stored[key][1]:
-                raw = fifth == ZLIB_RAW if zlib_store else fifth
+            for so, sl, do, dl, fifth, raw in plan.stored[key][1]:
                 # a long raw entry (a memcpyed chunk, a chunk decoded on the host) goes to several wavefronts
                 for at in (range(0, sl, RAW_PIECE) if raw else (0,)):
                     ln = min(RAW_PIECE, sl - at) if raw else sl
-                    rows.append((i * stride + so + at, ln, plan.offsets[key] + do + at, ln if raw else dl, fifth))
+                    rows.append((i * stride + so + at, ln, plan.offsets[key] + do + at, ln if raw else dl, fifth, raw))
                     owner.append(i)
-        plan.row_chunk = owner
-        return np.asarray(rows, dtype=np.int64).reshape(-1, 5)
+        table = np.asarray(rows, dtype=np.int64).reshape(-1, 6)
+        if not CODECS[self.src.first.device_codec].copies_raw:
+            order = np.argsort(table[:, 5], kind="stable")
+            table, owner = table[order], [owner[i] for i in order]
+        plan.row_chunk, plan.row_raw = owner, table[:, 5] != 0
+        return np.ascontiguousarray(table[:, :5])
+
+
+def decode_rows(codec: DeviceCodec, stored: torch.Tensor, table: torch.Tensor, raw: np.ndarray, out: torch.Tensor, status: torch.Tensor,
+                work: Optional[torch.Tensor] = None) -> int:
+    """(current stream) the rows of ``ChunkStager.stage_stored`` decoded from ``stored`` into ``out``: table int64 [rows, 5] and
+    status int32 [rows] on the device, raw bool [rows] on the host (``plan.row_raw``).  Either the codec's kernel over all rows in
+    one launch, or -- a kernel that does not copy raw rows -- over the coded rows, and ``yogo_blosc_lz4_decode`` over the raw ones
+    behind them.  work: the workspace of a codec that takes one, ``zstd_work_bytes`` of the coded rows.  -> how many rows the
+    first launch took"""
+    first = len(raw) if codec.copies_raw else len(raw) - int(np.count_nonzero(raw))
+    if not codec.copies_raw and raw[:first].any():
+        raise ValueError("decode_rows: a raw row lies before a coded one")
+    if first:
+        codec.launch(stored, table[:first], out, status[:first], *((work,) if codec.workspace else ()))
+    if first < len(raw):
+        decode_blocks(stored, table[first:], out, status[first:])
+    return first
 
 
 def unpack(staged: torch.Tensor, tile_off: np.ndarray, tile_k: np.ndarray, *, chunks: Sequence[int], order_f: bool, fill: int,
@@ -313,13 +381,7 @@ class ZarrDeviceFeed(PrefetchFeed):
 
     def __init__(self, dataset, batch_size: int, device, crop: Optional[Tuple[int, int]] = None, normalize: bool = False,
                  num_frames: Optional[int] = None, device_decode: bool = True):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"yogo_amd: the zarr feed unpacks on an MI355X device (got {dev}); there is no CPU fallback")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        if batch_size < 1 or batch_size > 65535:
-            raise ValueError(f"batch size {batch_size} outside [1, 65535]")
+        dev = feed_device(device, batch_size, "the zarr feed unpacks")
         self.dataset, self.batch_size, self.device, self.normalize = dataset, int(batch_size), dev, bool(normalize)
         self.src = src = FrameSource(dataset.zarr_store)
         n = min(len(dataset) if num_frames is None else int(num_frames), src.num_frames)
@@ -331,8 +393,8 @@ class ZarrDeviceFeed(PrefetchFeed):
         self._host = [p.numpy() for p in self._pinned]
         self._dev = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(2)]
         self.codec = src.first.device_codec
-        self.device_decode = bool(device_decode) and self.codec is not None and (self.codec != "zlib" or DEVICE_DECODE_ZLIB) \
-            and (self.codec != "zstd" or DEVICE_DECODE_ZSTD)
+        self.route = CODECS.get(self.codec)
+        self.device_decode = bool(device_decode) and self.route is not None and self.route.on()
         self._zwork: Optional[torch.Tensor] = None   # yogo_zstd_decode's workspace
         if self.device_decode:
             scap = src.max_chunks(self.batch_size) * src.stored_stride
@@ -364,37 +426,20 @@ class ZarrDeviceFeed(PrefetchFeed):
             self._sdev[slot][a:b].copy_(self._spinned[slot][a:b], non_blocking=True)
 
     def _decode(self, plan: BatchPlan, table: np.ndarray, slot: int) -> Tuple[Optional[torch.Tensor], int]:
-        """(side stream) stored bytes and table up, one decode launch into the slot's device buffer (a zlib stack: one inflate launch,
-        and one of raw rows where a chunk was decoded on the host; a zstd stack: one launch over the frames, and one of the raw rows
-        -- raw blocks, memcpyed and host-decoded chunks --, which need no workspace) -> (the per-row status, None without a launch;
-        how many rows the first launch took)"""
+        """(side stream) stored bytes and table up, the rows decoded into the slot's device buffer (``decode_rows``: one launch, and
+        one of the raw rows -- raw blocks, memcpyed and host-decoded chunks -- where the codec's kernel does not copy them)
+        -> (the per-row status, None without a launch; how many rows the first launch took)"""
         if not len(table):
             return None, 0
-        n_inflate = 0
         self._upload_stored(plan, slot)
-        if self.codec == "zlib":   # host-decoded chunks are copied by the Blosc decoder's raw rows, behind the inflate rows
-            raw = table[:, 4] == ZLIB_RAW
-            order = np.argsort(raw, kind="stable")
-            table, n_inflate = table[order], int((~raw).sum())
-            table[n_inflate:, 4] = 1
-            plan.row_chunk = [plan.row_chunk[i] for i in order]
-        elif self.codec in ("blosc-zstd", "zstd"):
-            raw = table[:, 4] != 0
-            order = np.argsort(raw, kind="stable")
-            table, n_inflate = table[order], int((~raw).sum())
-            plan.row_chunk = [plan.row_chunk[i] for i in order]
-        table_dev = torch.from_numpy(table).to(self.device)
+        coded = len(table) - int(np.count_nonzero(plan.row_raw))
+        if self.route.workspace and coded and (self._zwork is None or self._zwork.numel() < zstd_work_bytes(coded)):
+            self._zwork = torch.empty(zstd_work_bytes(coded), dtype=torch.uint8, device=self.device)   # (grows; the launches of both
+            #                                                                     slots run on the side stream, in order)
         status = torch.empty(len(table), dtype=torch.int32, device=self.device)
-        if n_inflate and self.codec == "zlib":
-            inflate_streams(self._sdev[slot], table_dev[:n_inflate], self._dev[slot], status[:n_inflate])
-        elif n_inflate:
-            need = zstd_work_bytes(n_inflate)
-            if self._zwork is None or self._zwork.numel() < need:   # (grows; the launches of both slots run on the side stream, in order)
-                self._zwork = torch.empty(need, dtype=torch.uint8, device=self.device)
-            zstd_frames(self._sdev[slot], table_dev[:n_inflate], self._dev[slot], status[:n_inflate], self._zwork)
-        if n_inflate < len(table):
-            decode_blocks(self._sdev[slot], table_dev[n_inflate:], self._dev[slot], status[n_inflate:])
-        return status, n_inflate
+        first = decode_rows(self.route, self._sdev[slot], torch.from_numpy(table).to(self.device), plan.row_raw, self._dev[slot], status,
+                            self._zwork)
+        return status, first
 
     def _load(self, n: int):
         """(loader thread) stage batch n and start its upload on the side stream; through the device decoder: the stored bytes are
@@ -426,7 +471,7 @@ class ZarrDeviceFeed(PrefetchFeed):
         if bad is not None and bool(bad.any()):
             self._last = None   # what a bad chunk left in the device buffer is not handed on
             names = [f"zarr store {plan.chunks[i][0].where}: chunk {plan.keys[i]!r}" for i in plan.row_chunk]
-            raise_first_bad(bad[:n_inflate], inflate.INF_STATUS if self.codec == "zlib" else zstd.ZSTD_STATUS, names.__getitem__)
+            raise_first_bad(bad[:n_inflate], self.route.status, names.__getitem__)
             raise_first_bad(bad[n_inflate:], blosc.LZ4_STATUS, names[n_inflate:].__getitem__)
         return plan, toff, tk, ev
 
