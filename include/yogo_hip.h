@@ -234,7 +234,8 @@ int yogo_conv2d_fwd_bf16_stats_shape(int B, int Cin, int Cout, int IH, int IW, i
  * compute, 4 load / store), everything else on the tiled conv_bf16_kernel.  The two families agree bit for bit where the tiled plan
  * also steps the contraction in 16-channel chunks (every shape of the training step), within one bf16 ulp otherwise.  The library has
  * no run-time plan switch and no mutable global state besides its lazily-loaded module handles and the launch log: the A/B switches
- * used by tests/ and tools/ (yogo_hook_*) exist only in libyogo_hip_hooks.so (build.sh, -DYOGO_TEST_HOOKS), which the package never loads. */
+ * used by tests/ and tools/ (yogo_hook_*) exist only in libyogo_hip_hooks.so, which the package never loads: the product's object files
+ * with the one host-only unit that owns every plan switch (csrc/plan_switches.hip) compiled under -DYOGO_TEST_HOOKS (build.sh). */
 /* y = chan_scale * act(conv(x) + bias); out: bf16 NCHW8c, or fp32 NCHW when out_f32 != NULL (the head);
  * stats_part (optional): BatchNorm partial (sum, sumsq) of the fp32 pre-activation */
 int yogo_conv2d_fwd_bf16(const void* in, const void* packed, const float* bias, void* out, float* out_f32,

@@ -646,7 +646,7 @@ def cosine_lr(step: int, base_lr: float, t_max: int, eta_min: float) -> float:
 # every gradient by ~1 %).  This function restates the SAME arithmetic as `yogo_forward` + `yogo_loss` + autograd, but
 # rounds to bf16 exactly where the HIP path stores bf16 -- so the whole step can be held to ~1e-3, and a kernel error of
 # a few per cent is no longer hidden behind "bf16 noise".  Rounding points (file:kernel of yogo_amd/csrc):
-#   * weights multiplied as bf16 (conv_bf16.hip:conv_bf16_pack_kernel; layer 0: conv_first_mfma.hip `wa`)
+#   * weights multiplied as bf16 (conv_bf16_pack.hip:conv_bf16_pack_kernel; layer 0: conv_first_mfma.hip `wa`)
 #   * block without BatchNorm: y = bf16(act(conv + bias) * mask); LeakyReLU sign taken from that value (sign map / stored y)
 #   * block with BatchNorm: z = bf16(conv + bias); batch statistics of the STORED z (layer 0 on the matrix cores: of the
 #     unrounded convolution, from the exact patch Gram matrix); y = bf16(act(z * sc + sh)), sc = invstd * gamma,
@@ -731,14 +731,14 @@ def bf16_block_forward(i: int, x_in: torch.Tensor, sd: Dict[str, torch.Tensor], 
 # every layer can be held to one bf16 ulp given its actual input (tests/_util.py: teacher_forced_infer_check).  Rounding points:
 #   * scale = gamma / sqrt(running_var + eps), bias' = beta + (bias_or_0 - running_mean) * scale, fp32, in that order of operations
 #     (engine.py: InferEngineBF16._prepare)
-#   * layers >= 1: weights bf16(w * scale) -- one fp32 product, one rounding (conv_bf16.hip: conv_bf16_pack_kernel, `w[...] * sc`
-#     then `(__bf16)v`); fp32 accumulation; y = bf16(act(conv + bias')) (the lean / merged epilogues of conv_bf16.hip: conv_bf16_kernel,
+#   * layers >= 1: weights bf16(w * scale) -- one fp32 product, one rounding (conv_bf16_pack.hip: conv_bf16_pack_kernel, `w[...] * sc`
+#     then `(__bf16)v`); fp32 accumulation; y = bf16(act(conv + bias')) (the lean / merged epilogues of conv_bf16_tiled.hip: conv_bf16_kernel,
 #     conv_bf16_ws.hip, conv_bf16_ws3.hip, conv_bf16_staged.hip)
 #   * layer 0 on the matrix cores: the folded fp32 weights w * scale are rounded to bf16 by the kernel (conv_first_mfma.hip:
 #     conv_first_mfma2_kernel `wa`); 8-bit pixels are exact in bf16, every product and the sum of nine are exact in fp32;
 #     z = bf16(act(sum + bias')) (its `p.y == nullptr` branch)
 #   * layer 0 on the direct kernel (odd sizes, rgb or float input): the folded fp32 weights UNROUNDED in an fp32 fma chain, then
-#     bf16(act(acc + bias')) (conv_bf16.hip: conv_first_bf16_kernel)
+#     bf16(act(acc + bias')) (conv_first_infer_bf16.hip: conv_first_bf16_kernel)
 #   * last layer: fp32 output, no rounding (conv_bf16_head.hip: conv_bf16_1x1_f32_kernel; conv_bf16_kernel with F32 = true)
 #   * a block without BatchNorm: as in training's emulation (bf16(w), bias unchanged), without dropout mask and without sign map
 # ---------------------------------------------------------------------------

@@ -524,9 +524,10 @@ def teacher_forced_both_plans(O, run_step, x, lab, spec, sd0, what):
 
 
 # ---- the test-hooks library ------------------------------------------------------------------------------------------------------
-# libyogo_hip_hooks.so (yogo_amd/csrc/build.sh) = the product's objects with the three files that own a plan choice recompiled under
-# -DYOGO_TEST_HOOKS: the same kernels plus yogo_hook_conv_bf16_persistent / yogo_hook_conv_first_mfma_pairs /
-# yogo_hook_conv_first_bn_wgrad_pairs / yogo_hook_conv_bf16_direct (0 = the tiled kernel in place of the direct stride-2 data gradients).
+# libyogo_hip_hooks.so (yogo_amd/csrc/build.sh) = the product's object files -- every kernel is the very object the product links -- with
+# plan_switches.o (host code only: the accessor of every plan switch) compiled under -DYOGO_TEST_HOOKS, which turns the switches into
+# variables with setters: yogo_hook_conv_bf16_persistent / _ws16 / _direct (0 = the tiled kernel in place of the direct stride-2 data
+# gradients) / _staged / _head, yogo_hook_conv_first_mfma_pairs, yogo_hook_conv_first_bn_wgrad_pairs.
 # The product library has no such switch (no mutable global state); A/B and bit-identity tests bind the hooks library in place of the
 # product's for their duration.
 @contextlib.contextmanager

@@ -13,8 +13,9 @@ Per case (the smallest shapes that reach the inference kernels; tests/golden/lau
 Kernel coverage: the union of the cases' convolution launches holds every conv_bf16* / conv_first* entry of the newest committed
 profile of the batch-256 inference path (profiles/r*_infer_kernel_stats.txt) -- the small shapes reach every member, none is excused.
 
-Then two entry points no other test calls in this form: yogo_conv_bf16_pack WITH a scale (training never passes one), and the direct
-layer-0 kernel yogo_conv_first_fwd_bf16 alone against float64 with a derived bound."""
+Then entry points no other test calls in this form: yogo_conv_bf16_pack WITH a scale (training never passes one), the bytes of
+yogo_conv_bf16_pack and yogo_conv_bf16_pack_multi against a numpy packing of the documented layout, and the direct layer-0 kernel
+yogo_conv_first_fwd_bf16 alone against float64 with a derived bound."""
 import glob
 import os
 import re
@@ -205,6 +206,67 @@ def test_pack_with_a_scale_is_the_pack_of_the_scaled_weights(Cin, Cout, k):
     assert not torch.equal(a, pack(w, None, 0))   # (the scale does reach the kernel)
     for mode in (1, 2) if k == 3 else (1,):
         assert torch.equal(pack(w, scale, mode), pack(w, None, mode)), mode
+
+
+# ---- the two packing kernels write one layout ---------------------------------------------------------------------------------------
+# (Cin, Cout, ks, mode): channel counts 7 and 12 are padded to 16 contraction channels / 32 GEMM rows; 128 -> 7 has Mpad = 32 (one
+# 32-row tile) against Kb = 16 channel blocks; mode 2 stores the taps in the parity-class order of the stride-2 data gradient
+PACK_CASES = ((16, 32, 3, 0), (32, 16, 3, 1), (64, 128, 3, 2), (128, 7, 1, 0), (12, 7, 1, 1), (7, 12, 3, 0))
+
+
+def _pack_numpy(w, scale, ks, mode):
+    """the layout comment of conv_bf16_pack.hip: [T][Kb][Mpad] units of 8 contraction channels of one GEMM row; mode 0: k = ci, m = co,
+    weights times scale[co]; modes 1 / 2: k = co, m = ci, taps flipped; mode 2: slice t holds tap nibble t of 0x862071534; zero padding"""
+    import numpy as np
+
+    Cout, Cin = w.shape[:2]
+    Kc, Mc = (Cout, Cin) if mode else (Cin, Cout)
+    Kb = (Kc + 15) // 16 * 2
+    tile = 32 * (1 if Mc <= 32 else 2 if Mc <= 64 else 4)
+    Mpad = (Mc + tile - 1) // tile * tile
+    T = ks * ks
+    full = np.zeros((T, Kb * 8, Mpad), dtype=np.float32)
+    for t in range(T):
+        ts = (0x862071534 >> (4 * t)) & 15 if mode == 2 else t
+        tt = T - 1 - ts if mode else ts
+        tap = w[:, :, tt // ks, tt % ks]   # [co][ci]
+        if mode:
+            full[t, :Cout, :Cin] = tap
+        else:
+            full[t, :Cin, :Cout] = (tap * scale[:, None] if scale is not None else tap).T
+    units = np.ascontiguousarray(full.reshape(T, Kb, 8, Mpad).transpose(0, 1, 3, 2))
+    u = units.view(np.uint32)
+    bf = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype("<u2")   # round to nearest even (finite values)
+    return bf.tobytes()
+
+
+@pytest.mark.parametrize("scaled", [False, True])
+def test_pack_multi_and_pack_write_the_layout_of_the_comment(scaled):
+    """yogo_conv_bf16_pack_multi for a table of all the cases == one yogo_conv_bf16_pack per case == the numpy packing, byte for byte
+    (scaled: the mode-0 cases take a per-output-channel scale)"""
+    from yogo_amd import _hip
+
+    st = _hip.stream_ptr()
+    g = torch.Generator().manual_seed(7)
+    ws, scs, singles, multis, rows, blk = [], [], [], [], [], 0
+    for Cin, Cout, ks, mode in PACK_CASES:
+        w = (torch.randn(Cout, Cin, ks, ks, generator=g) * 0.1).cuda()
+        sc = (torch.randn(Cout, generator=g) + 2.0).cuda() if scaled and mode == 0 else None
+        nbytes = _hip.query_size("yogo_conv_bf16_packed_bytes", Cin, Cout, ks, mode)
+        one = torch.full((nbytes,), 0xAB, dtype=torch.uint8, device="cuda")
+        _hip.call("yogo_conv_bf16_pack", w, sc, one, Cin, Cout, ks, mode, st)
+        multi = torch.full((nbytes,), 0xCD, dtype=torch.uint8, device="cuda")
+        rows.append([w.data_ptr(), sc.data_ptr() if sc is not None else 0, multi.data_ptr(), Cin, Cout, ks, mode, blk])
+        blk += _hip.query_ints("yogo_conv_bf16_pack_blocks", 1, Cin, Cout, ks, mode)[0]
+        ws.append(w); scs.append(sc); singles.append(one); multis.append(multi)
+    table = torch.tensor(rows, dtype=torch.int64, device="cuda")
+    _hip.call("yogo_conv_bf16_pack_multi", table, len(rows), blk, st)
+    torch.cuda.synchronize()
+    for case, w, sc, one, multi in zip(PACK_CASES, ws, scs, singles, multis):
+        want = _pack_numpy(w.cpu().numpy(), sc.cpu().numpy() if sc is not None else None, case[2], case[3])
+        assert len(want) == one.numel(), (case, len(want), one.numel())
+        assert one.cpu().numpy().tobytes() == want, (case, "yogo_conv_bf16_pack")
+        assert multi.cpu().numpy().tobytes() == want, (case, "yogo_conv_bf16_pack_multi")
 
 
 # ---- yogo_conv_first_fwd_bf16 alone -----------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-// The channel-group loop of conv_bf16_kernel's bf16 epilogue (included by conv_bf16.hip inside the kernel body, with MODE in
+// The channel-group loop of conv_bf16_kernel's bf16 epilogue (included by conv_bf16_tiled.hip inside the kernel body, with MODE in
 // scope: 0 = lean order of operations, 1 = general, 2 = both behind a run-time test).  A fragment, not a translation unit.
 #pragma unroll
     for (int mb = 0; mb < MW; ++mb) {

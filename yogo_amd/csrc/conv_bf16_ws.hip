@@ -1,7 +1,7 @@
 // Persistent, wavefront-specialised bf16 convolution for the stride-1 3x3 layers with 128 output channels (forward of layers
 // 3/5/6 and the data gradients of layers 5/6 of base_model: yogo/model_defns.py:49-65 and their autograd) -- the dominant kernel
 // of the training step.  Same arithmetic, accumulation order and epilogue formula as conv_bf16_kernel<4,2,8,...,PP>
-// (conv_bf16.hip): outputs are bit-identical (tests/test_gpu_ws.py).
+// (conv_bf16_tiled.hip): outputs are bit-identical (tests/test_gpu_ws.py).
 //
 // Why this shape.  Measured on the first persistent form (4 wavefronts of 128 x 96 outputs with 192 AGPR accumulators, one per
 // SIMD, everything issued from the MFMA wavefronts; round 4, gpurun_out/r4_p4_stamps1.log): parity-green and exactly as fast

@@ -6,6 +6,7 @@
 // image at 772x1032): a direct VALU kernel, one output pixel per lane (coalesced NCHW stores per channel),
 // weights through the scalar cache, BatchNorm partial sums carried in registers across the thread's pixels.
 #include "common.h"
+#include "plan_switches.h"
 
 #define CF_THREADS 256
 #define CF_PPT 4       // pixels per thread
@@ -976,16 +977,6 @@ extern "C" int yogo_conv_first_bn_wgrad_bf16_xg(const void* in, int in_dtype, co
   return conv_first_bn_wgrad_impl(in, in_dtype, g, z, nullptr, mean, invstd, gamma, beta, part, B, Cin, Cout, IH, IW, stride, act, 1, stream);
 }
 extern "C" int yogo_conv_first_mfma_supported(int in_dtype, int Cin, int Cout, int IH, int IW, int stride);   // conv_first_mfma.hip
-// the sign-map sweep takes two pixels per lane where the output width is even; a switch only in the test-hooks / diagnostic builds
-#if defined(YOGO_TEST_HOOKS) || defined(YOGO_DIAG)
-static bool g_cf_pairs = true;
-extern "C" int yogo_hook_conv_first_bn_wgrad_pairs(int on) {
-  g_cf_pairs = on != 0;
-  return YOGO_OK;
-}
-#else
-static constexpr bool g_cf_pairs = true;
-#endif
 // 1 when the sweep can run WITHOUT the saved conv output: from the sign map of yogo_conv_first_mfma_signs (uint8 one-channel image,
 // stride 2, even sizes, Cout = 8 or 16, no activation or LeakyReLU, no conv bias, caller-held Gram matrix)
 static bool conv_first_fast_shape(int in_dtype, int Cin, int IH, int IW, int stride) {
@@ -1020,7 +1011,7 @@ static int conv_first_bn_wgrad_impl(const void* in, int in_dtype, const void* g,
   dim3 grid(first_wgrad_tiles(p.OH, p.OW), B);
   const bool fast = conv_first_fast_shape(in_dtype, Cin, IH, IW, stride);
   p.m_ow2 = p.OW >= 4 ? (unsigned)(((1ull << 32) + (unsigned)(p.OW / 2) - 1ull) / (unsigned)(p.OW / 2)) : 0u;
-  if (z == nullptr && p.OW % 2 == 0 && p.OW >= 4 && p.m_ow != 0 && g_cf_pairs)   // (yogo_conv_first_bn_wgrad_bf16_xs checked the shape)
+  if (z == nullptr && p.OW % 2 == 0 && p.OW >= 4 && p.m_ow != 0 && plan_first_bn_wgrad_pairs())   // (yogo_conv_first_bn_wgrad_bf16_xs checked the shape)
     hipLaunchKernelGGL(conv_first_bn_wgrad_pk2_kernel, grid, dim3(CF_THREADS), 0, stream, p);
   else if (z == nullptr)
     hipLaunchKernelGGL(conv_first_bn_wgrad_pk_kernel<true>, grid, dim3(CF_THREADS), 0, stream, p);

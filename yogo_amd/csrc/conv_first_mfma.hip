@@ -15,6 +15,7 @@
 // z (saved for backward) and y = act(BN(z)) (the next layer's input) -- 0.1 + 0.1 GB read and 1.6 GB written per 128 images
 // where conv + separate BatchNorm apply read 0.9 GB and wrote 1.6 GB.
 #include "bf16_dev.h"
+#include "plan_switches.h"
 #ifndef CFM_ST_AUX
 #define CFM_ST_AUX 2   // non-temporal y / z stores of the pair kernel: 0.243 -> 0.211 ms in the same-box A/B (gpurun_out/r5_nt_ab5.log; A/B variant builds: 0 = cached)
 #endif
@@ -582,16 +583,6 @@ extern "C" int yogo_conv_first_mfma_stats_rows(int B, int IH, int IW, int* rows)
 //   stats_part: partial (sum, sumsq) of conv + bias (fp32, before rounding) -> yogo_bn_finalize(part, rows, 16, ...)
 //   z: conv + bias in bf16 NCHW8c;  y: act((z - mean) * invstd * gamma + beta) in bf16 NCHW8c (needs mean/invstd/gamma/beta);
 //   without y the activation goes onto z (inference with BatchNorm folded into w and bias): z = act(conv + bias)
-// two pixels per lane where the output width is even; a switch only in the test-hooks / diagnostic builds (see conv_bf16.hip)
-#if defined(YOGO_TEST_HOOKS) || defined(YOGO_DIAG)
-static bool g_cfm_pairs = true;
-extern "C" int yogo_hook_conv_first_mfma_pairs(int on) {
-  g_cfm_pairs = on != 0;
-  return YOGO_OK;
-}
-#else
-static constexpr bool g_cfm_pairs = true;
-#endif
 static int conv_first_mfma_impl(const void* in, const float* w, const float* bias, void* z, void* y, void* signs, const float* mean,
                                const float* invstd, const float* gamma, const float* beta, float* stats_part, int B, int Cout,
                                int IH, int IW, int act, hipStream_t stream);
@@ -625,7 +616,7 @@ static int conv_first_mfma_impl(const void* in, const float* w, const float* bia
   p.m_ow = cfm_magic(p.OW);
   YOGO_CHECK_ARG((long long)p.total * 32 < (1ll << 31) && (long long)p.OH * p.OW * p.OW < (1ll << 32), "conv_first_mfma: batch / image too large");
   // the sweeps that write tensors (training: y [+ z] [+ sign map]; inference: z = act(conv + bias)) at an even output width: two pixels per lane
-  const bool pairs = g_cfm_pairs && (y != nullptr || z != nullptr) && stats_part == nullptr && p.OW % 2 == 0 && p.OW >= 4;
+  const bool pairs = plan_first_mfma_pairs() && (y != nullptr || z != nullptr) && stats_part == nullptr && p.OW % 2 == 0 && p.OW >= 4;
   if (pairs)
     hipLaunchKernelGGL(conv_first_mfma2_kernel, dim3(cfm_grid(B * cdiv(p.OH * p.OW, 64))), dim3(256), 0, stream, p);
   else
