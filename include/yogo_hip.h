@@ -588,6 +588,42 @@ int yogo_png_unpack_any(unsigned char* scan, long long scan_bytes, const long lo
 int yogo_resize_aa_u8(const unsigned char* src, int n, int C, int Hs, int Ws, unsigned char* dst, int N, int Hd, int Wd,
                       const void* tables_host, const void* tables_dev, int Ky, int Kx, yogo_stream_t stream);
 
+/* ---- drawn boxes and their PNG files (yogo_amd/draw.py, `yogo infer --draw-boxes --device-draw`) --------------------------------
+ * yogo_draw_boxes: the RGBA frames yogo_amd.utils.utils.draw_yogo_prediction makes PIL draw, for a whole batch in one launch, pixel
+ * for pixel (tests/_draw_ref.py is the same arithmetic in numpy, held to PIL).  img: [B][Cimg][H][W], Cimg 1 or 3, uint8
+ * (img_fp32 = 0) or float32 (img_fp32 = 1; truncated toward zero, after one fp32 multiply by 255 when normalised = 1 -- not
+ * rounded, as the host route); grey is replicated, alpha is 255.  rows: [B][cap][P] fp32 and counts: [B] int32 as
+ * yogo_format_preds_batched leaves them with box_format xyxy, P = 5 + classes; image b draws rows [0, counts[b]) in order, each its
+ * outline and then its label.  Corners: x = fp32(W) * row[0|2], y = fp32(H) * row[1|3] in fp32, truncated toward zero; the outline
+ * one pixel wide and clipped -- rows y0 and y1 from x0 to x1, columns x0 and x1 from min(y0 + 1, y1) to max(y0 + 1, y1) -- in
+ * colours[class] ([classes][4] RGBA bytes, 4-byte aligned), class the first maximum of row[5:].  The label is a mask of the glyph
+ * atlas blended with black, per channel t = (255 - m) * old + 128, new = ((t >> 8) + t) >> 8, alpha left at 255, at
+ * (int(x) + offset x, int(y) + offset y) of the first corner.  Atlas (yogo_amd.draw.GlyphAtlas.tables): label_meta [classes][6]
+ * int32 { first x cut, x cuts, first y cut, y cuts, first variant, 0 }; cuts [n_cuts] fp32; variants [n_variants][5] int32
+ * { width, height, offset x, offset y, where its width * height bytes start in glyphs }; the variant of a label is
+ * first + ix * (y cuts + 1) + iy with ix / iy the number of the axis' cuts at or below the fraction of the corner's x / y (the
+ * fraction carries the coordinate's sign; compared as ordered bit patterns, so denormal cuts hold).  A variant outside the tables
+ * or the glyph bytes draws no text.  out: [B][H][W][4] uint8, 4-byte aligned.  One workgroup per 16 x 64 tile; the operations that
+ * meet the tile are compacted in order into LDS and every lane applies them to its pixels in that order. */
+int yogo_draw_boxes(const void* img, int img_fp32, int normalised, int B, int Cimg, int H, int W, const float* rows, const int* counts,
+                    int cap, int P, const unsigned char* colours, const int* label_meta, const float* cuts, int n_cuts,
+                    const int* variants, int n_variants, const unsigned char* glyphs, long long glyph_bytes, unsigned char* out,
+                    yogo_stream_t stream);
+/* yogo_png_encode: [B][H][W][bpp] uint8 pixels on the device -> B complete PNG files (8 bits per sample; bpp 1 grey, 2 grey+alpha,
+ * 3 RGB, 4 RGBA; no interlace), byte for byte what yogo_amd.png_encode.encode_png_host writes, which states the choices: the filter
+ * per scanline by the smallest sum of absolute signed values (ties to the lowest type), bands of 16 scanlines each one
+ * dynamic-Huffman block of literals only (or stored blocks when that is not smaller) in an IDAT chunk of its own, CRC-32 and
+ * Adler-32 computed on the device.  yogo_png_encode_bound (on the host): slot_bytes, which no file of that shape exceeds, and
+ * work_bytes, the work space ONE image needs.  files: device memory of B * slot_bytes bytes; file b starts at b * slot_bytes
+ * (packed = 0) or at offsets[b], the files one after the other (packed = 1).  offsets: [B + 1] int64 device, the running sum of
+ * the files' lengths in both modes (the length of file b is offsets[b + 1] - offsets[b]).  status: [B] int32 device, 0, 1 (the file
+ * is longer than slot_bytes: nothing of it is written, its length counts as 0) or 2 (a band passed its part of the work space;
+ * the stored fallback bounds every band, so this is a defect).  work: work_bytes >= B * the per-image size, 16-byte aligned.  Two
+ * launches (bands; assembly).  No byte outside a file's slot and the work space is written.  B <= 65535, H, W <= 65535. */
+int yogo_png_encode_bound(int H, int W, int bpp, size_t* slot_bytes, size_t* work_bytes);
+int yogo_png_encode(const unsigned char* pixels, int B, int H, int W, int bpp, unsigned char* files, long long slot_bytes, int packed,
+                    long long* offsets, int* status, unsigned char* work, long long work_bytes, yogo_stream_t stream);
+
 /* ---- optimiser: torch.optim.AdamW over one flat buffer, yogo/train.py:213-217,324 ---------------------------------------- */
 int yogo_adamw_step(float* p, const float* g, float* m, float* v, long long n, int step, double lr, double beta1,
                     double beta2, double eps, double weight_decay, double grad_scale, yogo_stream_t stream);

@@ -37,7 +37,7 @@ WS_FILES="conv_bf16_ws conv_bf16_ws3 conv_bf16_ws16"
 extra_flags() {
   extra=()
   case "$1" in
-    nms|match|decode_loss|conv_bf16_head) extra=(-ffp-contract=off) ;;
+    nms|match|decode_loss|conv_bf16_head|draw_boxes) extra=(-ffp-contract=off) ;;
     conv_bf16_ws|conv_bf16_ws3|conv_bf16_ws16) extra=(-save-temps=obj -fno-slp-vectorize) ;;   # the assembly is audited below (asm-owned accumulator registers); no SLP packing: v_pk_*_f32 beside MFMAs costs more than it saves
     conv_bf16_tiled) extra=(-fno-slp-vectorize) ;;   # the same for the tiled kernels: the merged-epilogue forward instantiations -5 ... -9.5 % in the same-box A/B; the training step's launches take the lean epilogue with its explicit packed math and do not change
     conv_bf16_pack|conv_first_infer_bf16) extra=(-fno-slp-vectorize) ;;   # (these kernels were compiled beside the tiled one, with its flags: kept)

@@ -16,6 +16,11 @@ counts.
 ``device_image_decode=True`` (``yogo infer --path-to-images DIR --device-image-decode``) replaces the DataLoader and its PIL-decoding
 workers by a ``PngDeviceFeed`` (yogo_amd/png_feed.py): the files' zlib streams are inflated and their PNG filters reversed on the
 device, crop and ``/ 255`` included.  Same batches and names; ``ValueError`` with ``path_to_zarr`` and for an RGB model.
+
+``device_draw=True`` (``yogo infer --draw-boxes --device-draw --output-dir DIR``) draws the boxes and encodes the PNG files on the
+device (yogo_amd/draw.py): per batch one threshold + NMS launch, one render launch, one encode call, one read of the finished file
+bytes; the files are written on a small pool of threads.  Same file names, and every file decodes to the same pixels as the host
+route's; the PNG bytes are compressed differently.  Independent of ``device_outputs``.
 """
 from __future__ import annotations
 
@@ -74,7 +79,16 @@ def predict(
     device_outputs: bool = False,
     device_image_decode: bool = False,
     device_image_decode_all: bool = False,
+    device_draw: bool = False,
 ) -> Optional[torch.Tensor]:
+    if device_draw:   # (before anything touches a device or the output directory)
+        from yogo_amd.draw import check_labels
+
+        if not draw_boxes:
+            raise ValueError("device_draw draws what draw_boxes asks for: it needs draw_boxes")
+        if output_dir is None:
+            raise ValueError("device_draw writes files: it needs output_dir (showing the images interactively stays on the host)")
+        check_labels(class_names or [])
     if save_preds and draw_boxes:
         raise ValueError("cannot save predictions in YOGO format and draw_boxes at the same time")
     elif output_dir is not None and not (save_preds or draw_boxes or save_npy):
@@ -150,6 +164,12 @@ def predict(
     count_sink = PredictionSink(device, num_classes, "rows") if device_outputs and count_predictions else None
     txt_names: List[Path] = []
     npy_chunks: list = []   # (records, per-image counts) per drain
+    draw_sink = None
+    if device_draw:
+        from yogo_amd.draw import DrawSink
+
+        draw_sink = DrawSink(device, class_names or [str(c) for c in range(num_classes)], bool(model.normalize_images), output_dir,
+                             output_img_ftype)
 
     def drain_txt() -> None:
         # the files' bytes come ready from the device (PredictionSink.drain_text: what prediction_rows_to_text gives, byte for byte)
@@ -172,16 +192,21 @@ def predict(
             warnings.warn(f"got error {e}; continuing")
             continue
         x = img_batch.to(device, non_blocking=True)
-        if draw_boxes and img_batch.is_cuda:
+        if draw_boxes and img_batch.is_cuda and not device_draw:
             img_batch = img_batch.cpu()   # (zarr / PNG feed) drawing is host work
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=bool(half)):
             # the decoded tensor itself is only needed for drawing and for return_full_predictions; every other output goes
             # through the threshold + NMS kernel, which decodes the head's raw output as it loads it
-            res = model(x) if (draw_boxes or return_full_predictions) else model.forward_raw(x)
+            res = model(x) if ((draw_boxes and not device_draw) or return_full_predictions) else model.forward_raw(x)
         # the fused launch re-runs the decode per consumer: with more than one post-process output of this batch, decode ONCE
         if sum(map(bool, (save_preds, save_npy, count_predictions))) > 1 and hasattr(res, "decoded"):
             res = res.decoded()
-        if draw_boxes:
+        if device_draw:
+            # the rows of the per-image _format_tensor_for_rects in the same order, for the whole batch; drawn, encoded and read
+            # back by the sink (yogo_amd/draw.py), the batch as the model saw it: nothing of it is copied to the host
+            rows, _, counts = format_preds_batched(res, obj_thresh, iou_thresh, "xyxy", min_class_confidence_threshold)
+            draw_sink.submit(x, rows, counts, fnames)
+        elif draw_boxes:
             for k in range(img_batch.shape[0]):
                 bbox_img = draw_yogo_prediction(img=img_batch[k, ...], prediction=res[k, ...], obj_thresh=obj_thresh, iou_thresh=iou_thresh,
                                                 min_class_confidence_threshold=min_class_confidence_threshold, labels=class_names,
@@ -232,6 +257,8 @@ def predict(
 
     if txt_sink is not None:
         drain_txt()
+    if draw_sink is not None:
+        draw_sink.close()
     if count_sink is not None:
         tot_counts = count_sink.class_counts()
     if count_predictions:
@@ -260,4 +287,5 @@ def do_infer(args) -> None:
         vertical_crop_height=args.crop_height, count_predictions=args.count, output_img_ftype=args.output_img_filetype,
         min_class_confidence_threshold=args.min_class_confidence_threshold, half=args.half, device_outputs=args.device_outputs,
         device_image_decode=args.device_image_decode, device_image_decode_all=args.device_image_decode_all,
+        device_draw=args.device_draw,
     )

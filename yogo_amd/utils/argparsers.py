@@ -107,6 +107,16 @@ def _decode_all_needs_decode(ns):
     return None
 
 
+def _device_draw_needs(ns):
+    if ns.device_draw and not ns.draw_boxes:
+        return "--device-draw draws what --draw-boxes asks for: it needs --draw-boxes"
+    if ns.device_draw and ns.output_dir is None:
+        return "--device-draw writes files: it needs --output-dir (showing the images interactively stays on the host)"
+    if ns.device_draw and any("\n" in n or "\r" in n for n in (ns.class_names or [])):
+        return "--device-draw: a class name contains a line break; PIL lays such text out as several lines, which the device route does not do"
+    return None
+
+
 def global_parser():
     parser = argparse.ArgumentParser(description="what can yogo do for you today?", allow_abbrev=False)
     sub = parser.add_subparsers(help="here is what you can do", dest="task", parser_class=CheckedParser)
@@ -233,6 +243,11 @@ def infer_parser(parser=None):
                         help="with --device-image-decode: decode on the GPU every PNG colour type and bit depth (palette, 1 / 2 / 4-bit and "
                              "16-bit, grey+alpha, RGBA, RGB, with tRNS, Adam7-interlaced), converted as the host's decoder converts them, "
                              "and accept an RGB model; only files that are no PNG stay on the host (default: False)")
+    parser.add_argument("--device-draw", default=False, action=boolean_action,
+                        help="with --draw-boxes and --output-dir: draw the boxes and encode the PNG files on the GPU, one launch each per "
+                             "batch, instead of PIL on the host image by image; the files decode to the same pixels, their bytes are "
+                             "compressed differently.  With --output-img-filetype .tif / .tiff only the drawing moves: an uncompressed "
+                             "TIFF has nothing to encode, PIL writes the file from the pixels read back (default: False)")
     parser.add_argument("--output-dir", type=Path, default=None,
                         help="path to directory for results, either --draw-boxes or --save-preds")
     parser.add_argument("--class-names", help="list of class names - will default to integers if not provided", nargs="*", type=str, default=None)
@@ -251,4 +266,5 @@ def infer_parser(parser=None):
                         help="path to heatmap mask for the run (accepted for compatibility, unused -- as in the reference)")
     parser.add_argument("--use-tqdm", default=True, action=boolean_action, help="use tqdm progress bar (default: True)")
     parser.checks.append(_decode_all_needs_decode)
+    parser.checks.append(_device_draw_needs)
     return parser
