@@ -465,7 +465,7 @@ int yogo_image_cache_gather(const unsigned char* cache, int S, const int* slots,
  * (out_fp32 = 1): out[b][0][oy][ox] = frame_b[top + oy][left + ox], 1 <= OH <= H - top, 1 <= OW <= W - left (CenterCrop:
  * top = int(round((H - OH) / 2.0)), likewise left).  B <= 65535, H, W <= 65535.  Paths (named in the launch log): rows (C order,
  * cn == 1; 16-byte accesses when every segment is 16-byte aligned, else byte-wise), deinterleave (C order, 1 < cn <= 1024;
- * consecutive batch rows with one tile offset are served by one read of the chunk), gather (F order; byte-wise). */
+ * consecutive batch rows with one tile offset are served by one read of the chunk), gather (F order, or C order with cn > 1024; byte-wise). */
 int yogo_zarr_unpack(const unsigned char* staged, long long staged_bytes, const long long* tile_off, const int* tile_k, int B, int gh,
                      int gw, int ch, int cw, int cn, int order_f, int fill, int H, int W, int top, int left, int OH, int OW, void* out,
                      int out_fp32, yogo_stream_t stream);

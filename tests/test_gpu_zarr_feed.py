@@ -148,6 +148,34 @@ def test_feed_batches_equal_the_stack(tmp_path, normalize):
     assert torch.equal(torch.cat([b.cpu() for b, _ in batches]), want / 255 if normalize else want)
 
 
+@pytest.fixture(scope="module")
+def production_stack(tmp_path_factory):
+    """five 772 x 1032 frames, one raw chunk each: the stacks the scopes write"""
+    frames = np.random.default_rng(8).integers(0, 256, size=(772, 1032, 5), dtype=np.uint8)
+    return frames, ZW.write_stack(tmp_path_factory.mktemp("zarr_prod") / "s.zarr", frames, (772, 1032, 1))
+
+
+@pytest.mark.parametrize("normalize", [False, True], ids=["u8", "f32"])
+def test_feed_at_the_production_frame_shape(production_stack, normalize):
+    """772 x 1032: no multiple of 16 in a row, one in the frame -- every batch is one rows_vec launch of 49 workgroups per frame,
+    the last of them partial (tests/test_gpu_zarr_unpack_edges.py holds the kernel alone to it)"""
+    from yogo_amd import _hip
+    from yogo_amd.zarr_feed import ZarrDeviceFeed
+
+    frames, p = production_stack
+    _hip.launch_log(True)
+    try:
+        feed = ZarrDeviceFeed(ZarrDataset(p), 2, "cuda", normalize=normalize)
+        batches = [b.cpu() for b, _ in feed]
+        log = [ln.split(" | ")[0] for ln in _hip.read_launch_log() if ln.startswith("zarr_unpack")]
+    finally:
+        _hip.launch_log(False)
+    assert [tuple(b.shape) for b in batches] == [(2, 1, 772, 1032), (2, 1, 772, 1032), (1, 1, 772, 1032)]
+    assert log == [f"zarr_unpack_rows_vec_kernel<{'f32' if normalize else 'u8'}>"] * 3, log
+    want = torch.from_numpy(frames).permute(2, 0, 1)[:, None].contiguous()
+    assert torch.equal(torch.cat(batches), want / 255 if normalize else want)
+
+
 def test_feed_shares_chunks_between_batches_and_crops(tmp_path):
     from yogo_amd.zarr_feed import ZarrDeviceFeed
 

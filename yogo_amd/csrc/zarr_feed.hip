@@ -55,12 +55,14 @@ __device__ __forceinline__ void store_px(void* __restrict__ out, long long i, un
 // grid (seg16 / (BLOCK * UNROLL), nseg, B)
 template <bool F32>
 __global__ __launch_bounds__(BLOCK) void zarr_unpack_rows_vec_kernel(const unsigned char* __restrict__ staged,
-                                                                     const long long* __restrict__ tile_off, Geo g, int rows_per_seg,
-                                                                     long long seg16, void* __restrict__ out) {
+                                                                     const long long* __restrict__ tile_off, const int* __restrict__ tile_k,
+                                                                     Geo g, int rows_per_seg, long long seg16, void* __restrict__ out) {
   const int b = blockIdx.z, s = blockIdx.y;
   const int iy = g.top + s * rows_per_seg;
   const int ty = iy / g.ch;
-  const long long off = tile_base(tile_off, g, b, ty, 0);
+  // a row whose tile_k is no position of the chunk is fill, as on the byte path: one test per workgroup (b is uniform)
+  const bool k_ok = (unsigned)tile_k[b] < (unsigned)g.cn;
+  const long long off = k_ok ? tile_base(tile_off, g, b, ty, 0) : -1;
   const uint4* src = off < 0 ? nullptr : reinterpret_cast<const uint4*>(staged + off + (long long)(iy - ty * g.ch) * g.cw + g.left);
   const unsigned f4 = 0x01010101u * (unsigned)g.fill;
   const long long i0 = (long long)blockIdx.x * (BLOCK * UNROLL) + threadIdx.x;
@@ -248,9 +250,11 @@ extern "C" int yogo_zarr_unpack(const unsigned char* staged, long long staged_by
     const long long seg16 = (span ? n : (long long)OW) / 16, per_block = (long long)BLOCK * UNROLL;
     const dim3 grid((unsigned)((seg16 + per_block - 1) / per_block), nseg, B);
     if (out_fp32)
-      hipLaunchKernelGGL(zarr_unpack_rows_vec_kernel<true>, grid, dim3(BLOCK), 0, stream, staged, tile_off, g, rows_per_seg, seg16, out);
+      hipLaunchKernelGGL(zarr_unpack_rows_vec_kernel<true>, grid, dim3(BLOCK), 0, stream, staged, tile_off, tile_k, g, rows_per_seg, seg16,
+                         out);
     else
-      hipLaunchKernelGGL(zarr_unpack_rows_vec_kernel<false>, grid, dim3(BLOCK), 0, stream, staged, tile_off, g, rows_per_seg, seg16, out);
+      hipLaunchKernelGGL(zarr_unpack_rows_vec_kernel<false>, grid, dim3(BLOCK), 0, stream, staged, tile_off, tile_k, g, rows_per_seg, seg16,
+                         out);
     path = "rows_vec";
   } else if (!order_f && cn > 1 && cn <= DEINT_MAX_CN) {
     const int XS = (SLAB / cn) & ~3;   // >= 4 pixels, a whole number of quads
