@@ -76,6 +76,7 @@ int yogo_conv_first_wgrad(const void* in, int in_dtype, const float* dy, float* 
 int yogo_bn_finalize(const float* part, int rows, int row_stride, int C, long long count, float eps, float momentum,
                      float* mean_out, float* invstd_out, float* running_mean, float* running_var,
                      long long* num_batches_tracked, yogo_stream_t stream);
+/* yogo_bn_apply_act, yogo_bn_bwd: one grid row per (image, channel) plane, B * C <= 65535 (an argument error beyond) */
 int yogo_bn_apply_act(const float* z, float* y, const float* mean, const float* invstd_or_var, int stat_is_var, float eps,
                       const float* gamma, const float* beta, int B, int C, int HW, int act, yogo_stream_t stream);
 int yogo_bn_invstd(const float* var, float eps, float* invstd, int C, yogo_stream_t stream);
@@ -325,6 +326,8 @@ int yogo_bn_bwd_bf16(const void* g, const void* z, void* dz, const float* mean, 
 int yogo_bn_bwd_bf16_head(const void* gh, const float* head_w, int P, const void* z, void* dz, const float* mean, const float* invstd,
                           const float* gamma, const float* beta, int act, float* dgamma, float* dbeta, float* part, float* sums, int B,
                           int C, int HW, int training, float clip, yogo_stream_t stream);
+/* fp32 NCHW <-> bf16 NCHW8c (C padded to a multiple of 16, padding lanes written as zero / not read back); the rounding is to nearest
+ * even, NaN stays NaN.  B * 2 * ceil(C / 16) <= 65535 (an argument error beyond), as for every bf16 entry point above. */
 int yogo_nchw_f32_to_bf16_8c(const float* in, void* out, int B, int C, int HW, yogo_stream_t stream);
 int yogo_bf16_8c_to_nchw_f32(const void* in, float* out, int B, int C, int HW, yogo_stream_t stream);
 

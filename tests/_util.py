@@ -554,3 +554,26 @@ def hooks_library():
         for name in hooks:   # back to the product's plan
             getattr(L, name)(1)
         _hip._lib = prev
+
+
+# ---- canaries: an exact-size device buffer between sentinel words (test_gpu_round2.py, test_gpu_bn_edges.py) -------------------------
+GUARD = 4096
+
+
+class Guarded:
+    """n elements between two runs of GUARD sentinel words; the payload starts as NaN (floats) / 0x7F bytes so unwritten rows show"""
+
+    def __init__(self, n, dtype=torch.float32):
+        self.n = n
+        self.sent = {torch.float32: 12345.678, torch.int32: 0x5A5A5A5A, torch.float64: -7.25}[dtype]
+        self.buf = torch.full((n + 2 * GUARD,), self.sent, dtype=dtype, device="cuda")
+        self.view = self.buf[GUARD:GUARD + n]
+        if dtype.is_floating_point:
+            self.view.fill_(float("nan"))
+        else:
+            self.view.fill_(0x7F7F7F7F)
+
+    def check(self, what):
+        torch.cuda.synchronize()
+        lo, hi = self.buf[:GUARD], self.buf[GUARD + self.n:]
+        assert bool((lo == self.sent).all()) and bool((hi == self.sent).all()), f"{what}: wrote outside its buffer"

@@ -228,3 +228,36 @@ def test_adamw_matches_oracle():
         H.call("yogo_adamw_step", pd, dev(gr), md, vd, n, step, lr, 0.9, 0.999, 1e-8, 5e-2, 1.0, H.stream_ptr())
         torch.testing.assert_close(pd.cpu(), p, rtol=1e-6, atol=1e-7)
         torch.testing.assert_close(vd.cpu(), v, rtol=1e-6, atol=1e-12)
+        torch.testing.assert_close(md.cpu(), m, rtol=1e-6, atol=1e-8)
+    # ---- per element against float64 (tests/_bn_ref.py: adamw), given the state the kernel was given.  u = 2^-24; every host scalar is
+    # rounded to fp32 once (u each).  Counting the kernel's operations (optim.hip):
+    #   m' = m + w1 (gs g - m): g gs, the subtraction, w1, the product, the sum: u |m'| + w1 (u |gs g| + 3 u |gs g - m|) <= 4 u (|m'| + 0.1 (|gs g| + |gs g - m|))
+    #   v' = v beta2 + (w2 gs g) gs g, all terms >= 0: beta2, w2, gs g twice, three products, the sum: 6 u v'
+    #   denom = sqrt(v') / bc2_sqrt + eps: the square root halves v's 6 u (3 u) and adds its own, bc2_sqrt, the division, eps, the sum: 7 u denom
+    #   p' = p decay - step_size (m' / denom): decay and its product 2 u |p|; the update: m's bound / |m'| + 7 u + the division, step_size, the
+    #        product (10 u |update| + step_size dm / denom); the last subtraction u |p'|
+    import _bn_ref as R
+
+    u = 2.0 ** -24
+    worst = {"p": 0.0, "m": 0.0, "v": 0.0}
+    for n in (1, 255, 257, 10007, 524288 + 257):   # 524288 = 2048 workgroups x 256: the first size whose grid-stride loop takes a second pass
+        for gs, step in ((1.0, 1), (0.25, 1), (0.25, 1000)):
+            gn = torch.Generator().manual_seed(n % 1000 + step)
+            p0, gr = torch.randn(n, generator=gn), torch.randn(n, generator=gn) * 0.1
+            m0 = torch.zeros(n) if step == 1 else torch.randn(n, generator=gn) * 0.02
+            v0 = torch.zeros(n) if step == 1 else torch.rand(n, generator=gn) * 1e-3
+            lr = O.cosine_lr(step - 1, 3e-4, 2000, 3e-5)
+            pd, md, vd = dev(p0), dev(m0), dev(v0)
+            H.call("yogo_adamw_step", pd, dev(gr), md, vd, n, step, lr, 0.9, 0.999, 1e-8, 5e-2, gs, H.stream_ptr())
+            pr, mr, vr = R.adamw(p0, gr, m0, v0, step, lr, (0.9, 0.999), 1e-8, 5e-2, gs)
+            gi = gr.double() * gs
+            bm = 4 * u * (mr.abs() + 0.1 * (gi.abs() + (gi - m0.double()).abs()))
+            bv = 6 * u * vr
+            denom = vr.sqrt() / (1 - 0.999 ** step) ** 0.5 + 1e-8
+            ss = lr / (1 - 0.9 ** step)
+            bp = 2 * u * p0.double().abs() + 10 * u * (ss * mr / denom).abs() + ss * bm / denom + u * pr.abs()
+            for name, got, ref, bnd in (("p", pd, pr, bp), ("m", md, mr, bm), ("v", vd, vr, bv)):
+                r = float(((got.cpu().double() - ref).abs() / bnd.clamp_min(1e-300)).max())
+                worst[name] = max(worst[name], r)
+                assert r <= 1.0, (name, n, gs, step, r)
+    print(f"[bn_edges] yogo_adamw_step | worst d / bound: p {worst['p']:.4f} m {worst['m']:.4f} v {worst['v']:.4f}")

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import yogo_oracle as O
+from _util import GUARD, Guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -162,28 +163,6 @@ def test_trainer_state_dict_round_trip():
 # ---------------------------------------------------------------------------------------------------------------------
 # canaries: every partial-sum / scratch buffer of the layer-0 kernels, exact size, between sentinel words
 # ---------------------------------------------------------------------------------------------------------------------
-GUARD = 4096
-
-
-class Guarded:
-    """n elements between two runs of GUARD sentinel words; the payload starts as NaN (floats) / 0x7F bytes so unwritten rows show"""
-
-    def __init__(self, n, dtype=torch.float32):
-        self.n = n
-        self.sent = {torch.float32: 12345.678, torch.int32: 0x5A5A5A5A, torch.float64: -7.25}[dtype]
-        self.buf = torch.full((n + 2 * GUARD,), self.sent, dtype=dtype, device="cuda")
-        self.view = self.buf[GUARD:GUARD + n]
-        if dtype.is_floating_point:
-            self.view.fill_(float("nan"))
-        else:
-            self.view.fill_(0x7F7F7F7F)
-
-    def check(self, what):
-        torch.cuda.synchronize()
-        lo, hi = self.buf[:GUARD], self.buf[GUARD + self.n:]
-        assert bool((lo == self.sent).all()) and bool((hi == self.sent).all()), f"{what}: wrote outside its buffer"
-
-
 @pytest.mark.parametrize("B,IH,IW", [(4, 96, 128), (2, 772, 1032), (1, 130, 258), (3, 20, 24)])
 def test_layer0_partial_buffers_exact_size(B, IH, IW):
     """the abort of round 1 (gpurun_out/crash.log, 03:52) happened inside a HipTrainer.step(half=True) while the row counts of the

@@ -258,6 +258,7 @@ extern "C" int yogo_bn_apply_act(const float* z, float* y, const float* mean, co
                                  hipStream_t stream) {
   YOGO_CHECK_ARG(z && y && mean && invstd_or_var && gamma && beta && C > 0 && HW > 0 && B >= 0, "bn_apply_act: bad arguments");
   if (B == 0) return YOGO_OK;
+  YOGO_CHECK_ARG((long long)B * C <= 65535, "bn_apply_act: batch * channels exceeds 65535");
   if ((HW & 3) == 0) {
     dim3 grid(plane_blocks(HW, 8), B * C);
     hipLaunchKernelGGL((bn_apply_act_kernel<true>), grid, dim3(256), 0, stream, z, y, mean, invstd_or_var, stat_is_var, eps,
@@ -291,6 +292,7 @@ extern "C" int yogo_bn_bwd(const float* g, const float* z, float* dz, const floa
                            float* sums, int B, int C, int HW, int training, float clip, hipStream_t stream) {
   YOGO_CHECK_ARG(g && z && dz && mean && invstd && gamma && beta && dgamma && dbeta && part && sums, "bn_bwd: null pointer");
   YOGO_CHECK_ARG(B > 0 && C > 0 && HW > 0, "bn_bwd: bad shape");
+  YOGO_CHECK_ARG((long long)B * C <= 65535, "bn_bwd: batch * channels exceeds 65535");
   const int nb = plane_blocks(HW, 8);
   hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(nb, B * C), dim3(256), 0, stream, g, z, mean, invstd, gamma, beta, act, part, C, HW);
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, stream, part, B * nb, C, clip, dgamma, dbeta, sums, sums + C);
@@ -734,6 +736,7 @@ extern "C" int yogo_bn_stats_bf16(const void* z, float* part, int B, int C, int 
 extern "C" int yogo_nchw_f32_to_bf16_8c(const float* in, void* out, int B, int C, int HW, hipStream_t stream) {
   YOGO_CHECK_ARG(in && out && B > 0 && C > 0 && HW > 0, "nchw_f32_to_bf16_8c: bad arguments");
   const int Cb = cb_of(C);
+  YOGO_CHECK_ARG((long long)B * Cb <= 65535, "nchw_f32_to_bf16_8c: batch * channel blocks exceeds 65535");
   hipLaunchKernelGGL(nchw_f32_to_8c_kernel, dim3(plane_blocks(HW, 2), B * Cb), dim3(256), 0, stream, in,
                      reinterpret_cast<u32x4_t*>(out), C, Cb, HW);
   YOGO_CHECK_LAUNCH("nchw_f32_to_bf16_8c");
@@ -743,6 +746,7 @@ extern "C" int yogo_nchw_f32_to_bf16_8c(const float* in, void* out, int B, int C
 extern "C" int yogo_bf16_8c_to_nchw_f32(const void* in, float* out, int B, int C, int HW, hipStream_t stream) {
   YOGO_CHECK_ARG(in && out && B > 0 && C > 0 && HW > 0, "bf16_8c_to_nchw_f32: bad arguments");
   const int Cb = cb_of(C);
+  YOGO_CHECK_ARG((long long)B * Cb <= 65535, "bf16_8c_to_nchw_f32: batch * channel blocks exceeds 65535");
   hipLaunchKernelGGL(nchw8c_to_f32_kernel, dim3(plane_blocks(HW, 2), B * Cb), dim3(256), 0, stream,
                      reinterpret_cast<const u32x4_t*>(in), out, C, Cb, HW);
   YOGO_CHECK_LAUNCH("bf16_8c_to_nchw_f32");
