@@ -261,6 +261,17 @@ int yogo_bf16_signs_bytes(int B, int C, int H, int W, size_t* bytes);
 int yogo_conv2d_fwd_bf16_signs(const void* in, const void* packed, const float* bias, void* out, void* signs,
                                const float* chan_scale, int B, int Cin, int Cout, int IH, int IW, int ksize, int stride, int act,
                                yogo_stream_t stream);
+/* Two LeakyReLU blocks without BatchNorm in one call (yogo/model_defns.py:39-46, blocks 2 and 3 of base_model: Conv2d(16, 32, 3, padding=1)
+ * and Conv2d(32, 64, 3, stride=2, padding=1), each with LeakyReLU and -- the second -- Dropout2d): out1 / signs1 = yogo_conv2d_fwd_bf16_signs
+ * (in, packed1, bias1, scale1; C0 -> C1, stride 1), out2 / signs2 = the same of out1 (packed2, bias2, scale2; C1 -> C2, stride 2), every
+ * stored byte identical to the two calls.  Where yogo_conv2d_fwd_bf16_signs_pair_eligible returns 1 (C0 = 16, C1 = 32 < C2 <= 64, extents
+ * below 2^31) and act is LeakyReLU the pair runs as ONE launch whose second layer reads out1 from LDS instead of memory; otherwise as the
+ * two launches.  out1 and signs1 are written either way (the backward pass reads them). */
+int yogo_conv2d_fwd_bf16_signs_pair_eligible(int B, int C0, int C1, int C2, int IH, int IW);
+int yogo_conv2d_fwd_bf16_signs_pair(const void* in, const void* packed1, const float* bias1, void* out1, void* signs1,
+                                    const float* scale1, const void* packed2, const float* bias2, void* out2, void* signs2,
+                                    const float* scale2, int B, int C0, int C1, int C2, int IH, int IW, int act,
+                                    yogo_stream_t stream);
 /* yogo_conv2d_dgrad_bf16 for a LeakyReLU reference given as its sign map: dx = conv_transpose(dy) * (bit ? 1 : 0.01) * chan_scale.
  * Contract against yogo_conv2d_dgrad_bf16 with the bf16 reference tensor: the same bits wherever both run on the same kernel; the
  * stride-2 3x3 shapes conv_bf16_s2d_direct_kernel takes (<= 32 or 65..128 input channels of the forward convolution) step the

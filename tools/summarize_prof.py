@@ -26,7 +26,12 @@ if stats:
     rows = list(csv.DictReader(open(stats)))
     lines.append(f"# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-inference   ({tag}; bf16, per-GPU batch 128)")
     lines.append(f"{'kernel':70s} {'calls':>6s} {'total_ms':>10s} {'avg_us':>10s} {'pct':>6s}")
-    for r in rows[:36]:
+    # every kernel that takes at least 0.05 % of the profiled time, and two once-per-step kernels of a few microseconds that
+    # tests/test_gpu_production_shapes.py wants a row of (the optimiser; the finalize of layer 0's fused backward sums, the only kernel of its
+    # family left in the step).  A share, not a row count: a count moves the cut whenever two kernels become one, and the kernels around it are a
+    # dozen 5-microsecond helpers whose order changes from box to box
+    always = ("adamw_kernel", "conv_first_bn_wgrad")
+    for r in [r for r in rows if float(r["Percentage"]) >= 0.05 or r["Name"].replace("(anonymous namespace)::", "").startswith(always)]:
         name = r["Name"].replace("(anonymous namespace)::", "").split("(")[0][:70]
         lines.append(f"{name:70s} {r['Calls']:>6s} {float(r['TotalDurationNs'])/1e6:10.3f} {float(r['AverageNs'])/1e3:10.1f} {float(r['Percentage']):6.2f}")
     # the same kernel name covers launches of different shapes (the 128-channel weight gradient: layer 3 vs layers 5 / 6; the persistent

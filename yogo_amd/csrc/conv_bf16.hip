@@ -309,6 +309,23 @@ extern "C" int yogo_conv2d_fwd_bf16_signs(const void* in, const void* packed, co
   return launch_conv_bf16(r, stream);
 }
 
+// A stride-1 3x3 C0 -> C1 block and the stride-2 3x3 C1 -> C2 block behind it (both with bias / activation / channel scale and a sign map,
+// yogo/model_defns.py:39-46) in one call: bit-identical to yogo_conv2d_fwd_bf16_signs twice.  Shapes conv_bf16_staged_pair_kernel takes run
+// in ONE launch in which layer 2 reads y1 from LDS; every other shape, and every shape with the plan switch off, runs the two launches.
+extern "C" int yogo_conv2d_fwd_bf16_signs_pair_eligible(int B, int C0, int C1, int C2, int IH, int IW) {
+  return conv_bf16_staged_pair_eligible(C0, C1, C2, IH, IW, B) ? 1 : 0;
+}
+extern "C" int yogo_conv2d_fwd_bf16_signs_pair(const void* in, const void* packed1, const float* bias1, void* out1, void* signs1, const float* scale1,
+                                               const void* packed2, const float* bias2, void* out2, void* signs2, const float* scale2, int B, int C0,
+                                               int C1, int C2, int IH, int IW, int act, hipStream_t stream) {
+  YOGO_CHECK_ARG(in && packed1 && out1 && signs1 && packed2 && out2 && signs2, "conv2d_fwd_bf16_signs_pair: null pointer");
+  YOGO_CHECK_ARG(B >= 0 && C0 > 0 && C1 > 0 && C2 > 0 && IH > 0 && IW > 0, "conv2d_fwd_bf16_signs_pair: unsupported shape");
+  if (plan_staged_pair() && act == ACT_LEAKY && conv_bf16_staged_pair_eligible(C0, C1, C2, IH, IW, B))
+    return launch_conv_bf16_staged_pair(in, packed1, bias1, out1, signs1, scale1, packed2, bias2, out2, signs2, scale2, B, C1, C2, IH, IW, act, stream);
+  if (int e = yogo_conv2d_fwd_bf16_signs(in, packed1, bias1, out1, signs1, scale1, B, C0, C1, IH, IW, 3, 1, act, stream)) return e;
+  return yogo_conv2d_fwd_bf16_signs(out1, packed2, bias2, out2, signs2, scale2, B, C1, C2, IH, IW, 3, 2, act, stream);
+}
+
 // yogo_conv2d_dgrad_bf16 with act = LeakyReLU and the sign map of the reference in place of the reference:
 // dx = conv_transpose(dy) * (sign bit ? 1 : 0.01) * chan_scale
 extern "C" int yogo_conv2d_dgrad_bf16_signs(const void* dy, const void* packed_dgrad, void* dx, const void* signs,

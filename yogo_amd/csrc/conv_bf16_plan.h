@@ -3,7 +3,7 @@
 //   conv_bf16.hip        request, planner (bf_plan, bf_plan_rows, bf_plan_tiled), dispatcher, the C entry points -- no kernel
 //   conv_bf16_tiled.hip  conv_bf16_kernel, its instantiation table and launch_conv_bf16_tiled
 //   conv_bf16_pack.hip   the weight-packing kernels and their entry points
-//   conv_bf16_{ws,ws3,ws16}.hip (own headers), conv_bf16_{direct,staged,head}.hip (declared below): the specialised kernels
+//   conv_bf16_{ws,ws3,ws16}.hip (own headers), conv_bf16_{direct,staged,staged_pair,head}.hip (declared below): the specialised kernels
 #pragma once
 #include "common.h"
 
@@ -70,6 +70,11 @@ int launch_conv_bf16_s2d_direct(const void* in, const void* packed, void* out, c
 bool conv_bf16_staged_eligible(int K, int M, int stride, int IH, int IW, int OH, int OW, int B);
 int launch_conv_bf16_staged(const void* in, const void* packed, const float* bias, void* out, void* signs, const float* chan_scale, int B, int K, int M, int IH,
                             int IW, int OH, int OW, int stride, int act, hipStream_t stream);
+// conv_bf16_staged_pair.hip: a stride-1 16 -> C1 layer and the stride-2 C1 -> C2 layer behind it in one launch (y1 through LDS)
+bool conv_bf16_staged_pair_eligible(int C0, int C1, int C2, int IH, int IW, int B);
+int launch_conv_bf16_staged_pair(const void* in, const void* packed1, const float* bias1, void* out1, void* signs1, const float* scale1, const void* packed2,
+                                 const float* bias2, void* out2, void* signs2, const float* scale2, int B, int C1, int C2, int IH, int IW, int act,
+                                 hipStream_t stream);
 // conv_bf16_head.hip
 bool conv_bf16_head_fwd_eligible(int K, int M, int plane, int B);
 int launch_conv_bf16_head_fwd(const void* in, const void* packed, const float* bias, float* out_f32, int B, int K, int M, int plane, hipStream_t stream);

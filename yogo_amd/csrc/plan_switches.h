@@ -1,7 +1,7 @@
 // Every plan switch of the library, one out-of-line accessor each (plan_switches.hip).  A launcher asks here which kernel family or
 // loop variant a launch may take; no other file of csrc/ knows whether a switch is a constant or a variable.
 //   product (libyogo_hip.so):              each accessor returns a constant -- no mutable plan state, no setter
-//   -DYOGO_TEST_HOOKS (libyogo_hip_hooks.so, tests/ and tools/ only) and -DYOGO_DIAG: the seven below are variables with yogo_hook_* setters
+//   -DYOGO_TEST_HOOKS (libyogo_hip_hooks.so, tests/ and tools/ only) and -DYOGO_DIAG: the eight below are variables with yogo_hook_* setters
 //   -DYOGO_DIAG (libyogo_hip_diag.so):     the tiled planner's four are variables too (yogo_diag_conv_bf16_* setters)
 #pragma once
 
@@ -12,6 +12,7 @@ bool plan_ws();          // the persistent wavefront-specialised kernels (conv_b
 int plan_ws16_mode();
 bool plan_direct();      // the direct (weights-resident, no staging) stride-2 data gradients (conv_bf16_direct.hip)
 bool plan_staged();      // the independent-wavefront kernel of the thin forward-type layers (conv_bf16_staged.hip)
+bool plan_staged_pair(); // layers 1 + 2 forward in one launch (conv_bf16_staged_pair.hip); off: the two launches of yogo_conv2d_fwd_bf16_signs
 bool plan_head();        // the 1x1 head's forward with the weights in registers (conv_bf16_head.hip)
 // layer 0: two pixels per lane where the output width is even
 bool plan_first_bn_wgrad_pairs();   // conv_first.hip, the sign-map sweep

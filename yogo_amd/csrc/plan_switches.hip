@@ -22,6 +22,7 @@
   X(int, plan_ws16_mode, BF_WS16_MODE, yogo_hook_conv_bf16_ws16)                           \
   X(bool, plan_direct, true, yogo_hook_conv_bf16_direct)                                   \
   X(bool, plan_staged, true, yogo_hook_conv_bf16_staged)                                   \
+  X(bool, plan_staged_pair, true, yogo_hook_conv_bf16_staged_pair)                         \
   X(bool, plan_head, true, yogo_hook_conv_bf16_head)                                       \
   X(bool, plan_first_bn_wgrad_pairs, true, yogo_hook_conv_first_bn_wgrad_pairs)            \
   X(bool, plan_first_mfma_pairs, true, yogo_hook_conv_first_mfma_pairs)

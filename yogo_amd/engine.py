@@ -399,6 +399,7 @@ _FUSE_LAYER0_BWD = True     # BatchNorm backward + activation derivative + first
 _L0_NO_Z = True             # ... without layer 0's conv output in memory: sign map + derived sums, yogo_conv_first_*_xs (tests/test_gpu_bf16.py)
 _WGRAD_DEFER_REDUCE = True  # the per-layer split-K reductions of the weight gradients in one launch at the end of the backward pass (tests/test_gpu_bf16.py)
 _L01_FUSE_BWD = True        # layer 1's data gradient folded into layer 0's backward sums, yogo_conv2d_dgrad_wgrad_bf16_first_bwd: no dy of layer 0 in memory (tests/test_gpu_first_fused_bwd.py)
+_PAIR_FWD = True            # the forward of a stride-1 16 -> 32 and the stride-2 32 -> 64 block behind it in one launch, yogo_conv2d_fwd_bf16_signs_pair (tests/test_gpu_pair_fwd.py)
 _HEAD_BN_FUSE = True        # the 1x1 head's data gradient computed inside the BatchNorm backward of the block under it, yogo_bn_bwd_bf16_head (tests/test_gpu_head_bn_fused.py)
 
 
@@ -572,6 +573,41 @@ def _layer_fwd_bf16(eng: Engine, i: int, L: Layer, S: Saved, bias, bn_train: boo
     return y
 
 
+def _pair_fwd_eligible(eng: Engine, i: int, B: int, H: int, W: int) -> bool:
+    """layers i and i + 1 are a stride-1 3x3 16 -> 32 and a stride-2 3x3 32 -> <= 64 LeakyReLU block without BatchNorm, neither the first
+    nor the last layer, at a shape the one-launch pair takes (yogo_conv2d_fwd_bf16_signs_pair: layer i + 1 reads layer i's output from LDS)"""
+    if i < 1 or i + 2 >= len(eng.layers):
+        return False
+    La, Lb = eng.layers[i], eng.layers[i + 1]
+    if not all(L.k == 3 and L.bn is None and L.act == ACT_LEAKY for L in (La, Lb)) or La.s != 1 or Lb.s != 2:
+        return False
+    return bool(_hip.lib().yogo_conv2d_fwd_bf16_signs_pair_eligible(B, La.cin, La.cout, Lb.cout, H, W))
+
+
+def _pair_fwd_bf16(eng: Engine, i: int, Sa: Saved, Sb: Saved, B: int, H: int, W: int, st) -> torch.Tensor:
+    """_layer_fwd_bf16 of layers i and i + 1 (both the sign-map branch) in one call: fills both records as the two calls do"""
+    La, Lb = eng.layers[i], eng.layers[i + 1]
+    dev = Sa.x_in.device
+    OH, OW = Lb.out_hw(H, W)
+    bias_a = _f32(La.conv.bias.detach()) if La.conv.bias is not None else None
+    bias_b = _f32(Lb.conv.bias.detach()) if Lb.conv.bias is not None else None
+    pk_a, pk_b = _packed_bf16(eng, i, 0), _packed_bf16(eng, i + 1, 0)
+    y1 = torch.empty(B, _blocks(La.cout), H, W, 8, dtype=torch.bfloat16, device=dev)
+    y2 = torch.empty(B, _blocks(Lb.cout), OH, OW, 8, dtype=torch.bfloat16, device=dev)
+    Sa.signs = torch.empty(_hip.query_size("yogo_bf16_signs_bytes", B, La.cout, H, W), dtype=torch.uint8, device=dev)
+    Sb.signs = torch.empty(_hip.query_size("yogo_bf16_signs_bytes", B, Lb.cout, OH, OW), dtype=torch.uint8, device=dev)
+    # one event for the pair, under layer i: the summed FLOPs, and the bytes the pair has to move (y0 in, y1 and y2 out; y1 is not read back)
+    flops = 2.0 * B * 9 * (La.cout * La.cin * H * W + Lb.cout * Lb.cin * OH * OW)
+    nbytes = B * 16 * ((_blocks(La.cin) + _blocks(La.cout)) * H * W + _blocks(Lb.cout) * OH * OW)
+    eng._tick("fwd", i, flops, mw=30, nbytes=nbytes)
+    _hip.call("yogo_conv2d_fwd_bf16_signs_pair", Sa.x_in, pk_a, bias_a, y1, Sa.signs, Sa.mask, pk_b, bias_b, y2, Sb.signs, Sb.mask,
+              B, La.cin, La.cout, Lb.cout, H, W, ACT_LEAKY, st)
+    eng._tock()
+    Sb.x_in = y1
+    Sa.y, Sb.y = y1, y2
+    return y2
+
+
 def forward_bf16_train(eng: Engine, x: torch.Tensor) -> Tuple[torch.Tensor, List[Saved]]:
     _check_bf16_train_input(eng, x)
     dev, st, B = x.device, _hip.stream_ptr(), x.shape[0]
@@ -581,7 +617,11 @@ def forward_bf16_train(eng: Engine, x: torch.Tensor) -> Tuple[torch.Tensor, List
     H, W = int(cur.shape[2]), int(cur.shape[3])
     saved: List[Saved] = []
     n = len(eng.layers)
+    paired = -1   # the layer the pair call of the layer before it has already run
     for i, L in enumerate(eng.layers):
+        if i == paired:
+            H, W = L.out_hw(H, W)
+            continue
         OH, OW = L.out_hw(H, W)
         if OH <= 0 or OW <= 0:
             raise RuntimeError(f"yogo_amd: image too small at layer {i}")
@@ -592,6 +632,16 @@ def forward_bf16_train(eng: Engine, x: torch.Tensor) -> Tuple[torch.Tensor, List
         bias = _f32(L.conv.bias.detach()) if L.conv.bias is not None else None
         S = Saved(x_in=cur, mask=masks.get(i))
         bn_train = has_bn and (L.bn.training or L.bn.running_mean is None)
+        if _PAIR_FWD and _pair_fwd_eligible(eng, i, B, H, W):
+            OH2, OW2 = eng.layers[i + 1].out_hw(OH, OW)
+            if OH2 <= 0 or OW2 <= 0:
+                raise RuntimeError(f"yogo_amd: image too small at layer {i + 1}")
+            S2 = Saved(x_in=None, mask=masks.get(i + 1))
+            cur = _pair_fwd_bf16(eng, i, S, S2, B, H, W, st)
+            saved += [S, S2]
+            paired = i + 1
+            H, W = OH, OW
+            continue
         if (i == 0 and has_bn and S.mask is None and not last and cur.dtype == torch.uint8
                 and _hip.lib().yogo_conv_first_mfma_supported(0, L.cin, L.cout, H, W, L.s)):
             cur = _first_mfma_fwd_bf16(eng, L, S, bias, bn_train, B, H, W, st)
