@@ -633,8 +633,16 @@ int yogo_draw_boxes(const void* img, int img_fp32, int normalised, int B, int Ci
  * the files' lengths in both modes (the length of file b is offsets[b + 1] - offsets[b]).  status: [B] int32 device, 0, 1 (the file
  * is longer than slot_bytes: nothing of it is written, its length counts as 0) or 2 (a band passed its part of the work space;
  * the stored fallback bounds every band, so this is a defect).  work: work_bytes >= B * the per-image size, 16-byte aligned.  Two
- * launches (bands; assembly).  No byte outside a file's slot and the work space is written.  B <= 65535, H, W <= 65535. */
+ * launches (bands; assembly).  No byte outside a file's slot and the work space is written.  B <= 65535, H, W <= 65535.
+ * The _level forms take the compression level: 0 is the above (what the forms without a level mean), 1 codes a band as one
+ * dynamic-Huffman block of literals and LZ77 matches (candidates at the distances bpp * k, k = 1 .. 64; pieces of 512 bytes parsed
+ * greedily on their own: yogo_amd/png_encode.py) and is smaller or, for a band that does not compress, the same stored blocks.
+ * slot_bytes is the same at both levels; work_bytes is larger at level 1 (a band's filtered bytes and its tokens are kept there) and
+ * work space sized for another level is refused.  Any other level is refused. */
 int yogo_png_encode_bound(int H, int W, int bpp, size_t* slot_bytes, size_t* work_bytes);
+int yogo_png_encode_bound_level(int H, int W, int bpp, int level, size_t* slot_bytes, size_t* work_bytes);
+int yogo_png_encode_level(const unsigned char* pixels, int B, int H, int W, int bpp, int level, unsigned char* files, long long slot_bytes,
+                          int packed, long long* offsets, int* status, unsigned char* work, long long work_bytes, yogo_stream_t stream);
 int yogo_png_encode(const unsigned char* pixels, int B, int H, int W, int bpp, unsigned char* files, long long slot_bytes, int packed,
                     long long* offsets, int* status, unsigned char* work, long long work_bytes, yogo_stream_t stream);
 

@@ -15,167 +15,19 @@
 // multiplying with x^(8 n) mod P.  png_assemble_kernel, one workgroup per image: the bands' offsets, the Adler-32 from the bands'
 // (a, b, n) in closed form, signature / IHDR / lengths / CRCs / IEND, and the bands copied into the file (wave_copy.h).
 // Every store is held to the band's part of the work buffer or to the file's slot.
+// Level 1 (literals and matches) is png_encode_matches.hip: another band kernel, this file's assembly; what both share is png_deflate.h.
 #include "common.h"
+#include "png_deflate.h"
 #include "wave_copy.h"
 
 namespace {
 
-using yogo_wave::WAVE;
+using namespace yogo_png;
 
-constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / WAVE;
-constexpr int BAND_ROWS = 16;
-constexpr int MAX_STORED = 65535;
 constexpr int LIT = 257;            // literals and end-of-block
 constexpr int PER_LANE = 16;        // bytes a lane codes per chunk
 constexpr int CHUNK = THREADS * PER_LANE;
 constexpr int OUTW = CHUNK * 15 / 32 + 72;   // words of the LDS bit buffer: a chunk at 15 bits per byte, the header, the carry
-constexpr int META_WORDS = 8;       // per band: data bytes, CRC register, Adler s1, s2, n, overflow
-constexpr unsigned ADLER_MOD = 65521u;
-constexpr unsigned CRC_POLY = 0xEDB88320u;
-constexpr int MAX_BANDS = 4096;     // H <= 65535
-constexpr int ST_SLOT = 1, ST_BAND = 2;
-
-__host__ __device__ inline long long stored_bytes(long long n) { return n + 5 * ((n + MAX_STORED - 1) / MAX_STORED); }
-__host__ __device__ inline long long band_stride(int rb) { return (8 + stored_bytes((long long)BAND_ROWS * (rb + 1)) + 2 + 4 + 15) & ~15LL; }
-__host__ __device__ inline int band_count(int H) { return (H + BAND_ROWS - 1) / BAND_ROWS; }
-
-// a * b mod P, polynomials over GF(2) in the CRC's reflected order (bit 31 is x^0)
-__device__ __forceinline__ unsigned mulmod(unsigned a, unsigned b) {
-  unsigned p = 0;
-  for (int i = 0; i < 32; ++i) {
-    if (a & (0x80000000u >> i)) p ^= b;
-    b = (b & 1u) ? (b >> 1) ^ CRC_POLY : b >> 1;
-  }
-  return p;
-}
-// x^(8 n) mod P
-__device__ __forceinline__ unsigned xpow8(unsigned long long n) {
-  unsigned r = 0x80000000u, base = 0x00800000u;   // 1, x^8
-  for (; n; n >>= 1) {
-    if (n & 1ull) r = mulmod(r, base);
-    base = mulmod(base, base);
-  }
-  return r;
-}
-__device__ __forceinline__ unsigned crc_byte_bitwise(unsigned c, unsigned byte) {
-  c ^= byte;
-  for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ CRC_POLY : c >> 1;
-  return c;
-}
-
-__device__ __forceinline__ int paeth(int a, int b, int c) {
-  const int p = a + b - c, pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
-  return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
-}
-// byte i of row y of the image at img, filtered with type ft
-__device__ __forceinline__ unsigned filtered(const unsigned char* __restrict__ img, int y, int i, int rb, int bpp, int ft) {
-  const unsigned char* cur = img + (long long)y * rb;
-  const int x = cur[i];
-  if (ft == 0) return x;
-  const int a = i >= bpp ? cur[i - bpp] : 0;
-  if (ft == 1) return (x - a) & 255;
-  const int b = y > 0 ? cur[i - rb] : 0;
-  if (ft == 2) return (x - b) & 255;
-  if (ft == 3) return (x - ((a + b) >> 1)) & 255;
-  const int c = (y > 0 && i >= bpp) ? cur[i - rb - bpp] : 0;
-  return (x - paeth(a, b, c)) & 255;
-}
-
-struct HuffScratch {
-  unsigned leaf_f[LIT], node_f[LIT];
-  unsigned short sym[LIT], leaf_parent[LIT], node_parent[LIT], depth[LIT];
-  int used;
-};
-
-// code lengths of at most `limit` bits for the nsym counts at freq -> len (0 for an unused symbol); called by the whole workgroup
-__device__ void huffman_lengths(const unsigned* freq, int nsym, int limit, unsigned char* len, HuffScratch& s, int tid) {
-  if (tid == 0) s.used = 0;
-  __syncthreads();
-  for (int t = tid; t < nsym; t += THREADS) {
-    len[t] = 0;
-    const unsigned f = freq[t];
-    if (f == 0) continue;
-    int rank = 0;
-    for (int u = 0; u < nsym; ++u) {
-      const unsigned g = freq[u];
-      rank += (g != 0 && (g < f || (g == f && u < t))) ? 1 : 0;
-    }
-    s.sym[rank] = (unsigned short)t;
-    s.leaf_f[rank] = f;
-    atomicAdd(&s.used, 1);
-  }
-  __syncthreads();
-  if (tid == 0) {
-    const int n = s.used;
-    if (n == 1) {
-      len[s.sym[0]] = 1;
-    } else if (n > 1) {
-      int li = 0, ni = 0;
-      for (int k = 0; k < n - 1; ++k) {   // the two smallest of the leaves left and the internal nodes made so far
-        unsigned total = 0;
-        for (int two = 0; two < 2; ++two) {
-          if (li < n && (ni >= k || s.leaf_f[li] <= s.node_f[ni])) {
-            total += s.leaf_f[li];
-            s.leaf_parent[li++] = (unsigned short)k;
-          } else {
-            total += s.node_f[ni];
-            s.node_parent[ni++] = (unsigned short)k;
-          }
-        }
-        s.node_f[k] = total;
-      }
-      s.depth[n - 2] = 0;
-      for (int k = n - 3; k >= 0; --k) s.depth[k] = s.depth[s.node_parent[k]] + 1;
-      int count[16];
-      for (int b = 0; b < 16; ++b) count[b] = 0;
-      for (int i = 0; i < n; ++i) {
-        const int d = s.depth[s.leaf_parent[i]] + 1;
-        ++count[d < limit ? d : limit];
-      }
-      unsigned kraft = 0;
-      for (int b = 1; b <= limit; ++b) kraft += (unsigned)count[b] << (limit - b);
-      while (kraft > (1u << limit)) {
-        --count[limit];
-        int b = limit - 1;
-        while (count[b] == 0) --b;
-        --count[b];
-        count[b + 1] += 2;
-        --kraft;
-      }
-      int i = 0;
-      for (int b = limit; b >= 1; --b)
-        for (int c = 0; c < count[b]; ++c) len[s.sym[i++]] = (unsigned char)b;
-    }
-  }
-  __syncthreads();
-}
-
-// canonical codes, bit-reversed (the stream fills bytes from the least significant bit); lane 0
-__device__ void canonical_codes(const unsigned char* len, int nsym, int limit, unsigned short* code) {
-  int count[17], next[17];
-  for (int b = 0; b <= 16; ++b) count[b] = 0;
-  for (int t = 0; t < nsym; ++t) ++count[len[t]];
-  count[0] = 0;
-  int c = 0;
-  next[0] = 0;
-  for (int b = 1; b <= limit; ++b) {
-    c = (c + count[b - 1]) << 1;
-    next[b] = c;
-  }
-  for (int t = 0; t < nsym; ++t) {
-    const int b = len[t];
-    code[t] = b ? (unsigned short)(__brev((unsigned)next[b]++) >> (32 - b)) : 0;
-  }
-}
-
-// `bits` bits of v at bit `pos` of the LDS buffer (one lane, plain stores)
-__device__ __forceinline__ void put_bits(unsigned* buf, int& pos, unsigned v, int bits) {
-  const int w = pos >> 5, sh = pos & 31;
-  buf[w] |= v << sh;
-  if (sh + bits > 32) buf[w + 1] |= v >> (32 - sh);
-  pos += bits;
-}
 
 struct BandShared {
   unsigned hist[LIT + 3];
@@ -190,7 +42,7 @@ struct BandShared {
   unsigned char ftype[BAND_ROWS];
   int use_huff, overflow;
   long long data_bytes;
-  HuffScratch huff;
+  HuffScratch<LIT> huff;
 };
 
 __global__ __launch_bounds__(THREADS) void png_band_kernel(const unsigned char* __restrict__ pixels, int H, int W, int bpp,
@@ -534,9 +386,14 @@ __global__ __launch_bounds__(THREADS) void png_assemble_kernel(const unsigned ch
 
 }  // namespace
 
-extern "C" int yogo_png_encode_bound(int H, int W, int bpp, size_t* slot_bytes, size_t* work_bytes) {
+// (png_encode_matches.hip) the band launch of level 1
+int yogo_png_band_matches_launch(const unsigned char* pixels, int B, int H, int W, int bpp, unsigned char* work, long long work_per,
+                                 hipStream_t stream);
+
+extern "C" int yogo_png_encode_bound_level(int H, int W, int bpp, int level, size_t* slot_bytes, size_t* work_bytes) {
   YOGO_CHECK_ARG(slot_bytes && work_bytes, "png_encode_bound: null argument");
   YOGO_CHECK_ARG(H >= 1 && W >= 1 && H <= 65535 && W <= 65535 && bpp >= 1 && bpp <= 4, "png_encode_bound: bad image shape %d x %d x %d", H, W, bpp);
+  YOGO_CHECK_ARG(level == 0 || level == 1, "png_encode_bound: level %d (0: literals only, 1: literals and matches)", level);
   const int rb = W * bpp, nb = band_count(H);
   long long total = 8 + 25 + 12;
   for (int k = 0; k < nb; ++k) {
@@ -545,33 +402,47 @@ extern "C" int yogo_png_encode_bound(int H, int W, int bpp, size_t* slot_bytes, 
   }
   YOGO_CHECK_ARG(total < (1LL << 31), "png_encode_bound: an image of %d x %d x %d bytes (files below 2 GiB)", H, W, bpp);
   *slot_bytes = (size_t)total;
-  *work_bytes = (size_t)((long long)nb * META_WORDS * 4 + (long long)nb * band_stride(rb));
+  *work_bytes = (size_t)work_per_image(H, rb, level);
+  return YOGO_OK;
+}
+
+extern "C" int yogo_png_encode_bound(int H, int W, int bpp, size_t* slot_bytes, size_t* work_bytes) {
+  return yogo_png_encode_bound_level(H, W, bpp, 0, slot_bytes, work_bytes);
+}
+
+extern "C" int yogo_png_encode_level(const unsigned char* pixels, int B, int H, int W, int bpp, int level, unsigned char* files,
+                                     long long slot_bytes, int packed, long long* offsets, int* status, unsigned char* work,
+                                     long long work_bytes, hipStream_t stream) {
+  YOGO_CHECK_ARG(pixels && files && offsets && status && work, "png_encode: null argument");
+  YOGO_CHECK_ARG(B >= 0 && B <= 65535, "png_encode: B = %d images, at most 65535 per call", B);
+  size_t bound = 0, per_image = 0;
+  if (int rc = yogo_png_encode_bound_level(H, W, bpp, level, &bound, &per_image)) return rc;
+  YOGO_CHECK_ARG(slot_bytes >= 0 && (packed == 0 || packed == 1), "png_encode: bad slot size or packed flag");
+  YOGO_CHECK_ARG(work_bytes >= (long long)B * (long long)per_image, "png_encode: %lld bytes of work space, %d images need %lld at level %d",
+                 work_bytes, B, (long long)B * (long long)per_image, level);
+  YOGO_CHECK_ARG((reinterpret_cast<uintptr_t>(work) & 15) == 0 && (reinterpret_cast<uintptr_t>(offsets) & 7) == 0 &&
+                     (reinterpret_cast<uintptr_t>(status) & 3) == 0,
+                 "png_encode: the work space must be 16-byte, the offsets 8-byte, the status 4-byte aligned");
+  if (B == 0) return YOGO_OK;
+  const int nb = band_count(H);
+  if (level == 0) {
+    hipLaunchKernelGGL(png_band_kernel, dim3(nb, B), dim3(THREADS), 0, stream, pixels, H, W, bpp, work, (long long)per_image);
+    YOGO_CHECK_LAUNCH("png_encode (bands)");
+  } else if (int rc = yogo_png_band_matches_launch(pixels, B, H, W, bpp, work, (long long)per_image, stream)) {
+    return rc;
+  }
+  hipLaunchKernelGGL(png_assemble_kernel, dim3(B), dim3(THREADS), 0, stream, work, (long long)per_image, B, H, W, bpp, files, slot_bytes,
+                     packed, offsets, status);
+  YOGO_CHECK_LAUNCH("png_encode (assembly)");
+  if (yogo_launch_log_enabled()) {
+    if (level == 0) yogo_launch_log("png_band_kernel | B=%d image=%dx%dx%d bands=%d", B, H, W, bpp, nb);
+    yogo_launch_log("png_assemble_kernel | B=%d slot=%lld packed=%d", B, slot_bytes, packed);
+  }
   return YOGO_OK;
 }
 
 extern "C" int yogo_png_encode(const unsigned char* pixels, int B, int H, int W, int bpp, unsigned char* files, long long slot_bytes,
                                int packed, long long* offsets, int* status, unsigned char* work, long long work_bytes,
                                hipStream_t stream) {
-  YOGO_CHECK_ARG(pixels && files && offsets && status && work, "png_encode: null argument");
-  YOGO_CHECK_ARG(B >= 0 && B <= 65535, "png_encode: B = %d images, at most 65535 per call", B);
-  size_t bound = 0, per_image = 0;
-  if (int rc = yogo_png_encode_bound(H, W, bpp, &bound, &per_image)) return rc;
-  YOGO_CHECK_ARG(slot_bytes >= 0 && (packed == 0 || packed == 1), "png_encode: bad slot size or packed flag");
-  YOGO_CHECK_ARG(work_bytes >= (long long)B * (long long)per_image, "png_encode: %lld bytes of work space, %d images need %lld", work_bytes, B,
-                 (long long)B * (long long)per_image);
-  YOGO_CHECK_ARG((reinterpret_cast<uintptr_t>(work) & 15) == 0 && (reinterpret_cast<uintptr_t>(offsets) & 7) == 0 &&
-                     (reinterpret_cast<uintptr_t>(status) & 3) == 0,
-                 "png_encode: the work space must be 16-byte, the offsets 8-byte, the status 4-byte aligned");
-  if (B == 0) return YOGO_OK;
-  const int nb = band_count(H);
-  hipLaunchKernelGGL(png_band_kernel, dim3(nb, B), dim3(THREADS), 0, stream, pixels, H, W, bpp, work, (long long)per_image);
-  YOGO_CHECK_LAUNCH("png_encode (bands)");
-  hipLaunchKernelGGL(png_assemble_kernel, dim3(B), dim3(THREADS), 0, stream, work, (long long)per_image, B, H, W, bpp, files, slot_bytes,
-                     packed, offsets, status);
-  YOGO_CHECK_LAUNCH("png_encode (assembly)");
-  if (yogo_launch_log_enabled()) {
-    yogo_launch_log("png_band_kernel | B=%d image=%dx%dx%d bands=%d", B, H, W, bpp, nb);
-    yogo_launch_log("png_assemble_kernel | B=%d slot=%lld packed=%d", B, slot_bytes, packed);
-  }
-  return YOGO_OK;
+  return yogo_png_encode_level(pixels, B, H, W, bpp, 0, files, slot_bytes, packed, offsets, status, work, work_bytes, stream);
 }

@@ -177,30 +177,39 @@ def render_boxes(images: torch.Tensor, rows: torch.Tensor, counts: torch.Tensor,
     return out
 
 
-def encode_bound(H: int, W: int, bpp: int = 4) -> Tuple[int, int]:
-    """(bytes of a file slot, bytes of work space per image) of ``yogo_png_encode`` (``yogo_png_encode_bound``; runs on the host)"""
+def check_level(level) -> int:
+    from yogo_amd.png_encode import LEVELS
+
+    if isinstance(level, bool) or not isinstance(level, int) or level not in LEVELS:
+        raise ValueError(f"the PNG encoder's level must be one of {LEVELS} (0: literals only, 1: literals and matches), got {level!r}")
+    return level
+
+
+def encode_bound(H: int, W: int, bpp: int = 4, level: int = 0) -> Tuple[int, int]:
+    """(bytes of a file slot, bytes of work space per image) of ``yogo_png_encode_level`` (``yogo_png_encode_bound_level``; runs on
+    the host).  The slot is the same at every level; level 1 keeps a band's filtered bytes and tokens in the work space."""
     import ctypes
 
     from yogo_amd import _hip
 
     slot, work = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    _hip.call("yogo_png_encode_bound", int(H), int(W), int(bpp), ctypes.addressof(slot), ctypes.addressof(work))
+    _hip.call("yogo_png_encode_bound_level", int(H), int(W), int(bpp), check_level(level), ctypes.addressof(slot), ctypes.addressof(work))
     return int(slot.value), int(work.value)
 
 
 def encode_png(pixels: torch.Tensor, files: Optional[torch.Tensor] = None, work: Optional[torch.Tensor] = None, packed: bool = False,
-               slot_bytes: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+               slot_bytes: Optional[int] = None, level: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """pixels [B, H, W, bpp] uint8 on the device -> (files uint8, offsets int64 [B + 1], status int32 [B]).  File b is
     ``files[offsets[b]: offsets[b + 1]]`` when `packed`, else ``files[b * slot: b * slot + offsets[b + 1] - offsets[b]]`` in its own
-    slot of `slot_bytes` (default: the bound); a nonzero status means the image has no file (length 0).  Two launches: the bands,
-    then the assembly."""
+    slot of `slot_bytes` (default: the bound); a nonzero status means the image has no file (length 0).  `level` 0 codes literals
+    only, 1 literals and matches (yogo_amd/png_encode.py); the work space is sized by it.  Two launches: the bands, then the assembly."""
     from yogo_amd import _hip
 
     _hip.require_cuda(pixels, "the pixels to encode")
     if pixels.ndim != 4 or pixels.dtype != torch.uint8 or not 1 <= pixels.shape[3] <= 4 or not pixels.is_contiguous():
         raise ValueError(f"pixels must be contiguous uint8 [B, H, W, 1 .. 4], got {pixels.dtype} {tuple(pixels.shape)}")
     B, H, W, bpp = (int(v) for v in pixels.shape)
-    bound, work_per = encode_bound(H, W, bpp)
+    bound, work_per = encode_bound(H, W, bpp, level)
     slot = bound if slot_bytes is None else int(slot_bytes)
     dev = pixels.device
     if files is None:
@@ -208,13 +217,13 @@ def encode_png(pixels: torch.Tensor, files: Optional[torch.Tensor] = None, work:
     if work is None:
         work = torch.empty(max(B * work_per, 16), dtype=torch.uint8, device=dev)
     if files.numel() < B * slot or work.numel() < B * work_per:
-        raise ValueError(f"encode_png: {B} images need {B * slot} bytes of files and {B * work_per} of work space")
+        raise ValueError(f"encode_png: {B} images need {B * slot} bytes of files and {B * work_per} of work space at level {level}")
     offsets = torch.empty(B + 1, dtype=torch.int64, device=dev)
     status = torch.empty(max(B, 1), dtype=torch.int32, device=dev)[:B]
     if B:
         with torch.cuda.device(dev):
-            _hip.call("yogo_png_encode", pixels, B, H, W, bpp, files, slot, int(bool(packed)), offsets, status, work, int(work.numel()),
-                      _hip.stream_ptr())
+            _hip.call("yogo_png_encode_level", pixels, B, H, W, bpp, level, files, slot, int(bool(packed)), offsets, status, work,
+                      int(work.numel()), _hip.stream_ptr())
     else:
         offsets.zero_()
     return files, offsets, status
@@ -234,9 +243,13 @@ def _save_pil(path: Path, rgba: np.ndarray) -> None:
 class DrawSink:
     """Owns what a batch of drawn images needs -- the RGBA frames, the file slots, the encoder's work space, the writer pool -- and
     reuses it from batch to batch.  The buffers are allocated at the first batch for its size (B frames of 4 H W bytes, B slots of
-    about as many and as much work space again: at 772 x 1032 and B = 256 three times 0.8 GB) and are kept until ``close()``."""
+    about as many and as much work space again: at 772 x 1032 and B = 256 three times 0.8 GB; at `level` 1 the work space is four
+    times that, 3.3 GB) and are kept until ``close()``."""
 
-    def __init__(self, device, labels: Sequence[str], normalised: bool, output_dir, filetype: str = ".png") -> None:
+    def __init__(self, device, labels: Sequence[str], normalised: bool, output_dir, filetype: str = ".png", level: int = 0) -> None:
+        self.level = check_level(level)
+        if self.level and filetype != ".png":
+            raise ValueError(f"level {level} is the PNG encoder's: nothing is encoded for {filetype} files")
         self.device = torch.device(device)
         self.glyphs = GlyphAtlas(labels)
         self.atlas: Optional[DeviceAtlas] = None   # uploaded at the first batch: the colours depend on its channel count
@@ -252,7 +265,7 @@ class DrawSink:
         if self.rgba is None or self.rgba.shape[0] < B or tuple(self.rgba.shape[1:3]) != (H, W):
             self.rgba = torch.empty(B, H, W, 4, dtype=torch.uint8, device=self.device)
             if self.filetype == ".png":
-                slot, work = encode_bound(H, W, 4)
+                slot, work = encode_bound(H, W, 4, self.level)
                 self.files = torch.empty(B * slot, dtype=torch.uint8, device=self.device)
                 self.work = torch.empty(B * work, dtype=torch.uint8, device=self.device)
 
@@ -274,7 +287,7 @@ class DrawSink:
             self._wait()
             self.pending = [self.pool.submit(_save_pil, p, host[k]) for k, p in enumerate(paths)]
             return
-        _, offsets, status = encode_png(rgba, self.files, self.work, packed=True)
+        _, offsets, status = encode_png(rgba, self.files, self.work, packed=True, level=self.level)
         head = torch.cat([offsets, status.to(torch.int64)]).cpu().numpy()
         off, st = head[: B + 1], head[B + 1:]
         data = self.files[: int(off[B])].cpu().numpy()

@@ -80,7 +80,16 @@ def predict(
     device_image_decode: bool = False,
     device_image_decode_all: bool = False,
     device_draw: bool = False,
+    device_draw_level: int = 0,
 ) -> Optional[torch.Tensor]:
+    if device_draw_level != 0:   # (0 is valid everywhere: it asks for nothing)
+        from yogo_amd.draw import check_level
+
+        check_level(device_draw_level)
+        if not device_draw:
+            raise ValueError("device_draw_level is the level of device_draw's PNG encoder: it needs device_draw")
+        if output_img_ftype != ".png":
+            raise ValueError(f"device_draw_level is the level of the PNG encoder: nothing is encoded for {output_img_ftype} files")
     if device_draw:   # (before anything touches a device or the output directory)
         from yogo_amd.draw import check_labels
 
@@ -169,7 +178,7 @@ def predict(
         from yogo_amd.draw import DrawSink
 
         draw_sink = DrawSink(device, class_names or [str(c) for c in range(num_classes)], bool(model.normalize_images), output_dir,
-                             output_img_ftype)
+                             output_img_ftype, level=device_draw_level)
 
     def drain_txt() -> None:
         # the files' bytes come ready from the device (PredictionSink.drain_text: what prediction_rows_to_text gives, byte for byte)
@@ -288,4 +297,5 @@ def do_infer(args) -> None:
         min_class_confidence_threshold=args.min_class_confidence_threshold, half=args.half, device_outputs=args.device_outputs,
         device_image_decode=args.device_image_decode, device_image_decode_all=args.device_image_decode_all,
         device_draw=args.device_draw,
+        device_draw_level=args.device_draw_level,
     )

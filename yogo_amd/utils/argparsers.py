@@ -114,6 +114,10 @@ def _device_draw_needs(ns):
         return "--device-draw writes files: it needs --output-dir (showing the images interactively stays on the host)"
     if ns.device_draw and any("\n" in n or "\r" in n for n in (ns.class_names or [])):
         return "--device-draw: a class name contains a line break; PIL lays such text out as several lines, which the device route does not do"
+    if ns.device_draw_level != 0 and not ns.device_draw:
+        return "--device-draw-level is the level of --device-draw's PNG encoder: it needs --device-draw"
+    if ns.device_draw_level != 0 and ns.output_img_filetype != ".png":
+        return f"--device-draw-level is the level of the PNG encoder: nothing is encoded for {ns.output_img_filetype} files"
     return None
 
 
@@ -248,6 +252,10 @@ def infer_parser(parser=None):
                              "batch, instead of PIL on the host image by image; the files decode to the same pixels, their bytes are "
                              "compressed differently.  With --output-img-filetype .tif / .tiff only the drawing moves: an uncompressed "
                              "TIFF has nothing to encode, PIL writes the file from the pixels read back (default: False)")
+    parser.add_argument("--device-draw-level", type=int, choices=[0, 1], default=0,
+                        help="with --device-draw and PNG output: 0 codes every band of a file as Huffman-coded literals, 1 adds LZ77 "
+                             "matches -- smaller files, so less to read back and write, for a longer encode launch and four times the "
+                             "encoder's work space (default: 0)")
     parser.add_argument("--output-dir", type=Path, default=None,
                         help="path to directory for results, either --draw-boxes or --save-preds")
     parser.add_argument("--class-names", help="list of class names - will default to integers if not provided", nargs="*", type=str, default=None)
