@@ -383,7 +383,11 @@ int yogo_conv_first_mfma_signs(const void* in, const float* w, const float* bias
                                const float* invstd, const float* gamma, const float* beta, int B, int Cout, int IH, int IW, int act,
                                yogo_stream_t stream);
 int yogo_conv_first_bn_wgrad_xs_supported(int in_dtype, int Cin, int Cout, int IH, int IW, int stride, int act);
-/* (both sweeps take two adjacent pixels per lane where the output width is even, one otherwise) */
+/* (both sweeps take two adjacent pixels per lane where the output width is even, one otherwise)
+ * Image alignment: no sweep of the yogo_conv_first_bn_wgrad_bf16* family loads wider than `in` is aligned.  The two-pixel sweep reads
+ * aligned dwords and runs only when in % 4 == 0; the one-pixel sweeps read 16-bit words and need in % 2 == 0; _bf16 and _bf16_xg fall
+ * back to their byte-wise kernel for an odd address (same sums).  _xs has no byte-wise route: an image at an odd address is REFUSED
+ * (YOGO_ERR_ARG, "aligned to 2 bytes"); at in % 4 == 2 it runs the one-pixel sweep. */
 int yogo_conv_first_bn_wgrad_bf16_xs(const void* in, int in_dtype, const void* g, const void* signs, const float* mean,
                                      const float* invstd, const float* gamma, const float* beta, float* part, int B, int Cin,
                                      int Cout, int IH, int IW, int stride, int act, yogo_stream_t stream);

@@ -8,6 +8,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _first_layer_ref import sign_bits as _sign_bits   # (the sign map's bit layout: stated once, next to the first layer's fp64 restatement)
+
 pytestmark = pytest.mark.gpu
 
 NJ, PER = 9, 20
@@ -17,17 +19,6 @@ def _to8c(t):
     """fp32 NCHW [B][C][H][W] (C a multiple of 8) -> bf16 NCHW8c [B][C/8][H][W][8]"""
     B, C, H, W = t.shape
     return t.reshape(B, C // 8, 8, H, W).permute(0, 1, 3, 4, 2).contiguous().to(torch.bfloat16)
-
-
-def _sign_bits(signs_u8, H, W):
-    """[B][H*W][2] bytes -> bool [B][16][H][W]: byte h of a pixel: bit i = channel 4h + i, bit 4 + i = channel 8 + 4h + i (include/yogo_hip.h)"""
-    s = signs_u8.reshape(-1, H, W, 2).to(torch.int32)
-    out = torch.zeros(s.shape[0], 16, H, W, dtype=torch.bool)
-    for h in range(2):
-        for i in range(4):
-            out[:, 4 * h + i] = ((s[..., h] >> i) & 1).bool()
-            out[:, 8 + 4 * h + i] = ((s[..., h] >> (4 + i)) & 1).bool()
-    return out
 
 
 def _run_pair(h, g8, pk, img, signs, B, H, W, act0, fused, x8=None, clip=0.0):

@@ -1011,13 +1011,19 @@ static int conv_first_bn_wgrad_impl(const void* in, int in_dtype, const void* g,
   dim3 grid(first_wgrad_tiles(p.OH, p.OW), B);
   const bool fast = conv_first_fast_shape(in_dtype, Cin, IH, IW, stride);
   p.m_ow2 = p.OW >= 4 ? (unsigned)(((1ull << 32) + (unsigned)(p.OW / 2) - 1ull) / (unsigned)(p.OW / 2)) : 0u;
-  if (z == nullptr && p.OW % 2 == 0 && p.OW >= 4 && p.m_ow != 0 && plan_first_bn_wgrad_pairs())   // (yogo_conv_first_bn_wgrad_bf16_xs checked the shape)
+  // No load is wider than the image pointer's alignment (every image and row offset of these shapes is a multiple of 4 bytes where
+  // OW is even, of 2 otherwise): pk2 reads aligned dwords, pk and the generic FAST kernel 16-bit words; a less aligned image takes the
+  // next narrower route, down to the byte-wise generic kernel.  The sign-map sweep has no byte-wise route: refused.
+  const uintptr_t ia = reinterpret_cast<uintptr_t>(in);
+  const bool al4 = (ia & 3) == 0, al2 = (ia & 1) == 0;
+  YOGO_CHECK_ARG(z != nullptr || al2, "conv_first_bn_wgrad_bf16_xs: the image must be aligned to 2 bytes (the sign-map sweep has no byte-wise route)");
+  if (z == nullptr && al4 && p.OW % 2 == 0 && p.OW >= 4 && p.m_ow != 0 && plan_first_bn_wgrad_pairs())   // (yogo_conv_first_bn_wgrad_bf16_xs checked the shape)
     hipLaunchKernelGGL(conv_first_bn_wgrad_pk2_kernel, grid, dim3(CF_THREADS), 0, stream, p);
   else if (z == nullptr)
     hipLaunchKernelGGL(conv_first_bn_wgrad_pk_kernel<true>, grid, dim3(CF_THREADS), 0, stream, p);
-  else if (fast && ext_gram && Cout % 8 == 0 && (act == ACT_NONE || act == ACT_LEAKY))
+  else if (fast && al2 && ext_gram && Cout % 8 == 0 && (act == ACT_NONE || act == ACT_LEAKY))
     hipLaunchKernelGGL(conv_first_bn_wgrad_pk_kernel<false>, grid, dim3(CF_THREADS), 0, stream, p);
-  else if (fast)
+  else if (fast && al2)
     hipLaunchKernelGGL((conv_first_bn_wgrad_kernel<uint8_t, 1, 8, true, true>), grid, dim3(CF_THREADS), 0, stream, p);
   else if (in_dtype == 0 && Cin == 1) hipLaunchKernelGGL((conv_first_bn_wgrad_kernel<uint8_t, 1, 8, true>), grid, dim3(CF_THREADS), 0, stream, p);
   else if (in_dtype == 0) hipLaunchKernelGGL((conv_first_bn_wgrad_kernel<uint8_t, 3, 2, false>), grid, dim3(CF_THREADS), 0, stream, p);

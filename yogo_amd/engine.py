@@ -504,7 +504,8 @@ def _first_mfma_fwd_bf16(eng: Engine, L: Layer, S: Saved, bias, bn_train: bool, 
         mean = bn.running_mean
     # sweep 2: the convolution again, y = act(BatchNorm(z)) and what backward needs of z: its sign map when the fused backward
     # sweep can take that (it derives everything else from its own sums), else z itself
-    no_z = (_L0_NO_Z and _FUSE_LAYER0_BWD and S.gram is not None and L.conv.bias is None
+    # (the sign-map sweep has no byte-wise route: a batch at an odd address -- a view into a byte buffer -- keeps z)
+    no_z = (_L0_NO_Z and _FUSE_LAYER0_BWD and S.gram is not None and L.conv.bias is None and cur.data_ptr() % 2 == 0
             and _hip.lib().yogo_conv_first_bn_wgrad_xs_supported(0, L.cin, L.cout, H, W, L.s, L.act))
     if no_z:
         out8 = None
