@@ -292,7 +292,7 @@ def test_conv_first_fwd_bf16_against_float64(Cin, as_float):
     st = _hip.stream_ptr()
     B = 2
     worst = 0.0
-    for (H, W) in ((37, 53), (9, 7)):
+    for (H, W) in ((37, 53), (9, 7), (1, 1), (2, 1)):   # (the last two: every tap but the centre is padding; stride 2 leaves one output)
         g = torch.Generator().manual_seed(H * 100 + Cin)
         n = B * Cin * H * W
         esz = 4 if as_float else 1

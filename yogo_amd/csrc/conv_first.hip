@@ -5,18 +5,16 @@
 // K = 9*Cin is far too short for the matrix cores and the layer is HBM-bound (0.8 MB in, 12.75 MB out per
 // image at 772x1032): a direct VALU kernel, one output pixel per lane (coalesced NCHW stores per channel),
 // weights through the scalar cache, BatchNorm partial sums carried in registers across the thread's pixels.
-#include "common.h"
+#include "conv_first_dev.h"
+#include "conv_bf16_plan.h"
 #include "plan_switches.h"
 
 #define CF_THREADS 256
 #define CF_PPT 4       // pixels per thread
 #define CF_COCHUNK 16  // output channels per register pass
 
-typedef __bf16 cf_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int cf_u32x4 __attribute__((ext_vector_type(4)));
-
 struct ConvFirstParams {
-  cf_u32x4* out_bf16;      // when set: output goes to bf16 NCHW8c [B][Mb][OH][OW] units instead of `out`
+  u32x4* out_bf16;         // conv_first_train_bf16_kernel: the output, bf16 NCHW8c [B][Mb][OH][OW] units
   int Mb;
   const void* in;
   const float* w;          // OIHW [Cout][Cin][3][3]
@@ -27,6 +25,15 @@ struct ConvFirstParams {
   float* stats_part;       // optional [B*gridDim.x][Cout][2]
   int B, Cin, Cout, IH, IW, OH, OW, stride, act;
 };
+
+// BatchNorm partial sums of a 16-channel pass, red[wave][2 * c + {0: sum, 1: sum of squares}] -> this workgroup's row of stats_part
+__device__ __forceinline__ void cf_stats_store(const float (&red)[4][2 * CF_COCHUNK], const ConvFirstParams& p, int co0, int b, int tid) {
+  if (tid < 2 * CF_COCHUNK) {
+    const int c = tid >> 1;
+    if (co0 + c < p.Cout)
+      p.stats_part[((size_t)(b * gridDim.x + blockIdx.x) * p.Cout + co0 + c) * 2 + (tid & 1)] = cf_sum4(red, tid);
+  }
+}
 
 template <typename TIn, int CIN>
 __global__ __launch_bounds__(CF_THREADS) void conv_first_kernel(const ConvFirstParams p) {
@@ -49,22 +56,14 @@ __global__ __launch_bounds__(CF_THREADS) void conv_first_kernel(const ConvFirstP
       const int oy = ok ? pix / p.OW : 0;
       const int ox = ok ? pix - oy * p.OW : 0;
       float x[CIN * 9];
-#pragma unroll
-      for (int ci = 0; ci < CIN; ++ci)
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-          for (int kw = 0; kw < 3; ++kw) {
-            const int iy = oy * p.stride + kh - 1, ix = ox * p.stride + kw - 1;
-            float v = 0.f;
-            if (ok && iy >= 0 && iy < p.IH && ix >= 0 && ix < p.IW) v = (float)inb[((size_t)ci * p.IH + iy) * p.IW + ix];
-            x[(ci * 3 + kh) * 3 + kw] = v;
-          }
-      float vout[CF_COCHUNK];
+      // The form per image type is measured (us per launch to 16 channels at stride 2: select form / branch form / this kernel before it
+      // took either helper): uint8 grey 8 x 772 x 1032 83.6 / 90.8 / 101.0, uint8 rgb 4 x 386 x 516 47.9 / 52.1 / 51.9, fp32 grey
+      // 4 x 386 x 516 33.0 / 30.8 / 33.1, fp32 rgb 47.4 / 43.4 / 44.7
+      if constexpr (std::is_same_v<TIn, float>) cf_gather_branch<CIN>(x, inb, p, ok, oy, ox);
+      else cf_gather<CIN>(x, inb, p, ok, oy, ox);
 #pragma unroll
       for (int c = 0; c < CF_COCHUNK; ++c) {
         const int co = co0 + c;
-        vout[c] = 0.f;
         if (co < p.Cout) {  // uniform
           float acc = 0.f;
 #pragma unroll
@@ -72,48 +71,21 @@ __global__ __launch_bounds__(CF_THREADS) void conv_first_kernel(const ConvFirstP
           if (p.bias != nullptr) acc += p.bias[co];
           float v = act_fwd(acc, p.act);
           if (p.chan_scale != nullptr) v *= p.chan_scale[(size_t)b * p.Cout + co];
-          vout[c] = v;
           if (ok) {
             s[c] += acc;
             q[c] += acc * acc;
-            if (p.out_bf16 == nullptr) {
-              const size_t idx = ((size_t)b * p.Cout + co) * npix + pix;
-              if (p.out_pre != nullptr) p.out_pre[idx] = acc;
-              p.out[idx] = v;
-            }
-          }
-        }
-      }
-      if (p.out_bf16 != nullptr && ok) {  // two 16-byte units (8 channels each) per pixel and 16-channel pass
-#pragma unroll
-        for (int hb = 0; hb < 2; ++hb) {
-          const int cb = (co0 >> 3) + hb;
-          if (cb < p.Mb) {
-            cf_bf16x8 o;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = (__bf16)vout[hb * 8 + j];
-            p.out_bf16[((size_t)b * p.Mb + cb) * npix + pix] = __builtin_bit_cast(cf_u32x4, o);
+            const size_t idx = ((size_t)b * p.Cout + co) * npix + pix;
+            if (p.out_pre != nullptr) p.out_pre[idx] = acc;
+            p.out[idx] = v;
           }
         }
       }
     }
     if (p.stats_part != nullptr) {
 #pragma unroll
-      for (int c = 0; c < CF_COCHUNK; ++c) {
-        const float ss = wave_sum(s[c]), qq = wave_sum(q[c]);
-        if (lane == 0) {
-          red[wave][2 * c] = ss;
-          red[wave][2 * c + 1] = qq;
-        }
-      }
+      for (int c = 0; c < CF_COCHUNK; ++c) cf_wave_put2(red[wave], lane, 2 * c, s[c], q[c]);
       __syncthreads();
-      if (tid < 2 * CF_COCHUNK) {
-        const int c = tid >> 1;
-        if (co0 + c < p.Cout) {
-          const float v = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
-          p.stats_part[((size_t)(b * gridDim.x + blockIdx.x) * p.Cout + co0 + c) * 2 + (tid & 1)] = v;
-        }
-      }
+      cf_stats_store(red, p, co0, b, tid);
       __syncthreads();
     }
   }
@@ -173,12 +145,7 @@ __global__ __launch_bounds__(CF_THREADS) void conv_first_train_bf16_kernel(const
           const int j = (ci * 3 + kh) * 3 + kw;
           float x[CF_PPT];
 #pragma unroll
-          for (int k = 0; k < CF_PPT; ++k) {
-            const int iy = oy[k] * p.stride + kh - 1, ix = ox[k] * p.stride + kw - 1;
-            const bool in = iy >= 0 && iy < p.IH && ix >= 0 && ix < p.IW;
-            const float v = (float)inb[in ? ((size_t)ci * p.IH + iy) * p.IW + ix : 0];
-            x[k] = in ? v : 0.f;
-          }
+          for (int k = 0; k < CF_PPT; ++k) x[k] = cf_tap(inb, p, true, oy[k], ox[k], ci, kh, kw);   // (a tail pixel reads pixel 0's patch)
 #pragma unroll
           for (int c4 = 0; c4 < CF_COCHUNK; c4 += 4) {
             const float4 wv = *reinterpret_cast<const float4*>(&wsh[j][c4]);
@@ -202,11 +169,7 @@ __global__ __launch_bounds__(CF_THREADS) void conv_first_train_bf16_kernel(const
           sc += vm;
           qc += vm * vm;
         }
-        const float ss = wave_sum(sc), qq = wave_sum(qc);
-        if (lane == 0) {
-          red[wave][2 * c] = ss;
-          red[wave][2 * c + 1] = qq;
-        }
+        cf_wave_put2(red[wave], lane, 2 * c, sc, qc);
       }
     }
     // activation + channel scale + bf16 store
@@ -220,7 +183,7 @@ __global__ __launch_bounds__(CF_THREADS) void conv_first_train_bf16_kernel(const
       for (int hb = 0; hb < 2; ++hb) {
         const int cb = (co0 >> 3) + hb;
         if (cb < p.Mb && okk[k]) {
-          cf_bf16x8 o;
+          bf16x8 o;
           if (p.act == ACT_NONE) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) o[j] = (__bf16)(acc[k][hb * 8 + j] * cs[hb * 8 + j]);
@@ -228,19 +191,13 @@ __global__ __launch_bounds__(CF_THREADS) void conv_first_train_bf16_kernel(const
 #pragma unroll
             for (int j = 0; j < 8; ++j) o[j] = (__bf16)(act_fwd(acc[k][hb * 8 + j], p.act) * cs[hb * 8 + j]);
           }
-          p.out_bf16[((size_t)b * p.Mb + cb) * npix + pix] = __builtin_bit_cast(cf_u32x4, o);
+          p.out_bf16[((size_t)b * p.Mb + cb) * npix + pix] = __builtin_bit_cast(u32x4, o);
         }
       }
     }
     if (p.stats_part != nullptr) {
       __syncthreads();
-      if (tid < 2 * CF_COCHUNK) {
-        const int c = tid >> 1;
-        if (co0 + c < p.Cout) {
-          const float v = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
-          p.stats_part[((size_t)(b * gridDim.x + blockIdx.x) * p.Cout + co0 + c) * 2 + (tid & 1)] = v;
-        }
-      }
+      cf_stats_store(red, p, co0, b, tid);
     }
   }
 }
@@ -248,13 +205,21 @@ __global__ __launch_bounds__(CF_THREADS) void conv_first_train_bf16_kernel(const
 // dW[co][ci][kh][kw] = sum_{b,pix} dy[b][co][pix] * x[b][ci][pix*stride + tap]; db likewise without x.
 // One workgroup per (pixel tile, image); partials [rows][Cout][CIN*9 + 1] are summed by channel_partials_reduce.
 struct ConvFirstWgradParams {
-  const cf_u32x4* dy_bf16;  // when set: gradient in bf16 NCHW8c [B][Mb][OH][OW] units
+  const u32x4* dy_bf16;  // when set: gradient in bf16 NCHW8c [B][Mb][OH][OW] units
   int Mb;
   const void* in;
   const float* dy;    // [B][Cout][OH][OW] (already multiplied by act'/mask)
   float* part;        // [B*gridDim.x][Cout][CIN*9+1]
   int B, Cin, Cout, IH, IW, OH, OW, stride;
 };
+
+// channel idx (wave-uniform, not a compile-time constant) of a unit: a select chain, not an indexed read of the register vector
+__device__ __forceinline__ float cf_pick(bf16x8 u, int idx) {
+  float sel = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) sel = idx == j ? (float)u[j] : sel;
+  return sel;
+}
 
 #define CFW_PPT 32  // pixels per thread of the weight-gradient kernels (accumulators live in registers across them; the
                     // cross-lane reductions at the end cost ~1800 instructions per wavefront, so fewer, longer workgroups)
@@ -283,36 +248,21 @@ __global__ __launch_bounds__(CF_THREADS) void conv_first_wgrad_kernel(const Conv
       const int pc = ok ? pix : 0;
       const int oy = pc / p.OW, ox = pc - oy * p.OW;
       float x[CIN * 9];
-#pragma unroll
-      for (int ci = 0; ci < CIN; ++ci)
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-          for (int kw = 0; kw < 3; ++kw) {
-            const int iy = oy * p.stride + kh - 1, ix = ox * p.stride + kw - 1;
-            const bool in = ok && iy >= 0 && iy < p.IH && ix >= 0 && ix < p.IW;
-            const float v = (float)inb[in ? ((size_t)ci * p.IH + iy) * p.IW + ix : 0];
-            x[(ci * 3 + kh) * 3 + kw] = in ? v : 0.f;
-          }
+      cf_gather<CIN>(x, inb, p, ok, oy, ox);
       float g[COC];
       if constexpr (BF16G) {
         if constexpr (COC == 16) {
 #pragma unroll
           for (int hb = 0; hb < 2; ++hb) {
             const int cb = min((co0 >> 3) + hb, p.Mb - 1);
-            const cf_bf16x8 u = __builtin_bit_cast(cf_bf16x8, p.dy_bf16[((size_t)b * p.Mb + cb) * npix + pc]);
+            const bf16x8 u = __builtin_bit_cast(bf16x8, p.dy_bf16[((size_t)b * p.Mb + cb) * npix + pc]);
 #pragma unroll
             for (int j = 0; j < 8; ++j) g[hb * 8 + j] = (ok && co0 + hb * 8 + j < p.Cout) ? (float)u[j] : 0.f;
           }
         } else {
-          const cf_bf16x8 u = __builtin_bit_cast(cf_bf16x8, p.dy_bf16[((size_t)b * p.Mb + (co0 >> 3)) * npix + pc]);
+          const bf16x8 u = __builtin_bit_cast(bf16x8, p.dy_bf16[((size_t)b * p.Mb + (co0 >> 3)) * npix + pc]);
 #pragma unroll
-          for (int c = 0; c < COC; ++c) {
-            float sel = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) sel = ((co0 & 7) + c == j) ? (float)u[j] : sel;
-            g[c] = (ok && co0 + c < p.Cout) ? sel : 0.f;
-          }
+          for (int c = 0; c < COC; ++c) g[c] = (ok && co0 + c < p.Cout) ? cf_pick(u, (co0 & 7) + c) : 0.f;
         }
       } else {
 #pragma unroll
@@ -332,15 +282,11 @@ __global__ __launch_bounds__(CF_THREADS) void conv_first_wgrad_kernel(const Conv
 #pragma unroll
     for (int c = 0; c < COC; ++c)
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const float v = wave_sum(acc[c][j]);
-        if (lane == 0) red[wave][c * NJ + j] = v;
-      }
+      for (int j = 0; j < NJ; ++j) cf_wave_put(red[wave], lane, c * NJ + j, acc[c][j]);
     __syncthreads();
     if (tid < COC * NJ) {
       const int c = tid / NJ, j = tid - c * NJ;
-      if (co0 + c < p.Cout)
-        p.part[((size_t)(b * gridDim.x + blockIdx.x) * p.Cout + co0 + c) * NJ + j] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+      if (co0 + c < p.Cout) p.part[((size_t)(b * gridDim.x + blockIdx.x) * p.Cout + co0 + c) * NJ + j] = cf_sum4(red, tid);
     }
     __syncthreads();
   }
@@ -358,8 +304,8 @@ __global__ __launch_bounds__(CF_THREADS) void conv_first_wgrad_kernel(const Conv
 // conv_first_bn_wgrad_finalize.
 struct ConvFirstBnWgradParams {
   const void* in;
-  const cf_u32x4* g;   // gradient w.r.t. the block output, bf16 NCHW8c [B][Mb][OH][OW]
-  const cf_u32x4* z;   // saved conv output (pre-BatchNorm), same layout
+  const u32x4* g;   // gradient w.r.t. the block output, bf16 NCHW8c [B][Mb][OH][OW]
+  const u32x4* z;   // saved conv output (pre-BatchNorm), same layout
   const unsigned short* signs;   // ... or (conv_first_bn_wgrad_pk_kernel<true>) the sign map of the BatchNorm output, yogo_conv_first_mfma_signs
   const float *mean, *invstd, *gamma, *beta;
   float* part;
@@ -387,6 +333,11 @@ __global__ __launch_bounds__(CF_THREADS, GRAM ? 3 : 2) void conv_first_bn_wgrad_
   const int ncol = p.Cout * PER + NJ + (GRAM ? NJ * NJ : 0);
   const TIn* inb = reinterpret_cast<const TIn*>(p.in) + (size_t)b * CIN * p.IH * p.IW;
   float* prow = p.part + (size_t)(b * gridDim.x + blockIdx.x) * ncol;
+// This kernel keeps its gather (as a macro for its two passes: the text of cf_gather_u8s2 / cf_gather) and its reduction open-coded, and
+// compiles to the instruction stream it had before conv_first_dev.h.  With the gather helpers (same values, same instruction count +-10,
+// same registers) the three-channel sweep of 4 x 386 x 516 images to 16 channels went from 363 to 441 us (uint8) and 444 us (fp32) and the
+// FAST one of 8 x 772 x 1032 from 101.8 to 102.8 us; open-coded in a lambda the three-channel sweep took 554 us; with the reduction
+// helpers alone 369 us.  (28 workgroups, one wavefront per SIMD: nothing hides the order hipcc gives the bounds tests.)
 // this lane's k-th pixel: validity, pixel index and the input patch (zero outside the image / beyond the tail)
 #define CFB_PIXEL(K)                                                                                       \
   const int pix = pbase + (K) * CF_THREADS + tid;                                                           \
@@ -489,8 +440,8 @@ __global__ __launch_bounds__(CF_THREADS, GRAM ? 3 : 2) void conv_first_bn_wgrad_
       CFB_PIXEL(k)
       // COC consecutive channels live inside one 8-channel unit (COC divides 8)
       const size_t u = ((size_t)b * p.Mb + (co0 >> 3)) * npix + pc;
-      const cf_bf16x8 gu = __builtin_bit_cast(cf_bf16x8, p.g[u]);
-      const cf_bf16x8 zu = __builtin_bit_cast(cf_bf16x8, p.z[u]);
+      const bf16x8 gu = __builtin_bit_cast(bf16x8, p.g[u]);
+      const bf16x8 zu = __builtin_bit_cast(bf16x8, p.z[u]);
 #pragma unroll
       for (int c = 0; c < COC; ++c) {
         float gv = 0.f, zv = 0.f;
@@ -579,12 +530,41 @@ __global__ __launch_bounds__(CF_THREADS, GRAM ? 3 : 2) void conv_first_bn_wgrad_
 // pass wrote that as one bit per value -- and through S2 = sum gb * xh, which is LINEAR in z = W . patch:
 //   sum gb * z = sum_j W[c][j] * A1[c][j]   =>   S2 = invstd * (W[c] . A1[c] - mean * S1)      (the finalize kernel, derive_s2)
 // so the layer's conv output is neither written by the forward pass nor read here (0.82 GB each way at 128 x 772 x 1032).
-typedef float cf_f32x2 __attribute__((ext_vector_type(2)));
+//
+// First what this kernel and the pair sweep below share, the end of a pass (8 channels as 4 pairs): cross-lane sums (DPP), then the four wavefronts through LDS, into
+// the column layout of conv_first_bn_wgrad_kernel.  s2 = nullptr: the S2 column is written as zero (derived by the finalize kernel).
+__device__ __forceinline__ void cf_pk_reduce_store(float (&red)[4][8 * 20], float* prow, int co0, const f32x2 (&a1)[4][9],
+                                                   const f32x2 (&s1)[4], const f32x2* s2) {
+  constexpr int NJ = 9, PER = 2 * NJ + 2, COC = 8, NP = COC / 2;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int q = 0; q < NP; ++q) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int c = 2 * q + h;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) cf_wave_put(red[wave], lane, c * PER + j, h ? a1[q][j].y : a1[q][j].x);
+      if (s2 != nullptr) {
+        cf_wave_put2(red[wave], lane, c * PER + 2 * NJ, h ? s1[q].y : s1[q].x, h ? s2[q].y : s2[q].x);
+      } else {
+        cf_wave_put(red[wave], lane, c * PER + 2 * NJ, h ? s1[q].y : s1[q].x);
+        if (lane == 0) red[wave][c * PER + 2 * NJ + 1] = 0.f;
+      }
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < COC * PER; e += CF_THREADS) {
+    const int c = e / PER, kk = e - c * PER;
+    if (!(kk >= NJ && kk < 2 * NJ)) prow[(co0 + c) * PER + kk] = cf_sum4(red, e);   // (the A2 columns come from the Gram matrix)
+  }
+  __syncthreads();
+}
+
 template <bool SIGNS>
 __global__ __launch_bounds__(CF_THREADS, 3) void conv_first_bn_wgrad_pk_kernel(const ConvFirstBnWgradParams p) {
   constexpr int NJ = 9, PER = 2 * NJ + 2, COC = 8, NP = COC / 2;
   __shared__ float red[4][COC * PER];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int b = blockIdx.y;
   const int npix = p.OH * p.OW;
   const int pbase = blockIdx.x * (CF_THREADS * CFW_PPT);
@@ -594,17 +574,17 @@ __global__ __launch_bounds__(CF_THREADS, 3) void conv_first_bn_wgrad_pk_kernel(c
   for (int e = tid; e < NJ + NJ * NJ; e += CF_THREADS) prow[p.Cout * PER + e] = 0.f;   // P / G: the finalize reads the caller's
   const bool leaky = p.act == ACT_LEAKY;   // (uniform; the launcher takes ACT_NONE / ACT_LEAKY only)
   for (int co0 = 0; co0 < p.Cout; co0 += COC) {
-    cf_f32x2 a1[NP][NJ], s1[NP], s2[NP], mu[NP], is[NP], ga[NP], be[NP];
+    f32x2 a1[NP][NJ], s1[NP], s2[NP], mu[NP], is[NP], ga[NP], be[NP];
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
       const int c = co0 + 2 * q;
-      mu[q] = cf_f32x2{p.mean[c], p.mean[c + 1]};
-      is[q] = cf_f32x2{p.invstd[c], p.invstd[c + 1]};
-      ga[q] = cf_f32x2{p.gamma[c], p.gamma[c + 1]};
-      be[q] = cf_f32x2{p.beta[c], p.beta[c + 1]};
-      s1[q] = s2[q] = cf_f32x2{0.f, 0.f};
+      mu[q] = f32x2{p.mean[c], p.mean[c + 1]};
+      is[q] = f32x2{p.invstd[c], p.invstd[c + 1]};
+      ga[q] = f32x2{p.gamma[c], p.gamma[c + 1]};
+      be[q] = f32x2{p.beta[c], p.beta[c + 1]};
+      s1[q] = s2[q] = f32x2{0.f, 0.f};
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) a1[q][j] = cf_f32x2{0.f, 0.f};
+      for (int j = 0; j < NJ; ++j) a1[q][j] = f32x2{0.f, 0.f};
     }
     for (int k = 0; k < CFW_PPT; ++k) {
       const int pix = pbase + k * CF_THREADS + tid;
@@ -615,80 +595,41 @@ __global__ __launch_bounds__(CF_THREADS, 3) void conv_first_bn_wgrad_pk_kernel(c
       //  arithmetic of pixel k -- 356 -> 426 us)
       const int oy = p.m_ow ? (int)__umulhi((unsigned)pc, p.m_ow) : pc / p.OW, ox = pc - oy * p.OW;
       float x[NJ];
-#pragma unroll
-      for (int kh = 0; kh < 3; ++kh) {
-        const int iy = 2 * oy + kh - 1;  // <= IH - 1 (even sizes)
-        const bool rok = ok && iy >= 0;
-        const int o_ = rok ? iy * p.IW + 2 * ox : 0;  // bytes o_ - 2 .. o_ + 1
-        const unsigned hi_ = *reinterpret_cast<const unsigned short*>(ib + o_);
-        const unsigned lo_ = *reinterpret_cast<const unsigned short*>(ib + ((rok && ox > 0) ? o_ - 2 : o_));
-        x[kh * 3 + 0] = (rok && ox > 0) ? (float)(lo_ >> 8) : 0.f;
-        x[kh * 3 + 1] = rok ? (float)(hi_ & 0xFFu) : 0.f;
-        x[kh * 3 + 2] = rok ? (float)(hi_ >> 8) : 0.f;
-      }
+      cf_gather_u8s2(x, ib, p.IW, ok, oy, ox);
       const size_t u = ((size_t)b * p.Mb + (co0 >> 3)) * npix + pc;
-      cf_u32x4 gw = p.g[u];
-      cf_u32x4 zw = {0u, 0u, 0u, 0u};
+      u32x4 gw = p.g[u];
+      u32x4 zw = {0u, 0u, 0u, 0u};
       unsigned sgn = 0;
       if constexpr (SIGNS) {
-        // the pixel's 16 bits: channel c < 4 or >= 12 at bit c, 4..7 at c + 4, 8..11 at c - 4 (two bytes in the forward kernel's lane order)
-        if (leaky) sgn = (unsigned)p.signs[(size_t)b * npix + pc] >> (co0 ? 4 : 0);
+        if (leaky) sgn = (unsigned)p.signs[(size_t)b * npix + pc] >> (co0 ? 4 : 0);   // (the bit order: cf_leaky_pair)
       } else {
         zw = p.z[u];
       }
-      if (!ok) gw = cf_u32x4{0u, 0u, 0u, 0u};   // a pixel beyond the tail contributes gb = 0 to every sum
+      if (!ok) gw = u32x4{0u, 0u, 0u, 0u};   // a pixel beyond the tail contributes gb = 0 to every sum
       const unsigned gws[4] = {gw.x, gw.y, gw.z, gw.w}, zws[4] = {zw.x, zw.y, zw.z, zw.w};
 #pragma unroll
       for (int q = 0; q < NP; ++q) {
-        // the two bf16 of a dword, widened: low half << 16, high half masked
-        const cf_f32x2 gv = {__builtin_bit_cast(float, gws[q] << 16), __builtin_bit_cast(float, gws[q] & 0xFFFF0000u)};
-        cf_f32x2 gb = gv;
+        const f32x2 gv = cf_widen(gws[q]);
+        f32x2 gb = gv;
         if constexpr (SIGNS) {
-          if (leaky) {
-            const int pos = q < 2 ? 2 * q : 8 + 2 * (q - 2);   // (a constant of the unrolled loop)
-            const cf_f32x2 f = {(sgn >> pos) & 1u ? 1.f : LEAKY_SLOPE, (sgn >> (pos + 1)) & 1u ? 1.f : LEAKY_SLOPE};
-            gb = gv * f;
-          }
+          if (leaky) gb = gv * cf_leaky_pair(sgn, q);
           s1[q] += gb;
         } else {
-          const cf_f32x2 zv = {__builtin_bit_cast(float, zws[q] << 16), __builtin_bit_cast(float, zws[q] & 0xFFFF0000u)};
-          const cf_f32x2 xh = (zv - mu[q]) * is[q];
+          const f32x2 zv = cf_widen(zws[q]);
+          const f32x2 xh = (zv - mu[q]) * is[q];
           if (leaky) {
-            const cf_f32x2 yb = __builtin_elementwise_fma(ga[q], xh, be[q]);
-            const cf_f32x2 f = {yb.x > 0.f ? 1.f : LEAKY_SLOPE, yb.y > 0.f ? 1.f : LEAKY_SLOPE};
+            const f32x2 yb = __builtin_elementwise_fma(ga[q], xh, be[q]);
+            const f32x2 f = {yb.x > 0.f ? 1.f : LEAKY_SLOPE, yb.y > 0.f ? 1.f : LEAKY_SLOPE};
             gb = gv * f;
           }
           s1[q] += gb;
           s2[q] = __builtin_elementwise_fma(gb, xh, s2[q]);
         }
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) a1[q][j] = __builtin_elementwise_fma(gb, cf_f32x2{x[j], x[j]}, a1[q][j]);
+        for (int j = 0; j < NJ; ++j) a1[q][j] = __builtin_elementwise_fma(gb, f32x2{x[j], x[j]}, a1[q][j]);
       }
     }
-    // cross-lane sums (DPP), then the four wavefronts through LDS -- the column layout of conv_first_bn_wgrad_kernel
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int c = 2 * q + h;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          const float v1 = wave_sum(h ? a1[q][j].y : a1[q][j].x);
-          if (lane == 0) red[wave][c * PER + j] = v1;
-        }
-        const float t1 = wave_sum(h ? s1[q].y : s1[q].x), t2 = wave_sum(h ? s2[q].y : s2[q].x);
-        if (lane == 0) {
-          red[wave][c * PER + 2 * NJ] = t1;
-          red[wave][c * PER + 2 * NJ + 1] = t2;
-        }
-      }
-    }
-    __syncthreads();
-    for (int e = tid; e < COC * PER; e += CF_THREADS) {
-      const int c = e / PER, kk = e - c * PER;
-      if (!(kk >= NJ && kk < 2 * NJ)) prow[(co0 + c) * PER + kk] = red[0][e] + red[1][e] + red[2][e] + red[3][e];   // (the A2 columns come from the Gram matrix)
-    }
-    __syncthreads();
+    cf_pk_reduce_store(red, prow, co0, a1, s1, SIGNS ? nullptr : s2);   // (SIGNS: S2 was never summed)
   }
 }
 
@@ -701,7 +642,7 @@ __global__ __launch_bounds__(CF_THREADS, 3) void conv_first_bn_wgrad_pk_kernel(c
 __global__ __launch_bounds__(CF_THREADS, 3) void conv_first_bn_wgrad_pk2_kernel(const ConvFirstBnWgradParams p) {
   constexpr int NJ = 9, PER = 2 * NJ + 2, COC = 8, NP = COC / 2;
   __shared__ float red[4][COC * PER];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int b = blockIdx.y;
   const int npix = p.OH * p.OW, npair = npix >> 1, ow2 = p.OW >> 1;
   const int qbase = blockIdx.x * (CF_THREADS * CFW_PPT / 2);
@@ -712,12 +653,12 @@ __global__ __launch_bounds__(CF_THREADS, 3) void conv_first_bn_wgrad_pk2_kernel(
   for (int e = tid; e < NJ + NJ * NJ; e += CF_THREADS) prow[p.Cout * PER + e] = 0.f;   // P / G: the finalize reads the caller's
   const bool leaky = p.act == ACT_LEAKY;   // (uniform)
   for (int co0 = 0; co0 < p.Cout; co0 += COC) {
-    cf_f32x2 a1[NP][NJ], s1[NP];
+    f32x2 a1[NP][NJ], s1[NP];
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
-      s1[q] = cf_f32x2{0.f, 0.f};
+      s1[q] = f32x2{0.f, 0.f};
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) a1[q][j] = cf_f32x2{0.f, 0.f};
+      for (int j = 0; j < NJ; ++j) a1[q][j] = f32x2{0.f, 0.f};
     }
     for (int k = 0; k < CFW_PPT / 2; ++k) {
       const int pr = qbase + k * CF_THREADS + tid;
@@ -742,53 +683,26 @@ __global__ __launch_bounds__(CF_THREADS, 3) void conv_first_bn_wgrad_pk2_kernel(
         x[1][kh * 3 + 2] = (float)(w >> 24);
       }
       const size_t u = ((size_t)b * p.Mb + (co0 >> 3)) * npix + 2 * (size_t)pc;
-      cf_u32x4 gw[2] = {p.g[u], p.g[u + 1]};
-      // a pixel's 16 sign bits: channel c < 4 or >= 12 at bit c, 4..7 at c + 4, 8..11 at c - 4; the pair's two words are one dword
+      u32x4 gw[2] = {p.g[u], p.g[u + 1]};
+      // the pair's two sign words (cf_leaky_pair) are one dword
       unsigned sg2 = leaky ? sgp[pc] >> (co0 ? 4 : 0) : 0u;
-      if (!ok) gw[0] = gw[1] = cf_u32x4{0u, 0u, 0u, 0u};   // a pair beyond the tail contributes gb = 0 to every sum
+      if (!ok) gw[0] = gw[1] = u32x4{0u, 0u, 0u, 0u};   // a pair beyond the tail contributes gb = 0 to every sum
 #pragma unroll
       for (int e = 0; e < 2; ++e) {
         const unsigned gws[4] = {gw[e].x, gw[e].y, gw[e].z, gw[e].w};
         const unsigned sgn = e ? sg2 >> 16 : sg2;
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
-          const cf_f32x2 gv = {__builtin_bit_cast(float, gws[q] << 16), __builtin_bit_cast(float, gws[q] & 0xFFFF0000u)};
-          cf_f32x2 gb = gv;
-          if (leaky) {
-            const int pos = q < 2 ? 2 * q : 8 + 2 * (q - 2);   // (a constant of the unrolled loop)
-            const cf_f32x2 f = {(sgn >> pos) & 1u ? 1.f : LEAKY_SLOPE, (sgn >> (pos + 1)) & 1u ? 1.f : LEAKY_SLOPE};
-            gb = gv * f;
-          }
+          const f32x2 gv = cf_widen(gws[q]);
+          f32x2 gb = gv;
+          if (leaky) gb = gv * cf_leaky_pair(sgn, q);
           s1[q] += gb;
 #pragma unroll
-          for (int j = 0; j < NJ; ++j) a1[q][j] = __builtin_elementwise_fma(gb, cf_f32x2{x[e][j], x[e][j]}, a1[q][j]);
+          for (int j = 0; j < NJ; ++j) a1[q][j] = __builtin_elementwise_fma(gb, f32x2{x[e][j], x[e][j]}, a1[q][j]);
         }
       }
     }
-    // cross-lane sums (DPP), then the four wavefronts through LDS -- the column layout of conv_first_bn_wgrad_kernel
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int c = 2 * q + h;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          const float v1 = wave_sum(h ? a1[q][j].y : a1[q][j].x);
-          if (lane == 0) red[wave][c * PER + j] = v1;
-        }
-        const float t1 = wave_sum(h ? s1[q].y : s1[q].x);
-        if (lane == 0) {
-          red[wave][c * PER + 2 * NJ] = t1;
-          red[wave][c * PER + 2 * NJ + 1] = 0.f;   // (S2: derived by the finalize kernel)
-        }
-      }
-    }
-    __syncthreads();
-    for (int e = tid; e < COC * PER; e += CF_THREADS) {
-      const int c = e / PER, kk = e - c * PER;
-      if (!(kk >= NJ && kk < 2 * NJ)) prow[(co0 + c) * PER + kk] = red[0][e] + red[1][e] + red[2][e] + red[3][e];   // (the A2 columns come from the Gram matrix)
-    }
-    __syncthreads();
+    cf_pk_reduce_store(red, prow, co0, a1, s1, nullptr);
   }
 }
 
@@ -846,21 +760,39 @@ static int first_wgrad_tiles(int OH, int OW) { return cdiv(OH * OW, CF_THREADS *
 // rows of the partial buffer the weight-gradient kernels fill
 extern "C" int yogo_conv_first_wgrad_rows(int B, int IH, int IW, int stride, int* rows) {
   YOGO_CHECK_ARG(rows && (stride == 1 || stride == 2), "conv_first_wgrad_rows: bad arguments");
-  const int OH = (IH - 1) / stride + 1, OW = (IW - 1) / stride + 1;
-  *rows = B * first_wgrad_tiles(OH, OW);
+  *rows = B * first_wgrad_tiles(cf_out_dim(IH, stride), cf_out_dim(IW, stride));
   return YOGO_OK;
 }
 
 extern "C" int yogo_conv_first_stats_rows(int B, int IH, int IW, int stride, int* rows) {
   YOGO_CHECK_ARG(rows && (stride == 1 || stride == 2), "conv_first_stats_rows: bad arguments");
-  const int OH = (IH - 1) / stride + 1, OW = (IW - 1) / stride + 1;
-  *rows = B * first_tiles(OH, OW);
+  *rows = B * first_tiles(cf_out_dim(IH, stride), cf_out_dim(IW, stride));
   return YOGO_OK;
 }
 
 static int conv_first_fwd_impl(const void* in, int in_dtype, const float* w, const float* bias, float* out, void* out_bf16,
                                float* out_pre, const float* chan_scale, float* stats_part, int B, int Cin, int Cout, int IH,
-                               int IW, int stride, int act, hipStream_t stream);
+                               int IW, int stride, int act, hipStream_t stream) {
+  YOGO_CHECK_ARG(in && w, "conv_first_fwd: null pointer");
+  YOGO_CHECK_ARG((Cin == 1 || Cin == 3) && Cout > 0 && IH > 0 && IW > 0 && (stride == 1 || stride == 2) && B >= 0,
+                 "conv_first_fwd: unsupported shape Cin=%d Cout=%d stride=%d", Cin, Cout, stride);
+  YOGO_CHECK_ARG(in_dtype == 0 || in_dtype == 1, "conv_first_fwd: in_dtype must be 0 (uint8) or 1 (float32)");
+  ConvFirstParams p{};
+  p.out_bf16 = reinterpret_cast<u32x4*>(out_bf16); p.Mb = bf_kb_of(Cout);
+  p.in = in; p.w = w; p.bias = bias; p.out = out; p.out_pre = out_pre; p.chan_scale = chan_scale; p.stats_part = stats_part;
+  p.B = B; p.Cin = Cin; p.Cout = Cout; p.IH = IH; p.IW = IW; p.stride = stride; p.act = act;
+  p.OH = cf_out_dim(IH, stride); p.OW = cf_out_dim(IW, stride);
+  if (B == 0) return YOGO_OK;
+  dim3 grid(first_tiles(p.OH, p.OW), B);
+  cf_dispatch(in_dtype, Cin, [&](auto tin, auto cin) {
+    using TIn = decltype(tin);
+    constexpr int CIN = decltype(cin)::value;
+    if (out_bf16 != nullptr) hipLaunchKernelGGL((conv_first_train_bf16_kernel<TIn, CIN>), grid, dim3(CF_THREADS), 0, stream, p);   // training, bf16 NCHW8c output
+    else hipLaunchKernelGGL((conv_first_kernel<TIn, CIN>), grid, dim3(CF_THREADS), 0, stream, p);
+  });
+  YOGO_CHECK_LAUNCH("conv_first_fwd");
+  return YOGO_OK;
+}
 
 // in_dtype: 0 = uint8, 1 = float32
 extern "C" int yogo_conv_first_fwd(const void* in, int in_dtype, const float* w, const float* bias, float* out,
@@ -880,38 +812,25 @@ extern "C" int yogo_conv_first_fwd_train_bf16(const void* in, int in_dtype, cons
                              act, stream);
 }
 
-static int conv_first_fwd_impl(const void* in, int in_dtype, const float* w, const float* bias, float* out, void* out_bf16,
-                               float* out_pre, const float* chan_scale, float* stats_part, int B, int Cin, int Cout, int IH,
-                               int IW, int stride, int act, hipStream_t stream) {
-  YOGO_CHECK_ARG(in && w, "conv_first_fwd: null pointer");
-  YOGO_CHECK_ARG((Cin == 1 || Cin == 3) && Cout > 0 && IH > 0 && IW > 0 && (stride == 1 || stride == 2) && B >= 0,
-                 "conv_first_fwd: unsupported shape Cin=%d Cout=%d stride=%d", Cin, Cout, stride);
-  YOGO_CHECK_ARG(in_dtype == 0 || in_dtype == 1, "conv_first_fwd: in_dtype must be 0 (uint8) or 1 (float32)");
-  ConvFirstParams p{};
-  p.out_bf16 = reinterpret_cast<cf_u32x4*>(out_bf16); p.Mb = ((Cout + 15) / 16) * 2;
-  p.in = in; p.w = w; p.bias = bias; p.out = out; p.out_pre = out_pre; p.chan_scale = chan_scale; p.stats_part = stats_part;
-  p.B = B; p.Cin = Cin; p.Cout = Cout; p.IH = IH; p.IW = IW; p.stride = stride; p.act = act;
-  p.OH = (IH - 1) / stride + 1; p.OW = (IW - 1) / stride + 1;
+static int conv_first_wgrad_impl(const void* in, int in_dtype, const float* dy, const void* dy_bf16, float* part, int B, int Cin,
+                                 int Cout, int IH, int IW, int stride, hipStream_t stream) {
+  YOGO_CHECK_ARG(in && part, "conv_first_wgrad: null pointer");
+  YOGO_CHECK_ARG((Cin == 1 || Cin == 3) && Cout > 0 && (stride == 1 || stride == 2), "conv_first_wgrad: unsupported shape");
+  ConvFirstWgradParams p{};
+  p.dy_bf16 = reinterpret_cast<const u32x4*>(dy_bf16); p.Mb = bf_kb_of(Cout);
+  p.in = in; p.dy = dy; p.part = part; p.B = B; p.Cin = Cin; p.Cout = Cout; p.IH = IH; p.IW = IW; p.stride = stride;
+  p.OH = cf_out_dim(IH, stride); p.OW = cf_out_dim(IW, stride);
   if (B == 0) return YOGO_OK;
-  dim3 grid(first_tiles(p.OH, p.OW), B);
-  if (out_bf16 != nullptr) {  // training, bf16 NCHW8c output
-    if (in_dtype == 0 && Cin == 1) hipLaunchKernelGGL((conv_first_train_bf16_kernel<uint8_t, 1>), grid, dim3(CF_THREADS), 0, stream, p);
-    else if (in_dtype == 0) hipLaunchKernelGGL((conv_first_train_bf16_kernel<uint8_t, 3>), grid, dim3(CF_THREADS), 0, stream, p);
-    else if (Cin == 1) hipLaunchKernelGGL((conv_first_train_bf16_kernel<float, 1>), grid, dim3(CF_THREADS), 0, stream, p);
-    else hipLaunchKernelGGL((conv_first_train_bf16_kernel<float, 3>), grid, dim3(CF_THREADS), 0, stream, p);
-    YOGO_CHECK_LAUNCH("conv_first_fwd");
-    return YOGO_OK;
-  }
-  if (in_dtype == 0 && Cin == 1) hipLaunchKernelGGL((conv_first_kernel<uint8_t, 1>), grid, dim3(CF_THREADS), 0, stream, p);
-  else if (in_dtype == 0) hipLaunchKernelGGL((conv_first_kernel<uint8_t, 3>), grid, dim3(CF_THREADS), 0, stream, p);
-  else if (Cin == 1) hipLaunchKernelGGL((conv_first_kernel<float, 1>), grid, dim3(CF_THREADS), 0, stream, p);
-  else hipLaunchKernelGGL((conv_first_kernel<float, 3>), grid, dim3(CF_THREADS), 0, stream, p);
-  YOGO_CHECK_LAUNCH("conv_first_fwd");
+  dim3 grid(first_wgrad_tiles(p.OH, p.OW), B);
+  cf_dispatch(in_dtype, Cin, [&](auto tin, auto cin) {
+    using TIn = decltype(tin);
+    constexpr int CIN = decltype(cin)::value;
+    if (dy_bf16 != nullptr) hipLaunchKernelGGL((conv_first_wgrad_kernel<TIn, CIN, true>), grid, dim3(CF_THREADS), 0, stream, p);
+    else hipLaunchKernelGGL((conv_first_wgrad_kernel<TIn, CIN, false>), grid, dim3(CF_THREADS), 0, stream, p);
+  });
+  YOGO_CHECK_LAUNCH("conv_first_wgrad");
   return YOGO_OK;
 }
-
-static int conv_first_wgrad_impl(const void* in, int in_dtype, const float* dy, const void* dy_bf16, float* part, int B, int Cin,
-                                 int Cout, int IH, int IW, int stride, hipStream_t stream);
 
 // partial weight/bias gradients; part must hold rows*Cout*(Cin*9+1) floats with rows from yogo_conv_first_wgrad_rows
 extern "C" int yogo_conv_first_wgrad(const void* in, int in_dtype, const float* dy, float* part, int B, int Cin, int Cout,
@@ -927,30 +846,6 @@ extern "C" int yogo_conv_first_wgrad_bf16g(const void* in, int in_dtype, const v
   return conv_first_wgrad_impl(in, in_dtype, nullptr, dy_bf16, part, B, Cin, Cout, IH, IW, stride, stream);
 }
 
-static int conv_first_wgrad_impl(const void* in, int in_dtype, const float* dy, const void* dy_bf16, float* part, int B, int Cin,
-                                 int Cout, int IH, int IW, int stride, hipStream_t stream) {
-  YOGO_CHECK_ARG(in && part, "conv_first_wgrad: null pointer");
-  YOGO_CHECK_ARG((Cin == 1 || Cin == 3) && Cout > 0 && (stride == 1 || stride == 2), "conv_first_wgrad: unsupported shape");
-  ConvFirstWgradParams p{};
-  p.dy_bf16 = reinterpret_cast<const cf_u32x4*>(dy_bf16); p.Mb = ((Cout + 15) / 16) * 2;
-  p.in = in; p.dy = dy; p.part = part; p.B = B; p.Cin = Cin; p.Cout = Cout; p.IH = IH; p.IW = IW; p.stride = stride;
-  p.OH = (IH - 1) / stride + 1; p.OW = (IW - 1) / stride + 1;
-  if (B == 0) return YOGO_OK;
-  dim3 grid(first_wgrad_tiles(p.OH, p.OW), B);
-#define CFW_LAUNCH(TIN, CIN_)                                                                                          \
-  do {                                                                                                                 \
-    if (dy_bf16 != nullptr) hipLaunchKernelGGL((conv_first_wgrad_kernel<TIN, CIN_, true>), grid, dim3(CF_THREADS), 0, stream, p); \
-    else hipLaunchKernelGGL((conv_first_wgrad_kernel<TIN, CIN_, false>), grid, dim3(CF_THREADS), 0, stream, p);        \
-  } while (0)
-  if (in_dtype == 0 && Cin == 1) CFW_LAUNCH(uint8_t, 1);
-  else if (in_dtype == 0) CFW_LAUNCH(uint8_t, 3);
-  else if (Cin == 1) CFW_LAUNCH(float, 1);
-  else CFW_LAUNCH(float, 3);
-#undef CFW_LAUNCH
-  YOGO_CHECK_LAUNCH("conv_first_wgrad");
-  return YOGO_OK;
-}
-
 // ---- fused layer-0 backward (BatchNorm + activation + first-conv weight gradient), bf16 NCHW8c g / z ----------------------
 extern "C" int yogo_conv_first_bn_wgrad_cols(int Cin, int Cout, int* cols) {
   YOGO_CHECK_ARG(cols && (Cin == 1 || Cin == 3) && Cout > 0, "conv_first_bn_wgrad_cols: bad arguments");
@@ -958,11 +853,51 @@ extern "C" int yogo_conv_first_bn_wgrad_cols(int Cin, int Cout, int* cols) {
   return YOGO_OK;
 }
 
-// part: rows (yogo_conv_first_wgrad_rows) x cols floats.  Follow with yogo_partials_reduce(part, rows, cols, 0, sums) and
-// yogo_conv_first_bn_wgrad_finalize.
+// the shape of cf_gather_u8s2 (and a byte offset that fits an int)
+static bool conv_first_fast_shape(int in_dtype, int Cin, int IH, int IW, int stride) {
+  return in_dtype == 0 && Cin == 1 && stride == 2 && IH % 2 == 0 && IW % 2 == 0 && (long long)IH * IW < (1ll << 31);
+}
 static int conv_first_bn_wgrad_impl(const void* in, int in_dtype, const void* g, const void* z, const void* signs, const float* mean,
                                     const float* invstd, const float* gamma, const float* beta, float* part, int B, int Cin, int Cout,
-                                    int IH, int IW, int stride, int act, int ext_gram, hipStream_t stream);
+                                    int IH, int IW, int stride, int act, int ext_gram, hipStream_t stream) {
+  YOGO_CHECK_ARG(in && g && (z || signs) && mean && invstd && gamma && beta && part, "conv_first_bn_wgrad_bf16: null pointer");
+  YOGO_CHECK_ARG((Cin == 1 || Cin == 3) && Cout > 0 && (stride == 1 || stride == 2) && (in_dtype == 0 || in_dtype == 1),
+                 "conv_first_bn_wgrad_bf16: unsupported shape");
+  ConvFirstBnWgradParams p{};
+  p.in = in; p.g = reinterpret_cast<const u32x4*>(g); p.z = reinterpret_cast<const u32x4*>(z); p.signs = reinterpret_cast<const unsigned short*>(signs);
+  p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.beta = beta; p.part = part;
+  p.B = B; p.Cin = Cin; p.Cout = Cout; p.Mb = bf_kb_of(Cout); p.IH = IH; p.IW = IW; p.stride = stride; p.act = act;
+  p.OH = cf_out_dim(IH, stride); p.OW = cf_out_dim(IW, stride); p.ext_gram = ext_gram;
+  p.m_ow = ((long long)p.OH * p.OW * p.OW < (1ll << 32) && p.OW > 1) ? magic_u32(p.OW) : 0u;
+  p.m_ow2 = p.OW >= 4 ? magic_u32(p.OW / 2) : 0u;
+  if (B == 0) return YOGO_OK;
+  dim3 grid(first_wgrad_tiles(p.OH, p.OW), B);
+  const bool fast = conv_first_fast_shape(in_dtype, Cin, IH, IW, stride);
+  // No load is wider than the image pointer's alignment (every image and row offset of these shapes is a multiple of 4 bytes where
+  // OW is even, of 2 otherwise): pk2 reads aligned dwords, pk and the generic FAST kernel 16-bit words; a less aligned image takes the
+  // next narrower route, down to the byte-wise generic kernel.  The sign-map sweep has no byte-wise route: refused.
+  const uintptr_t ia = reinterpret_cast<uintptr_t>(in);
+  const bool al4 = (ia & 3) == 0, al2 = (ia & 1) == 0;
+  YOGO_CHECK_ARG(z != nullptr || al2, "conv_first_bn_wgrad_bf16_xs: the image must be aligned to 2 bytes (the sign-map sweep has no byte-wise route)");
+  if (z == nullptr && al4 && p.OW % 2 == 0 && p.OW >= 4 && p.m_ow != 0 && plan_first_bn_wgrad_pairs())   // (yogo_conv_first_bn_wgrad_bf16_xs checked the shape)
+    hipLaunchKernelGGL(conv_first_bn_wgrad_pk2_kernel, grid, dim3(CF_THREADS), 0, stream, p);
+  else if (z == nullptr)
+    hipLaunchKernelGGL(conv_first_bn_wgrad_pk_kernel<true>, grid, dim3(CF_THREADS), 0, stream, p);
+  else if (fast && al2 && ext_gram && Cout % 8 == 0 && (act == ACT_NONE || act == ACT_LEAKY))
+    hipLaunchKernelGGL(conv_first_bn_wgrad_pk_kernel<false>, grid, dim3(CF_THREADS), 0, stream, p);
+  else if (fast && al2)
+    hipLaunchKernelGGL((conv_first_bn_wgrad_kernel<uint8_t, 1, 8, true, true>), grid, dim3(CF_THREADS), 0, stream, p);
+  else
+    cf_dispatch(in_dtype, Cin, [&](auto tin, auto cin) {   // one channel: passes of 8 channels and the Gram form; three: passes of 2
+      constexpr int CIN = decltype(cin)::value;
+      hipLaunchKernelGGL((conv_first_bn_wgrad_kernel<decltype(tin), CIN, CIN == 1 ? 8 : 2, CIN == 1>), grid, dim3(CF_THREADS), 0, stream, p);
+    });
+  YOGO_CHECK_LAUNCH("conv_first_bn_wgrad_bf16");
+  return YOGO_OK;
+}
+
+// part: rows (yogo_conv_first_wgrad_rows) x cols floats.  Follow with yogo_partials_reduce(part, rows, cols, 0, sums) and
+// yogo_conv_first_bn_wgrad_finalize.
 extern "C" int yogo_conv_first_bn_wgrad_bf16(const void* in, int in_dtype, const void* g, const void* z, const float* mean,
                                              const float* invstd, const float* gamma, const float* beta, float* part, int B,
                                              int Cin, int Cout, int IH, int IW, int stride, int act, hipStream_t stream) {
@@ -979,9 +914,6 @@ extern "C" int yogo_conv_first_bn_wgrad_bf16_xg(const void* in, int in_dtype, co
 extern "C" int yogo_conv_first_mfma_supported(int in_dtype, int Cin, int Cout, int IH, int IW, int stride);   // conv_first_mfma.hip
 // 1 when the sweep can run WITHOUT the saved conv output: from the sign map of yogo_conv_first_mfma_signs (uint8 one-channel image,
 // stride 2, even sizes, Cout = 8 or 16, no activation or LeakyReLU, no conv bias, caller-held Gram matrix)
-static bool conv_first_fast_shape(int in_dtype, int Cin, int IH, int IW, int stride) {
-  return in_dtype == 0 && Cin == 1 && stride == 2 && IH % 2 == 0 && IW % 2 == 0 && (long long)IH * IW < (1ll << 31);
-}
 extern "C" int yogo_conv_first_bn_wgrad_xs_supported(int in_dtype, int Cin, int Cout, int IH, int IW, int stride, int act) {
   return conv_first_fast_shape(in_dtype, Cin, IH, IW, stride) && (Cout == 8 || Cout == 16) && (act == ACT_NONE || act == ACT_LEAKY) &&
          yogo_conv_first_mfma_supported(in_dtype, Cin, Cout, IH, IW, stride);
@@ -995,48 +927,19 @@ extern "C" int yogo_conv_first_bn_wgrad_bf16_xs(const void* in, int in_dtype, co
   YOGO_CHECK_ARG(signs != nullptr || act == ACT_NONE, "conv_first_bn_wgrad_bf16_xs: LeakyReLU needs the sign map");
   return conv_first_bn_wgrad_impl(in, in_dtype, g, nullptr, signs != nullptr ? signs : g, mean, invstd, gamma, beta, part, B, Cin, Cout, IH, IW, stride, act, 1, stream);
 }
-static int conv_first_bn_wgrad_impl(const void* in, int in_dtype, const void* g, const void* z, const void* signs, const float* mean,
-                                    const float* invstd, const float* gamma, const float* beta, float* part, int B, int Cin, int Cout,
-                                    int IH, int IW, int stride, int act, int ext_gram, hipStream_t stream) {
-  YOGO_CHECK_ARG(in && g && (z || signs) && mean && invstd && gamma && beta && part, "conv_first_bn_wgrad_bf16: null pointer");
-  YOGO_CHECK_ARG((Cin == 1 || Cin == 3) && Cout > 0 && (stride == 1 || stride == 2) && (in_dtype == 0 || in_dtype == 1),
-                 "conv_first_bn_wgrad_bf16: unsupported shape");
-  ConvFirstBnWgradParams p{};
-  p.in = in; p.g = reinterpret_cast<const cf_u32x4*>(g); p.z = reinterpret_cast<const cf_u32x4*>(z); p.signs = reinterpret_cast<const unsigned short*>(signs);
-  p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.beta = beta; p.part = part;
-  p.B = B; p.Cin = Cin; p.Cout = Cout; p.Mb = ((Cout + 15) / 16) * 2; p.IH = IH; p.IW = IW; p.stride = stride; p.act = act;
-  p.OH = (IH - 1) / stride + 1; p.OW = (IW - 1) / stride + 1; p.ext_gram = ext_gram;
-  p.m_ow = ((long long)p.OH * p.OW * p.OW < (1ll << 32) && p.OW > 1) ? (unsigned)(((1ull << 32) + (unsigned)p.OW - 1ull) / (unsigned)p.OW) : 0u;
-  if (B == 0) return YOGO_OK;
-  dim3 grid(first_wgrad_tiles(p.OH, p.OW), B);
-  const bool fast = conv_first_fast_shape(in_dtype, Cin, IH, IW, stride);
-  p.m_ow2 = p.OW >= 4 ? (unsigned)(((1ull << 32) + (unsigned)(p.OW / 2) - 1ull) / (unsigned)(p.OW / 2)) : 0u;
-  // No load is wider than the image pointer's alignment (every image and row offset of these shapes is a multiple of 4 bytes where
-  // OW is even, of 2 otherwise): pk2 reads aligned dwords, pk and the generic FAST kernel 16-bit words; a less aligned image takes the
-  // next narrower route, down to the byte-wise generic kernel.  The sign-map sweep has no byte-wise route: refused.
-  const uintptr_t ia = reinterpret_cast<uintptr_t>(in);
-  const bool al4 = (ia & 3) == 0, al2 = (ia & 1) == 0;
-  YOGO_CHECK_ARG(z != nullptr || al2, "conv_first_bn_wgrad_bf16_xs: the image must be aligned to 2 bytes (the sign-map sweep has no byte-wise route)");
-  if (z == nullptr && al4 && p.OW % 2 == 0 && p.OW >= 4 && p.m_ow != 0 && plan_first_bn_wgrad_pairs())   // (yogo_conv_first_bn_wgrad_bf16_xs checked the shape)
-    hipLaunchKernelGGL(conv_first_bn_wgrad_pk2_kernel, grid, dim3(CF_THREADS), 0, stream, p);
-  else if (z == nullptr)
-    hipLaunchKernelGGL(conv_first_bn_wgrad_pk_kernel<true>, grid, dim3(CF_THREADS), 0, stream, p);
-  else if (fast && al2 && ext_gram && Cout % 8 == 0 && (act == ACT_NONE || act == ACT_LEAKY))
-    hipLaunchKernelGGL(conv_first_bn_wgrad_pk_kernel<false>, grid, dim3(CF_THREADS), 0, stream, p);
-  else if (fast && al2)
-    hipLaunchKernelGGL((conv_first_bn_wgrad_kernel<uint8_t, 1, 8, true, true>), grid, dim3(CF_THREADS), 0, stream, p);
-  else if (in_dtype == 0 && Cin == 1) hipLaunchKernelGGL((conv_first_bn_wgrad_kernel<uint8_t, 1, 8, true>), grid, dim3(CF_THREADS), 0, stream, p);
-  else if (in_dtype == 0) hipLaunchKernelGGL((conv_first_bn_wgrad_kernel<uint8_t, 3, 2, false>), grid, dim3(CF_THREADS), 0, stream, p);
-  else if (Cin == 1) hipLaunchKernelGGL((conv_first_bn_wgrad_kernel<float, 1, 8, true>), grid, dim3(CF_THREADS), 0, stream, p);
-  else hipLaunchKernelGGL((conv_first_bn_wgrad_kernel<float, 3, 2, false>), grid, dim3(CF_THREADS), 0, stream, p);
-  YOGO_CHECK_LAUNCH("conv_first_bn_wgrad_bf16");
-  return YOGO_OK;
-}
 
 static int conv_first_bn_wgrad_finalize_impl(const float* sums, const float* ext_pg, const float* mean, const float* invstd,
                                              const float* gamma, const float* w_oihw, float* dw, float* dgamma, float* dbeta, int B,
                                              int Cin, int Cout, int IH, int IW, int stride, int training, float clip, int derive_s2,
-                                             hipStream_t stream);
+                                             hipStream_t stream) {
+  YOGO_CHECK_ARG(sums && mean && invstd && gamma && w_oihw && dw && dgamma && dbeta, "conv_first_bn_wgrad_finalize: null pointer");
+  const int OH = cf_out_dim(IH, stride), OW = cf_out_dim(IW, stride), NJ = Cin * 9;
+  const int n = Cout * (NJ + 2);
+  hipLaunchKernelGGL(conv_first_bn_wgrad_finalize_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, sums, mean, invstd, gamma,
+                     w_oihw, dw, dgamma, dbeta, Cout, NJ, 1.0f / ((float)B * (float)OH * (float)OW), training, Cin == 1 ? 1 : 0, clip, ext_pg, derive_s2);
+  YOGO_CHECK_LAUNCH("conv_first_bn_wgrad_finalize");
+  return YOGO_OK;
+}
 extern "C" int yogo_conv_first_bn_wgrad_finalize(const float* sums, const float* mean, const float* invstd, const float* gamma,
                                                  const float* w_oihw, float* dw, float* dgamma, float* dbeta, int B, int Cin,
                                                  int Cout, int IH, int IW, int stride, int training, float clip,
@@ -1062,16 +965,4 @@ extern "C" int yogo_conv_first_bn_wgrad_finalize_xs(const float* sums, const flo
   YOGO_CHECK_ARG(gram != nullptr && Cin == 1, "conv_first_bn_wgrad_finalize_xs: bad arguments");
   return conv_first_bn_wgrad_finalize_impl(sums, gram, mean, invstd, gamma, w_oihw, dw, dgamma, dbeta, B, Cin, Cout, IH, IW, stride,
                                            training, clip, 1, stream);
-}
-static int conv_first_bn_wgrad_finalize_impl(const float* sums, const float* ext_pg, const float* mean, const float* invstd,
-                                             const float* gamma, const float* w_oihw, float* dw, float* dgamma, float* dbeta, int B,
-                                             int Cin, int Cout, int IH, int IW, int stride, int training, float clip, int derive_s2,
-                                             hipStream_t stream) {
-  YOGO_CHECK_ARG(sums && mean && invstd && gamma && w_oihw && dw && dgamma && dbeta, "conv_first_bn_wgrad_finalize: null pointer");
-  const int OH = (IH - 1) / stride + 1, OW = (IW - 1) / stride + 1, NJ = Cin * 9;
-  const int n = Cout * (NJ + 2);
-  hipLaunchKernelGGL(conv_first_bn_wgrad_finalize_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, sums, mean, invstd, gamma,
-                     w_oihw, dw, dgamma, dbeta, Cout, NJ, 1.0f / ((float)B * (float)OH * (float)OW), training, Cin == 1 ? 1 : 0, clip, ext_pg, derive_s2);
-  YOGO_CHECK_LAUNCH("conv_first_bn_wgrad_finalize");
-  return YOGO_OK;
 }

@@ -1,5 +1,5 @@
 // Layer 0's inference forward of the bf16 path (the training step's layer 0 is conv_first_mfma.hip).
-#include "bf16_dev.h"
+#include "conv_first_dev.h"
 #include "conv_bf16_plan.h"
 
 // ---- first convolution, bf16 NCHW8c output: Cin = 1|3, uint8 or fp32 input (weights fp32, BatchNorm pre-folded) -----------
@@ -21,17 +21,7 @@ __global__ __launch_bounds__(256) void conv_first_bf16_kernel(const ConvFirstBf1
   const TIn* inb = reinterpret_cast<const TIn*>(p.in) + (size_t)b * CIN * p.IH * p.IW;
   const float* __restrict__ w = p.w;
   float x[CIN * 9];
-#pragma unroll
-  for (int ci = 0; ci < CIN; ++ci)
-#pragma unroll
-    for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-      for (int kw = 0; kw < 3; ++kw) {
-        const int iy = oy * p.stride + kh - 1, ix = ox * p.stride + kw - 1;
-        float v = 0.f;
-        if (iy >= 0 && iy < p.IH && ix >= 0 && ix < p.IW) v = (float)inb[((size_t)ci * p.IH + iy) * p.IW + ix];
-        x[(ci * 3 + kh) * 3 + kw] = v;
-      }
+  cf_gather<CIN>(x, inb, p, true, oy, ox);
   for (int cb = 0; cb < p.Mb; ++cb) {
     bf16x8 o;
 #pragma unroll
@@ -60,13 +50,12 @@ extern "C" int yogo_conv_first_fwd_bf16(const void* in, int in_dtype, const floa
   ConvFirstBf16Params p{};
   p.in = in; p.w = w; p.bias = bias; p.out = reinterpret_cast<u32x4*>(out);
   p.B = B; p.Cin = Cin; p.Cout = Cout; p.Mb = bf_kb_of(Cout); p.IH = IH; p.IW = IW; p.stride = stride; p.act = act;
-  p.OH = (IH - 1) / stride + 1; p.OW = (IW - 1) / stride + 1;
+  p.OH = cf_out_dim(IH, stride); p.OW = cf_out_dim(IW, stride);
   if (B == 0) return YOGO_OK;
   dim3 grid(cdiv(p.OH * p.OW, 256), B);
-  if (in_dtype == 0 && Cin == 1) hipLaunchKernelGGL((conv_first_bf16_kernel<uint8_t, 1>), grid, dim3(256), 0, stream, p);
-  else if (in_dtype == 0) hipLaunchKernelGGL((conv_first_bf16_kernel<uint8_t, 3>), grid, dim3(256), 0, stream, p);
-  else if (Cin == 1) hipLaunchKernelGGL((conv_first_bf16_kernel<float, 1>), grid, dim3(256), 0, stream, p);
-  else hipLaunchKernelGGL((conv_first_bf16_kernel<float, 3>), grid, dim3(256), 0, stream, p);
+  cf_dispatch(in_dtype, Cin, [&](auto tin, auto cin) {
+    hipLaunchKernelGGL((conv_first_bf16_kernel<decltype(tin), decltype(cin)::value>), grid, dim3(256), 0, stream, p);
+  });
   YOGO_CHECK_LAUNCH("conv_first_fwd_bf16");
   if (yogo_launch_log_enabled())
     yogo_launch_log("conv_first_bf16_kernel<%s, %d> | B=%d Cout=%d in=%dx%d out=%dx%d stride=%d act=%d bias=%d", in_dtype == 0 ? "uint8_t" : "float", Cin, B, Cout, IH, IW,

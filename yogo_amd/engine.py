@@ -148,6 +148,21 @@ def _bn_finalize(eng: "Engine", L: Layer, fn: str, *lead_args, count: int, dev, 
     return mean, invstd
 
 
+def _first_wgrad(fn: str, L: Layer, x_in: torch.Tensor, g: torch.Tensor, dw: torch.Tensor, db: Optional[torch.Tensor], clip: float, st) -> None:
+    """Plain weight gradient of a direct layer 0 by ``fn`` (yogo_conv_first_wgrad for an fp32 NCHW gradient, yogo_conv_first_wgrad_bf16g
+    for bf16 NCHW8c): partial sums over the image rows, then one reduction of weight and bias gradient together"""
+    B, _, IH, IW = x_in.shape
+    rows = _hip.query_ints("yogo_conv_first_wgrad_rows", 1, B, IH, IW, L.s)[0]
+    nj = L.cin * 9 + 1
+    part = torch.empty(rows * L.cout * nj, dtype=torch.float32, device=x_in.device)
+    red = torch.empty(L.cout, nj, dtype=torch.float32, device=x_in.device)
+    _hip.call(fn, x_in, 0 if x_in.dtype == torch.uint8 else 1, g, part, B, L.cin, L.cout, IH, IW, L.s, st)
+    _hip.call("yogo_partials_reduce", part, rows, L.cout * nj, clip, red, st)
+    dw.view(L.cout, nj - 1).copy_(red[:, : nj - 1])
+    if db is not None:
+        db.copy_(red[:, nj - 1])
+
+
 def _pack_hit(eng: "Engine", key: Tuple[int, int], w: torch.Tensor) -> Optional[torch.Tensor]:
     """the cached packing ``key`` of weight ``w``, unless torch has seen ``w`` written or moved since it was made"""
     hit = eng._pack.get(key)
@@ -330,30 +345,17 @@ class Engine:
                           OH * OW, 1 if S.bn_train else 0, clip, st)
             # ---- weight / bias gradient -------------------------------------------------------------------------
             dw = dst(L.conv.weight)
-            has_bias = L.conv.bias is not None
+            db = dst(L.conv.bias) if L.conv.bias is not None else None
             if self._first_direct(i):
-                rows = _hip.query_ints("yogo_conv_first_wgrad_rows", 1, B, IH, IW, L.s)[0]
-                nj = L.cin * 9 + 1
-                part = torch.empty(rows * L.cout * nj, dtype=torch.float32, device=dev)
-                x_in = S.x_in
-                _hip.call("yogo_conv_first_wgrad", x_in, 0 if x_in.dtype == torch.uint8 else 1, g, part, B, L.cin, L.cout, IH,
-                          IW, L.s, st)
-                red = torch.empty(L.cout, nj, dtype=torch.float32, device=dev)
-                _hip.call("yogo_partials_reduce", part, rows, L.cout * nj, clip, red, st)
-                dw.copy_(red[:, : nj - 1].reshape(dw.shape))
-                if has_bias:
-                    db = dst(L.conv.bias)
-                    db.copy_(red[:, nj - 1])
-                    grads[id(L.conv.bias)] = db
+                _first_wgrad("yogo_conv_first_wgrad", L, S.x_in, g, dw, db, clip, st)
             else:
                 wsb = _hip.query_size("yogo_conv2d_wgrad_workspace_bytes", B, L.cin, L.cout, IH, IW, L.k, L.s)
                 ws = torch.empty(wsb // 4, dtype=torch.float32, device=dev)
-                db = dst(L.conv.bias) if has_bias else None
                 self._tick("wgrad", i, 2.0 * B * L.cout * L.cin * L.k * L.k * OH * OW)
                 _hip.call("yogo_conv2d_wgrad_f32", S.x_in, g, dw, db, ws, B, L.cin, L.cout, IH, IW, L.k, L.s, clip, st)
                 self._tock()
-                if has_bias:
-                    grads[id(L.conv.bias)] = db
+            if db is not None:
+                grads[id(L.conv.bias)] = db
             grads[id(L.conv.weight)] = dw
             if on_layer is not None:
                 on_layer(i)
@@ -751,18 +753,6 @@ def backward_bf16_train(eng: Engine, saved: List[Saved], graw: torch.Tensor,
         eng._tock()
         return part, rows, IH, IW
 
-    def wgrad_first(L, S, g, dw, db, IH, IW):
-        """any other layer 0: partial sums over the image rows, then one reduction of weight and bias gradient together"""
-        rows = _hip.query_ints("yogo_conv_first_wgrad_rows", 1, B, IH, IW, L.s)[0]
-        nj = L.cin * 9 + 1
-        part = torch.empty(rows * L.cout * nj, dtype=torch.float32, device=dev)
-        red = torch.empty(L.cout, nj, dtype=torch.float32, device=dev)
-        _hip.call("yogo_conv_first_wgrad_bf16g", S.x_in, 0 if S.x_in.dtype == torch.uint8 else 1, g, part, B, L.cin, L.cout, IH, IW, L.s, st)
-        _hip.call("yogo_partials_reduce", part, rows, L.cout * nj, clip, red, st)
-        dw.view(L.cout, nj - 1).copy_(red[:, : nj - 1])
-        if db is not None:
-            db.copy_(red[:, nj - 1])
-
     def wgrad(i, L, S, g, dw, db, IH, IW, OH, OW):
         """layers > 0 on the bf16 matrix cores; with the queue, the split-K reduction waits for the next flush"""
         ws = torch.empty(_hip.query_size("yogo_conv2d_wgrad_bf16_workspace_bytes", B, L.cin, L.cout, IH, IW, L.k, L.s) // 4,
@@ -833,8 +823,8 @@ def backward_bf16_train(eng: Engine, saved: List[Saved], graw: torch.Tensor,
             wgrad_first_bn(L, S, g, fused01, dw, IH, IW)
         elif fuse01:
             fused01 = wgrad_dgrad_first(L, S, g, dw, db, IH, IW, OH, OW)
-        elif i == 0:
-            wgrad_first(L, S, g, dw, db, IH, IW)
+        elif i == 0:   # any other layer 0
+            _first_wgrad("yogo_conv_first_wgrad_bf16g", L, S.x_in, g, dw, db, clip, st)
         else:
             wgrad(i, L, S, g, dw, db, IH, IW, OH, OW)
         if db is not None:
