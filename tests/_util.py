@@ -527,7 +527,7 @@ def teacher_forced_both_plans(O, run_step, x, lab, spec, sd0, what):
 # libyogo_hip_hooks.so (yogo_amd/csrc/build.sh) = the product's object files -- every kernel is the very object the product links -- with
 # plan_switches.o (host code only: the accessor of every plan switch) compiled under -DYOGO_TEST_HOOKS, which turns the switches into
 # variables with setters: yogo_hook_conv_bf16_persistent / _ws16 / _direct (0 = the tiled kernel in place of the direct stride-2 data
-# gradients) / _staged / _head, yogo_hook_conv_first_mfma_pairs, yogo_hook_conv_first_bn_wgrad_pairs.
+# gradients) / _staged / _staged_pair / _head, yogo_hook_conv_first_mfma_pairs, yogo_hook_conv_first_bn_wgrad_pairs.
 # The product library has no such switch (no mutable global state); A/B and bit-identity tests bind the hooks library in place of the
 # product's for their duration.
 @contextlib.contextmanager
@@ -542,7 +542,7 @@ def hooks_library():
         raise RuntimeError(f"{path} missing: run `bash yogo_amd/csrc/build.sh` (it builds the product and the hooks library)")
     _hip.lib()
     L = _hip.bind(path, _hip.prototypes())
-    hooks = ("yogo_hook_conv_bf16_persistent", "yogo_hook_conv_first_mfma_pairs", "yogo_hook_conv_first_bn_wgrad_pairs", "yogo_hook_conv_bf16_direct", "yogo_hook_conv_bf16_staged", "yogo_hook_conv_bf16_head", "yogo_hook_conv_bf16_ws16")
+    hooks = ("yogo_hook_conv_bf16_persistent", "yogo_hook_conv_first_mfma_pairs", "yogo_hook_conv_first_bn_wgrad_pairs", "yogo_hook_conv_bf16_direct", "yogo_hook_conv_bf16_staged", "yogo_hook_conv_bf16_head", "yogo_hook_conv_bf16_ws16", "yogo_hook_conv_bf16_staged_pair")
     for name in hooks:
         fn = getattr(L, name)
         fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_int]
@@ -561,15 +561,18 @@ GUARD = 4096
 
 
 class Guarded:
-    """n elements between two runs of GUARD sentinel words; the payload starts as NaN (floats) / 0x7F bytes so unwritten rows show"""
+    """n elements between two runs of GUARD sentinel words; the payload starts as NaN (floats) / 0x7F bytes (int32) / 0xA5 (uint8) so
+    unwritten rows show.  Every sentinel is a value its dtype holds exactly (bf16 has 8 significand bits)."""
 
     def __init__(self, n, dtype=torch.float32):
         self.n = n
-        self.sent = {torch.float32: 12345.678, torch.int32: 0x5A5A5A5A, torch.float64: -7.25}[dtype]
+        self.sent = {torch.float32: 12345.678, torch.int32: 0x5A5A5A5A, torch.float64: -7.25, torch.bfloat16: -7.25, torch.uint8: 0x5A}[dtype]
         self.buf = torch.full((n + 2 * GUARD,), self.sent, dtype=dtype, device="cuda")
         self.view = self.buf[GUARD:GUARD + n]
         if dtype.is_floating_point:
             self.view.fill_(float("nan"))
+        elif dtype == torch.uint8:
+            self.view.fill_(0xA5)
         else:
             self.view.fill_(0x7F7F7F7F)
 
