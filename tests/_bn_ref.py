@@ -159,6 +159,15 @@ def bf16_shapes():
     return out
 
 
+def head_shapes():
+    """(B, C, P, HW) of yogo_bn_bwd_bf16_head: every HW around its 16-pixel stripes, a wavefront's 64 pixels and a workgroup's 1024 at one
+    (B, C, P); then, at the first multi-block HW, head outputs P of one operand half (<= 8), both (9..16), one and several channel pairs;
+    the 64-workgroup cap."""
+    out = [(3, 32, 9, hw) for hw in (1, 15, 16, 17, 63, 64, 65, 1023, 1024, 1025)]
+    out += [(1, 16, 1, 1025), (1, 16, 8, 1025), (3, 16, 16, 1025), (1, 32, 12, 1025), (3, 128, 12, 1025)]
+    return out + [(1, 16, 12, 65540)]
+
+
 def _seed(*k):
     s = 17
     for v in k:
@@ -185,6 +194,24 @@ def bn_case(B, C, HW, bf16, offset=0.0, seed=0):
     gamma[::3] = -gamma[::3]
     beta = torch.randn(C, generator=gen) * 0.3
     return dict(z=z, g=g, mean=mean.float(), invstd=invstd.float(), var=var.float(), gamma=gamma, beta=beta)
+
+
+def head_case(B, C, P, HW):
+    """bn_case(B, C, HW, bf16=True) with g replaced by the head's data gradient g[b][c][i] = sum_k gh[b][k][i] * w[k][c], gh [B][P][HW] and
+    w [P][C] integers in {-2..2}: with P <= 16 every g is an integer of magnitude <= 64, exact in bf16 and in fp32 in any order, so the
+    kernel's MFMA sum and its bf16 rounding of g are the identity and the reference may take g as given."""
+    k = bn_case(B, C, HW, True)
+    gen = torch.Generator().manual_seed(_seed(B, C, P, HW, 5))
+    k["gh"] = torch.randint(-2, 3, (B, P, HW), generator=gen).float()
+    k["w"] = torch.randint(-2, 3, (P, C), generator=gen).float()
+    while True:   # no channel without a weight (its g would be all zero): such columns are drawn again
+        dead = (k["w"] == 0).all(0)
+        if not bool(dead.any()):
+            break
+        k["w"][:, dead] = torch.randint(-2, 3, (P, int(dead.sum())), generator=gen).float()
+    # (+ 0.0: a zero of g is +0 as the kernel's is -- its sum starts from a +0 accumulator -- where 0 * -2 alone would leave -0)
+    k["g"] = (torch.einsum("bki,kc->bci", k["gh"].double(), k["w"].double()) + 0.0).float()
+    return k
 
 
 def branch_case(B, C, HW, bf16):

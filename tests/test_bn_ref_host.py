@@ -162,6 +162,36 @@ def test_generated_cases_stay_within_the_edge_cap(bf16, B, C, HW):
             R.clip_both_signs(torch.cat([dg, db]))   # asserts
 
 
+def test_head_shape_list_is_what_the_tiling_needs():
+    s = R.head_shapes()
+    assert {hw for b, c, p, hw in s if (b, c, p) == (3, 32, 9)} == {1, 15, 16, 17, 63, 64, 65, 1023, 1024, 1025}
+    assert {(b, c, p) for b, c, p, hw in s if hw == 1025} == {(3, 32, 9), (1, 16, 1), (1, 16, 8), (3, 16, 16), (1, 32, 12), (3, 128, 12)}
+    assert [x for x in s if x[3] == 65540] == [(1, 16, 12, 65540)] and len(s) == 16
+    assert all(c % 16 == 0 and 1 <= p <= 16 for b, c, p, hw in s) and max(b * c * hw for b, c, p, hw in s) * 2 <= 2 ** 22
+
+
+@pytest.mark.parametrize("B,C,P,HW", R.head_shapes())
+def test_head_cases_have_an_exact_gradient_within_the_caps(B, C, P, HW):
+    """g = sum_k gh w is an integer of magnitude <= 64: its own bf16 value, so the kernel's rounding of g is the identity; no channel of g is
+    all zero; z stays within the edge cap; and at the multi-block HW the clip of the backward tests binds on both sides"""
+    k = R.head_case(B, C, P, HW)
+    g, gh, w = k["g"], k["gh"], k["w"]
+    assert gh.shape == (B, P, HW) and w.shape == (P, C) and g.shape == (B, C, HW)
+    for t in (gh, w):
+        assert torch.equal(t, t.round()) and float(t.abs().max()) <= 2
+    assert torch.equal(g, g.to(torch.bfloat16).float()) and torch.equal(g, g.round()) and float(g.abs().max()) <= 4 * P <= 64
+    assert torch.equal(g, torch.einsum("bki,kc->bci", gh, w))          # fp32, another order: the same integers
+    assert not bool(torch.signbit(g[g == 0]).any()), "a zero of g is -0: the kernel's sum gives +0, the bit comparison would see it"
+    assert bool((g != 0).any(2).any(0).all()), "a channel of g is all zero"
+    assert torch.equal(k["z"], R.bn_case(B, C, HW, True)["z"])
+    edge = R.leaky_edge_mask(k["z"], k["mean"], k["invstd"], k["gamma"], k["beta"])
+    assert int(edge.sum()) <= R.EDGE_CAP * edge.numel(), (int(edge.sum()), edge.numel())
+    if HW == 1025:
+        for act in (R.NONE, R.LEAKY, R.SILU):
+            _, dg, db, _ = R.backward(g, k["z"], k["mean"], k["invstd"], k["gamma"], k["beta"], act, 1, 0.0)
+            R.clip_both_signs(torch.cat([dg, db]))   # asserts
+
+
 @pytest.mark.parametrize("bf16,B,C,HW", [(False, 3, 5, 2049), (True, 3, 5, 1025)])
 def test_branch_case_puts_a_few_elements_within_tau(bf16, B, C, HW):
     k = R.branch_case(B, C, HW, bf16)   # asserts: those elements are within tau, and the case stays within the cap

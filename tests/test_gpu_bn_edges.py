@@ -186,22 +186,28 @@ def test_apply_bf16(B, C, HW):
 # ============================================================================================================================
 # backward
 # ============================================================================================================================
-def run_bwd(h, bf16, k, gd, zd, act, training, clip, inplace=False):
-    """gd / zd: device inputs (fp32 [B][C][HW] or bf16 8c).  Returns dz (CPU; fp32 [B][C][HW] or bf16 8c), dgamma, dbeta, sums, part."""
+def run_bwd(h, bf16, k, gd, zd, act, training, clip, inplace=False, head=None):
+    """gd / zd: device inputs (fp32 [B][C][HW] or bf16 8c).  Returns dz (CPU; fp32 [B][C][HW] or bf16 8c), dgamma, dbeta, sums, part.
+    head = (gh 8c, w, P) on the device: yogo_bn_bwd_bf16_head forms g from them (gd is not read; dz must not alias gh: never in place)."""
     B, C, HW = k["z"].shape
     st = h.stream_ptr()
     rows = h.query_ints("yogo_bn_bwd_bf16_rows" if bf16 else "yogo_bn_bwd_rows", 1, B, HW)[0]
     assert rows == B * max(1, min(64, -(-HW // (1024 if bf16 else 2048))))
     part, sums, dg, db = Guarded(rows * C * 2), Guarded(2 * C), Guarded(C), Guarded(C)
     if bf16:
-        G, dz = gbf16(tuple(gd.shape))
+        G, dz = gbf16(tuple(zd.shape))
     else:
         G = Guarded(B * C * HW)
         dz = G.view.view(B, C, HW)
     if inplace:
         dz.copy_(gd)
-    h.call("yogo_bn_bwd_bf16" if bf16 else "yogo_bn_bwd", dz if inplace else gd, zd, dz, dev(k["mean"]), dev(k["invstd"]), dev(k["gamma"]),
-           dev(k["beta"]), act, dg.view, db.view, part.view, sums.view, B, C, HW, training, clip, st)
+    if head is not None:
+        assert bf16 and not inplace
+        h.call("yogo_bn_bwd_bf16_head", head[0], head[1], head[2], zd, dz, dev(k["mean"]), dev(k["invstd"]), dev(k["gamma"]), dev(k["beta"]), act,
+               dg.view, db.view, part.view, sums.view, B, C, HW, training, clip, st)
+    else:
+        h.call("yogo_bn_bwd_bf16" if bf16 else "yogo_bn_bwd", dz if inplace else gd, zd, dz, dev(k["mean"]), dev(k["invstd"]), dev(k["gamma"]),
+               dev(k["beta"]), act, dg.view, db.view, part.view, sums.view, B, C, HW, training, clip, st)
     for b_, w in ((G, "dz"), (part, "part"), (sums, "sums"), (dg, "dgamma"), (db, "dbeta")):
         b_.check("bn_bwd " + w)
     out = dict(dz=dz.cpu(), dgamma=dg.view.cpu(), dbeta=db.view.cpu(), sums=sums.view.cpu(), part=part.view.cpu())
@@ -384,6 +390,43 @@ def test_bwd_f32(B, C, HW):
 @pytest.mark.parametrize("B,C,HW", R.bf16_shapes())
 def test_bwd_bf16(B, C, HW):
     _bwd_case(True, B, C, HW)
+
+
+@pytest.mark.parametrize("B,C,P,HW", R.head_shapes())
+def test_bwd_bf16_head(B, C, P, HW):
+    """yogo_bn_bwd_bf16_head through the checker of yogo_bn_bwd_bf16: gh and w are small integers (R.head_case), so the g the kernel forms
+    with its MFMA and rounds to bf16 is exactly k["g"] and every bound of check_bwd holds unchanged.  The shapes walk the 16-pixel stripes
+    and their `px < HW` guards, one operand half and both (P <= 8, P > 8), one and several channel pairs, the 64-workgroup cap."""
+    h = H()
+    entry = "yogo_bn_bwd_bf16_head"
+    k = R.head_case(B, C, P, HW)
+    zd = dev(R.to8c(k["z"]))
+    gh8 = R.to8c(k["gh"])
+    assert gh8.shape == (B, 2, HW, 8)
+    head = (dev(gh8), dev(k["w"]), P)
+    multi = HW == 1025
+    combos = BWD_COMBOS if multi else [(LEAKY, 1, False)]
+    worst = 0.0
+    refs = {}
+    g8d = None
+    for act, training, clipped in combos:
+        if act not in refs:
+            refs[act] = bwd_reference(k, act)
+        rf = refs[act]
+        clip = R.clip_both_signs(torch.cat([rf["S2"], rf["S1"]])) if clipped else 0.0
+        case = f"B={B} C={C} P={P} HW={HW} act={act} training={training} clip={clip:.4g}"
+        out = run_bwd(h, True, k, None, zd, act, training, clip, head=head)
+        worst = max(worst, check_bwd(entry, case, k, rf, out, act, training, clip, True))
+        again = run_bwd(h, True, k, None, zd, act, training, clip, head=head)
+        for n in ("dz", "dgamma", "dbeta", "sums", "part"):
+            assert torch.equal(bits(out[n]), bits(again[n])), (case, n, "a second identical call gave other bits")
+        if training == 0 and act in (NONE, LEAKY):
+            # both kernels compute sc * (ge - 0 - xh * 0) = sc * ge from the same g, under either contraction
+            if g8d is None:
+                g8d = dev(R.to8c(k["g"]))
+            unfused = run_bwd(h, True, k, g8d, zd, act, training, clip)
+            assert torch.equal(bits(out["dz"]), bits(unfused["dz"])), (case, "dz differs from yogo_bn_bwd_bf16 fed the same g")
+    log_ratio(entry + " dz", f"B={B} C={C} P={P} HW={HW}", worst)
 
 
 @pytest.mark.parametrize("bf16", [False, True])

@@ -6,7 +6,69 @@
 // in fp64 in a fixed order (deterministic), producing mean / invstd and the momentum-0.1 running-stat update
 // (biased variance to normalise, unbiased into running_var -- torch semantics).
 // All element-wise kernels here are HBM-bound: one read + one write per element, float4 where the plane allows.
-#include "common.h"
+#include "bf16_dev.h"
+
+// ---- what the kernels of this file share, each defined once ------------------------------------------------------
+// the elements i < n of a plane that this thread takes: the plane's gridDim.x workgroups stride over it together.  (A macro: as a function
+// taking the body as a lambda the backward kernels contract their products differently -- other bits.)
+#define PLANE_WALK(i, n) for (int i = blockIdx.x * 256 + threadIdx.x; i < (n); i += gridDim.x * 256)
+
+// per-channel parameters of N channels.  bn_chan_load fills them for channels c0 .. c0 + N - 1: scalars (N = 1, the fp32 kernels) or a
+// 16-byte unit (8); a channel beyond C - 1 (a padding lane of a unit) takes channel C - 1's: what it computes is never stored.  The head
+// pair fills a lane's half unit (N = 4) in its own loop (see there).
+// stat_is_var != 0: `invstd_or_var` holds a variance (eval mode: running_var) and invstd is computed here.
+template <int N>
+struct BnChan {
+  float mu[N], is[N], ga[N], be[N], sc[N];   // mean, invstd, gamma, beta, invstd * gamma
+};
+template <int N>
+__device__ __forceinline__ void bn_chan_load(BnChan<N>& q, int c0, int C, const float* mean, const float* invstd_or_var, int stat_is_var,
+                                             float eps, const float* gamma, const float* beta) {
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    const int c = min(c0 + j, C - 1);
+    const float is = stat_is_var ? 1.0f / sqrtf(invstd_or_var[c] + eps) : invstd_or_var[c];
+    q.mu[j] = mean[c];
+    q.is[j] = is;
+    q.ga[j] = gamma[c];
+    q.be[j] = beta[c];
+    q.sc[j] = is * gamma[c];
+  }
+}
+// a mean term of dz, sum_g / n or sum_gx / n of channel c: with batch statistics; nothing with frozen ones
+__device__ __forceinline__ float bn_mean_term(const float* sum, int c, float inv_count, int training) {
+  return training ? sum[c] * inv_count : 0.f;
+}
+
+// One element of the backward pass.  g is the gradient w.r.t. the block output; when act != none the activation derivative is applied
+// here, from the recomputed pre-activation xhat*gamma + beta (so no pre-activation tensor has to be saved, LeakyReLU and SiLU alike).
+struct BnGrad {
+  float xh, ge;   // xhat, g' = g * act'(xhat*gamma + beta)
+};
+template <int N>
+__device__ __forceinline__ BnGrad bn_grad(const BnChan<N>& q, int j, float z, float g, int act) {
+  const float xh = (z - q.mu[j]) * q.is[j];
+  return {xh, g * act_bwd_factor(fmaf(xh, q.ga[j], q.be[j]), act)};
+}
+// the apply sweeps: dz = gamma * invstd * (g' - sum_g/n - xhat * sum_gx/n)   (training);  dz = gamma * invstd * g'  (frozen stats)
+template <int N>
+__device__ __forceinline__ float bn_dz(const BnChan<N>& q, int j, float z, float g, int act, float mg, float mgx) {
+  const BnGrad e = bn_grad(q, j, z, g, act);
+  return q.sc[j] * (e.ge - mg - e.xh * mgx);
+}
+
+// Partial rows [rows][C][2], rows = images * workgroups per plane (the *_rows queries): the pair of channel c in this workgroup's row
+__device__ __forceinline__ float* bn_part_row(float* part, int b, int C, int c) {
+  return part + ((size_t)(b * gridDim.x + blockIdx.x) * C + c) * 2;
+}
+// The tail of a reduce sweep, after every wavefront's block_put of its W / 2 channels' pairs into red[wave]: thread e < W adds the four
+// wavefronts' entry e (common.h: left to right) and stores it, sum e & 1 of channel c0 + e / 2.
+template <int W>
+__device__ __forceinline__ void bn_part_store(const float (&red)[4][W], float* part, int b, int C, int c0) {
+  __syncthreads();
+  const int e = threadIdx.x, c = c0 + (e >> 1);
+  if (e < W && c < C) bn_part_row(part, b, C, c)[e & 1] = block_sum4(red, e);
+}
 
 // ---- finalize: partial rows -> mean, invstd, running stats ---------------------------------------------------
 // One workgroup per 8 channels: lane t sums the rows t / 8, t / 8 + 32, ... of channel 8 * blockIdx.x + t % 8 (8 adjacent
@@ -65,76 +127,58 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
 }
 
 // ---- apply: y = act((z - mean) * (invstd * gamma) + beta) ------------------------------------------------------
-// stat_is_var != 0: `invstd_or_var` holds a variance (eval mode: running_var) and invstd is computed here.
 template <bool VEC4>
 __global__ __launch_bounds__(256) void bn_apply_act_kernel(const float* __restrict__ z, float* __restrict__ y,
                                                            const float* __restrict__ mean, const float* __restrict__ invstd_or_var,
                                                            int stat_is_var, float eps, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, int C, int HW, int act) {
   const int plane = blockIdx.y;
-  const int c = plane % C;
-  const float mu = mean[c];
-  const float is = stat_is_var ? 1.0f / sqrtf(invstd_or_var[c] + eps) : invstd_or_var[c];
-  const float sc = is * gamma[c];
-  const float sh = beta[c];
+  BnChan<1> q;
+  bn_chan_load(q, plane % C, C, mean, invstd_or_var, stat_is_var, eps, gamma, beta);
   const float* zp = z + (size_t)plane * HW;
   float* yp = y + (size_t)plane * HW;
+  const auto fwd = [&](float v) { return act_fwd(fmaf(v - q.mu[0], q.sc[0], q.be[0]), act); };
   if (VEC4) {
-    const int n4 = HW >> 2;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+    PLANE_WALK(i, HW >> 2) {
       float4 v = reinterpret_cast<const float4*>(zp)[i];
-      v.x = act_fwd(fmaf(v.x - mu, sc, sh), act);
-      v.y = act_fwd(fmaf(v.y - mu, sc, sh), act);
-      v.z = act_fwd(fmaf(v.z - mu, sc, sh), act);
-      v.w = act_fwd(fmaf(v.w - mu, sc, sh), act);
+      v.x = fwd(v.x);
+      v.y = fwd(v.y);
+      v.z = fwd(v.z);
+      v.w = fwd(v.w);
       reinterpret_cast<float4*>(yp)[i] = v;
     }
   } else {
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256) yp[i] = act_fwd(fmaf(zp[i] - mu, sc, sh), act);
+    PLANE_WALK(i, HW) yp[i] = fwd(zp[i]);
   }
 }
 
-// ---- backward reduce: per (plane chunk) partial sums of g and g * xhat -------------------------------------------
-// g is the gradient w.r.t. the block output; when act != none the activation derivative is applied here, from the
-// recomputed pre-activation xhat*gamma + beta (so no pre-activation tensor has to be saved, LeakyReLU and SiLU alike).
+// ---- backward reduce: per (plane chunk) partial sums of g' and g' * xhat ----------------------------------------
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restrict__ g, const float* __restrict__ z,
                                                             const float* __restrict__ mean, const float* __restrict__ invstd,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
                                                             int act, float* __restrict__ part, int C, int HW) {
-  __shared__ float sh[2][4];
+  __shared__ float sh[4][2];
   const int plane = blockIdx.y;  // b*C + c
   const int c = plane % C;
-  const int b = plane / C;
-  const float mu = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
+  BnChan<1> q;
+  bn_chan_load(q, c, C, mean, invstd, 0, 0.f, gamma, beta);
   const float* gp = g + (size_t)plane * HW;
   const float* zp = z + (size_t)plane * HW;
-  float s = 0.f, q = 0.f;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256) {
-    const float xh = (zp[i] - mu) * is;
-    const float gv = gp[i] * act_bwd_factor(fmaf(xh, ga, be), act);
-    s += gv;
-    q += gv * xh;
+  float s = 0.f, t = 0.f;
+  PLANE_WALK(i, HW) {
+    const BnGrad e = bn_grad(q, 0, zp[i], gp[i], act);
+    s += e.ge;
+    t += e.ge * e.xh;
   }
-  s = wave_sum(s);
-  q = wave_sum(q);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    sh[0][wave] = s;
-    sh[1][wave] = q;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float* dst = part + ((size_t)(b * gridDim.x + blockIdx.x) * C + c) * 2;
-    dst[0] = sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3];
-    dst[1] = sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3];
-  }
+  block_put2(sh[threadIdx.x >> 6], threadIdx.x & 63, 0, s, t);
+  bn_part_store(sh, part, plane / C, C, c);
 }
 
 // dbeta = sum g, dgamma = sum g*xhat (fp64, fixed order), optionally clamped (the reference's per-parameter hook)
 __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __restrict__ part, int rows, int C, float clip,
                                                               float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                               float* __restrict__ sum_g, float* __restrict__ sum_gx) {
-  __shared__ double sh[2][4];
+  __shared__ double sh[4][2];
   const int c = blockIdx.x;
   double s = 0.0, q = 0.0;
   for (int r = threadIdx.x; r < rows; r += 256) {
@@ -142,17 +186,11 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
     s += (double)src[0];
     q += (double)src[1];
   }
-  s = wave_sum_d(s);
-  q = wave_sum_d(q);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    sh[0][wave] = s;
-    sh[1][wave] = q;
-  }
+  block_put2(sh[threadIdx.x >> 6], threadIdx.x & 63, 0, s, q);
   __syncthreads();
   if (threadIdx.x == 0) {
-    s = sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3];
-    q = sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3];
+    s = block_sum4(sh, 0);
+    q = block_sum4(sh, 1);
     sum_g[c] = (float)s;
     sum_gx[c] = (float)q;
     float db = (float)s, dg = (float)q;
@@ -165,7 +203,6 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
   }
 }
 
-// dz = gamma * invstd * (g - sum_g/n - xhat * sum_gx/n)   (training);  dz = gamma * invstd * g  (frozen stats)
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ g, const float* __restrict__ z,
                                                            float* __restrict__ dz, const float* __restrict__ mean,
                                                            const float* __restrict__ invstd, const float* __restrict__ gamma,
@@ -174,17 +211,13 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
                                                            float inv_count, int training, int C, int HW) {
   const int plane = blockIdx.y;
   const int c = plane % C;
-  const float mu = mean[c], is = invstd[c], ga = gamma[c], be = beta[c], gi = ga * is;
-  const float mg = training ? sum_g[c] * inv_count : 0.f;
-  const float mgx = training ? sum_gx[c] * inv_count : 0.f;
+  BnChan<1> q;
+  bn_chan_load(q, c, C, mean, invstd, 0, 0.f, gamma, beta);
+  const float mg = bn_mean_term(sum_g, c, inv_count, training), mgx = bn_mean_term(sum_gx, c, inv_count, training);
   const float* gp = g + (size_t)plane * HW;
   const float* zp = z + (size_t)plane * HW;
   float* dp = dz + (size_t)plane * HW;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256) {
-    const float xh = (zp[i] - mu) * is;
-    const float gv = gp[i] * act_bwd_factor(fmaf(xh, ga, be), act);
-    dp[i] = gi * (gv - mg - xh * mgx);
-  }
+  PLANE_WALK(i, HW) dp[i] = bn_dz(q, 0, zp[i], gp[i], act, mg, mgx);
 }
 
 // eval-mode helper: invstd = 1/sqrt(var + eps)
@@ -217,7 +250,7 @@ __global__ __launch_bounds__(256) void partials_reduce_kernel(const float* __res
 // per-channel sum over (b, h, w) of an NCHW tensor (bias gradients): one workgroup per channel, fixed order
 __global__ __launch_bounds__(256) void channel_sum_kernel(const float* __restrict__ g, int B, int C, int HW, float clip,
                                                           float* __restrict__ out) {
-  __shared__ double sh[4];
+  __shared__ double sh[4][1];
   const int c = blockIdx.x;
   double s = 0.0;
   for (int b = 0; b < B; ++b) {
@@ -226,18 +259,53 @@ __global__ __launch_bounds__(256) void channel_sum_kernel(const float* __restric
     for (int i = threadIdx.x; i < HW; i += 256) ps += gp[i];
     s += (double)ps;
   }
-  s = wave_sum_d(s);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) sh[wave] = s;
+  block_put(sh[threadIdx.x >> 6], threadIdx.x & 63, 0, s);
   __syncthreads();
   if (threadIdx.x == 0) {
-    float v = (float)(sh[0] + sh[1] + sh[2] + sh[3]);
+    float v = (float)block_sum4(sh, 0);
     if (clip > 0.f) v = fminf(fmaxf(v, -clip), clip);
     out[c] = v;
   }
 }
 
+// =========================================================================================================
+// Launch geometry.  grid = (workgroups per plane, planes): a plane is (image, channel) in fp32 and (image, channel block) in NCHW8c.
+// Workgroups per plane, by family: 256 threads x the pixels a thread takes, 64 at the most.  The *_rows queries report images x this, and
+// the launchers that write those rows call the same function.
+// =========================================================================================================
 static inline int plane_blocks(int HW, int per_thread) { return max(1, min(64, cdiv(HW, 256 * per_thread))); }
+static inline int f32_blocks(int HW) { return plane_blocks(HW, 8); }
+static inline int c8_blocks(int HW) { return plane_blocks(HW, 4); }
+static inline int convert_blocks(int HW) { return plane_blocks(HW, 2); }
+static inline int cb_of(int C) { return ((C + 15) / 16) * 2; }  // channel blocks: C padded to a multiple of 16
+
+// gridDim.y holds the planes: the hardware's limit, refused before any launch
+static int check_planes(const char* entry, int B, int per_image, const char* unit) {
+  const long long limit = 65535;
+  YOGO_CHECK_ARG((long long)B * per_image <= limit, "%s: batch * %s exceeds %lld", entry, unit, limit);
+  return YOGO_OK;
+}
+
+// What the three backward entry points share.  Each runs bn_bwd_check, its reduce sweep, bn_bwd_finalize, its apply sweep.
+struct BnBwdArgs {
+  const float *mean, *invstd, *gamma, *beta;
+  float *dgamma, *dbeta, *part, *sums;
+  int B, C, HW;
+  float clip;
+  hipStream_t stream;
+};
+// io: the entry point's own tensors are there; shape: its further conditions on the shape
+static int bn_bwd_check(const char* entry, bool io, bool shape, int planes_per_image, const char* unit, const BnBwdArgs& a) {
+  YOGO_CHECK_ARG(io && a.mean && a.invstd && a.gamma && a.beta && a.dgamma && a.dbeta && a.part && a.sums, "%s: null pointer", entry);
+  YOGO_CHECK_ARG(shape && a.B > 0 && a.C > 0 && a.HW > 0, "%s: bad shape", entry);
+  return check_planes(entry, a.B, planes_per_image, unit);
+}
+// the fp64 sums of the B * nb partial rows -> sums (sum_g, then sum_gx), dgamma, dbeta; returns the apply sweep's 1 / (B HW)
+static float bn_bwd_finalize(const BnBwdArgs& a, int nb) {
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(a.C), dim3(256), 0, a.stream, a.part, a.B * nb, a.C, a.clip, a.dgamma, a.dbeta, a.sums,
+                     a.sums + a.C);
+  return 1.0f / ((float)a.B * (float)a.HW);
+}
 
 // =========================================================================================================
 // C ABI
@@ -258,13 +326,13 @@ extern "C" int yogo_bn_apply_act(const float* z, float* y, const float* mean, co
                                  hipStream_t stream) {
   YOGO_CHECK_ARG(z && y && mean && invstd_or_var && gamma && beta && C > 0 && HW > 0 && B >= 0, "bn_apply_act: bad arguments");
   if (B == 0) return YOGO_OK;
-  YOGO_CHECK_ARG((long long)B * C <= 65535, "bn_apply_act: batch * channels exceeds 65535");
+  if (int rc = check_planes("bn_apply_act", B, C, "channels")) return rc;
   if ((HW & 3) == 0) {
-    dim3 grid(plane_blocks(HW, 8), B * C);
+    dim3 grid(f32_blocks(HW), B * C);
     hipLaunchKernelGGL((bn_apply_act_kernel<true>), grid, dim3(256), 0, stream, z, y, mean, invstd_or_var, stat_is_var, eps,
                        gamma, beta, C, HW, act);
   } else {
-    dim3 grid(plane_blocks(HW, 4), B * C);
+    dim3 grid(plane_blocks(HW, 4), B * C);   // (the scalar walk: 4 pixels per thread; no partial rows depend on it)
     hipLaunchKernelGGL((bn_apply_act_kernel<false>), grid, dim3(256), 0, stream, z, y, mean, invstd_or_var, stat_is_var, eps,
                        gamma, beta, C, HW, act);
   }
@@ -281,7 +349,7 @@ extern "C" int yogo_bn_invstd(const float* var, float eps, float* invstd, int C,
 
 extern "C" int yogo_bn_bwd_rows(int B, int HW, int* rows) {
   YOGO_CHECK_ARG(rows != nullptr, "bn_bwd_rows: null");
-  *rows = B * plane_blocks(HW, 8);
+  *rows = B * f32_blocks(HW);
   return YOGO_OK;
 }
 
@@ -290,14 +358,14 @@ extern "C" int yogo_bn_bwd_rows(int B, int HW, int* rows) {
 extern "C" int yogo_bn_bwd(const float* g, const float* z, float* dz, const float* mean, const float* invstd,
                            const float* gamma, const float* beta, int act, float* dgamma, float* dbeta, float* part,
                            float* sums, int B, int C, int HW, int training, float clip, hipStream_t stream) {
-  YOGO_CHECK_ARG(g && z && dz && mean && invstd && gamma && beta && dgamma && dbeta && part && sums, "bn_bwd: null pointer");
-  YOGO_CHECK_ARG(B > 0 && C > 0 && HW > 0, "bn_bwd: bad shape");
-  YOGO_CHECK_ARG((long long)B * C <= 65535, "bn_bwd: batch * channels exceeds 65535");
-  const int nb = plane_blocks(HW, 8);
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(nb, B * C), dim3(256), 0, stream, g, z, mean, invstd, gamma, beta, act, part, C, HW);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, stream, part, B * nb, C, clip, dgamma, dbeta, sums, sums + C);
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(nb, B * C), dim3(256), 0, stream, g, z, dz, mean, invstd, gamma, beta, act, sums,
-                     sums + C, 1.0f / ((float)B * (float)HW), training, C, HW);
+  const BnBwdArgs a{mean, invstd, gamma, beta, dgamma, dbeta, part, sums, B, C, HW, clip, stream};
+  if (int rc = bn_bwd_check("bn_bwd", g && z && dz, true, C, "channels", a)) return rc;
+  const int nb = f32_blocks(HW);
+  const dim3 grid(nb, B * C);
+  hipLaunchKernelGGL(bn_bwd_reduce_kernel, grid, dim3(256), 0, stream, g, z, mean, invstd, gamma, beta, act, part, C, HW);
+  const float inv_count = bn_bwd_finalize(a, nb);
+  hipLaunchKernelGGL(bn_bwd_apply_kernel, grid, dim3(256), 0, stream, g, z, dz, mean, invstd, gamma, beta, act, sums, sums + C, inv_count,
+                     training, C, HW);
   YOGO_CHECK_LAUNCH("bn_bwd");
   return YOGO_OK;
 }
@@ -344,200 +412,140 @@ extern "C" int yogo_channel_sum(const float* g, int B, int C, int HW, float clip
 // bf16 NCHW8c variants (training in bf16 storage): one 16-byte unit = 8 consecutive channels of one pixel.
 // A "plane" is (image, channel block); statistics stay fp32 / fp64.
 // =========================================================================================================
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-
-struct Bn8cParams {
-  float mu[8], sc[8], sh[8], ga[8], is[8];
+// this workgroup's plane: image, channel block, index of the plane's first unit
+struct Plane8c {
+  int b, cb;
+  size_t at;
 };
-
-__device__ __forceinline__ void bn8c_load(Bn8cParams& q, int cb, int C, const float* mean, const float* invstd_or_var,
-                                          int stat_is_var, float eps, const float* gamma, const float* beta) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = min(cb * 8 + j, C - 1);
-    const float is = stat_is_var ? 1.0f / sqrtf(invstd_or_var[c] + eps) : invstd_or_var[c];
-    q.mu[j] = mean[c];
-    q.is[j] = is;
-    q.ga[j] = gamma[c];
-    q.sc[j] = is * gamma[c];
-    q.sh[j] = beta[c];
-  }
+__device__ __forceinline__ Plane8c plane_8c(int Cb, int HW) {
+  const int plane = blockIdx.y;  // b*Cb + cb
+  return {plane / Cb, plane % Cb, (size_t)plane * HW};
 }
+__device__ __forceinline__ bf16x8 unit_load(const u32x4* p) { return __builtin_bit_cast(bf16x8, *p); }
+// lane j of the unit of channel block cb: the result, or zero in a padding channel (>= C)
+__device__ __forceinline__ __bf16 unit_lane(float r, int cb, int j, int C) { return (cb * 8 + j < C) ? (__bf16)r : (__bf16)0.f; }
 
-__global__ __launch_bounds__(256) void bn_apply_act_8c_kernel(const u32x4_t* __restrict__ z, u32x4_t* __restrict__ y,
+__global__ __launch_bounds__(256) void bn_apply_act_8c_kernel(const u32x4* __restrict__ z, u32x4* __restrict__ y,
                                                               const float* __restrict__ mean,
                                                               const float* __restrict__ invstd_or_var, int stat_is_var, float eps,
                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
                                                               int C, int Cb, int HW, int act) {
-  const int plane = blockIdx.y;  // b*Cb + cb
-  const int cb = plane % Cb;
-  Bn8cParams q;
-  bn8c_load(q, cb, C, mean, invstd_or_var, stat_is_var, eps, gamma, beta);
-  const u32x4_t* zp = z + (size_t)plane * HW;
-  u32x4_t* yp = y + (size_t)plane * HW;
+  const Plane8c p = plane_8c(Cb, HW);
+  BnChan<8> q;
+  bn_chan_load(q, p.cb * 8, C, mean, invstd_or_var, stat_is_var, eps, gamma, beta);
   float sh2[8];  // y = z * sc + (beta - mean * sc): one FMA per value (conv_first_mfma_kernel applies the same form)
 #pragma unroll
-  for (int j = 0; j < 8; ++j) sh2[j] = fmaf(-q.mu[j], q.sc[j], q.sh[j]);
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256) {
-    const bf16x8_t v = __builtin_bit_cast(bf16x8_t, zp[i]);
-    bf16x8_t o;
+  for (int j = 0; j < 8; ++j) sh2[j] = fmaf(-q.mu[j], q.sc[j], q.be[j]);
+  PLANE_WALK(i, HW) {
+    const bf16x8 v = unit_load(z + p.at + i);
+    bf16x8 o;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float r = act_fwd(fmaf((float)v[j], q.sc[j], sh2[j]), act);
-      o[j] = (cb * 8 + j < C) ? (__bf16)r : (__bf16)0.f;
-    }
-    yp[i] = __builtin_bit_cast(u32x4_t, o);
+    for (int j = 0; j < 8; ++j) o[j] = unit_lane(act_fwd(fmaf((float)v[j], q.sc[j], sh2[j]), act), p.cb, j, C);
+    y[p.at + i] = __builtin_bit_cast(u32x4, o);
   }
 }
 
-// batch statistics of a stored bf16 tensor: partial (sum, sum of squares) per channel, rows = B * gridDim.x
-__global__ __launch_bounds__(256) void bn_stats_8c_kernel(const u32x4_t* __restrict__ z, float* __restrict__ part, int C, int Cb,
-                                                          int HW) {
+// A reduce sweep over the planes of an 8c tensor: add(i, s, t) adds pixel i of plane p into the two running sums of its eight channels,
+// then the block reduction and the partial row.  rows = B * gridDim.x.
+template <class F>
+__device__ __forceinline__ void reduce_8c(const Plane8c& p, float* part, int C, int HW, F&& add) {
   __shared__ float sh[4][16];
-  const int plane = blockIdx.y;
-  const int cb = plane % Cb, b = plane / Cb;
-  const u32x4_t* zp = z + (size_t)plane * HW;
   float s[8], t[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) s[j] = t[j] = 0.f;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256) {
-    const bf16x8_t zv = __builtin_bit_cast(bf16x8_t, zp[i]);
+  PLANE_WALK(i, HW) add(i, s, t);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) block_put2(sh[wave], lane, 2 * j, s[j], t[j]);
+  bn_part_store(sh, part, p.b, C, p.cb * 8);
+}
+
+// batch statistics of a stored bf16 tensor: partial (sum, sum of squares) per channel
+__global__ __launch_bounds__(256) void bn_stats_8c_kernel(const u32x4* __restrict__ z, float* __restrict__ part, int C, int Cb,
+                                                          int HW) {
+  const Plane8c p = plane_8c(Cb, HW);
+  reduce_8c(p, part, C, HW, [&](int i, float (&s)[8], float (&t)[8]) {
+    const bf16x8 zv = unit_load(z + p.at + i);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float v = (float)zv[j];
       s[j] += v;
       t[j] = fmaf(v, v, t[j]);
     }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float a = wave_sum(s[j]), c = wave_sum(t[j]);
-    if (lane == 0) {
-      sh[wave][2 * j] = a;
-      sh[wave][2 * j + 1] = c;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < 16) {
-    const int j = threadIdx.x >> 1;
-    if (cb * 8 + j < C)
-      part[((size_t)(b * gridDim.x + blockIdx.x) * C + cb * 8 + j) * 2 + (threadIdx.x & 1)] =
-          sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
-  }
+  });
 }
 
-// partial sums of g' and g' * xhat per channel, g' = g * act'(xhat*gamma + beta)
-__global__ __launch_bounds__(256) void bn_bwd_reduce_8c_kernel(const u32x4_t* __restrict__ g, const u32x4_t* __restrict__ z,
+// partial sums of g' and g' * xhat per channel
+__global__ __launch_bounds__(256) void bn_bwd_reduce_8c_kernel(const u32x4* __restrict__ g, const u32x4* __restrict__ z,
                                                                const float* __restrict__ mean, const float* __restrict__ invstd,
                                                                const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                int act, float* __restrict__ part, int C, int Cb, int HW) {
-  __shared__ float sh[4][16];
-  const int plane = blockIdx.y;
-  const int cb = plane % Cb, b = plane / Cb;
-  Bn8cParams q;
-  bn8c_load(q, cb, C, mean, invstd, 0, 0.f, gamma, beta);
-  const u32x4_t* gp = g + (size_t)plane * HW;
-  const u32x4_t* zp = z + (size_t)plane * HW;
-  float s[8], t[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) s[j] = t[j] = 0.f;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256) {
-    const bf16x8_t gv = __builtin_bit_cast(bf16x8_t, gp[i]);
-    const bf16x8_t zv = __builtin_bit_cast(bf16x8_t, zp[i]);
+  const Plane8c p = plane_8c(Cb, HW);
+  BnChan<8> q;
+  bn_chan_load(q, p.cb * 8, C, mean, invstd, 0, 0.f, gamma, beta);
+  reduce_8c(p, part, C, HW, [&](int i, float (&s)[8], float (&t)[8]) {
+    const bf16x8 gv = unit_load(g + p.at + i), zv = unit_load(z + p.at + i);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float xh = ((float)zv[j] - q.mu[j]) * q.is[j];
-      const float ge = (float)gv[j] * act_bwd_factor(fmaf(xh, q.ga[j], q.sh[j]), act);
-      s[j] += ge;
-      t[j] += ge * xh;
+      const BnGrad e = bn_grad(q, j, (float)zv[j], (float)gv[j], act);
+      s[j] += e.ge;
+      t[j] += e.ge * e.xh;
     }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float a = wave_sum(s[j]), c = wave_sum(t[j]);
-    if (lane == 0) {
-      sh[wave][2 * j] = a;
-      sh[wave][2 * j + 1] = c;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < 16) {
-    const int j = threadIdx.x >> 1;
-    if (cb * 8 + j < C)
-      part[((size_t)(b * gridDim.x + blockIdx.x) * C + cb * 8 + j) * 2 + (threadIdx.x & 1)] =
-          sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
-  }
+  });
 }
 
-__global__ __launch_bounds__(256) void bn_bwd_apply_8c_kernel(const u32x4_t* __restrict__ g, const u32x4_t* __restrict__ z,
-                                                              u32x4_t* __restrict__ dz, const float* __restrict__ mean,
+__global__ __launch_bounds__(256) void bn_bwd_apply_8c_kernel(const u32x4* __restrict__ g, const u32x4* __restrict__ z,
+                                                              u32x4* __restrict__ dz, const float* __restrict__ mean,
                                                               const float* __restrict__ invstd, const float* __restrict__ gamma,
                                                               const float* __restrict__ beta, int act,
                                                               const float* __restrict__ sum_g, const float* __restrict__ sum_gx,
                                                               float inv_count, int training, int C, int Cb, int HW) {
-  const int plane = blockIdx.y;
-  const int cb = plane % Cb;
-  Bn8cParams q;
-  bn8c_load(q, cb, C, mean, invstd, 0, 0.f, gamma, beta);
+  const Plane8c p = plane_8c(Cb, HW);
+  BnChan<8> q;
+  bn_chan_load(q, p.cb * 8, C, mean, invstd, 0, 0.f, gamma, beta);
   float mg[8], mgx[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    const int c = min(cb * 8 + j, C - 1);
-    mg[j] = training ? sum_g[c] * inv_count : 0.f;
-    mgx[j] = training ? sum_gx[c] * inv_count : 0.f;
+    const int c = min(p.cb * 8 + j, C - 1);   // (a padding lane: bn_chan_load's rule)
+    mg[j] = bn_mean_term(sum_g, c, inv_count, training);
+    mgx[j] = bn_mean_term(sum_gx, c, inv_count, training);
   }
-  const u32x4_t* gp = g + (size_t)plane * HW;
-  const u32x4_t* zp = z + (size_t)plane * HW;
-  u32x4_t* dp = dz + (size_t)plane * HW;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256) {
-    const bf16x8_t gv = __builtin_bit_cast(bf16x8_t, gp[i]);
-    const bf16x8_t zv = __builtin_bit_cast(bf16x8_t, zp[i]);
-    bf16x8_t o;
+  PLANE_WALK(i, HW) {
+    const bf16x8 gv = unit_load(g + p.at + i), zv = unit_load(z + p.at + i);
+    bf16x8 o;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float xh = ((float)zv[j] - q.mu[j]) * q.is[j];
-      const float ge = (float)gv[j] * act_bwd_factor(fmaf(xh, q.ga[j], q.sh[j]), act);
-      const float r = q.sc[j] * (ge - mg[j] - xh * mgx[j]);
-      o[j] = (cb * 8 + j < C) ? (__bf16)r : (__bf16)0.f;
-    }
-    dp[i] = __builtin_bit_cast(u32x4_t, o);
+    for (int j = 0; j < 8; ++j) o[j] = unit_lane(bn_dz(q, j, (float)zv[j], (float)gv[j], act, mg[j], mgx[j]), p.cb, j, C);
+    dz[p.at + i] = __builtin_bit_cast(u32x4, o);
   }
 }
 
 // fp32 NCHW -> bf16 NCHW8c (Cb channel blocks, padding channels zero) and back
-__global__ __launch_bounds__(256) void nchw_f32_to_8c_kernel(const float* __restrict__ in, u32x4_t* __restrict__ out, int C, int Cb,
+__global__ __launch_bounds__(256) void nchw_f32_to_8c_kernel(const float* __restrict__ in, u32x4* __restrict__ out, int C, int Cb,
                                                              int HW) {
-  const int plane = blockIdx.y;  // b*Cb + cb
-  const int cb = plane % Cb, b = plane / Cb;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256) {
-    bf16x8_t o;
+  const Plane8c p = plane_8c(Cb, HW);
+  PLANE_WALK(i, HW) {
+    bf16x8 o;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const int c = cb * 8 + j;
-      o[j] = (c < C) ? (__bf16)in[((size_t)b * C + c) * HW + i] : (__bf16)0.f;
+      const int c = p.cb * 8 + j;
+      o[j] = (c < C) ? (__bf16)in[((size_t)p.b * C + c) * HW + i] : (__bf16)0.f;   // (unit_lane's test, in front of the load)
     }
-    out[(size_t)plane * HW + i] = __builtin_bit_cast(u32x4_t, o);
+    out[p.at + i] = __builtin_bit_cast(u32x4, o);
   }
 }
 
-__global__ __launch_bounds__(256) void nchw8c_to_f32_kernel(const u32x4_t* __restrict__ in, float* __restrict__ out, int C, int Cb,
+__global__ __launch_bounds__(256) void nchw8c_to_f32_kernel(const u32x4* __restrict__ in, float* __restrict__ out, int C, int Cb,
                                                             int HW) {
-  const int plane = blockIdx.y;
-  const int cb = plane % Cb, b = plane / Cb;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256) {
-    const bf16x8_t v = __builtin_bit_cast(bf16x8_t, in[(size_t)plane * HW + i]);
+  const Plane8c p = plane_8c(Cb, HW);
+  PLANE_WALK(i, HW) {
+    const bf16x8 v = unit_load(in + p.at + i);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const int c = cb * 8 + j;
-      if (c < C) out[((size_t)b * C + c) * HW + i] = (float)v[j];
+      const int c = p.cb * 8 + j;
+      if (c < C) out[((size_t)p.b * C + c) * HW + i] = (float)v[j];
     }
   }
 }
-
-static inline int cb_of(int C) { return ((C + 15) / 16) * 2; }  // channel blocks: C padded to a multiple of 16
 
 extern "C" int yogo_bn_apply_act_bf16(const void* z, void* y, const float* mean, const float* invstd_or_var, int stat_is_var,
                                       float eps, const float* gamma, const float* beta, int B, int C, int HW, int act,
@@ -545,17 +553,16 @@ extern "C" int yogo_bn_apply_act_bf16(const void* z, void* y, const float* mean,
   YOGO_CHECK_ARG(z && y && mean && invstd_or_var && gamma && beta && C > 0 && HW > 0 && B >= 0, "bn_apply_act_bf16: bad arguments");
   if (B == 0) return YOGO_OK;
   const int Cb = cb_of(C);
-  YOGO_CHECK_ARG(B * Cb <= 65535, "bn_apply_act_bf16: batch * channel blocks exceeds 65535");
-  hipLaunchKernelGGL(bn_apply_act_8c_kernel, dim3(plane_blocks(HW, 4), B * Cb), dim3(256), 0, stream,
-                     reinterpret_cast<const u32x4_t*>(z), reinterpret_cast<u32x4_t*>(y), mean, invstd_or_var, stat_is_var, eps,
-                     gamma, beta, C, Cb, HW, act);
+  if (int rc = check_planes("bn_apply_act_bf16", B, Cb, "channel blocks")) return rc;
+  hipLaunchKernelGGL(bn_apply_act_8c_kernel, dim3(c8_blocks(HW), B * Cb), dim3(256), 0, stream, reinterpret_cast<const u32x4*>(z),
+                     reinterpret_cast<u32x4*>(y), mean, invstd_or_var, stat_is_var, eps, gamma, beta, C, Cb, HW, act);
   YOGO_CHECK_LAUNCH("bn_apply_act_bf16");
   return YOGO_OK;
 }
 
 extern "C" int yogo_bn_bwd_bf16_rows(int B, int HW, int* rows) {
   YOGO_CHECK_ARG(rows != nullptr, "bn_bwd_bf16_rows: null");
-  *rows = B * plane_blocks(HW, 4);
+  *rows = B * c8_blocks(HW);
   return YOGO_OK;
 }
 
@@ -563,17 +570,16 @@ extern "C" int yogo_bn_bwd_bf16_rows(int B, int HW, int* rows) {
 extern "C" int yogo_bn_bwd_bf16(const void* g, const void* z, void* dz, const float* mean, const float* invstd,
                                 const float* gamma, const float* beta, int act, float* dgamma, float* dbeta, float* part,
                                 float* sums, int B, int C, int HW, int training, float clip, hipStream_t stream) {
-  YOGO_CHECK_ARG(g && z && dz && mean && invstd && gamma && beta && dgamma && dbeta && part && sums, "bn_bwd_bf16: null pointer");
-  YOGO_CHECK_ARG(B > 0 && C > 0 && HW > 0, "bn_bwd_bf16: bad shape");
-  const int Cb = cb_of(C), nb = plane_blocks(HW, 4);
-  YOGO_CHECK_ARG(B * Cb <= 65535, "bn_bwd_bf16: batch * channel blocks exceeds 65535");
-  const u32x4_t* g4 = reinterpret_cast<const u32x4_t*>(g);
-  const u32x4_t* z4 = reinterpret_cast<const u32x4_t*>(z);
-  hipLaunchKernelGGL(bn_bwd_reduce_8c_kernel, dim3(nb, B * Cb), dim3(256), 0, stream, g4, z4, mean, invstd, gamma, beta, act, part, C,
-                     Cb, HW);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, stream, part, B * nb, C, clip, dgamma, dbeta, sums, sums + C);
-  hipLaunchKernelGGL(bn_bwd_apply_8c_kernel, dim3(nb, B * Cb), dim3(256), 0, stream, g4, z4, reinterpret_cast<u32x4_t*>(dz), mean,
-                     invstd, gamma, beta, act, sums, sums + C, 1.0f / ((float)B * (float)HW), training, C, Cb, HW);
+  const BnBwdArgs a{mean, invstd, gamma, beta, dgamma, dbeta, part, sums, B, C, HW, clip, stream};
+  const int Cb = cb_of(C), nb = c8_blocks(HW);
+  if (int rc = bn_bwd_check("bn_bwd_bf16", g && z && dz, true, Cb, "channel blocks", a)) return rc;
+  const dim3 grid(nb, B * Cb);
+  const u32x4* g4 = reinterpret_cast<const u32x4*>(g);
+  const u32x4* z4 = reinterpret_cast<const u32x4*>(z);
+  hipLaunchKernelGGL(bn_bwd_reduce_8c_kernel, grid, dim3(256), 0, stream, g4, z4, mean, invstd, gamma, beta, act, part, C, Cb, HW);
+  const float inv_count = bn_bwd_finalize(a, nb);
+  hipLaunchKernelGGL(bn_bwd_apply_8c_kernel, grid, dim3(256), 0, stream, g4, z4, reinterpret_cast<u32x4*>(dz), mean, invstd, gamma, beta, act,
+                     sums, sums + C, inv_count, training, C, Cb, HW);
   YOGO_CHECK_LAUNCH("bn_bwd_bf16");
   return YOGO_OK;
 }
@@ -584,12 +590,12 @@ extern "C" int yogo_bn_bwd_bf16(const void* g, const void* z, void* dz, const fl
 // as they lie in memory), so lane (c16, g4) gets channels 4 g4 .. 4 g4 + 3 of pixel c16 -- the half of a 16-byte unit of z it then works on.
 // Both sweeps compute the same g (rounded to bf16 as the data-gradient kernel's output would have been): the 128-channel gradient tensor is
 // never written or read (-0.41 GB written, -0.82 GB read per step of base_model at batch 128).
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+// The pair keeps its own lane set-up, parameter loop and stripe loop (every channel 16 cp + 4 g4 + i exists: no clamp): with the set-up
+// behind one struct, the walk behind a macro and bn_chan_load's clamped loop, yogo_bn_bwd_bf16_head at 128 x 128 x 97*129 took 356.6 against
+// 354.6 us (LeakyReLU, frozen statistics) and 444.7 against 437.8 us (SiLU, batch statistics), outside the earlier text's own spread (profiles/bn_one_definition.log, 3a).
 struct BnHeadLane {
-  bf16x8_t wop;                            // A operand: channel 16 cp + c16, head outputs 8 g4 .. 8 g4 + 7
-  float mu[4], is[4], ga[4], sh[4], sc[4];  // channels 16 cp + 4 g4 + i
+  bf16x8 wop;     // A operand: channel 16 cp + c16, head outputs 8 g4 .. 8 g4 + 7
+  BnChan<4> q;    // channels 16 cp + 4 g4 + i
 };
 __device__ __forceinline__ void bn_head_lane(BnHeadLane& L, const float* __restrict__ hw, int P, int C, int cp, int c16, int g4, const float* mean,
                                              const float* invstd, const float* gamma, const float* beta) {
@@ -601,27 +607,27 @@ __device__ __forceinline__ void bn_head_lane(BnHeadLane& L, const float* __restr
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int c = 16 * cp + 4 * g4 + i;
-    L.mu[i] = mean[c]; L.is[i] = invstd[c]; L.ga[i] = gamma[c]; L.sh[i] = beta[c]; L.sc[i] = invstd[c] * gamma[c];
+    L.q.mu[i] = mean[c]; L.q.is[i] = invstd[c]; L.q.ga[i] = gamma[c]; L.q.be[i] = beta[c]; L.q.sc[i] = invstd[c] * gamma[c];
   }
 }
 // this lane's four gradients (bf16-rounded, widened) and pre-activations of pixel px (nothing beyond the plane: zeros)
-__device__ __forceinline__ void bn_head_fetch(const BnHeadLane& L, const u32x4_t* __restrict__ ghp, const u32x2_t* __restrict__ zp2, int HW, int px, int g4,
+__device__ __forceinline__ void bn_head_fetch(const BnHeadLane& L, const u32x4* __restrict__ ghp, const u32x2* __restrict__ zp2, int HW, int px, int g4,
                                               float (&gb)[4], float (&zf)[4]) {
   const bool valid = px < HW;
-  u32x4_t gop = {0u, 0u, 0u, 0u};
+  u32x4 gop = {0u, 0u, 0u, 0u};
   if (valid && g4 < 2) gop = ghp[(size_t)g4 * HW + px];
-  u32x2_t zr = {0u, 0u};
+  u32x2 zr = {0u, 0u};
   if (valid) zr = zp2[(size_t)px * 2];
-  const f32x4_t d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(L.wop, __builtin_bit_cast(bf16x8_t, gop), f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-  const bf16x4_t zv = __builtin_bit_cast(bf16x4_t, zr);
+  const f32x4 d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(L.wop, __builtin_bit_cast(bf16x8, gop), f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+  const bf16x4 zv = __builtin_bit_cast(bf16x4, zr);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     gb[i] = (float)(__bf16)d[i];
     zf[i] = (float)zv[i];
   }
 }
-__global__ __launch_bounds__(256) void bn_bwd_reduce_head_kernel(const u32x4_t* __restrict__ gh, const float* __restrict__ hw, int P,
-                                                                 const u32x4_t* __restrict__ z, const float* __restrict__ mean,
+__global__ __launch_bounds__(256) void bn_bwd_reduce_head_kernel(const u32x4* __restrict__ gh, const float* __restrict__ hw, int P,
+                                                                 const u32x4* __restrict__ z, const float* __restrict__ mean,
                                                                  const float* __restrict__ invstd, const float* __restrict__ gamma,
                                                                  const float* __restrict__ beta, int act, float* __restrict__ part, int C, int Cb, int HW) {
   __shared__ float sh[4][32];
@@ -629,21 +635,21 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_head_kernel(const u32x4_t* 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c16 = lane & 15, g4 = lane >> 4;
   BnHeadLane L;
   bn_head_lane(L, hw, P, C, cp, c16, g4, mean, invstd, gamma, beta);
-  const u32x4_t* ghp = gh + (size_t)b * 2 * HW;
-  const u32x2_t* zp2 = reinterpret_cast<const u32x2_t*>(z + ((size_t)b * Cb + 2 * cp + (g4 >> 1)) * HW) + (g4 & 1);
+  const u32x4* ghp = gh + (size_t)b * 2 * HW;
+  const u32x2* zp2 = reinterpret_cast<const u32x2*>(z + ((size_t)b * Cb + 2 * cp + (g4 >> 1)) * HW) + (g4 & 1);
   float s[4] = {0.f, 0.f, 0.f, 0.f}, t[4] = {0.f, 0.f, 0.f, 0.f};
   for (int px0 = (blockIdx.x * 4 + wave) * 16; px0 < HW; px0 += gridDim.x * 64) {
     float gb[4], zf[4];
     bn_head_fetch(L, ghp, zp2, HW, px0 + c16, g4, gb, zf);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const float xh = (zf[i] - L.mu[i]) * L.is[i];
-      const float ge = gb[i] * act_bwd_factor(fmaf(xh, L.ga[i], L.sh[i]), act);
-      s[i] += ge;
-      t[i] += ge * xh;
+      const BnGrad e = bn_grad(L.q, i, zf[i], gb[i], act);
+      s[i] += e.ge;
+      t[i] += e.ge * e.xh;
     }
   }
-  // sums over the 16 pixels of a lane group, then the four wavefronts
+  // sums over the 16 pixels of a lane group (not block_put's whole wavefront: its four groups hold different channels); the four
+  // wavefronts' entries then meet as everywhere
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     float a = s[i], c = t[i];
@@ -657,13 +663,10 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_head_kernel(const u32x4_t* 
       sh[wave][2 * (4 * g4 + i) + 1] = c;
     }
   }
-  __syncthreads();
-  if (threadIdx.x < 32)
-    part[((size_t)(b * gridDim.x + blockIdx.x) * C + 16 * cp + (threadIdx.x >> 1)) * 2 + (threadIdx.x & 1)] =
-        sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+  bn_part_store(sh, part, b, C, 16 * cp);
 }
-__global__ __launch_bounds__(256) void bn_bwd_apply_head_kernel(const u32x4_t* __restrict__ gh, const float* __restrict__ hw, int P,
-                                                                const u32x4_t* __restrict__ z, u32x4_t* __restrict__ dz, const float* __restrict__ mean,
+__global__ __launch_bounds__(256) void bn_bwd_apply_head_kernel(const u32x4* __restrict__ gh, const float* __restrict__ hw, int P,
+                                                                const u32x4* __restrict__ z, u32x4* __restrict__ dz, const float* __restrict__ mean,
                                                                 const float* __restrict__ invstd, const float* __restrict__ gamma,
                                                                 const float* __restrict__ beta, int act, const float* __restrict__ sum_g,
                                                                 const float* __restrict__ sum_gx, float inv_count, int training, int C, int Cb, int HW) {
@@ -674,26 +677,21 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_head_kernel(const u32x4_t* _
   float mg[4], mgx[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int c = 16 * cp + 4 * g4 + i;
-    mg[i] = training ? sum_g[c] * inv_count : 0.f;
-    mgx[i] = training ? sum_gx[c] * inv_count : 0.f;
+    mg[i] = bn_mean_term(sum_g, 16 * cp + 4 * g4 + i, inv_count, training);
+    mgx[i] = bn_mean_term(sum_gx, 16 * cp + 4 * g4 + i, inv_count, training);
   }
-  const u32x4_t* ghp = gh + (size_t)b * 2 * HW;
+  const u32x4* ghp = gh + (size_t)b * 2 * HW;
   const size_t plane_u = ((size_t)b * Cb + 2 * cp + (g4 >> 1)) * HW;
-  const u32x2_t* zp2 = reinterpret_cast<const u32x2_t*>(z + plane_u) + (g4 & 1);
-  u32x2_t* dp2 = reinterpret_cast<u32x2_t*>(dz + plane_u) + (g4 & 1);
+  const u32x2* zp2 = reinterpret_cast<const u32x2*>(z + plane_u) + (g4 & 1);
+  u32x2* dp2 = reinterpret_cast<u32x2*>(dz + plane_u) + (g4 & 1);
   for (int px0 = (blockIdx.x * 4 + wave) * 16; px0 < HW; px0 += gridDim.x * 64) {
     const int px = px0 + c16;
     float gb[4], zf[4];
     bn_head_fetch(L, ghp, zp2, HW, px, g4, gb, zf);
-    bf16x4_t o;
+    bf16x4 o;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float xh = (zf[i] - L.mu[i]) * L.is[i];
-      const float ge = gb[i] * act_bwd_factor(fmaf(xh, L.ga[i], L.sh[i]), act);
-      o[i] = (__bf16)(L.sc[i] * (ge - mg[i] - xh * mgx[i]));
-    }
-    if (px < HW) dp2[(size_t)px * 2] = __builtin_bit_cast(u32x2_t, o);
+    for (int i = 0; i < 4; ++i) o[i] = (__bf16)bn_dz(L.q, i, zf[i], gb[i], act, mg[i], mgx[i]);
+    if (px < HW) dp2[(size_t)px * 2] = __builtin_bit_cast(u32x2, o);
   }
 }
 // yogo_bn_bwd_bf16 with g computed from the head's output gradient gh (bf16 NCHW8c [B][2][HW], channels >= P zero) and the head's weights
@@ -702,21 +700,20 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_head_kernel(const u32x4_t* _
 extern "C" int yogo_bn_bwd_bf16_head(const void* gh, const float* head_w, int P, const void* z, void* dz, const float* mean, const float* invstd,
                                      const float* gamma, const float* beta, int act, float* dgamma, float* dbeta, float* part, float* sums,
                                      int B, int C, int HW, int training, float clip, hipStream_t stream) {
-  YOGO_CHECK_ARG(gh && head_w && z && dz && mean && invstd && gamma && beta && dgamma && dbeta && part && sums, "bn_bwd_bf16_head: null pointer");
-  YOGO_CHECK_ARG(B > 0 && C > 0 && (C % 16) == 0 && HW > 0 && P > 0 && P <= 16, "bn_bwd_bf16_head: bad shape");
-  const int Cb = cb_of(C), nb = plane_blocks(HW, 4);
-  YOGO_CHECK_ARG(B * Cb <= 65535, "bn_bwd_bf16_head: batch * channel blocks exceeds 65535");
-  const u32x4_t* g4 = reinterpret_cast<const u32x4_t*>(gh);
-  const u32x4_t* z4 = reinterpret_cast<const u32x4_t*>(z);
+  const BnBwdArgs a{mean, invstd, gamma, beta, dgamma, dbeta, part, sums, B, C, HW, clip, stream};
+  const int Cb = cb_of(C), nb = c8_blocks(HW);
+  if (int rc = bn_bwd_check("bn_bwd_bf16_head", gh && head_w && z && dz, (C % 16) == 0 && P > 0 && P <= 16, Cb, "channel blocks", a)) return rc;
+  const dim3 grid(nb, B * (Cb / 2));   // a workgroup takes a PAIR of channel blocks
+  const u32x4* g4 = reinterpret_cast<const u32x4*>(gh);
+  const u32x4* z4 = reinterpret_cast<const u32x4*>(z);
   if (yogo_launch_log_enabled()) {
     yogo_launch_log("bn_bwd_reduce_head_kernel | B=%d C=%d HW=%d P=%d act=%d grid=%dx%d", B, C, HW, P, act, nb, B * (Cb / 2));
     yogo_launch_log("bn_bwd_apply_head_kernel | B=%d C=%d HW=%d P=%d act=%d training=%d grid=%dx%d", B, C, HW, P, act, training, nb, B * (Cb / 2));
   }
-  hipLaunchKernelGGL(bn_bwd_reduce_head_kernel, dim3(nb, B * (Cb / 2)), dim3(256), 0, stream, g4, head_w, P, z4, mean, invstd, gamma, beta, act, part, C, Cb,
-                     HW);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, stream, part, B * nb, C, clip, dgamma, dbeta, sums, sums + C);
-  hipLaunchKernelGGL(bn_bwd_apply_head_kernel, dim3(nb, B * (Cb / 2)), dim3(256), 0, stream, g4, head_w, P, z4, reinterpret_cast<u32x4_t*>(dz), mean, invstd,
-                     gamma, beta, act, sums, sums + C, 1.0f / ((float)B * (float)HW), training, C, Cb, HW);
+  hipLaunchKernelGGL(bn_bwd_reduce_head_kernel, grid, dim3(256), 0, stream, g4, head_w, P, z4, mean, invstd, gamma, beta, act, part, C, Cb, HW);
+  const float inv_count = bn_bwd_finalize(a, nb);
+  hipLaunchKernelGGL(bn_bwd_apply_head_kernel, grid, dim3(256), 0, stream, g4, head_w, P, z4, reinterpret_cast<u32x4*>(dz), mean, invstd, gamma, beta,
+                     act, sums, sums + C, inv_count, training, C, Cb, HW);
   YOGO_CHECK_LAUNCH("bn_bwd_bf16_head");
   return YOGO_OK;
 }
@@ -726,9 +723,9 @@ extern "C" int yogo_bn_bwd_bf16_head(const void* gh, const float* head_w, int P,
 // epilogue when that epilogue is on the critical path of a one-workgroup-per-CU kernel.
 extern "C" int yogo_bn_stats_bf16(const void* z, float* part, int B, int C, int HW, hipStream_t stream) {
   YOGO_CHECK_ARG(z && part && B > 0 && C > 0 && HW > 0, "bn_stats_bf16: bad arguments");
-  const int Cb = cb_of(C), nb = plane_blocks(HW, 4);
-  YOGO_CHECK_ARG(B * Cb <= 65535, "bn_stats_bf16: batch * channel blocks exceeds 65535");
-  hipLaunchKernelGGL(bn_stats_8c_kernel, dim3(nb, B * Cb), dim3(256), 0, stream, reinterpret_cast<const u32x4_t*>(z), part, C, Cb, HW);
+  const int Cb = cb_of(C);
+  if (int rc = check_planes("bn_stats_bf16", B, Cb, "channel blocks")) return rc;
+  hipLaunchKernelGGL(bn_stats_8c_kernel, dim3(c8_blocks(HW), B * Cb), dim3(256), 0, stream, reinterpret_cast<const u32x4*>(z), part, C, Cb, HW);
   YOGO_CHECK_LAUNCH("bn_stats_bf16");
   return YOGO_OK;
 }
@@ -736,9 +733,9 @@ extern "C" int yogo_bn_stats_bf16(const void* z, float* part, int B, int C, int 
 extern "C" int yogo_nchw_f32_to_bf16_8c(const float* in, void* out, int B, int C, int HW, hipStream_t stream) {
   YOGO_CHECK_ARG(in && out && B > 0 && C > 0 && HW > 0, "nchw_f32_to_bf16_8c: bad arguments");
   const int Cb = cb_of(C);
-  YOGO_CHECK_ARG((long long)B * Cb <= 65535, "nchw_f32_to_bf16_8c: batch * channel blocks exceeds 65535");
-  hipLaunchKernelGGL(nchw_f32_to_8c_kernel, dim3(plane_blocks(HW, 2), B * Cb), dim3(256), 0, stream, in,
-                     reinterpret_cast<u32x4_t*>(out), C, Cb, HW);
+  if (int rc = check_planes("nchw_f32_to_bf16_8c", B, Cb, "channel blocks")) return rc;
+  hipLaunchKernelGGL(nchw_f32_to_8c_kernel, dim3(convert_blocks(HW), B * Cb), dim3(256), 0, stream, in, reinterpret_cast<u32x4*>(out), C, Cb,
+                     HW);
   YOGO_CHECK_LAUNCH("nchw_f32_to_bf16_8c");
   return YOGO_OK;
 }
@@ -746,9 +743,9 @@ extern "C" int yogo_nchw_f32_to_bf16_8c(const float* in, void* out, int B, int C
 extern "C" int yogo_bf16_8c_to_nchw_f32(const void* in, float* out, int B, int C, int HW, hipStream_t stream) {
   YOGO_CHECK_ARG(in && out && B > 0 && C > 0 && HW > 0, "bf16_8c_to_nchw_f32: bad arguments");
   const int Cb = cb_of(C);
-  YOGO_CHECK_ARG((long long)B * Cb <= 65535, "bf16_8c_to_nchw_f32: batch * channel blocks exceeds 65535");
-  hipLaunchKernelGGL(nchw8c_to_f32_kernel, dim3(plane_blocks(HW, 2), B * Cb), dim3(256), 0, stream,
-                     reinterpret_cast<const u32x4_t*>(in), out, C, Cb, HW);
+  if (int rc = check_planes("bf16_8c_to_nchw_f32", B, Cb, "channel blocks")) return rc;
+  hipLaunchKernelGGL(nchw8c_to_f32_kernel, dim3(convert_blocks(HW), B * Cb), dim3(256), 0, stream, reinterpret_cast<const u32x4*>(in), out, C, Cb,
+                     HW);
   YOGO_CHECK_LAUNCH("bf16_8c_to_nchw_f32");
   return YOGO_OK;
 }

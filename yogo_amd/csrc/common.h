@@ -98,3 +98,28 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ float wave_total(float v) { return wave_sum(v); }
+__device__ __forceinline__ double wave_total(double v) { return wave_sum_d(v); }
+
+// ---- block reduction of per-lane sums, 256 lanes = four wavefronts: the wavefront's tree (wave_sum's DPP adds; wave_sum_d's shuffles for
+// double), lane 0 of each wavefront puts the total into red[wave][e], a barrier (the caller's), then block_sum4 adds the four wavefronts'
+// entries left to right, ((r0 + r1) + r2) + r3.  The error bounds of tests/test_gpu_first_layer_edges.py count exactly these levels.
+// Wave-uniform control flow only (wave_sum).
+template <typename T>
+__device__ __forceinline__ void block_put(T* red_wave, int lane, int e, T v) {
+  const T s = wave_total(v);
+  if (lane == 0) red_wave[e] = s;
+}
+// two sums that sit side by side in the row (a sum and its sum of squares, S1 and S2), stored under one test of the lane
+template <typename T>
+__device__ __forceinline__ void block_put2(T* red_wave, int lane, int e, T v0, T v1) {
+  const T s0 = wave_total(v0), s1 = wave_total(v1);
+  if (lane == 0) {
+    red_wave[e] = s0;
+    red_wave[e + 1] = s1;
+  }
+}
+template <typename T, int N>
+__device__ __forceinline__ T block_sum4(const T (&red)[4][N], int e) {
+  return red[0][e] + red[1][e] + red[2][e] + red[3][e];
+}

@@ -31,7 +31,7 @@ __device__ __forceinline__ void cf_stats_store(const float (&red)[4][2 * CF_COCH
   if (tid < 2 * CF_COCHUNK) {
     const int c = tid >> 1;
     if (co0 + c < p.Cout)
-      p.stats_part[((size_t)(b * gridDim.x + blockIdx.x) * p.Cout + co0 + c) * 2 + (tid & 1)] = cf_sum4(red, tid);
+      p.stats_part[((size_t)(b * gridDim.x + blockIdx.x) * p.Cout + co0 + c) * 2 + (tid & 1)] = block_sum4(red, tid);
   }
 }
 
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(CF_THREADS) void conv_first_kernel(const ConvFirstP
     }
     if (p.stats_part != nullptr) {
 #pragma unroll
-      for (int c = 0; c < CF_COCHUNK; ++c) cf_wave_put2(red[wave], lane, 2 * c, s[c], q[c]);
+      for (int c = 0; c < CF_COCHUNK; ++c) block_put2(red[wave], lane, 2 * c, s[c], q[c]);
       __syncthreads();
       cf_stats_store(red, p, co0, b, tid);
       __syncthreads();
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(CF_THREADS) void conv_first_train_bf16_kernel(const
           sc += vm;
           qc += vm * vm;
         }
-        cf_wave_put2(red[wave], lane, 2 * c, sc, qc);
+        block_put2(red[wave], lane, 2 * c, sc, qc);
       }
     }
     // activation + channel scale + bf16 store
@@ -282,11 +282,11 @@ __global__ __launch_bounds__(CF_THREADS) void conv_first_wgrad_kernel(const Conv
 #pragma unroll
     for (int c = 0; c < COC; ++c)
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) cf_wave_put(red[wave], lane, c * NJ + j, acc[c][j]);
+      for (int j = 0; j < NJ; ++j) block_put(red[wave], lane, c * NJ + j, acc[c][j]);
     __syncthreads();
     if (tid < COC * NJ) {
       const int c = tid / NJ, j = tid - c * NJ;
-      if (co0 + c < p.Cout) p.part[((size_t)(b * gridDim.x + blockIdx.x) * p.Cout + co0 + c) * NJ + j] = cf_sum4(red, tid);
+      if (co0 + c < p.Cout) p.part[((size_t)(b * gridDim.x + blockIdx.x) * p.Cout + co0 + c) * NJ + j] = block_sum4(red, tid);
     }
     __syncthreads();
   }
@@ -543,11 +543,11 @@ __device__ __forceinline__ void cf_pk_reduce_store(float (&red)[4][8 * 20], floa
     for (int h = 0; h < 2; ++h) {
       const int c = 2 * q + h;
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) cf_wave_put(red[wave], lane, c * PER + j, h ? a1[q][j].y : a1[q][j].x);
+      for (int j = 0; j < NJ; ++j) block_put(red[wave], lane, c * PER + j, h ? a1[q][j].y : a1[q][j].x);
       if (s2 != nullptr) {
-        cf_wave_put2(red[wave], lane, c * PER + 2 * NJ, h ? s1[q].y : s1[q].x, h ? s2[q].y : s2[q].x);
+        block_put2(red[wave], lane, c * PER + 2 * NJ, h ? s1[q].y : s1[q].x, h ? s2[q].y : s2[q].x);
       } else {
-        cf_wave_put(red[wave], lane, c * PER + 2 * NJ, h ? s1[q].y : s1[q].x);
+        block_put(red[wave], lane, c * PER + 2 * NJ, h ? s1[q].y : s1[q].x);
         if (lane == 0) red[wave][c * PER + 2 * NJ + 1] = 0.f;
       }
     }
@@ -555,7 +555,7 @@ __device__ __forceinline__ void cf_pk_reduce_store(float (&red)[4][8 * 20], floa
   __syncthreads();
   for (int e = tid; e < COC * PER; e += CF_THREADS) {
     const int c = e / PER, kk = e - c * PER;
-    if (!(kk >= NJ && kk < 2 * NJ)) prow[(co0 + c) * PER + kk] = cf_sum4(red, e);   // (the A2 columns come from the Gram matrix)
+    if (!(kk >= NJ && kk < 2 * NJ)) prow[(co0 + c) * PER + kk] = block_sum4(red, e);   // (the A2 columns come from the Gram matrix)
   }
   __syncthreads();
 }

@@ -1,6 +1,6 @@
-// What the VALU kernels of layer 0 share (conv_first.hip, conv_first_infer_bf16.hip): the zero-padded 3x3 gather, the block reduction of
-// per-lane sums into a partial row, the bf16 unpacking of the backward sweeps, and the host's choice of a <TIn, CIN> instantiation --
-// each defined once.  The rule of bf16_dev.h holds here too: a primitive used by two kernels lives here, what one kernel
+// What the VALU kernels of layer 0 share (conv_first.hip, conv_first_infer_bf16.hip): the zero-padded 3x3 gather, the bf16 unpacking of
+// the backward sweeps, and the host's choice of a <TIn, CIN> instantiation -- each defined once (the block reduction of per-lane sums
+// into a partial row is common.h's block_put / block_sum4).  The rule of bf16_dev.h holds here too: a primitive used by two kernels lives here, what one kernel
 // alone uses stays in its file.  conv_first_bn_wgrad_kernel keeps its own text of both gathers and of the reduction (measured: see there),
 // so cf_gather_u8s2 has one caller today, the packed sweep.  conv_first_mfma.hip and conv_first_fused_bwd.hip (the benched step's layer 0)
 // keep their own copies of the 16-bit row load and the sign decode, and their reductions add in another order: not to be merged with these.
@@ -58,26 +58,6 @@ __device__ __forceinline__ void cf_gather_u8s2(float (&x)[9], const unsigned cha
     x[kh * 3 + 1] = rok ? (float)(hi_ & 0xFFu) : 0.f;
     x[kh * 3 + 2] = rok ? (float)(hi_ >> 8) : 0.f;
   }
-}
-
-// ---- block reduction of per-lane sums, 256 lanes = four wavefronts: wave_sum's DPP tree, lane 0 of each wavefront puts the total into
-// red[wave][e], a barrier (the caller's), then cf_sum4 adds the four wavefronts' entries left to right, ((r0 + r1) + r2) + r3.  The
-// error bounds of tests/test_gpu_first_layer_edges.py count exactly these levels.  Wave-uniform control flow only (wave_sum).
-__device__ __forceinline__ void cf_wave_put(float* red_wave, int lane, int e, float v) {
-  const float s = wave_sum(v);
-  if (lane == 0) red_wave[e] = s;
-}
-// two sums that sit side by side in the row (a sum and its sum of squares, S1 and S2), stored under one test of the lane
-__device__ __forceinline__ void cf_wave_put2(float* red_wave, int lane, int e, float v0, float v1) {
-  const float s0 = wave_sum(v0), s1 = wave_sum(v1);
-  if (lane == 0) {
-    red_wave[e] = s0;
-    red_wave[e + 1] = s1;
-  }
-}
-template <int N>
-__device__ __forceinline__ float cf_sum4(const float (&red)[4][N], int e) {
-  return red[0][e] + red[1][e] + red[2][e] + red[3][e];
 }
 
 // ---- bf16 NCHW8c units in the backward kernels.  The two bf16 of a dword, widened: low half << 16, high half masked
