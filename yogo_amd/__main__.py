@@ -20,8 +20,10 @@ def main(argv=None) -> None:
     elif args.task == "test":
         from yogo_amd.trainer import device_metrics_scope
         from yogo_amd.utils.test_model import do_model_test
+        from yogo_amd.yogo_dataloader import device_image_stream_scope
 
-        with device_metrics_scope(args.device_metrics):
+        with device_metrics_scope(args.device_metrics), \
+                device_image_stream_scope(args.device_image_stream, args.device_image_decode_all, args.device_image_resize):
             do_model_test(args)
     elif args.task == "export":
         print("yogo_amd: `export` (ONNX / OpenVINO for another deployment target) is not part of this MI355X build; "

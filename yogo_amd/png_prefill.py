@@ -23,7 +23,8 @@ status is not 0.  If that returns None the sample is not made resident, exactly 
 One divergence: a file that PIL rejects but this route accepts (a defect in a chunk that only PIL checks) is resident here and
 not on the host route, where it stays with the workers.  Files both accept give the same bytes.
 
-The scratch -- two pinned slots, the stored streams and the scanlines on the device -- lives only while ``fill`` runs and is NOT
+The scratch -- two pinned slots, the stored streams and the scanlines on the device -- belongs to a ``Filler``; ``fill`` makes one
+for the call, so that there it lives only while ``fill`` runs (the per-epoch stream of yogo_amd/image_stream.py keeps one), and is NOT
 part of the cache budget: per chunk the files' bytes twice pinned, once on the device, and what its stream inflates to
 (``PngInfo.inflated_bytes``) of scanlines per image (``stats["scratch_device_bytes"]``, ``stats["scratch_pinned_bytes"]``).  torch's global RNG is not touched.
 
@@ -109,6 +110,133 @@ def _read(ds, j: int, room: np.ndarray, image_hw: Tuple[int, int], decodable: Ca
     return s
 
 
+class Filler:
+    """The scratch of ``fill`` kept between calls, for a caller that fills again and again (yogo_amd/image_stream.py: once per decode
+    group, every epoch): the two pinned slots, the device buffers of the stored streams and of the scanlines, the two thread pools and
+    the side stream.  Nothing is allocated before the first ``fill`` that has samples; the buffers only grow (a slot that has to grow a
+    second time takes an eighth more than it needs); ``close()`` gives everything back.  One ``fill`` at a time."""
+
+    def __init__(self, device, max_threads: int = MAX_THREADS):
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.threads = max(1, min(MAX_THREADS, int(max_threads), os.cpu_count() or 1))
+        self._pool: Optional[ThreadPoolExecutor] = None
+        self._stager: Optional[ThreadPoolExecutor] = None
+        self._pinned: List[torch.Tensor] = []
+        self._sdev: Optional[torch.Tensor] = None
+        self._scan: Optional[torch.Tensor] = None
+        self._side: Optional[torch.cuda.Stream] = None
+        self._staged = 0   # the most bytes a chunk's other-size files took, unpacked, while they waited for their resize
+
+    @property
+    def side(self) -> torch.cuda.Stream:
+        """the stream every fill runs on"""
+        if self._side is None:
+            self._side = torch.cuda.Stream(self.device)
+        return self._side
+
+    @property
+    def device_bytes(self) -> int:
+        return (self._sdev.numel() if self._sdev is not None else 0) + (self._scan.numel() if self._scan is not None else 0) + self._staged
+
+    @property
+    def pinned_bytes(self) -> int:
+        return sum(t.numel() for t in self._pinned)
+
+    def close(self) -> None:
+        """the pools down, the buffers back (after the side stream has finished with them)"""
+        for pool in (self._stager, self._pool):
+            if pool is not None:
+                pool.shutdown(wait=True)
+        if self._side is not None:
+            self._side.synchronize()
+        self._pool = self._stager = self._sdev = self._scan = None
+        self._pinned = []
+
+    def _slots(self, slot_bytes: int, count: int) -> None:
+        """`count` pinned slots and the device buffer, each of at least `slot_bytes` (side stream current)"""
+        have = self._pinned[0].numel() if self._pinned else 0
+        if have < slot_bytes:
+            count, size = max(count, len(self._pinned)), slot_bytes + (slot_bytes // 8 if have else 0)
+            self._pinned, self._sdev = [], None   # (the smaller ones go back first)
+            self._pinned = [torch.empty(size, dtype=torch.uint8).pin_memory() for _ in range(count)]
+            self._sdev = torch.empty(size, dtype=torch.uint8, device=self.device)
+        while len(self._pinned) < count:
+            self._pinned.append(torch.empty(self._pinned[0].numel(), dtype=torch.uint8).pin_memory())
+
+    def fill(self, images: torch.Tensor, samples: Sequence[Tuple[object, int]], decode_batch: int = DEFAULT_DECODE_BATCH,
+             stats: Optional[Dict] = None, device_resize: bool = False, decode_all: bool = False, raise_rows: bool = True,
+             after: Optional[torch.cuda.Event] = None) -> List[Optional[torch.Tensor]]:
+        """the module's ``fill`` on this object's scratch.  raise_rows False: a usable sample whose label file does not parse has its
+        exception in the result, in its rows' place, and nothing is raised for it.  after: the side stream waits for this event before
+        it touches ``images`` (None: for everything the caller's current stream holds so far)."""
+        _hip.require_cuda(images, "the image cache")
+        if images.dtype != torch.uint8 or images.ndim != 4 or images.shape[1] not in (1, 3) or not images.is_contiguous():
+            raise ValueError(f"fill: images must be a contiguous uint8 [N, 1 or 3, H, W] tensor, got {tuple(images.shape)} {images.dtype}")
+        N, C, H, W = (int(v) for v in images.shape)
+        if len(samples) != N:
+            raise ValueError(f"fill: {len(samples)} samples for {N} images")
+        decode_batch = check_decode_batch(decode_batch)
+        decodable, unpack = (attrgetter("any_decodable"), png_unpack_any) if decode_all else (attrgetter("prefill_decodable"), png_unpack_planes)
+        dev = images.device
+        if dev != self.device:
+            raise ValueError(f"fill: the images are on {dev}, this filler's scratch on {self.device}")
+        out: List[Optional[torch.Tensor]] = [None] * N
+        if stats is not None:
+            stats.update(scratch_device_bytes=0, scratch_pinned_bytes=0, host_decoded=0, inflate_ms=[], unpack_ms=[], device_resized=0, resize_ms=[])
+        if N == 0:
+            return out
+        chunks = [(lo, min(lo + decode_batch, N)) for lo in range(0, N, decode_batch)]
+        if self._pool is None:
+            self._pool = ThreadPoolExecutor(max_workers=self.threads, thread_name_prefix="png-prefill")
+            self._stager = ThreadPoolExecutor(max_workers=1, thread_name_prefix="png-prefill-stage")   # chunk n + 1 is read while n decodes
+        pool, stager = self._pool, self._stager
+        sizes = list(pool.map(_file_size, [str(ds._image_paths[j]) for ds, j in samples]))
+        layouts = [slot_layout(sizes[lo:hi]) for lo, hi in chunks]
+        slot_bytes = max(1, max(total for _, total in layouts))
+        side = self.side
+        if after is None:
+            side.wait_stream(torch.cuda.current_stream(dev))
+        else:
+            side.wait_event(after)
+        images.record_stream(side)
+        pending = None
+        try:
+            with torch.cuda.device(dev), torch.cuda.stream(side):
+                self._slots(slot_bytes, min(2, len(chunks)))
+                pinned, sdev = self._pinned, self._sdev
+
+                def stage(n: int) -> List[PngStream]:
+                    (lo, hi), (offsets, _) = chunks[n], layouts[n]
+                    host = pinned[n % 2].numpy()
+                    futures = [pool.submit(_read, *samples[i], host[int(offsets[i - lo]):int(offsets[i - lo]) + sizes[i]], (H, W), decodable, device_resize)
+                               for i in range(lo, hi)]
+                    return [f.result() for f in futures]
+
+                pending = stager.submit(stage, 0)
+                for n, (lo, hi) in enumerate(chunks):
+                    chunk, pending = pending.result(), None
+                    if n + 1 < len(chunks):
+                        pending = stager.submit(stage, n + 1)
+                    self._scan, staging = _decode(chunk, samples[lo:hi], layouts[n], pinned[n % 2], sdev, self._scan, images[lo:hi], stats, unpack)
+                    self._staged = max(self._staged, staging)
+                    for i, s in enumerate(chunk):
+                        if s.host and s.pixels is None:
+                            continue
+                        if isinstance(s.rows, BaseException) and raise_rows:
+                            raise s.rows
+                        out[lo + i] = s.rows
+                side.synchronize()
+        finally:
+            if pending is not None:   # (an error left the next chunk being read: the slot is free again only when that has ended)
+                pending.exception()
+        if stats is not None:
+            stats["scratch_device_bytes"] = self.device_bytes
+            stats["scratch_pinned_bytes"] = self.pinned_bytes
+        return out
+
+
 def fill(images: torch.Tensor, samples: Sequence[Tuple[object, int]], decode_batch: int = DEFAULT_DECODE_BATCH,
          stats: Optional[Dict] = None, device_resize: bool = False, decode_all: bool = False) -> List[Optional[torch.Tensor]]:
     """images[i] = the uint8 image of samples[i] = (ObjectDetectionDataset, index in it), what ``ds.image_uint8(index)`` gives, for
@@ -117,64 +245,14 @@ def fill(images: torch.Tensor, samples: Sequence[Tuple[object, int]], decode_bat
     the device has finished.  stats (optional dict) receives ``scratch_device_bytes``, ``scratch_pinned_bytes``, ``host_decoded`` and
     per chunk the device-event times ``inflate_ms`` / ``unpack_ms``.  device_resize: files of another size are resized on the device
     (see the module's text); stats then also counts them (``device_resized``) and times every resize launch (``resize_ms``).
-    decode_all: every PNG colour type, bit depth and Adam7 is decoded on the device (see the module's text)."""
+    decode_all: every PNG colour type, bit depth and Adam7 is decoded on the device (see the module's text).
+    A ``Filler`` that lives for this one call: its scratch is gone when the call returns."""
     _hip.require_cuda(images, "the image cache")
-    if images.dtype != torch.uint8 or images.ndim != 4 or images.shape[1] not in (1, 3) or not images.is_contiguous():
-        raise ValueError(f"fill: images must be a contiguous uint8 [N, 1 or 3, H, W] tensor, got {tuple(images.shape)} {images.dtype}")
-    N, C, H, W = (int(v) for v in images.shape)
-    if len(samples) != N:
-        raise ValueError(f"fill: {len(samples)} samples for {N} images")
-    decode_batch = check_decode_batch(decode_batch)
-    decodable, unpack = (attrgetter("any_decodable"), png_unpack_any) if decode_all else (attrgetter("prefill_decodable"), png_unpack_planes)
-    dev = images.device
-    out: List[Optional[torch.Tensor]] = [None] * N
-    if stats is not None:
-        stats.update(scratch_device_bytes=0, scratch_pinned_bytes=0, host_decoded=0, inflate_ms=[], unpack_ms=[], device_resized=0, resize_ms=[])
-    if N == 0:
-        return out
-    chunks = [(lo, min(lo + decode_batch, N)) for lo in range(0, N, decode_batch)]
-    pool = ThreadPoolExecutor(max_workers=max(1, min(MAX_THREADS, os.cpu_count() or 1)), thread_name_prefix="png-prefill")
-    stager = ThreadPoolExecutor(max_workers=1, thread_name_prefix="png-prefill-stage")   # chunk n + 1 is read while n decodes
+    filler = Filler(images.device)
     try:
-        sizes = list(pool.map(_file_size, [str(ds._image_paths[j]) for ds, j in samples]))
-        layouts = [slot_layout(sizes[lo:hi]) for lo, hi in chunks]
-        slot_bytes = max(1, max(total for _, total in layouts))
-        pinned = [torch.empty(slot_bytes, dtype=torch.uint8).pin_memory() for _ in range(min(2, len(chunks)))]
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        images.record_stream(side)
-
-        def stage(n: int) -> List[PngStream]:
-            (lo, hi), (offsets, _) = chunks[n], layouts[n]
-            host = pinned[n % 2].numpy()
-            futures = [pool.submit(_read, *samples[i], host[int(offsets[i - lo]):int(offsets[i - lo]) + sizes[i]], (H, W), decodable, device_resize) for i in range(lo, hi)]
-            return [f.result() for f in futures]
-
-        with torch.cuda.device(dev), torch.cuda.stream(side):
-            sdev = torch.empty(slot_bytes, dtype=torch.uint8, device=dev)
-            scan: Optional[torch.Tensor] = None
-            staged = 0   # the most bytes a chunk's other-size files took, unpacked, while they waited for their resize
-            pending = stager.submit(stage, 0)
-            for n, (lo, hi) in enumerate(chunks):
-                chunk = pending.result()
-                if n + 1 < len(chunks):
-                    pending = stager.submit(stage, n + 1)
-                scan, staging = _decode(chunk, samples[lo:hi], layouts[n], pinned[n % 2], sdev, scan, images[lo:hi], stats, unpack)
-                staged = max(staged, staging)
-                for i, s in enumerate(chunk):
-                    if s.host and s.pixels is None:
-                        continue
-                    if isinstance(s.rows, BaseException):
-                        raise s.rows
-                    out[lo + i] = s.rows
-            side.synchronize()
-        if stats is not None:
-            stats["scratch_device_bytes"] = slot_bytes + (scan.numel() if scan is not None else 0) + staged
-            stats["scratch_pinned_bytes"] = slot_bytes * len(pinned)
+        return filler.fill(images, samples, decode_batch, stats, device_resize=device_resize, decode_all=decode_all)
     finally:
-        stager.shutdown(wait=True)
-        pool.shutdown(wait=True)
-    return out
+        filler.close()
 
 
 def _decode(chunk: List[PngStream], samples, layout, pinned: torch.Tensor, sdev: torch.Tensor, scan: Optional[torch.Tensor],

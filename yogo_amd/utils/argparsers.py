@@ -96,15 +96,32 @@ def _decode_needs_cache(ns):
 
 
 def _resize_needs_decode(ns):
-    if ns.device_image_resize and not ns.device_image_decode:
+    if ns.device_image_resize and not (ns.device_image_decode or getattr(ns, "device_image_stream", False)):
         return "--device-image-resize resizes what the device decoded: it needs --device-image-decode"
     return None
 
 
 def _decode_all_needs_decode(ns):
-    if ns.device_image_decode_all and not ns.device_image_decode:
+    if ns.device_image_decode_all and not (ns.device_image_decode or getattr(ns, "device_image_stream", False)):
         return "--device-image-decode-all widens what --device-image-decode takes: it needs --device-image-decode"
     return None
+
+
+def _test_widening_needs_stream(ns):
+    for flag, on in (("--device-image-decode-all", ns.device_image_decode_all), ("--device-image-resize", ns.device_image_resize)):
+        if on and not ns.device_image_stream:
+            return f"{flag} widens what --device-image-stream decodes on the GPU: it needs --device-image-stream"
+    return None
+
+
+STREAM_HELP = ("decode on the GPU, every epoch, the labelled images that are not resident in the device image cache (all of them without "
+               "one; the test split always) instead of PIL-decoding them in DataLoader workers: no workers are started, the PNG files "
+               "are inflated and unfiltered in groups of 1024 images (8-bit greyscale and RGB; other files on the host) and the batches "
+               "are gathered from there; same batches.  Costs, outside the --device-image-cache budget and for as long as the loaders "
+               "live: two staging tensors of 1024 images in GPU memory (1.5 GiB at 772 x 1032 greyscale) plus the decoder's scratch "
+               "(about as much again, and 0.5-0.8 GiB of pinned host memory), and the first batch waits for the first whole group, "
+               "0.6-1.0 s there "
+               "(default: False)")
 
 
 def _device_draw_needs(ns):
@@ -175,6 +192,8 @@ def train_parser(parser=None):
                         help="with --device-image-decode: also resize on the GPU the 8-bit greyscale and RGB PNG files whose size is not "
                              "--image-hw (down to 1/8 per axis, or up) instead of handing them to the host; a few pixels of such an image "
                              "may differ by one grey level from the host's resize (default: False)")
+    parser.add_argument("--device-image-stream", default=False, action=boolean_action, help=STREAM_HELP + ".  Independent of "
+                        "--device-image-cache and composes with it; --device-image-decode-all and --device-image-resize widen what it decodes")
     parser.add_argument("--device-metrics", default=False, action=boolean_action,
                         help="match predictions to labels and accumulate the test metrics on the GPU instead of per image on the host; "
                              "same results (default: False)")
@@ -192,7 +211,7 @@ def train_parser(parser=None):
 
 def test_parser(parser=None):
     if parser is None:
-        parser = argparse.ArgumentParser(description="test a model", allow_abbrev=False)
+        parser = CheckedParser(description="test a model", allow_abbrev=False)
     parser.add_argument("pth_path", type=Path)
     parser.add_argument("dataset_defn_path", type=Path)
     parser.add_argument("--wandb", default=False, action=boolean_action, help="log to wandb - this will create a new run. If neither this nor --wandb-resume-id are provided, the run will be saved to a new folder")
@@ -205,8 +224,19 @@ def test_parser(parser=None):
     parser.add_argument("--device-metrics", default=False, action=boolean_action,
                         help="match predictions to labels and accumulate the test metrics on the GPU instead of per image on the host; "
                              "same results (default: False)")
+    parser.add_argument("--device-image-stream", default=False, action=boolean_action, help=STREAM_HELP)
+    parser.add_argument("--device-image-decode-all", default=False, action=boolean_action,
+                        help="with --device-image-stream: also decode on the GPU every other PNG colour type and bit depth (palette, 1 / 2 / "
+                             "4-bit and 16-bit, grey+alpha, RGBA, with tRNS, Adam7-interlaced); the same pixels as the host's decoder "
+                             "(default: False)")
+    parser.add_argument("--device-image-resize", default=False, action=boolean_action,
+                        help="with --device-image-stream: also resize on the GPU the PNG files whose size is not the model's (down to 1/8 "
+                             "per axis, or up); a few pixels of such an image may differ by one grey level from the host's resize "
+                             "(default: False)")
     parser.add_argument("--note", default=None, type=str, help="note for the run (e.g. 'run on a TI-82')")
     parser.add_argument("--tags", default=None, type=str, nargs="*", help="tags for the run (e.g. '--tags test fine-tune')")
+    if hasattr(parser, "checks"):
+        parser.checks.append(_test_widening_needs_stream)
     return parser
 
 

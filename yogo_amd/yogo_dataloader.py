@@ -21,9 +21,17 @@ resident and blob rows.  ``device_image_decode`` (``--device-image-decode``) fil
 (yogo_amd/png_prefill.py); the batches are the same.  ``device_image_resize`` (``--device-image-resize``) has that route resize
 files of another size than ``image_hw`` on the device too (a few pixels of those may differ by one grey level);
 ``device_image_decode_all`` (``--device-image-decode-all``) has it take every PNG colour type, bit depth and Adam7.  Without a budget nothing of this exists: the same ``DeviceLoader`` path, no allocation, no prefill.
+
+Device image stream (``device_image_stream``, ``yogo train | test --device-image-stream``; yogo_amd/image_stream.py): what is
+file-backed and not resident -- every split without a cache, the test split always -- is decoded on the device as well, every epoch,
+in groups of ``stream_decode_batch`` images that land in a staging tensor; ``DeviceLoader`` takes its items from the stream instead
+of the host DataLoader (which is never iterated: no workers) and gathers the streamed rows from the staging next to the cache's
+resident rows and the blob rows.  The two widening switches then widen the stream as they widen the prefill.  Off (the default),
+nothing of it exists.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import warnings
 from typing import Any, Dict, Iterable, List, MutableMapping, Optional, Tuple
@@ -35,10 +43,29 @@ from torch.utils.data.distributed import DistributedSampler
 from yogo_amd.blobgen import BlobDataset
 from yogo_amd.data import MultiArgSequential, RandomHorizontalFlipWithBBs, RandomVerticalFlipWithBBs, format_labels_batch
 from yogo_amd.dataset_definition_file import DatasetDefinition, SplitFractions
+from yogo_amd.image_stream import ImageStream, Scratch, Staged
 from yogo_amd.image_cache import DECODE_ALL_FLAG, DECODE_FLAG, FLAG, RESIZE_FLAG, ImageCache, ResidentMarkers, budget_bytes, collate_cached, gather, resident_count
+from yogo_amd.png_prefill import DEFAULT_DECODE_BATCH
 from yogo_amd.yogo_dataset import ObjectDetectionDataset
 
 SPLIT_SEED = 7271978   # yogo/data/yogo_dataloader.py:176
+
+_stream_scope = (False, False, False)   # device_image_stream, device_image_decode_all, device_image_resize
+
+
+@contextlib.contextmanager
+def device_image_stream_scope(enabled: bool, decode_all: bool = False, resize: bool = False):
+    """every ``get_dataloader`` call inside runs with ``device_image_stream=True`` when `enabled` (and then with the two widening
+    switches as given): how ``yogo test --device-image-stream`` reaches the call that ``yogo_amd.utils.test_model`` makes with the
+    reference's arguments, as ``trainer.device_metrics_scope`` does for ``--device-metrics``"""
+    global _stream_scope
+    prev = _stream_scope
+    if enabled:
+        _stream_scope = (True, bool(decode_all) or prev[1], bool(resize) or prev[2])
+    try:
+        yield
+    finally:
+        _stream_scope = prev
 
 
 def guess_suggested_num_workers() -> Optional[int]:
@@ -157,7 +184,8 @@ class DeviceLoader:
     attributes the training loop touches (``dataset``, ``sampler``, ``batch_size``, ``__len__``)."""
 
     def __init__(self, loader: DataLoader, Sx: int, Sy: int, transforms: MultiArgSequential, device=None, strict_steps: bool = False,
-                 blob: Optional[BlobDataset] = None, dataset: Optional[Dataset] = None, cache: Optional[ImageCache] = None):
+                 blob: Optional[BlobDataset] = None, dataset: Optional[Dataset] = None, cache: Optional[ImageCache] = None,
+                 stream: Optional[ImageStream] = None, normalize_images: bool = False):
         self.loader, self.Sx, self.Sy, self.transforms, self.device = loader, Sx, Sy, transforms, device
         # strict_steps (the TRAINING split only): every batch is one gradient all-reduce, so a skipped batch must fail loudly
         # under data parallelism; validation / test loaders issue no per-step collective and may skip, as the reference does
@@ -167,6 +195,9 @@ class DeviceLoader:
         self.blob = blob
         # cache: the resident images of the split (loader.dataset = ResidentMarkers, loader.collate_fn = collate_cached)
         self.cache = cache
+        # stream: what is file-backed and not resident is decoded on the device (yogo_amd/image_stream.py); the items are the stream's,
+        # in collate_cached's form, and the host loader is never iterated
+        self.stream, self.normalize_images = stream, bool(normalize_images)
         self.dataset = loader.dataset if dataset is None else dataset
         self.sampler, self.batch_size = loader.sampler, loader.batch_size
 
@@ -178,7 +209,13 @@ class DeviceLoader:
         multi = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
         if self.cache is not None:
             self.cache.prefill()   # once, before the split's first batch (and before its workers start)
-        for item in (self._resident_batches() if self.cache is not None and self.cache.full else self.loader):
+        if self.cache is not None and self.cache.full:
+            source = self._resident_batches()
+        elif self.stream is not None:
+            source = self.stream.batches([int(i) for i in iter(self.sampler)], self.batch_size)
+        else:
+            source = self.loader
+        for item in source:
             if item is None:
                 # every sample of the batch was unreadable (the robust collate of yogo/data/utils.py:49-63 returned nothing).  A
                 # single process just skips it; under data parallelism a rank that skips a step issues one gradient all-reduce
@@ -187,7 +224,7 @@ class DeviceLoader:
                     raise RuntimeError("yogo_amd: a whole batch of this rank was unreadable; in a data-parallel run every rank must "
                                        "take the same number of steps (fix or remove the unreadable files)")
                 continue
-            if self.cache is not None:
+            if self.cache is not None or self.stream is not None:
                 imgs, labels = self._assemble_cached(item, dev)
             elif self.blob is not None:
                 imgs, labels = self._assemble(item, dev)
@@ -224,15 +261,21 @@ class DeviceLoader:
             yield None, [], [], chunk, list(range(len(chunk))), [], [], len(chunk)
 
     def _assemble_cached(self, item, dev: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
-        """a batch of a cached split on the device: uploaded rows with index_copy_, resident rows with one gather launch, blob
-        rows composed; the label rows of all real samples (uploaded and resident, in batch order) rasterised by one launch"""
+        """a batch of a cached or streamed split on the device: uploaded rows with index_copy_ -- streamed rows (``Staged``) with a
+        gather launch from their staging tensor instead --, resident rows with one gather launch, blob rows composed; the label rows
+        of all real samples (uploaded or streamed, and resident, in batch order) rasterised by one launch"""
         up_imgs, up_rows, up_pos, res_idx, res_pos, blob_idx, blob_pos, B = item
         cache = self.cache
-        C, H, W = cache.image_shape
-        dtype = torch.float32 if cache.normalize_images else torch.uint8
+        C, H, W = cache.image_shape if cache is not None else self.stream.image_shape
+        dtype = torch.float32 if (cache.normalize_images if cache is not None else self.normalize_images) else torch.uint8
         with torch.cuda.device(dev):
             imgs = torch.empty(B, C, H, W, dtype=dtype, device=dev)
-            if up_pos:
+            if up_pos and isinstance(up_imgs, Staged):
+                slots = [-1] * B
+                for p, s in zip(up_pos, up_imgs.slots):
+                    slots[p] = s
+                gather(up_imgs.images, slots, imgs)
+            elif up_pos:
                 imgs.index_copy_(0, torch.tensor(up_pos, dtype=torch.long).to(dev, non_blocking=True),
                                  up_imgs.to(dev, non_blocking=True).to(dtype))
             if res_pos:
@@ -258,18 +301,26 @@ def get_dataloader(dataset_definition: DatasetDefinition, batch_size: int, Sx: i
                    image_hw: Tuple[int, int] = (772, 1032), rgb: bool = False, normalize_images: bool = False,
                    split_fraction_override: Optional[SplitFractions] = None, device=None,
                    device_image_cache_gib: Optional[float] = None, device_image_decode: bool = False,
-                   device_image_resize: bool = False, device_image_decode_all: bool = False) -> Dict[str, DeviceLoader]:
+                   device_image_resize: bool = False, device_image_decode_all: bool = False, device_image_stream: bool = False,
+                   stream_decode_batch: int = DEFAULT_DECODE_BATCH) -> Dict[str, DeviceLoader]:
     """{split: DeviceLoader}.  device_image_cache_gib: keep decoded images of the train split, then of the val split with what
     is left, resident in HBM within this many GiB (yogo_amd/image_cache.py); None: no cache.  device_image_decode: fill that
     cache from PNG files inflated and unfiltered on the device (yogo_amd/png_prefill.py) instead of a pool of PIL workers.
     device_image_resize: on that route, resize the files of another size than image_hw on the device as well.
     device_image_decode_all: on that route, decode every PNG colour type, bit depth and Adam7 on the device, not 8-bit greyscale
-    and RGB alone."""
+    and RGB alone.
+    device_image_stream: decode what is file-backed and not resident on the device too, every epoch, in groups of stream_decode_batch
+    images, without DataLoader workers (yogo_amd/image_stream.py); it needs no cache.  device_image_resize and
+    device_image_decode_all then widen what the stream decodes as well.  Its staging and scratch, shared by the splits, are allocated
+    at the first iteration, are not part of the GIB budget, and are released by ``loader.stream.scratch.close()``."""
+    if _stream_scope[0]:
+        device_image_stream = True
+        device_image_decode_all, device_image_resize = device_image_decode_all or _stream_scope[1], device_image_resize or _stream_scope[2]
     if device_image_decode and device_image_cache_gib is None:
         raise ValueError(f"{DECODE_FLAG} fills the device image cache: it needs {FLAG} GIB")
-    if device_image_resize and not device_image_decode:
+    if device_image_resize and not (device_image_decode or device_image_stream):
         raise ValueError(f"{RESIZE_FLAG} resizes what the device decoded: it needs {DECODE_FLAG}")
-    if device_image_decode_all and not device_image_decode:
+    if device_image_decode_all and not (device_image_decode or device_image_stream):
         raise ValueError(f"{DECODE_ALL_FLAG} widens what {DECODE_FLAG} takes: it needs {DECODE_FLAG}")
     budget = budget_bytes(device_image_cache_gib) if device_image_cache_gib is not None else None
     split_datasets = get_datasets(dataset_definition, Sx, Sy, rgb=rgb, image_hw=image_hw, normalize_images=normalize_images,
@@ -286,6 +337,11 @@ def get_dataloader(dataset_definition: DatasetDefinition, batch_size: int, Sx: i
         if budget is not None and designation in split_datasets:
             resident[designation] = resident_count(budget, _real_len(split_datasets[designation]), *image_shape)
             budget -= resident[designation] * image_shape[0] * image_shape[1] * image_shape[2]
+    stream_args = {}
+    if device_image_stream:   # one scratch for every split: the threads of a rank are its share of the CPUs, as its workers would be
+        stream_args = dict(scratch=Scratch(image_shape, batch_size, stream_decode_batch, device, bool(device_image_resize), bool(device_image_decode_all),
+                                           max_threads=max(1, (guess_suggested_num_workers() or 1) // world_size)),
+                           image_shape=image_shape, normalize_images=normalize_images, log=rank == 0)
     d: Dict[str, DeviceLoader] = {}
     for designation, dataset in split_datasets.items():
         if len(dataset) == 0:   # type: ignore[arg-type]
@@ -295,7 +351,10 @@ def get_dataloader(dataset_definition: DatasetDefinition, batch_size: int, Sx: i
         if resident.get(designation, 0) > 0:
             cache_args = dict(resident=resident[designation], image_shape=image_shape, normalize_images=normalize_images,
                               name=designation, log=rank == 0, device_decode=bool(device_image_decode),
-                              device_resize=bool(device_image_resize), device_decode_all=bool(device_image_decode_all))
+                              device_resize=bool(device_image_resize and device_image_decode),
+                              device_decode_all=bool(device_image_decode_all and device_image_decode))
+        if stream_args:
+            cache_args = {**stream_args, "name": designation, **cache_args}
         d[designation] = _get_dataloader(dataset, batch_size, augs, rank, world_size, Sx, Sy, device, strict_steps=designation == "train",
                                          **cache_args)
     return d
@@ -318,8 +377,9 @@ def _num_workers(dataset_size: int, world_size: int) -> int:
 def _get_dataloader(dataset: Dataset, batch_size: int, augmentations: list, rank: int, world_size: int, Sx: int, Sy: int,
                     device=None, strict_steps: bool = False, resident: int = 0, image_shape: Optional[Tuple[int, int, int]] = None,
                     normalize_images: bool = False, name: str = "train", log: bool = False, device_decode: bool = False,
-                    device_resize: bool = False, device_decode_all: bool = False) -> DeviceLoader:
-    """resident > 0: split indices 0 .. resident-1 are kept decoded on the device (image_shape = (C, H, W))"""
+                    device_resize: bool = False, device_decode_all: bool = False, scratch: Optional[Scratch] = None) -> DeviceLoader:
+    """resident > 0: split indices 0 .. resident-1 are kept decoded on the device (image_shape = (C, H, W)).  scratch: the split's
+    file-backed samples that are not resident are streamed through it (yogo_amd/image_stream.py); no worker is ever started"""
     blob = dataset.datasets[-1] if isinstance(dataset, ConcatDataset) and isinstance(dataset.datasets[-1], BlobDataset) else None
     # the workers iterate the split with its blob part replaced by the indices alone (same length: same sampler order)
     host_dataset = ConcatDataset([*dataset.datasets[:-1], BlobIndices(len(blob))]) if blob is not None else dataset
@@ -337,11 +397,16 @@ def _get_dataloader(dataset: Dataset, batch_size: int, augmentations: list, rank
         #                    tests/test_image_cache_host.py puts a recording class with the earlier signature in ImageCache's place)
         host_dataset = ResidentMarkers(host_dataset, cache.resident)
         collate_fn = collate_cached
+    stream = None
+    if scratch is not None:   # (the DataLoader below stays for dataset / sampler / batch_size / __len__ alone)
+        stream = ImageStream(dataset, _real_len(dataset), scratch, cache=cache, name=name, log=log)
+        num_workers = 0
     loader = DataLoader(host_dataset, shuffle=False, sampler=sampler, drop_last=False, pin_memory=torch.cuda.is_available(), batch_size=batch_size,
                         num_workers=num_workers, persistent_workers=num_workers > 0, generator=torch.Generator().manual_seed(SPLIT_SEED),
                         collate_fn=collate_fn, multiprocessing_context="spawn" if num_workers > 0 else None)
     return DeviceLoader(loader, Sx, Sy, MultiArgSequential(*augmentations), device, strict_steps=strict_steps, blob=blob,
-                        dataset=dataset if blob is not None or cache is not None else None, cache=cache)
+                        dataset=dataset if blob is not None or cache is not None else None, cache=cache, stream=stream,
+                        normalize_images=normalize_images)
 
 
 def get_class_counts(d, num_classes: int, verbose: bool = True) -> torch.Tensor:
