@@ -212,6 +212,32 @@ class Ref:
         assert bool((self.refy == 0).any()) and bool(torch.signbit(self.refy[self.refy == 0]).any()) and not bool(torch.signbit(self.refy[self.refy == 0]).all()), "reference lacks +0.0 / -0.0"
 
 
+class WgradRef(Ref):
+    """the weight-gradient part of Ref alone (x, dy, dw, db; the same draws): for the long walks, whose planes are too large for a forward and
+    a data-gradient reference they would not use"""
+
+    def __init__(self, case, seed=0):
+        B, Cin, Cout, IH, IW, k, s = case
+        self.case = case
+        self.OH, self.OW = out_hw(IH, IW, k, s)
+        g = torch.Generator().manual_seed(2000 + seed + 31 * Cin + 17 * Cout + 7 * IH + 3 * IW + k + s)
+        self.p = density(Cin, k)
+        self.x = draw_ints((B, Cin, IH, IW), self.p, g)
+        self.dy = draw_ints((B, Cout, self.OH, self.OW), density(Cout, k), g)
+        self.dy[:, Cout // 2] = 0
+        self.dw = wgrad64(self.x, self.dy, k, s)
+        self.db = self.dy.sum((0, 2, 3))
+
+    def check_preconditions(self):
+        hint = f"case {self.case}: lower the density ({self.p:.3f}) of x / dy in _conv_bf16_exact.WgradRef"
+        npix = self.case[0] * self.OH * self.OW
+        assert 4 * npix < LIMIT and float(self.dw.abs().max()) < LIMIT and float(self.db.abs().max()) < LIMIT, ("weight-gradient sums over pixels", hint)
+        for name, t in (("x", self.x), ("dy", self.dy)):
+            assert torch.equal(t, t.round()) and float(t.abs().max()) <= 2, (name, "not a small integer")
+        for name, t in (("dw", self.dw), ("db", self.db)):
+            assert bool((t == 0).any()) and bool((t < 0).any()) and bool((t > 0).any()), (name, "lacks zeros, negatives or positives", hint)
+
+
 class PairRef:
     """layers 1 + 2 of base_model (yogo/model_defns.py:39-46): 16 -> C1 (3x3, stride 1) -> C2 (3x3, stride 2), LeakyReLU, scale and sign map
     each; layer 2 reads y1 AS STORED in bf16.  Its terms are multiples of q = 2^-15: y1 = bf16(float32(0.01) n) * scale, scale >= 0.5."""

@@ -67,6 +67,13 @@ EDGES = [
     # three rows of 8000 / 10000 columns: 24 bands are not enough for the input tile to fit the LDS-DMA slots, the tiled kernel stages through
     # registers (dma=0; conv_bf16.hip, bf_plan: `ni + nw <= PF`)
     (1, 16, 32, 3, 8000, 3, 1), (1, 128, 128, 3, 10000, 3, 1),
+    # the wgrad_bf16_kernel instantiations no imported list reaches (WGRAD_EXPECTED below, in its order): <4,1,1> at 3x3 stride 1, 1x1 and
+    # stride 2; <2,2,1> at 1x1 and at stride 2 on 64 output channels (MPW 1); <2,1,2> at 1x1; <1,4,1> and <1,2,2> at stride 2; the tall
+    # R = 8 tiling on 32 input channels (no PACK2) with 1 and 3 steps per row
+    (1, 32, 128, 5, 9, 3, 1), (1, 32, 128, 4, 5, 1, 1), (1, 32, 128, 7, 9, 3, 2), (1, 64, 64, 4, 5, 1, 1), (1, 64, 64, 7, 9, 3, 2), (1, 32, 64, 4, 5, 1, 1),
+    (1, 128, 32, 7, 9, 3, 2), (1, 64, 32, 7, 9, 3, 2), (1, 32, 32, 70, 9, 3, 1), (1, 32, 32, 70, 40, 3, 1),
+    # LEAN2 + PACK2 with 2 steps per row (WGRAD_LOOPS below: the one (loop, steps per row) pair the lists above lack)
+    (1, 16, 32, 70, 20, 3, 1),
 ]
 
 CASES, SOURCES, EXCLUDED = [], {}, []
@@ -90,6 +97,21 @@ for _src, _c in _imported() + [("edge", c) for c in EDGES]:
 #  test_gpu_ws.py and test_gpu_production_shapes.py).  test_case_lists pins this list.
 EXCLUDED_EXPECTED = 13
 
+# Long walks of wgrad_bf16_kernel, through _wgrad alone (no forward, no data gradient): (case, loop, ring depth).  In every other case of this
+# file a workgroup walks at most 3 units, so the prologue fills the ring and the in-loop LDS-DMA issue -- the slot schedule riding behind the
+# MFMAs, the counted vmcnt, the ring index wrapping -- hardly runs.  Here units_per_split >= 2 * depth + 1 (several wraps, every value of the
+# counted wait) and units % units_per_split != 0 (a short last split), asserted from the launch log; one entry per loop of the kernel and ring
+# depth that loop can get (tools/wgrad_plan_sweep.cpp; its table: profiles/wgrad_bf16_one_definition.log).  Up to 16M elements per tensor.
+WALK_MAX_ELEMS = 16 * 1024 * 1024
+WGRAD_WALKS = [
+    ((2, 128, 128, 1027, 7, 3, 1), "BLK4", 2), ((4, 128, 128, 521, 33, 3, 1), "BLK4", 2),        # ordinary chunks; wide (33-column) chunks: 9 steps
+    ((3, 128, 64, 1027, 7, 3, 1), "LEAN", 3), ((3, 96, 128, 1027, 7, 3, 2), "LEAN", 3), ((2, 128, 64, 1027, 17, 3, 1), "LEAN", 2),
+    ((5, 32, 64, 2041, 3, 3, 1), "LEAN2", 3), ((5, 64, 32, 1034, 33, 3, 2), "LEAN2", 2),
+    ((5, 16, 16, 515, 65, 3, 1), "LEAN2+PACK2", 3), ((5, 16, 16, 2065, 49, 3, 1), "LEAN2+PACK2", 2),   # (the first: 5 chunks per row)
+    ((5, 16, 32, 2041, 3, 3, 2), "generic32", 3), ((5, 16, 64, 1033, 49, 3, 1), "generic32", 2),
+    ((5, 32, 32, 2041, 3, 3, 2), "generic64", 3), ((5, 32, 32, 1034, 97, 3, 2), "generic64", 2),
+]
+
 PAIR_CASES = [(B, 32, C2, IH, IW) for C2 in (64, 40) for (B, IH, IW) in ((2, 9, 34), (1, 4, 2), (3, 21, 63))]
 
 
@@ -103,9 +125,9 @@ SPECIALISED = ("conv_bf16_ws_kernel", "conv_bf16_ws16_kernel", "conv_bf16_ws3_ke
 _REFS, _LOGS, _FAILED = {}, {}, {}
 
 
-def _ref(case):
+def _ref(case, cls=None):
     if case not in _REFS:
-        r = X.Ref(case) if len(case) == 7 else X.PairRef(case)
+        r = cls(case) if cls else (X.Ref(case) if len(case) == 7 else X.PairRef(case))
         r.check_preconditions()     # on the reference alone, before any GPU result is looked at
         _REFS[case] = r
     return _REFS[case]
@@ -382,17 +404,71 @@ def test_small_planes_run_on_the_tiled_kernel_under_the_product_plan():
 
 # ---- coverage -------------------------------------------------------------------------------------------------------------------------
 TILED_RE = re.compile(r"conv_bf16_kernel<(\d+), (\d+), (\d+), (true|false), (\d+), (true|false), (\d+), (true|false), (true|false)> \| (.*)")
-# every wgrad_bf16_kernel instantiation the imported shape lists launch (wgrad_bf16.hip: conv2d_wgrad_bf16_impl), as logged:
-# <MBW, NBW, NPW, KS, T, S, R, MPW, ROT, PACK2, BLK4>
+# every wgrad_bf16_kernel instantiation the dispatcher can launch (wgrad_bf16.hip: WbTable), as logged: <MBW, NBW, KS, T, S, R, MPW, PACK2, BLK4>
 WGRAD_EXPECTED = [
-    "wgrad_bf16_kernel<1, 1, 1, 4, 1, 1, 4, 1, false, false, false>", "wgrad_bf16_kernel<1, 1, 1, 4, 9, 1, 4, 1, false, false, false>",
-    "wgrad_bf16_kernel<1, 1, 1, 4, 9, 1, 8, 1, false, true, false>", "wgrad_bf16_kernel<1, 1, 1, 4, 9, 2, 2, 1, false, false, false>",
-    "wgrad_bf16_kernel<1, 2, 1, 2, 1, 1, 4, 1, false, false, false>", "wgrad_bf16_kernel<1, 2, 1, 2, 9, 1, 4, 1, false, false, false>",
-    "wgrad_bf16_kernel<1, 4, 1, 1, 1, 1, 4, 1, false, false, false>", "wgrad_bf16_kernel<1, 4, 1, 1, 9, 1, 4, 1, false, false, false>",
-    "wgrad_bf16_kernel<2, 1, 1, 2, 9, 1, 4, 1, false, false, false>", "wgrad_bf16_kernel<2, 1, 1, 2, 9, 2, 2, 1, false, false, false>",
-    "wgrad_bf16_kernel<2, 2, 1, 1, 9, 1, 4, 1, false, false, false>", "wgrad_bf16_kernel<2, 2, 1, 1, 9, 1, 4, 2, false, false, true>",
-    "wgrad_bf16_kernel<2, 2, 1, 1, 9, 2, 2, 2, false, false, false>",
-]   # (measured: the route table of profiles/conv_bf16_exact.log; the edge cases of this file add none)
+    "wgrad_bf16_kernel<1, 1, 4, 1, 1, 4, 1, false, false>", "wgrad_bf16_kernel<1, 1, 4, 9, 1, 4, 1, false, false>",
+    "wgrad_bf16_kernel<1, 1, 4, 9, 1, 8, 1, true, false>", "wgrad_bf16_kernel<1, 1, 4, 9, 2, 2, 1, false, false>",
+    "wgrad_bf16_kernel<1, 2, 2, 1, 1, 4, 1, false, false>", "wgrad_bf16_kernel<1, 2, 2, 9, 1, 4, 1, false, false>",
+    "wgrad_bf16_kernel<1, 4, 1, 1, 1, 4, 1, false, false>", "wgrad_bf16_kernel<1, 4, 1, 9, 1, 4, 1, false, false>",
+    "wgrad_bf16_kernel<2, 1, 2, 9, 1, 4, 1, false, false>", "wgrad_bf16_kernel<2, 1, 2, 9, 2, 2, 1, false, false>",
+    "wgrad_bf16_kernel<2, 2, 1, 9, 1, 4, 1, false, false>", "wgrad_bf16_kernel<2, 2, 1, 9, 1, 4, 2, false, true>",
+    "wgrad_bf16_kernel<2, 2, 1, 9, 2, 2, 2, false, false>",
+    # ... and the nine the EDGES entries above add
+    "wgrad_bf16_kernel<4, 1, 1, 9, 1, 4, 1, false, false>", "wgrad_bf16_kernel<4, 1, 1, 1, 1, 4, 1, false, false>",
+    "wgrad_bf16_kernel<4, 1, 1, 9, 2, 2, 1, false, false>", "wgrad_bf16_kernel<2, 2, 1, 1, 1, 4, 1, false, false>",
+    "wgrad_bf16_kernel<2, 2, 1, 9, 2, 2, 1, false, false>", "wgrad_bf16_kernel<2, 1, 2, 1, 1, 4, 1, false, false>",
+    "wgrad_bf16_kernel<1, 4, 1, 9, 2, 2, 1, false, false>", "wgrad_bf16_kernel<1, 2, 2, 9, 2, 2, 1, false, false>",
+    "wgrad_bf16_kernel<1, 1, 4, 9, 1, 8, 1, false, false>",
+]   # 22: the instantiations of the planner sweep's table (profiles/wgrad_bf16_one_definition.log)
+WGRAD_RE = re.compile(r"wgrad_bf16_kernel<(\d+), (\d+), (\d+), (\d+), (\d+), (\d+), (\d+), (true|false), (true|false)> \| (.*)")
+# every (loop of the kernel, 16-pixel steps per staged row) pair a plan can ask for.  LEAN (KS = 1) never gets 4 steps per row: the planner
+# sweep finds no KS = 1 plan with wce = 64.  BLK4's steps are 4 x 4 pixels: 8 per chunk, 9 for a wide chunk (33 - 36 columns).
+WGRAD_LOOPS = ([("LEAN", n) for n in (1, 2, 3)] + [("LEAN2", n) for n in (1, 2, 3, 4)] + [("LEAN2+PACK2", n) for n in (1, 2, 3, 4)] +
+               [("BLK4", "ordinary"), ("BLK4", "wide"), ("generic32", None), ("generic64", None)])
+
+
+def _wgrad_plan(ln):
+    """a wgrad_bf16_kernel launch-log line -> dict(loop, steps, depth, units, units_per_split): the loop as the kernel picks it (wgrad_bf16.hip,
+    the dispatch at the end of the kernel) from the template arguments and the plan text"""
+    m = WGRAD_RE.match(ln)
+    assert m, ln
+    MBW, NBW, KS, T, S, R, MPW = (int(v) for v in m.groups()[:7])
+    PACK2, BLK4 = m.group(8) == "true", m.group(9) == "true"
+    kv = {k: int(v) for k, v in re.findall(r"(\w+)=(\d+)", m.group(10))}
+    if BLK4:
+        loop, steps = "BLK4", "wide" if kv["base_w"] + (1 if kv["rem_w"] else 0) > 32 else "ordinary"
+    elif KS == 1:
+        loop, steps = "LEAN", kv["wce"] >> 4
+    elif R % KS == 0 and MPW == 1 and kv["xcb"] == (2 if PACK2 else 4):
+        loop, steps = ("LEAN2+PACK2" if PACK2 else "LEAN2"), kv["wce"] >> 4
+    else:
+        loop, steps = "generic%d" % (16 * kv["xcb"]), None
+    return dict(loop=loop, steps=steps, depth=kv["depth"], units=kv["units"], units_per_split=kv["units_per_split"])
+
+
+@pytest.mark.parametrize("walk", WGRAD_WALKS, ids=lambda w: _id(w[0]) + "-" + w[1])
+def test_wgrad_long_walks_give_the_exact_integers(walk):
+    case, loop, depth = walk
+    B, Cin, Cout, IH, IW, k, s = case
+    ref = _ref(case, X.WgradRef)
+    P = _Plan(case, "product")
+    _wgrad(P, ref)
+    P.finish()
+    assert not P.errors, "\n".join(P.errors)
+    plans = [_wgrad_plan(ln) for ln in P.lines if ln.startswith("wgrad_bf16_kernel")]
+    print("\n" + _id(case), sorted({ln for ln in P.lines if ln.startswith("wgrad_bf16_kernel")}), end="")
+    assert len(plans) >= 4 and all(p == plans[0] for p in plans), plans     # (both clips of the immediate and the deferred entry at least)
+    p = plans[0]
+    assert (p["loop"], p["depth"]) == (loop, depth), p
+    assert p["units_per_split"] >= 2 * p["depth"] + 1 and p["units"] % p["units_per_split"] != 0, p
+
+
+def test_wgrad_walks_cover_every_loop_and_ring_depth():
+    """host side of the list: one entry per loop and per ring depth the planner sweep's table has for it (BLK4: 2 only), BLK4 with ordinary and wide chunks"""
+    have = {(loop, depth) for _, loop, depth in WGRAD_WALKS}
+    want = {("BLK4", 2)} | {(loop, d) for loop in ("LEAN", "LEAN2", "LEAN2+PACK2", "generic32", "generic64") for d in (2, 3)}
+    assert have == want, (sorted(have - want), sorted(want - have))
+    assert all(_largest(c) <= WALK_MAX_ELEMS for c, _, _ in WGRAD_WALKS)
 
 
 def test_coverage_of_kernel_families_and_tiled_variants():
@@ -425,4 +501,11 @@ def test_coverage_of_kernel_families_and_tiled_variants():
     assert seen["dma"] >= {0, 1, 2} and seen["CKb"] >= {2, 4, 8} and seen["rowpitch"] >= {0, 64, 128}, seen
     assert True in seen["ring"] and True in seen["wide64"], seen
     assert any(ln.startswith("conv_bf16_ws16_kernel<true>") for ln in lines) and any(ln.startswith("conv_bf16_ws16_kernel<false>") for ln in lines)
-    assert set(wg) >= set(WGRAD_EXPECTED), sorted(set(WGRAD_EXPECTED) - set(wg))
+    assert len(set(WGRAD_EXPECTED)) == 22 and set(wg) == set(WGRAD_EXPECTED), (sorted(set(WGRAD_EXPECTED) - set(wg)), sorted(set(wg) - set(WGRAD_EXPECTED)))
+    loops = {}
+    for ln in lines:
+        if ln.startswith("wgrad_bf16_kernel"):
+            p = _wgrad_plan(ln)
+            loops.setdefault((p["loop"], p["steps"]), ln.split("|")[1].strip().split(" B=")[0])
+    print("wgrad_bf16_kernel loop bodies seen (loop, steps per row): first shape\n    " + "\n    ".join(f"{k}: {v}" for k, v in sorted(loops.items(), key=str)))
+    assert set(loops) == set(WGRAD_LOOPS), (sorted(set(WGRAD_LOOPS) - set(loops), key=str), sorted(set(loops) - set(WGRAD_LOOPS), key=str))

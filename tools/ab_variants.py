@@ -32,7 +32,7 @@ if __name__ == "__main__":
         which = which or ["l5a", "l5d", "l3s", "l3m", "l4f"]
         run = lambda w: BC.bench(w[:-1], B, *BC.LAYERS[w[:-1]], w[-1], reps=int(os.environ.get("AB_REPS", "10")))
     else:
-        import ab_wgrad_bf16 as BW
+        import bench_wgrad_bf16 as BW
         which = which or list(BW.LAYERS)
         run = lambda w: BW.bench(w, B, *BW.LAYERS[w])
     import io, contextlib

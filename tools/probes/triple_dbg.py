@@ -31,8 +31,8 @@ def run(half, steps=2):
 
 print("fp32", run(False))
 for label, fn in (("all on", lambda: None), ("ring off", lambda: lib.yogo_diag_conv_bf16_ring(0)), ("lean4 off", lambda: lib.yogo_diag_conv_bf16_lean4(0)),
-                  ("pp off", lambda: lib.yogo_diag_conv_bf16_pp(0)), ("wgrad LEAN2 off", lambda: lib.yogo_diag_wgrad_bf16(32))):
-    lib.yogo_diag_conv_bf16_ring(1); lib.yogo_diag_conv_bf16_lean4(1); lib.yogo_diag_conv_bf16_pp(1); lib.yogo_diag_wgrad_bf16(0)
+                  ("pp off", lambda: lib.yogo_diag_conv_bf16_pp(0))):
+    lib.yogo_diag_conv_bf16_ring(1); lib.yogo_diag_conv_bf16_lean4(1); lib.yogo_diag_conv_bf16_pp(1)
     fn()
     print(f"bf16 {label}:", run(True), flush=True)
 
@@ -51,7 +51,7 @@ def grads(half):
     return names, sizes, tr.flat.grad.clone()
 
 
-lib.yogo_diag_conv_bf16_ring(1); lib.yogo_diag_conv_bf16_lean4(1); lib.yogo_diag_conv_bf16_pp(1); lib.yogo_diag_wgrad_bf16(0)
+lib.yogo_diag_conv_bf16_ring(1); lib.yogo_diag_conv_bf16_lean4(1); lib.yogo_diag_conv_bf16_pp(1)
 n, sz, g32 = grads(False)
 _, _, g16 = grads(True)
 off = 0

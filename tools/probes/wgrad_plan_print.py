@@ -6,7 +6,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from yogo_amd import _hip as H   # noqa: E402
-import ab_wgrad_bf16 as W        # noqa: E402
+import bench_wgrad_bf16 as W       # noqa: E402
 
 H.LIB_PATH = os.path.join(ROOT, "yogo_amd", "lib", "libyogo_hip.so")
 H.launch_log(True)

@@ -6,7 +6,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 from yogo_amd import _hip as H
 import ab_variants as AV
-import ab_wgrad_bf16 as BW
+import bench_wgrad_bf16 as BW
 tag = sys.argv[1]
 libs = {t: AV.load(t) for t in ("base", tag)}
 B = 4

@@ -103,6 +103,18 @@ __device__ __forceinline__ void dma4(i32x4 rs, unsigned lds, int v0, int v1, int
       "s_add_u32 m0, m0, 4096\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %4, %6 offen lds"
       ::"v"(v0), "v"(v1), "v"(v2), "v"(v3), "s"(rs), "s"(lds), "s"(soff) : "memory", "scc");
 }
+// ONE piece, 64 lanes x 16 bytes -> LDS bytes [lds, lds + 1024), with m0 saved and restored around it: for code the compiler schedules
+// LDS instructions of its own around (they read m0).  Issued from inline asm on purpose: hipcc (ROCm 7.2) makes every later LDS read wait
+// for ALL of its own LDS-DMA loads (vmcnt(0)), which would serialise a ring; these loads are invisible to it and the caller retires them
+// with a counted s_waitcnt vmcnt.  (conv_bf16_tiled.hip's bf_dma16 is this with a scalar offset register in place of the literal 0.)
+__device__ __forceinline__ void dma16(i32x4 rs, unsigned lds, int voff) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep)
+               : "v"(voff), "s"(lds), "s"(rs)
+               : "memory");
+}
+__device__ __forceinline__ void dma16_uniform(i32x4 rs, unsigned lds, int voff) { dma16(rs, uniform(lds), voff); }
 // 64 lanes x 4 bytes -> LDS bytes [lds, lds + 256)
 __device__ __forceinline__ void dma_dword(i32x4 rs, unsigned lds, int voff, unsigned soff) {
   asm volatile("s_mov_b32 m0, %1\n\ts_nop 4\n\tbuffer_load_dword %0, %2, %3 offen lds" ::"v"(voff), "s"(lds), "s"(rs), "s"(soff) : "memory");
@@ -123,6 +135,15 @@ __device__ __forceinline__ void store16(u32x4 data, int voff, i32x4 rs, unsigned
 __device__ __forceinline__ void store16_uniform(u32x4 data, int voff, i32x4 rs, unsigned soff) {
   rs = uniform4(rs); soff = uniform(soff);
   asm volatile("s_nop 4\n\tbuffer_store_dwordx4 %0, %1, %2, %3 offen\n\ts_nop 1" ::"v"(data), "v"(voff), "s"(rs), "s"(soff) : "memory");
+}
+
+// ---- the transposed LDS fetch of an MFMA operand staged as [pixel][channels] bf16: two ds_read_b64_tr_b16, each handing the lane 4
+// pixels of "its" channel, from the LDS bytes at lo and hi (generic pointers into the dynamic LDS block) -> 8 pixels
+__device__ __forceinline__ bf16x8 lds_tr8(const unsigned char* lo_addr, const unsigned char* hi_addr) {
+  typedef bf16x4 __attribute__((address_space(3))) * lds_v4;
+  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4)lo_addr);
+  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4)hi_addr);
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
 // ---- epilogue idioms of the MFMA kernels.  After a 32x32 MFMA a lane holds, per group of eight accumulator registers, channels

@@ -31,17 +31,9 @@ struct ConvStagedParams {
 };
 
 namespace {
-// One LDS-DMA piece: 64 lanes x 16 bytes from (descriptor, per-lane byte offset) to LDS bytes [lds_addr, lds_addr + 1024).  From inline asm:
-// hipcc would make every later LDS read wait for all of its own LDS-DMA loads AND stores (vmcnt(0)) wherever it liked; cs_wait_dma() below
-// is the one place this kernel waits.
-__device__ __forceinline__ void cs_dma16(i32x4 rs, unsigned lds_addr, int voff) {
-  unsigned keep;
-  rs = uniform4(rs); lds_addr = uniform(lds_addr);
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(lds_addr), "s"(rs)
-               : "memory");
-}
+// One LDS-DMA piece (bf16_dev.h: dma16, from inline asm) with descriptor and LDS address made uniform here; cs_wait_dma() below is the one
+// place this kernel waits for them.
+__device__ __forceinline__ void cs_dma16(i32x4 rs, unsigned lds_addr, int voff) { dma16_uniform(uniform4(rs), lds_addr, voff); }
 __device__ __forceinline__ void cs_wait_dma() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 }  // namespace
 

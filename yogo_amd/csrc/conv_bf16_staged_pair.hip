@@ -67,14 +67,7 @@ struct ConvPairParams {
 
 namespace {
 // (conv_bf16_staged.hip's cs_dma16 / cs_wait_dma: one LDS-DMA piece from inline asm, and the one place the kernel waits for them)
-__device__ __forceinline__ void cp_dma16(i32x4 rs, unsigned lds_addr, int voff) {
-  unsigned keep;
-  rs = uniform4(rs); lds_addr = uniform(lds_addr);
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(lds_addr), "s"(rs)
-               : "memory");
-}
+__device__ __forceinline__ void cp_dma16(i32x4 rs, unsigned lds_addr, int voff) { dma16_uniform(uniform4(rs), lds_addr, voff); }
 __device__ __forceinline__ void cp_wait_dma() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 // ... but for the N youngest vector-memory operations (N < 64: the counter has six bits)
 template <int N>

@@ -15,6 +15,7 @@
 // pair rounds 0.01 dy per element and sums in another order, so the two agree to fp32 rounding of sums over the whole batch, not bit for
 // bit (tests/test_gpu_first_fused_bwd.py: both against a CPU fp64 reference).
 #include "bf16_dev.h"
+#include "wgrad_reduce.h"
 
 struct DgFirstParams {
   const u32x4* g;                // bf16 NCHW8c [B][4][H][W] units: gradient w.r.t. layer 1's conv output
@@ -36,13 +37,7 @@ struct DgFirstParams {
 
 namespace {
 constexpr int DF_NJ = 9, DF_PER = 2 * DF_NJ + 2, DF_COUT = 16;   // the partial rows of conv_first_bn_wgrad_*: [Cout][A1 9 | A2 9 | S1 | S2] + P[9] + G[9][9]
-// LDS-DMA pieces (conv_bf16_staged.hip): 64 lanes x 16 bytes -> LDS [lds_addr, + 1024); 64 lanes x 4 bytes -> [lds_addr, + 256)
-__device__ __forceinline__ void df_dma16(i32x4 rs, unsigned lds_addr, int voff) {
-  unsigned keep;
-  lds_addr = uniform(lds_addr);
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(lds_addr), "s"(rs) : "memory");
-}
+// LDS-DMA pieces: 64 lanes x 16 bytes -> LDS [lds_addr, + 1024) is bf16_dev.h's dma16_uniform; 64 lanes x 4 bytes -> [lds_addr, + 256)
 __device__ __forceinline__ void df_dma4(i32x4 rs, unsigned lds_addr, int voff) {
   unsigned keep;
   lds_addr = uniform(lds_addr);
@@ -50,13 +45,8 @@ __device__ __forceinline__ void df_dma4(i32x4 rs, unsigned lds_addr, int voff) {
                : "=&s"(keep) : "v"(voff), "s"(lds_addr), "s"(rs) : "memory");
 }
 __device__ __forceinline__ void df_wait_dma() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-// eight pixels of this lane's channel: two transposed reads of four pixels each, `second` bytes apart (wgrad_bf16.hip: lds_tr8)
-__device__ __forceinline__ bf16x8 df_tr8(const unsigned char* a, int second) {
-  typedef bf16x4 __attribute__((address_space(3))) * lds_v4;
-  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4)(a));
-  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4)(a + second));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
+// eight pixels of this lane's channel: two transposed reads of four pixels each, `second` bytes apart
+__device__ __forceinline__ bf16x8 df_tr8(const unsigned char* a, int second) { return lds_tr8(a, a + second); }
 }  // namespace
 
 // R: output rows of a wavefront's tile (R x 32 pixels); NWV: wavefronts per workgroup.
@@ -178,13 +168,13 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(DF_WAV
       const int base = (iy0 * W + ix0) * 16;
       if (iy0 >= 0 && iy0 + NR <= H && ix0 >= 0 && ix0 + ROWU <= W) {   // (uniform) an interior tile: no border tests
 #pragma unroll
-        for (int i = 0; i < NDMA; ++i) df_dma16(rs_g, my_addr + (unsigned)i * 1024u, (i + 1) * 64 <= TU ? rel[i] + base : (rel[i] == (int)OOB ? (int)OOB : rel[i] + base));
+        for (int i = 0; i < NDMA; ++i) dma16_uniform(rs_g, my_addr + (unsigned)i * 1024u, (i + 1) * 64 <= TU ? rel[i] + base : (rel[i] == (int)OOB ? (int)OOB : rel[i] + base));
       } else {
 #pragma unroll
         for (int i = 0; i < NDMA; ++i) {
           const int r = (int)(rc[i] >> 16), c = (int)(rc[i] & 0xFFFFu);
           const bool ok = ((unsigned)(iy0 + r) < (unsigned)H) && ((unsigned)(ix0 + c) < (unsigned)W);   // (all ones: r = 65535 fails the row test)
-          df_dma16(rs_g, my_addr + (unsigned)i * 1024u, ok ? rel[i] + base : (int)OOB);
+          dma16_uniform(rs_g, my_addr + (unsigned)i * 1024u, ok ? rel[i] + base : (int)OOB);
         }
       }
       const i32x4 rs_i = uniform4(rsrc(p.img + (size_t)b * IH0 * IW0, (unsigned)(IH0 * IW0)));
@@ -214,7 +204,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(DF_WAV
         for (int i = 0; i < NXDMA; ++i) {
           constexpr int dummy = 0; (void)dummy;
           const int kb = (2 * i) / R, row0 = (2 * i) % R;
-          df_dma16(rs_x, my_x_addr + (unsigned)i * 1024u, (cok && oy0 + row0 + hi < H) ? xo + kb * kcb + row0 * W * 16 : (int)OOB);
+          dma16_uniform(rs_x, my_x_addr + (unsigned)i * 1024u, (cok && oy0 + row0 + hi < H) ? xo + kb * kcb + row0 * W * 16 : (int)OOB);
         }
       }
     }
@@ -458,10 +448,6 @@ int df_launch(DgFirstParams p, int B, int H, int W, int act0, const char* what, 
   return YOGO_OK;
 }
 }  // namespace
-
-// split-K reduction shared with the weight-gradient kernels (wgrad_f32.hip)
-extern "C" int yogo_internal_wgrad_reduce_q(void* queue, const float* slab, int nslab, int T, int M, int N, int Mpad, int Npad, float clip, float* dw,
-                                            const float* bias_part, int nbias, float* db, hipStream_t stream);
 
 // 1 when the fused sweep takes (layer 1: 3x3, stride 1, Cmid -> Cout1 channels at H x W; layer 0: one uint8 channel, stride 2, Cmid outputs)
 extern "C" int yogo_conv2d_dgrad_first_bwd_supported(int Cmid, int Cout1, int H, int W, int B, int act0) {

@@ -11,6 +11,7 @@
 // odd pitches (conflict-free channel-strided reads).  Slabs are summed in a fixed order by a second kernel
 // (bitwise reproducible; no float atomics), which also writes OIHW and clamps to +-clip.
 #include "common.h"
+#include "wgrad_reduce.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
@@ -402,9 +403,7 @@ struct WgradReduceQueue {
   int blocks;
 };
 
-// slab reduction shared with wgrad_bf16.hip (kernels cannot be launched across translation units without RDC)
-extern "C" int yogo_internal_wgrad_reduce(const float* slab, int nslab, int T, int M, int N, int Mpad, int Npad, float clip, float* dw,
-                                          const float* bias_part, int nbias, float* db, hipStream_t stream);
+// (the slab reduction is shared with wgrad_bf16.hip and conv_first_fused_bwd.hip: yogo_internal_wgrad_reduce / _q, wgrad_reduce.h)
 static int wgrad_reduce_flush(WgradReduceQueue* q, hipStream_t stream) {
   if (q->m.n == 0) return YOGO_OK;
   hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3(q->blocks), dim3(1024), 0, stream, q->m);
