@@ -532,6 +532,29 @@ int yogo_zstd_decode(const unsigned char* src, long long src_bytes, const long l
  * ranges is read or written, whatever the stored bytes say (the same checks, in the same order: yogo_amd.inflate.inflate_status). */
 int yogo_inflate_zlib(const unsigned char* src, long long src_bytes, const long long* table, int n, unsigned char* dst,
                       long long dst_bytes, int* status, yogo_stream_t stream);
+/* Baseline JPEG files decoded on the device to the planes `read_image` gives (PIL on libjpeg's defaults: JDCT_ISLOW, fancy
+ * upsampling), in front of the PNG unpack kernels, which take them as planar entries (yogo_amd/png_batch.py; `--device-image-decode-jpeg`).
+ * src: src_bytes of device memory holding the files as they came off the disk, at any alignment; table: [n][18] int64 device, one row
+ * { src_off, src_len, dst_off, dst_len, H, W, components | luma h << 8 | luma v << 16, restart interval, scan_off, quant[3], dc[3],
+ * ac[3] } per file (yogo_amd.jpeg.table_row): the file's bytes in src; where its C_out * H * W == dst_len output bytes belong in dst
+ * (dst_bytes of device memory, not overlapping src): [C_out][H][W] uint8, C_out 1 (grey; from colour PIL's luma of R, G, B) or 3 (R, G,
+ * B; from grey the plane three times); the frame; where the entropy-coded bytes start; per component 2 * the offset of its 64
+ * quantiser entries + (1: 16-bit entries) and the offsets of the 16 counts of its DC and AC Huffman tables, from the file's first byte,
+ * -1 for a table never defined.  The kernel reads DQT / DHT from the file at these offsets (no descriptor is uploaded) and trusts
+ * none of them.  Served: SOF0 / SOF1, 8 bits, one interleaved scan, grey or YCbCr at 4:4:4 / 4:2:2 / 4:2:0, restart intervals, W <=
+ * 1040 (the LDS band: one MCU row of coefficients).  One wavefront per file; two launches, the grey rows and the colour rows.
+ * status: [n] int32 device, per row 0 (every MCU decoded, the scan consumed exactly, EOI behind it) or the check that ended it:
+ * 1 the row does not lie inside src / dst or describes no frame the kernel takes, 2 a table the scan names was never defined or does
+ * not lie inside the file, 3 a DHT whose counts describe no prefix code (or use the all-ones code) or more than 256 symbols, 4 the
+ * source ends inside a code, inside extra bits or in front of a restart marker, 5 a bit pattern without a code, 6 a DC category
+ * above 11, an AC category above 10 or an AC symbol r/0 with r in 1 .. 14, 7 a run that passes coefficient 63, 8 a marker inside a
+ * restart interval, FF followed by neither 00 nor an allowed marker, bytes left over in front of a restart marker or another marker
+ * than the expected RSTm, 9 no EOI behind the last MCU, 10 EOI in front of the last MCU, 11 a dequantised coefficient outside
+ * +-2047.  Whatever libjpeg would repair with a warning is a nonzero status: the file is the host's.  A row with a nonzero status may
+ * have written part of its own dst range; no byte outside a row's two ranges is read or written, whatever the stored bytes say (the
+ * same checks, in the same order: yogo_amd.jpeg.jpeg_status). */
+int yogo_jpeg_decode(const unsigned char* src, long long src_bytes, const long long* table, int n, unsigned char* dst,
+                     long long dst_bytes, int C_out, int* status, yogo_stream_t stream);
 
 /* ---- PNG directories for inference (yogo_amd/png_feed.py, `yogo infer --path-to-images --device-image-decode`) ---------------
  * The scanlines of 8-bit greyscale, non-interlaced PNG files as yogo_inflate_zlib leaves them (the IDAT payloads of a file are one

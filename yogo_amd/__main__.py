@@ -20,10 +20,11 @@ def main(argv=None) -> None:
     elif args.task == "test":
         from yogo_amd.trainer import device_metrics_scope
         from yogo_amd.utils.test_model import do_model_test
-        from yogo_amd.yogo_dataloader import device_image_stream_scope
+        from yogo_amd.yogo_dataloader import device_image_jpeg_scope, device_image_stream_scope
 
         with device_metrics_scope(args.device_metrics), \
-                device_image_stream_scope(args.device_image_stream, args.device_image_decode_all, args.device_image_resize):
+                device_image_stream_scope(args.device_image_stream, args.device_image_decode_all, args.device_image_resize), \
+                device_image_jpeg_scope(args.device_image_stream and args.device_image_decode_jpeg):
             do_model_test(args)
     elif args.task == "export":
         print("yogo_amd: `export` (ONNX / OpenVINO for another deployment target) is not part of this MI355X build; "

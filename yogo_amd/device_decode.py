@@ -113,6 +113,28 @@ def zstd_frames(stored: torch.Tensor, table: torch.Tensor, out: torch.Tensor, st
     _decode_rows("yogo_zstd_decode", stored, table, out, status, work)
 
 
+JPEG_TABLE_COLS = 18   # yogo_amd.jpeg.TABLE_COLS
+
+
+def jpeg_decode(stored: torch.Tensor, table: torch.Tensor, out: torch.Tensor, planes: int, status: torch.Tensor) -> None:
+    """One ``yogo_jpeg_decode`` launch on the current stream.  stored: 1-D uint8 device tensor, the files as they came off the disk;
+    table: int64 [n, 18] device, rows of ``yogo_amd.jpeg.table_row``; out: 1-D uint8 device tensor, where every file's
+    [planes][H][W] bytes go (planes 1 or 3); status: int32 [n] device.  The kernel holds every row to the two buffers itself."""
+    for t, name in ((stored, "the stored files"), (table, "the table"), (out, "the decoded planes"), (status, "the status")):
+        _hip.require_cuda(t, name)
+    require_bytes("jpeg_decode", "stored and out", stored, out)
+    if planes not in (1, 3):
+        raise ValueError(f"jpeg_decode: {planes} planes, 1 or 3 are written")
+    n = int(table.shape[0])
+    require_table("jpeg_decode", table, JPEG_TABLE_COLS)
+    require_status("jpeg_decode", status, n)
+    require_same_device("jpeg_decode", stored, table, out, status)
+    if n == 0:
+        return
+    with torch.cuda.device(out.device):
+        _hip.call("yogo_jpeg_decode", stored, stored.numel(), table, n, out, out.numel(), int(planes), status, _hip.stream_ptr())
+
+
 def png_unpack(scan: torch.Tensor, table: torch.Tensor, image_hw: Tuple[int, int], out: torch.Tensor, status: torch.Tensor,
                top: int = 0, left: int = 0) -> torch.Tensor:
     """One ``yogo_png_unpack`` launch on the current stream.  scan: 1-D uint8 device tensor of inflated scanlines (written: the

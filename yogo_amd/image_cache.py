@@ -45,6 +45,7 @@ FLAG = "--device-image-cache"
 DECODE_FLAG = "--device-image-decode"
 RESIZE_FLAG = "--device-image-resize"
 DECODE_ALL_FLAG = "--device-image-decode-all"
+DECODE_JPEG_FLAG = "--device-image-decode-jpeg"
 
 
 def check_budget_gib(gib: float) -> float:
@@ -202,11 +203,14 @@ class ImageCache:
 
     def __init__(self, split: Dataset, S: int, image_shape: Tuple[int, int, int], normalize_images: bool, device=None,
                  num_workers: int = 0, batch_size: int = 64, name: str = "train", log: bool = False, device_decode: bool = False,
-                 decode_batch: int = DEFAULT_DECODE_BATCH, device_resize: bool = False, device_decode_all: bool = False):
+                 decode_batch: int = DEFAULT_DECODE_BATCH, device_resize: bool = False, device_decode_all: bool = False,
+                 device_decode_jpeg: bool = False):
         if device_resize and not device_decode:
             raise ValueError(f"{RESIZE_FLAG} resizes what the device decoded: it needs {DECODE_FLAG}")
         if device_decode_all and not device_decode:
             raise ValueError(f"{DECODE_ALL_FLAG} widens what {DECODE_FLAG} takes: it needs {DECODE_FLAG}")
+        if device_decode_jpeg and not device_decode:
+            raise ValueError(f"{DECODE_JPEG_FLAG} widens what {DECODE_FLAG} takes: it needs {DECODE_FLAG}")
         if not torch.cuda.is_available():
             raise RuntimeError(f"yogo_amd: {FLAG} keeps images on an MI355X device; there is no CPU fallback")
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -223,6 +227,7 @@ class ImageCache:
         self.num_workers, self.batch_size, self.name, self.log = int(num_workers), max(1, int(batch_size)), name, log
         self.device_decode, self.decode_batch = bool(device_decode), png_prefill.check_decode_batch(decode_batch)
         self.device_resize, self.device_decode_all = bool(device_resize), bool(device_decode_all)
+        self.device_decode_jpeg = bool(device_decode_jpeg)
         self.decode_stats: dict = {}   # what png_prefill.fill reports of a device prefill (chunk times, scratch bytes); empty otherwise
         self.nbytes = self.S * C * H * W
         try:
@@ -287,4 +292,5 @@ class ImageCache:
     def _fill_on_device(self) -> List[Optional[torch.Tensor]]:
         """the device route (yogo_amd/png_prefill.py): the same result, the PNG files inflated and unfiltered on the device"""
         return png_prefill.fill(self.images, [resolve_sample(self.split, i) for i in range(self.S)], self.decode_batch, self.decode_stats,
-                                device_resize=self.device_resize, **({"decode_all": True} if self.device_decode_all else {}))
+                                device_resize=self.device_resize, **({"decode_all": True} if self.device_decode_all else {}),
+                                **({"decode_jpeg": True} if self.device_decode_jpeg else {}))

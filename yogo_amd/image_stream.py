@@ -74,11 +74,11 @@ class Scratch:
     stream) and the two staging tensors, made at the first iteration and kept until ``close()``; and which iteration uses them now."""
 
     def __init__(self, image_shape: Tuple[int, int, int], batch_size: int, decode_batch: int = DEFAULT_DECODE_BATCH, device=None,
-                 device_resize: bool = False, decode_all: bool = False, max_threads: int = MAX_THREADS):
+                 device_resize: bool = False, decode_all: bool = False, max_threads: int = MAX_THREADS, decode_jpeg: bool = False):
         self.image_shape = tuple(int(v) for v in image_shape)
         self.decode_batch = check_decode_batch(decode_batch)
         self.capacity = max(self.decode_batch, int(batch_size))
-        self.device, self.device_resize, self.decode_all = device, bool(device_resize), bool(decode_all)
+        self.device, self.device_resize, self.decode_all, self.decode_jpeg = device, bool(device_resize), bool(decode_all), bool(decode_jpeg)
         self.max_threads = max(1, min(MAX_THREADS, int(max_threads)))
         self.filler: Optional[Filler] = None
         self.staging: List[torch.Tensor] = []
@@ -174,7 +174,8 @@ class _Iteration(PrefetchFeed):
         t0 = time.perf_counter()
         with torch.cuda.device(self.dev):
             rows = sc.filler.fill(staging[:len(order)], [resolve_sample(st.dataset, i) for i in order], sc.decode_batch, stats,
-                                  device_resize=sc.device_resize, decode_all=sc.decode_all, raise_rows=False, after=sc.released[g % 2])
+                                  device_resize=sc.device_resize, decode_all=sc.decode_all, raise_rows=False, after=sc.released[g % 2],
+                                  **({"decode_jpeg": True} if sc.decode_jpeg else {}))
             ev = torch.cuda.Event()
             ev.record(sc.filler.side)
         st._count(len(order), stats, time.perf_counter() - t0)
@@ -232,7 +233,8 @@ class ImageStream:
     """The stream of one split.  dataset: the split as ``get_datasets`` made it (its blob part, if any, last); cache: its device image
     cache or None.  ``batches(order, batch_size)`` yields the split's batches in ``collate_cached``'s form, ``Staged`` in the images'
     place.  ``stats`` adds up over the iterations: ``groups``, ``streamed`` samples, ``host_decoded``, ``device_resized``, the
-    per-chunk event times of ``fill`` (``inflate_ms``, ``unpack_ms``, ``resize_ms``), ``seconds`` spent filling, and the scratch's
+    per-chunk event times of ``fill`` (``inflate_ms``, ``unpack_ms``, ``resize_ms``; with the scratch's ``decode_jpeg`` also
+    ``jpeg_decoded`` and ``jpeg_ms``), ``seconds`` spent filling, and the scratch's
     ``hbm_bytes`` / ``pinned_bytes`` as they stood after the last group."""
 
     def __init__(self, dataset: Dataset, real_len: int, scratch: Scratch, cache: Optional[ImageCache] = None, name: str = "train", log: bool = False):
@@ -257,6 +259,9 @@ class ImageStream:
             s[key] += stats.get(key, 0)
         for key in ("inflate_ms", "unpack_ms", "resize_ms"):
             s[key].extend(stats.get(key, []))
+        if "jpeg_ms" in stats:   # (--device-image-decode-jpeg)
+            s["jpeg_decoded"] = s.get("jpeg_decoded", 0) + stats["jpeg_decoded"]
+            s.setdefault("jpeg_ms", []).extend(stats["jpeg_ms"])
         s["hbm_bytes"], s["pinned_bytes"] = self.scratch.hbm_bytes, self.scratch.pinned_bytes
 
     def batches(self, order: Sequence[int], batch_size: int):

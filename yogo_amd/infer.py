@@ -79,6 +79,7 @@ def predict(
     device_outputs: bool = False,
     device_image_decode: bool = False,
     device_image_decode_all: bool = False,
+    device_image_decode_jpeg: bool = False,
     device_draw: bool = False,
     device_draw_level: int = 0,
 ) -> Optional[torch.Tensor]:
@@ -111,6 +112,8 @@ def predict(
 
     if device_image_decode_all and not device_image_decode:
         raise ValueError("device_image_decode_all widens what device_image_decode takes: it needs device_image_decode")
+    if device_image_decode_jpeg and not device_image_decode:
+        raise ValueError("device_image_decode_jpeg widens what device_image_decode takes: it needs device_image_decode")
     if device_image_decode and path_to_zarr is not None:
         raise ValueError("device_image_decode decodes the PNG files of path_to_images; a zarr stack has its own device route")
     device = torch.device(device or choose_device())
@@ -152,7 +155,7 @@ def predict(
         with torch.cuda.device(device):
             loader = PngDeviceFeed(image_dataset, batch_size, device, crop=(img_h, img_w) if vertical_crop_height else None,
                                    normalize=bool(model.normalize_images), all_types=bool(device_image_decode_all),
-                                   rgb=bool(model.is_rgb))
+                                   rgb=bool(model.is_rgb), **({"jpeg": True} if device_image_decode_jpeg else {}))
     else:
         num_workers = choose_dataloader_num_workers(len(image_dataset), requested_num_workers=requested_num_workers)
         loader = DataLoader(image_dataset, batch_size=batch_size, shuffle=False, drop_last=False, pin_memory=True, collate_fn=collate_fn,
@@ -296,6 +299,7 @@ def do_infer(args) -> None:
         vertical_crop_height=args.crop_height, count_predictions=args.count, output_img_ftype=args.output_img_filetype,
         min_class_confidence_threshold=args.min_class_confidence_threshold, half=args.half, device_outputs=args.device_outputs,
         device_image_decode=args.device_image_decode, device_image_decode_all=args.device_image_decode_all,
+        device_image_decode_jpeg=args.device_image_decode_jpeg,
         device_draw=args.device_draw,
         device_draw_level=args.device_draw_level,
     )

@@ -7,7 +7,9 @@ cache (yogo_amd/png_prefill.py) both do between a file's bytes and the unpack la
   ``slot_layout``     file sizes -> every file's room in a pinned slot, at multiples of ``ALIGN``
   ``scan_layout``     inflated sizes -> every image's place in the scanline buffer at multiples of ``SCAN_ALIGN``, the palettes of
                       the batch's palette files (768 bytes each) behind the last image
+  ``read_jpeg_stream``  the same for a baseline JPEG file (``--device-image-decode-jpeg``): the file's bytes as they are in the room
   ``inflate_batch``   the slot up, ONE ``yogo_inflate_zlib`` launch over the batch's streams (rows of ``inflate_rows``)
+  ``jpeg_batch``      ONE ``yogo_jpeg_decode`` launch over the batch's JPEG files: their planes where host pixels would lie
   ``upload_host_parts``  the pixels of the images the host decoded and the palettes into the scanline buffer
   ``unpack_table``    the table of ``yogo_png_unpack`` / ``yogo_png_unpack_planes`` ([B, 2]) or ``yogo_png_unpack_any`` ([B, 3])
 
@@ -21,8 +23,8 @@ from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from yogo_amd import inflate, png
-from yogo_amd.device_decode import ALIGN, inflate_streams, png_stream_into, png_unpack, png_unpack_any, png_unpack_planes
+from yogo_amd import inflate, jpeg, png
+from yogo_amd.device_decode import ALIGN, inflate_streams, jpeg_decode, png_stream_into, png_unpack, png_unpack_any, png_unpack_planes
 
 SCAN_ALIGN = 16   # yogo_inflate_zlib asks for 16-byte aligned destinations
 KIND_GREY, KIND_PLANAR, KIND_RGB = 0, 1, 2   # yogo_png_unpack_planes' kinds
@@ -39,18 +41,25 @@ class PngStream:
     ``code`` of yogo_png_unpack_any's table, the ``palette`` (768 bytes) of a palette file; ``stream``: the bytes themselves where
     there was no room to copy them to.  For the host (``host``): ``pixels``, what the host decoder gave, None where it gave up.
     The prefill's own: ``rows`` (the sample's label rows, or the exception their parsing raised) and ``resize`` (the file has
-    another size than the cache and the device resizes it)."""
-    __slots__ = ("hw", "stored", "deflate", "adler", "need", "code", "palette", "stream", "host", "pixels", "rows", "resize")
+    another size than the cache and the device resizes it).  ``jpeg``: the ``JpegInfo`` of a JPEG file the device decodes -- its
+    ``stored`` bytes are the whole file, ``need`` its planes * H * W, and the unpack launch sees it as planar pixels (``planar``)."""
+    __slots__ = ("hw", "stored", "deflate", "adler", "need", "code", "palette", "stream", "host", "pixels", "rows", "resize", "jpeg")
 
     def __init__(self, hw=None, stored=0, deflate=(0, 0), adler=0, need=0, code=png.FMT_PLANAR, palette=None, stream=None,
-                 host=False, pixels=None):
+                 host=False, pixels=None, jpeg=None):
         self.hw, self.stored, self.deflate, self.adler, self.need, self.code = hw, stored, deflate, adler, need, code
         self.palette, self.stream, self.host, self.pixels, self.rows, self.resize = palette, stream, host, pixels, None, False
+        self.jpeg = jpeg
 
     @property
     def bpp(self) -> int:
         """bytes per pixel of an 8-bit file (``PngInfo.bytes_per_pixel``): 3 for colour type 2, the low byte of the format code"""
         return 3 if self.code & 0xFF == 2 else 1
+
+    @property
+    def planar(self) -> bool:
+        """the unpack launch finds [planes][H][W] pixels at the image's place: the host decoded it, or yogo_jpeg_decode did"""
+        return self.host or self.jpeg is not None
 
 
 def _file_size(path: str) -> int:
@@ -89,6 +98,19 @@ def read_stream(data: bytes, room: Optional[np.ndarray], accept: Callable[[png.P
                      png.palette_table(data, info) if info.color_type == 3 else None, stream)
 
 
+def read_jpeg_stream(data: bytes, room: Optional[np.ndarray], accept: Callable[[jpeg.JpegInfo], bool], planes: int) -> PngStream:
+    """(pool thread) ``read_stream`` for a JPEG file: its record, the file's bytes copied into ``room`` as they are (None: the record
+    keeps them).  ``accept``: ``JpegInfo.device_decodable`` and whatever else the caller asks of a file; ``planes``: 1 or 3, what the
+    batch is converted to.  Raises jpeg.NotJpeg, Refused (not accepted, or longer than its room) and ValueError (does not parse)."""
+    info = jpeg.parse_jpeg(data)
+    if not accept(info) or (room is not None and len(data) > len(room)):
+        raise Refused(f"JPEG: SOF{info.sof}, {len(info.components)} components at {info.precision} bits, {len(data)} bytes")
+    if room is not None:
+        room[:len(data)] = np.frombuffer(data, dtype=np.uint8)
+    return PngStream((info.height, info.width), len(data), need=planes * info.height * info.width, stream=None if room is not None else data,
+                     jpeg=info)
+
+
 class ScanLayout(NamedTuple):
     at: np.ndarray               # int64 [B + 1]: where image i starts in the scanline buffer; at[B]: where the palettes start
     palette_at: Dict[int, int]   # image -> where its palette starts
@@ -114,19 +136,22 @@ def inflate_rows(records: Sequence[PngStream], src_at: Sequence[int], layout: Sc
     """``inflate_streams``' table, int64 [n, 5], one row per record that is the device's: (where the DEFLATE bytes start in the slot
     -- ``src_at[i]``: where room i does --, how many, where the scanlines go, how many, the Adler-32)"""
     return np.asarray([(int(src_at[i]) + r.deflate[0], r.deflate[1], int(layout.at[i]), layout.need[i], r.adler)
-                       for i, r in enumerate(records) if not r.host], dtype=np.int64).reshape(-1, 5)
+                       for i, r in enumerate(records) if not r.planar], dtype=np.int64).reshape(-1, 5)
 
 
 def inflate_batch(records: Sequence[PngStream], src_at: Sequence[int], layout: ScanLayout, pinned: torch.Tensor, sdev: torch.Tensor,
                   scan: torch.Tensor, events=None) -> Tuple[Optional[torch.Tensor], List[int]]:
     """(current stream) the slot's bytes in use up (``pinned`` -> ``sdev``) and ONE yogo_inflate_zlib launch into ``scan``
     -> (its status, int32 per row, None where no record is the device's; which records its rows are).  ``events``: two events
-    recorded before and behind the launch."""
-    device_rows = [i for i, r in enumerate(records) if not r.host]
+    recorded before and behind the launch.  The JPEG files of the batch go up with the slot and are ``jpeg_batch``'s."""
+    device_rows = [i for i, r in enumerate(records) if not r.planar]
+    stored = [i for i, r in enumerate(records) if not r.host]
+    if not stored:
+        return None, device_rows
+    used = int(src_at[stored[-1]]) + records[stored[-1]].stored
+    sdev[:used].copy_(pinned[:used], non_blocking=True)
     if not device_rows:
         return None, device_rows
-    used = int(src_at[device_rows[-1]]) + records[device_rows[-1]].stored
-    sdev[:used].copy_(pinned[:used], non_blocking=True)
     status = torch.empty(len(device_rows), dtype=torch.int32, device=scan.device)
     if events:
         events[0].record()
@@ -134,6 +159,25 @@ def inflate_batch(records: Sequence[PngStream], src_at: Sequence[int], layout: S
     if events:
         events[1].record()
     return status, device_rows
+
+
+def jpeg_batch(records: Sequence[PngStream], src_at: Sequence[int], layout: ScanLayout, sdev: torch.Tensor, scan: torch.Tensor,
+               planes: int, events=None) -> Tuple[Optional[torch.Tensor], List[int]]:
+    """(current stream, behind ``inflate_batch``, which took the slot up) ONE yogo_jpeg_decode launch over the batch's JPEG files:
+    each one's [planes][H][W] bytes into ``scan`` at its place -> (its status, int32 per row, None where the batch has no JPEG
+    file; which records its rows are).  ``events``: two events recorded before and behind the launch."""
+    rows = [i for i, r in enumerate(records) if r.jpeg is not None]
+    if not rows:
+        return None, rows
+    table = np.asarray([jpeg.table_row(records[i].jpeg, int(src_at[i]), records[i].stored, int(layout.at[i]), planes) for i in rows],
+                       dtype=np.int64).reshape(-1, jpeg.TABLE_COLS)
+    status = torch.empty(len(rows), dtype=torch.int32, device=scan.device)
+    if events:
+        events[0].record()
+    jpeg_decode(sdev, torch.from_numpy(table).to(scan.device), scan, planes, status)
+    if events:
+        events[1].record()
+    return status, rows
 
 
 def upload_host_parts(records: Sequence[PngStream], layout: ScanLayout, scan: torch.Tensor) -> None:
@@ -153,10 +197,10 @@ def unpack_table(kernel, records: Sequence[PngStream], layout: ScanLayout, rows:
     png_unpack_any.  ``refused``: records that keep their place in the launch as an entry the kernel refuses."""
     def code(r: PngStream) -> int:
         if kernel is png_unpack:
-            return 1 if r.host else 0
+            return 1 if r.planar else 0
         if kernel is png_unpack_planes:
-            return KIND_PLANAR if r.host else KIND_RGB if r.bpp == 3 else KIND_GREY
-        return png.FMT_PLANAR if r.host else r.code
+            return KIND_PLANAR if r.planar else KIND_RGB if r.bpp == 3 else KIND_GREY
+        return png.FMT_PLANAR if r.planar else r.code
 
     width = 3 if kernel is png_unpack_any else 2
     table = [(int(layout.at[i]), REFUSED if i in refused else code(records[i]), layout.palette_at.get(i, 0))[:width]

@@ -23,6 +23,12 @@ tRNS or not, Adam7 (``PngInfo.any_decodable``), unpacked by ``yogo_png_unpack_an
 each be of another format: the palettes of the batch's palette files lie behind the last image of the scanline buffer, and the
 pinned slot gives every file room for its own size.  Still one inflate and one unpack launch per batch; the host keeps another
 format under a .png name, a stream larger than its room and a palette file without a usable PLTE chunk.
+
+``jpeg=True`` (``--device-image-decode-jpeg``) has the device take a baseline JPEG file found in the directory as well
+(``JpegInfo.device_decodable``; the reference globs ``*.png`` alone, so it is a file under the wrong name: it is taken by its first
+bytes): its bytes go into its room as they are, ONE ``yogo_jpeg_decode`` launch per batch that has such files (csrc/jpeg_decode.hip)
+leaves their planes in the scanline buffer, and the batch's unpack launch takes them as raw images.  A file the kernel gives a
+status is decoded by ``read_image`` after all and the batch is unpacked again.
 """
 from __future__ import annotations
 
@@ -36,8 +42,8 @@ import torch
 from yogo_amd import inflate, png
 from yogo_amd.device_decode import ALIGN, MAX_THREADS, PrefetchFeed, center_crop_origin, feed_device, gather, png_unpack, png_unpack_any, \
     raise_first_bad
-from yogo_amd.png_batch import PngStream, Refused, _file_size, batch_layout, inflate_batch, read_stream, slot_layout, unpack_table, \
-    upload_host_parts
+from yogo_amd.png_batch import PngStream, Refused, _file_size, batch_layout, inflate_batch, jpeg_batch, read_jpeg_stream, read_stream, slot_layout, \
+    unpack_table, upload_host_parts
 from yogo_amd.yogo_dataset import read_image
 
 UNPACK_STATUS = {1: "a filter-type byte above 4", 2: "the image lies outside the scanline buffer"}
@@ -47,17 +53,19 @@ class PngDeviceFeed(PrefetchFeed):
     """Iterator over ``(device batch [B, 1, OH, OW], tuple of paths)`` in the dataset's order; the last batch may be partial; a batch
     that raises RuntimeError costs that batch alone (device_decode.PrefetchFeed).  ``crop``: (OH, OW) of a centre crop done in the
     kernel; ``normalize``: fp32 ``/ 255`` in the kernel, else uint8.  ``all_types``: every PNG colour type, bit depth and Adam7 goes
-    to the device (see the module's text); ``rgb`` (with all_types only): batches of 3 planes, ``[B, 3, OH, OW]``."""
+    to the device (see the module's text); ``rgb`` (with all_types only): batches of 3 planes, ``[B, 3, OH, OW]``; ``jpeg``: baseline
+    JPEG files go to the device too (``jpeg_decoded`` counts them)."""
 
-    all_types = rgb = False   # (the defaults, also of an object made without __init__)
+    all_types = rgb = jpeg = False   # (the defaults, also of an object made without __init__)
 
     def __init__(self, dataset, batch_size: int, device, crop: Optional[Tuple[int, int]] = None, normalize: bool = False,
-                 all_types: bool = False, rgb: bool = False):
+                 all_types: bool = False, rgb: bool = False, jpeg: bool = False):
         dev = feed_device(device, batch_size, "the PNG feed decodes")
         if rgb and not all_types:
             raise ValueError("PngDeviceFeed: batches of 3 planes (rgb) need all_types: yogo_png_unpack writes one plane of 8-bit greyscale")
         self.dataset, self.batch_size, self.device, self.normalize = dataset, int(batch_size), dev, bool(normalize)
-        self.all_types, self.rgb = bool(all_types), bool(rgb)
+        self.all_types, self.rgb, self.jpeg = bool(all_types), bool(rgb), bool(jpeg)
+        self.jpeg_decoded = 0   # images yogo_jpeg_decode served
         self._unpack = png_unpack_any if self.all_types else png_unpack
         self.crop = None if crop is None else (int(crop[0]), int(crop[1]))
         self.paths = [str(p) for p in dataset.image_paths]
@@ -95,7 +103,15 @@ class PngDeviceFeed(PrefetchFeed):
         except OSError as e:
             raise RuntimeError(f"{path} could not be read ({type(e).__name__}: {e})") from e
         try:
-            return read_stream(data, room, self._accept)
+            try:
+                return read_stream(data, room, self._accept)
+            except png.NotPng:
+                if not self.jpeg:
+                    raise
+                try:
+                    return read_jpeg_stream(data, room, lambda info: info.device_decodable, 3 if self.rgb else 1)
+                except ValueError:   # (no JPEG either, one the kernel does not take or that does not parse: PIL's to read if it can)
+                    return self._host_image(path)
         except (png.NotPng, Refused):   # another format under a .png name (PIL's to read if it can), a PNG this feed's kernel
             return self._host_image(path)   # does not take, a stream longer than its room
         except ValueError as e:
@@ -160,7 +176,8 @@ class PngDeviceFeed(PrefetchFeed):
         scan = self._scan[slot]
         with torch.cuda.device(self.device), torch.cuda.stream(self._side):
             inflate_status, device_rows = inflate_batch(images, src_at, layout, self._pinned[slot], self._sdev[slot], scan)
-            self.host_decoded += B - len(device_rows)
+            jpeg_status, jpeg_rows = jpeg_batch(images, src_at, layout, self._sdev[slot], scan, C)
+            self.host_decoded += B - len(device_rows) - len(jpeg_rows)
             upload_host_parts(images, layout, scan)
             out = torch.empty((B, C, OH, OW), dtype=torch.float32 if self.normalize else torch.uint8, device=self.device)
             status = torch.empty(B, dtype=torch.int32, device=self.device)
@@ -170,6 +187,18 @@ class PngDeviceFeed(PrefetchFeed):
             ev.record(self._side)
             bad_inflate = inflate_status.cpu() if inflate_status is not None else None   # waits for the launches
             bad = status.cpu()
+            refused = [] if jpeg_status is None else [jpeg_rows[k] for k in torch.nonzero(jpeg_status.cpu()).reshape(-1).tolist()]
+            self.jpeg_decoded += len(jpeg_rows) - len(refused)
+            if refused:   # what the JPEG kernel handed back: the host decoder's pixels in their place, and the batch unpacked again
+                for i in refused:
+                    images[i] = self._host_image(paths[i])
+                    if images[i].hw != (H, W):
+                        raise RuntimeError(f"{paths[i]} is {images[i].hw[0]} x {images[i].hw[1]}, the first image of its batch ({paths[0]}) {H} x {W}")
+                    scan[int(layout.at[i]):int(layout.at[i]) + layout.need[i]].copy_(torch.as_tensor(images[i].pixels).contiguous().reshape(-1))
+                self.host_decoded += len(refused)
+                self._unpack(scan, torch.from_numpy(unpack_table(self._unpack, images, layout)).to(self.device), (H, W), out, status, top, left)
+                ev.record(self._side)
+                bad = status.cpu()
         raise_first_bad(bad_inflate, inflate.INF_STATUS, lambda row: paths[device_rows[row]])
         raise_first_bad(bad, UNPACK_STATUS, lambda row: paths[row])
         return out, tuple(paths), ev

@@ -43,6 +43,15 @@ not, Adam7-interlaced or not (``PngInfo.any_decodable``): the chunk's launch -- 
 a chunk of mixed files; every image has its own inflated size in the scanline buffer and the palettes of the chunk's palette files
 lie behind the last image.  The conversions are ``read_image``'s, bit for bit.  The host keeps what is no PNG, what does not parse,
 a palette file without a usable PLTE chunk, and whatever the inflate or unpack launch refuses.  Off (the default), nothing changes.
+
+``decode_jpeg=True`` (``--device-image-decode-jpeg``) has the device take baseline JPEG files too, by their first bytes and not their
+name (``JpegInfo.device_decodable``: Huffman sequential, 8 bits, one scan, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0, at most
+``jpeg.MAX_WIDTH`` wide): the file's bytes go into its room of the slot as they are, ONE ``yogo_jpeg_decode`` launch per chunk
+(csrc/jpeg_decode.hip) leaves every JPEG's planes in the scanline buffer where host-decoded pixels would lie, and the chunk's one
+unpack launch takes them as planar entries beside the PNG files.  A JPEG of another size follows the ``device_resize`` rule of a PNG.
+The host keeps progressive, arithmetic, 12-bit, CMYK, multi-scan and wider files and whatever the kernel gives a status
+(``jpeg.JPG_STATUS``: everything libjpeg would only warn about).  stats gains ``jpeg_decoded`` and, per chunk that has JPEG files,
+``jpeg_ms``.  Off (the default), nothing changes.
 """
 from __future__ import annotations
 
@@ -56,8 +65,8 @@ import torch
 
 from yogo_amd import _hip, png
 from yogo_amd.device_decode import MAX_THREADS, png_unpack_any, png_unpack_planes, resize_aa
-from yogo_amd.png_batch import KIND_PLANAR, PngStream, _file_size, batch_layout, inflate_batch, read_stream, slot_layout, unpack_table, \
-    upload_host_parts
+from yogo_amd.png_batch import KIND_PLANAR, PngStream, _file_size, batch_layout, inflate_batch, jpeg_batch, read_jpeg_stream, read_stream, \
+    slot_layout, unpack_table, upload_host_parts
 from yogo_amd.resize import aa_taps, device_serves
 
 # images per decode chunk, from tools/bench_prefill.py's sweep (profiles/prefill_decode.log: 772 x 1032 frames, three runs per size):
@@ -89,11 +98,12 @@ def _host_sample(ds, j: int, rows=None) -> PngStream:
 
 
 def _read(ds, j: int, room: np.ndarray, image_hw: Tuple[int, int], decodable: Callable[[png.PngInfo], bool] = attrgetter("prefill_decodable"),
-          device_resize: bool = False) -> PngStream:
+          device_resize: bool = False, jpeg_planes: int = 0) -> PngStream:
     """(pool thread) one sample: its file's zlib stream into ``room`` (its bytes of the pinned slot) and its label rows, or its
     pixels from the host decoder.  decodable: the formats the chunk's unpack kernel takes; device_resize: a file of another size than
-    ``image_hw`` stays on the device when the resize kernel serves both of its scales"""
-    def accept(info: png.PngInfo) -> bool:
+    ``image_hw`` stays on the device when the resize kernel serves both of its scales; jpeg_planes: 1 or 3 -- what is no PNG is
+    looked at as a JPEG, and one the device decodes gets a record with that many planes (0: it is the host's)"""
+    def accept(info, decodable=decodable) -> bool:
         resized = (info.height, info.width) != tuple(image_hw)
         return decodable(info) and (not resized or (device_resize and device_serves(info.height, image_hw[0]) and device_serves(info.width, image_hw[1])))
 
@@ -102,7 +112,12 @@ def _read(ds, j: int, room: np.ndarray, image_hw: Tuple[int, int], decodable: Ca
     try:
         with open(str(ds._image_paths[j]), "rb") as f:
             data = f.read()
-        s = read_stream(data, room, accept)
+        try:
+            s = read_stream(data, room, accept)
+        except png.NotPng:
+            if not jpeg_planes:
+                raise
+            s = read_jpeg_stream(data, room, lambda info: accept(info, attrgetter("device_decodable")), jpeg_planes)
     except (OSError, ValueError):
         return _host_sample(ds, j)
     s.resize = s.hw != tuple(image_hw)
@@ -167,7 +182,7 @@ class Filler:
 
     def fill(self, images: torch.Tensor, samples: Sequence[Tuple[object, int]], decode_batch: int = DEFAULT_DECODE_BATCH,
              stats: Optional[Dict] = None, device_resize: bool = False, decode_all: bool = False, raise_rows: bool = True,
-             after: Optional[torch.cuda.Event] = None) -> List[Optional[torch.Tensor]]:
+             after: Optional[torch.cuda.Event] = None, decode_jpeg: bool = False) -> List[Optional[torch.Tensor]]:
         """the module's ``fill`` on this object's scratch.  raise_rows False: a usable sample whose label file does not parse has its
         exception in the result, in its rows' place, and nothing is raised for it.  after: the side stream waits for this event before
         it touches ``images`` (None: for everything the caller's current stream holds so far)."""
@@ -185,6 +200,8 @@ class Filler:
         out: List[Optional[torch.Tensor]] = [None] * N
         if stats is not None:
             stats.update(scratch_device_bytes=0, scratch_pinned_bytes=0, host_decoded=0, inflate_ms=[], unpack_ms=[], device_resized=0, resize_ms=[])
+            if decode_jpeg:
+                stats.update(jpeg_decoded=0, jpeg_ms=[])
         if N == 0:
             return out
         chunks = [(lo, min(lo + decode_batch, N)) for lo in range(0, N, decode_batch)]
@@ -210,7 +227,8 @@ class Filler:
                 def stage(n: int) -> List[PngStream]:
                     (lo, hi), (offsets, _) = chunks[n], layouts[n]
                     host = pinned[n % 2].numpy()
-                    futures = [pool.submit(_read, *samples[i], host[int(offsets[i - lo]):int(offsets[i - lo]) + sizes[i]], (H, W), decodable, device_resize)
+                    futures = [pool.submit(_read, *samples[i], host[int(offsets[i - lo]):int(offsets[i - lo]) + sizes[i]], (H, W), decodable, device_resize,
+                                           C if decode_jpeg else 0)
                                for i in range(lo, hi)]
                     return [f.result() for f in futures]
 
@@ -238,19 +256,20 @@ class Filler:
 
 
 def fill(images: torch.Tensor, samples: Sequence[Tuple[object, int]], decode_batch: int = DEFAULT_DECODE_BATCH,
-         stats: Optional[Dict] = None, device_resize: bool = False, decode_all: bool = False) -> List[Optional[torch.Tensor]]:
+         stats: Optional[Dict] = None, device_resize: bool = False, decode_all: bool = False, decode_jpeg: bool = False) -> List[Optional[torch.Tensor]]:
     """images[i] = the uint8 image of samples[i] = (ObjectDetectionDataset, index in it), what ``ds.image_uint8(index)`` gives, for
     every sample that can be read.  images: contiguous uint8 [N, C, H, W] on an MI355X device (a view of the cache), C 1 or 3.
     -> per sample its fp32 [n, 5] label rows, or None for a sample nothing could decode (its image is left as it was).  Returns after
     the device has finished.  stats (optional dict) receives ``scratch_device_bytes``, ``scratch_pinned_bytes``, ``host_decoded`` and
     per chunk the device-event times ``inflate_ms`` / ``unpack_ms``.  device_resize: files of another size are resized on the device
     (see the module's text); stats then also counts them (``device_resized``) and times every resize launch (``resize_ms``).
-    decode_all: every PNG colour type, bit depth and Adam7 is decoded on the device (see the module's text).
+    decode_all: every PNG colour type, bit depth and Adam7 is decoded on the device (see the module's text).  decode_jpeg: baseline
+    JPEG files are decoded on the device too; stats then also has ``jpeg_decoded`` and ``jpeg_ms``.
     A ``Filler`` that lives for this one call: its scratch is gone when the call returns."""
     _hip.require_cuda(images, "the image cache")
     filler = Filler(images.device)
     try:
-        return filler.fill(images, samples, decode_batch, stats, device_resize=device_resize, decode_all=decode_all)
+        return filler.fill(images, samples, decode_batch, stats, device_resize=device_resize, decode_all=decode_all, decode_jpeg=decode_jpeg)
     finally:
         filler.close()
 
@@ -271,8 +290,10 @@ def _decode(chunk: List[PngStream], samples, layout, pinned: torch.Tensor, sdev:
     if all(s.host and s.pixels is None for s in chunk):
         return scan, 0
     timed = stats is not None
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timed else None
-    inflate_status, device_rows = inflate_batch(chunk, offsets, where, pinned, sdev, scan, ev)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)] if timed else None
+    inflate_status, png_rows = inflate_batch(chunk, offsets, where, pinned, sdev, scan, ev)
+    jpeg_status, jpeg_rows = jpeg_batch(chunk, offsets, where, sdev, scan, C, ev[4:] if timed else None)
+    device_rows = sorted(png_rows + jpeg_rows)   # the records the device decodes: their stored bytes are in the slot
     for i, s in enumerate(chunk):
         if s.pixels is not None and tuple(s.pixels.shape) != (C, H, W):
             raise ValueError(f"fill: {samples[i][0]._image_paths[samples[i][1]]} decodes to {tuple(s.pixels.shape)}, the cache holds {(C, H, W)}")
@@ -311,10 +332,15 @@ def _decode(chunk: List[PngStream], samples, layout, pinned: torch.Tensor, sdev:
         if timed:
             stats["resize_ms"].append(gev[0].elapsed_time(gev[1]))
     if inflate_status is not None:
-        bad[np.asarray(device_rows)[inflate_status.cpu().numpy() != 0]] = 1
+        bad[np.asarray(png_rows)[inflate_status.cpu().numpy() != 0]] = 1
+    if jpeg_status is not None:
+        bad[np.asarray(jpeg_rows)[jpeg_status.cpu().numpy() != 0]] = 1
     if timed:
-        if device_rows:
+        if png_rows:
             stats["inflate_ms"].append(ev[0].elapsed_time(ev[1]))
+        if jpeg_rows:
+            stats["jpeg_ms"].append(ev[4].elapsed_time(ev[5]))
+            stats["jpeg_decoded"] += sum(1 for i in jpeg_rows if not bad[i])
         stats["unpack_ms"].append(ev[2].elapsed_time(ev[3]))
         stats["host_decoded"] += sum(1 for s in chunk if s.host)
         stats["device_resized"] += sum(1 for i in device_rows if chunk[i].resize and not bad[i])

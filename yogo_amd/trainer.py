@@ -191,7 +191,8 @@ class Trainer:
                                      device_image_decode=bool(self.config.get("device_image_decode", False)),
                                      device_image_resize=bool(self.config.get("device_image_resize", False)),
                                      device_image_decode_all=bool(self.config.get("device_image_decode_all", False)),
-                                     **({"device_image_stream": True} if self.config.get("device_image_stream", False) else {}))
+                                     **({"device_image_stream": True} if self.config.get("device_image_stream", False) else {}),
+                                     **({"device_image_decode_jpeg": True} if self.config.get("device_image_decode_jpeg", False) else {}))
         self.train_dataloader = loaders["train"]
         self.validate_dataloader = loaders.get("val", [])
         self.test_dataloader = loaders.get("test", [])
@@ -418,6 +419,7 @@ def build_config(args) -> dict:
         "device_image_resize": args.device_image_resize,
         "device_image_decode_all": args.device_image_decode_all,
         "device_image_stream": getattr(args, "device_image_stream", False),
+        "device_image_decode_jpeg": getattr(args, "device_image_decode_jpeg", False),
         "device_metrics": args.device_metrics,
         "dataset_descriptor_file": args.dataset_descriptor_file,
         "slurm-job-id": os.getenv("SLURM_JOB_ID", default=None),

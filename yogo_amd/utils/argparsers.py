@@ -107,8 +107,20 @@ def _decode_all_needs_decode(ns):
     return None
 
 
+def _decode_jpeg_needs_decode(ns):
+    if ns.device_image_decode_jpeg and not (ns.device_image_decode or getattr(ns, "device_image_stream", False)):
+        return "--device-image-decode-jpeg widens what --device-image-decode takes: it needs --device-image-decode"
+    return None
+
+
+JPEG_HELP = ("also decode baseline JPEG files on the GPU (found by their first bytes, whatever their name: Huffman sequential, 8 bits, grey "
+             "or YCbCr 4:4:4 / 4:2:2 / 4:2:0, up to 1040 pixels wide); progressive, arithmetic, 12-bit, CMYK and damaged files stay on "
+             "the host; the same pixels as the host's decoder (default: False)")
+
+
 def _test_widening_needs_stream(ns):
-    for flag, on in (("--device-image-decode-all", ns.device_image_decode_all), ("--device-image-resize", ns.device_image_resize)):
+    for flag, on in (("--device-image-decode-all", ns.device_image_decode_all), ("--device-image-resize", ns.device_image_resize),
+                     ("--device-image-decode-jpeg", ns.device_image_decode_jpeg)):
         if on and not ns.device_image_stream:
             return f"{flag} widens what --device-image-stream decodes on the GPU: it needs --device-image-stream"
     return None
@@ -184,6 +196,7 @@ def train_parser(parser=None):
                              "and RGB) instead of a pool of PIL workers; other files are decoded on the host; same batches.  Its scratch "
                              "memory (pinned staging, stored streams, scanlines) is freed after the prefill and is not counted in the "
                              "GIB budget (default: False)")
+    parser.add_argument("--device-image-decode-jpeg", default=False, action=boolean_action, help="with --device-image-decode: " + JPEG_HELP)
     parser.add_argument("--device-image-decode-all", default=False, action=boolean_action,
                         help="with --device-image-decode: also decode on the GPU every other PNG colour type and bit depth (palette, 1 / 2 / "
                              "4-bit and 16-bit, grey+alpha, RGBA, with tRNS, Adam7-interlaced) instead of handing those files to the host; "
@@ -206,6 +219,7 @@ def train_parser(parser=None):
     parser.checks.append(_decode_needs_cache)
     parser.checks.append(_resize_needs_decode)
     parser.checks.append(_decode_all_needs_decode)
+    parser.checks.append(_decode_jpeg_needs_decode)
     return parser
 
 
@@ -225,6 +239,7 @@ def test_parser(parser=None):
                         help="match predictions to labels and accumulate the test metrics on the GPU instead of per image on the host; "
                              "same results (default: False)")
     parser.add_argument("--device-image-stream", default=False, action=boolean_action, help=STREAM_HELP)
+    parser.add_argument("--device-image-decode-jpeg", default=False, action=boolean_action, help="with --device-image-stream: " + JPEG_HELP)
     parser.add_argument("--device-image-decode-all", default=False, action=boolean_action,
                         help="with --device-image-stream: also decode on the GPU every other PNG colour type and bit depth (palette, 1 / 2 / "
                              "4-bit and 16-bit, grey+alpha, RGBA, with tRNS, Adam7-interlaced); the same pixels as the host's decoder "
@@ -273,6 +288,7 @@ def infer_parser(parser=None):
     parser.add_argument("--device-image-decode", default=False, action=boolean_action,
                         help="with --path-to-images: inflate and unfilter 8-bit greyscale PNG files on the GPU instead of decoding them "
                              "in DataLoader workers; other files are decoded on the host; same outputs (default: False)")
+    parser.add_argument("--device-image-decode-jpeg", default=False, action=boolean_action, help="with --device-image-decode: " + JPEG_HELP)
     parser.add_argument("--device-image-decode-all", default=False, action=boolean_action,
                         help="with --device-image-decode: decode on the GPU every PNG colour type and bit depth (palette, 1 / 2 / 4-bit and "
                              "16-bit, grey+alpha, RGBA, RGB, with tRNS, Adam7-interlaced), converted as the host's decoder converts them, "
@@ -304,5 +320,6 @@ def infer_parser(parser=None):
                         help="path to heatmap mask for the run (accepted for compatibility, unused -- as in the reference)")
     parser.add_argument("--use-tqdm", default=True, action=boolean_action, help="use tqdm progress bar (default: True)")
     parser.checks.append(_decode_all_needs_decode)
+    parser.checks.append(_decode_jpeg_needs_decode)
     parser.checks.append(_device_draw_needs)
     return parser

@@ -44,13 +44,14 @@ from yogo_amd.blobgen import BlobDataset
 from yogo_amd.data import MultiArgSequential, RandomHorizontalFlipWithBBs, RandomVerticalFlipWithBBs, format_labels_batch
 from yogo_amd.dataset_definition_file import DatasetDefinition, SplitFractions
 from yogo_amd.image_stream import ImageStream, Scratch, Staged
-from yogo_amd.image_cache import DECODE_ALL_FLAG, DECODE_FLAG, FLAG, RESIZE_FLAG, ImageCache, ResidentMarkers, budget_bytes, collate_cached, gather, resident_count
+from yogo_amd.image_cache import DECODE_ALL_FLAG, DECODE_FLAG, DECODE_JPEG_FLAG, FLAG, RESIZE_FLAG, ImageCache, ResidentMarkers, budget_bytes, collate_cached, gather, resident_count
 from yogo_amd.png_prefill import DEFAULT_DECODE_BATCH
 from yogo_amd.yogo_dataset import ObjectDetectionDataset
 
 SPLIT_SEED = 7271978   # yogo/data/yogo_dataloader.py:176
 
 _stream_scope = (False, False, False)   # device_image_stream, device_image_decode_all, device_image_resize
+_stream_jpeg = False                    # device_image_decode_jpeg, inside a stream scope
 
 
 @contextlib.contextmanager
@@ -66,6 +67,19 @@ def device_image_stream_scope(enabled: bool, decode_all: bool = False, resize: b
         yield
     finally:
         _stream_scope = prev
+
+
+@contextlib.contextmanager
+def device_image_jpeg_scope(enabled: bool):
+    """inside a ``device_image_stream_scope``: the stream decodes baseline JPEG files on the device as well (``yogo test
+    --device-image-stream --device-image-decode-jpeg``)"""
+    global _stream_jpeg
+    prev = _stream_jpeg
+    _stream_jpeg = bool(enabled) or prev
+    try:
+        yield
+    finally:
+        _stream_jpeg = prev
 
 
 def guess_suggested_num_workers() -> Optional[int]:
@@ -302,26 +316,31 @@ def get_dataloader(dataset_definition: DatasetDefinition, batch_size: int, Sx: i
                    split_fraction_override: Optional[SplitFractions] = None, device=None,
                    device_image_cache_gib: Optional[float] = None, device_image_decode: bool = False,
                    device_image_resize: bool = False, device_image_decode_all: bool = False, device_image_stream: bool = False,
-                   stream_decode_batch: int = DEFAULT_DECODE_BATCH) -> Dict[str, DeviceLoader]:
+                   stream_decode_batch: int = DEFAULT_DECODE_BATCH, device_image_decode_jpeg: bool = False) -> Dict[str, DeviceLoader]:
     """{split: DeviceLoader}.  device_image_cache_gib: keep decoded images of the train split, then of the val split with what
     is left, resident in HBM within this many GiB (yogo_amd/image_cache.py); None: no cache.  device_image_decode: fill that
     cache from PNG files inflated and unfiltered on the device (yogo_amd/png_prefill.py) instead of a pool of PIL workers.
     device_image_resize: on that route, resize the files of another size than image_hw on the device as well.
     device_image_decode_all: on that route, decode every PNG colour type, bit depth and Adam7 on the device, not 8-bit greyscale
     and RGB alone.
+    device_image_decode_jpeg: on that route, decode baseline JPEG files (found by their first bytes) on the device as well
+    (csrc/jpeg_decode.hip); progressive, CMYK, 12-bit and damaged ones stay on the host.
     device_image_stream: decode what is file-backed and not resident on the device too, every epoch, in groups of stream_decode_batch
     images, without DataLoader workers (yogo_amd/image_stream.py); it needs no cache.  device_image_resize and
-    device_image_decode_all then widen what the stream decodes as well.  Its staging and scratch, shared by the splits, are allocated
+    device_image_decode_all / device_image_decode_jpeg then widen what the stream decodes as well.  Its staging and scratch, shared by the splits, are allocated
     at the first iteration, are not part of the GIB budget, and are released by ``loader.stream.scratch.close()``."""
     if _stream_scope[0]:
         device_image_stream = True
         device_image_decode_all, device_image_resize = device_image_decode_all or _stream_scope[1], device_image_resize or _stream_scope[2]
+        device_image_decode_jpeg = device_image_decode_jpeg or _stream_jpeg
     if device_image_decode and device_image_cache_gib is None:
         raise ValueError(f"{DECODE_FLAG} fills the device image cache: it needs {FLAG} GIB")
     if device_image_resize and not (device_image_decode or device_image_stream):
         raise ValueError(f"{RESIZE_FLAG} resizes what the device decoded: it needs {DECODE_FLAG}")
     if device_image_decode_all and not (device_image_decode or device_image_stream):
         raise ValueError(f"{DECODE_ALL_FLAG} widens what {DECODE_FLAG} takes: it needs {DECODE_FLAG}")
+    if device_image_decode_jpeg and not (device_image_decode or device_image_stream):
+        raise ValueError(f"{DECODE_JPEG_FLAG} widens what {DECODE_FLAG} takes: it needs {DECODE_FLAG}")
     budget = budget_bytes(device_image_cache_gib) if device_image_cache_gib is not None else None
     split_datasets = get_datasets(dataset_definition, Sx, Sy, rgb=rgb, image_hw=image_hw, normalize_images=normalize_images,
                                   split_fraction_override=split_fraction_override)
@@ -340,7 +359,8 @@ def get_dataloader(dataset_definition: DatasetDefinition, batch_size: int, Sx: i
     stream_args = {}
     if device_image_stream:   # one scratch for every split: the threads of a rank are its share of the CPUs, as its workers would be
         stream_args = dict(scratch=Scratch(image_shape, batch_size, stream_decode_batch, device, bool(device_image_resize), bool(device_image_decode_all),
-                                           max_threads=max(1, (guess_suggested_num_workers() or 1) // world_size)),
+                                           max_threads=max(1, (guess_suggested_num_workers() or 1) // world_size),
+                                           **({"decode_jpeg": True} if device_image_decode_jpeg else {})),
                            image_shape=image_shape, normalize_images=normalize_images, log=rank == 0)
     d: Dict[str, DeviceLoader] = {}
     for designation, dataset in split_datasets.items():
@@ -352,7 +372,8 @@ def get_dataloader(dataset_definition: DatasetDefinition, batch_size: int, Sx: i
             cache_args = dict(resident=resident[designation], image_shape=image_shape, normalize_images=normalize_images,
                               name=designation, log=rank == 0, device_decode=bool(device_image_decode),
                               device_resize=bool(device_image_resize and device_image_decode),
-                              device_decode_all=bool(device_image_decode_all and device_image_decode))
+                              device_decode_all=bool(device_image_decode_all and device_image_decode),
+                              device_decode_jpeg=bool(device_image_decode_jpeg and device_image_decode))
         if stream_args:
             cache_args = {**stream_args, "name": designation, **cache_args}
         d[designation] = _get_dataloader(dataset, batch_size, augs, rank, world_size, Sx, Sy, device, strict_steps=designation == "train",
@@ -377,7 +398,8 @@ def _num_workers(dataset_size: int, world_size: int) -> int:
 def _get_dataloader(dataset: Dataset, batch_size: int, augmentations: list, rank: int, world_size: int, Sx: int, Sy: int,
                     device=None, strict_steps: bool = False, resident: int = 0, image_shape: Optional[Tuple[int, int, int]] = None,
                     normalize_images: bool = False, name: str = "train", log: bool = False, device_decode: bool = False,
-                    device_resize: bool = False, device_decode_all: bool = False, scratch: Optional[Scratch] = None) -> DeviceLoader:
+                    device_resize: bool = False, device_decode_all: bool = False, scratch: Optional[Scratch] = None,
+                    device_decode_jpeg: bool = False) -> DeviceLoader:
     """resident > 0: split indices 0 .. resident-1 are kept decoded on the device (image_shape = (C, H, W)).  scratch: the split's
     file-backed samples that are not resident are streamed through it (yogo_amd/image_stream.py); no worker is ever started"""
     blob = dataset.datasets[-1] if isinstance(dataset, ConcatDataset) and isinstance(dataset.datasets[-1], BlobDataset) else None
@@ -393,7 +415,8 @@ def _get_dataloader(dataset: Dataset, batch_size: int, augmentations: list, rank
         cache = ImageCache(dataset, resident, image_shape, normalize_images, device=device, num_workers=num_workers, batch_size=batch_size,
                            name=name, log=log, **({"device_decode": True} if device_decode else {}),
                            **({"device_resize": True} if device_resize else {}),
-                           **({"device_decode_all": True} if device_decode_all else {}))   # (the keywords only when set:
+                           **({"device_decode_all": True} if device_decode_all else {}),
+                           **({"device_decode_jpeg": True} if device_decode_jpeg else {}))   # (the keywords only when set:
         #                    tests/test_image_cache_host.py puts a recording class with the earlier signature in ImageCache's place)
         host_dataset = ResidentMarkers(host_dataset, cache.resident)
         collate_fn = collate_cached
